@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Benchmark of the FWI hot path (forward modelling -> misfit -> adjoint -> model gradient).
 
-    python bench.py --gpus N --steps K --warmup W [--workload NAME]
+    python bench.py --gpus N --steps K --warmup W [--workload NAME] [--dump-outputs DIR] [--full]
 
 A "step" is one full gradient evaluation over the rank's shots.  value = interior
 cells x time steps x shots (all ranks) / wall second, in Mcells*steps/s (BASELINE.json metric).
@@ -15,8 +15,16 @@ Inputs are synthetic and resident in HBM before timing st
 before this process touches the GPU; under torchrun it is one of the ranks.
 
 Default invocation: headline = elastic Marmousi-II (BASELINE configs[2], the stencil the
-north-star roofline target is stated on); `also` = acoustic configs[1] and the elastic survey
-on the 10 m grid 350x1700 (per-step kernels, HBM-bound).
+north-star roofline target is stated on).  A plain run sets up, warms up, times the K steps and
+prints the line; per-kernel figures come from events recorded inside the timed steps.
+
+`--full` adds what the headline figure does not need: the CPU baseline, the untimed cross-check of
+the two kernel families, per-kernel durations of a time-checkpointed run (a run of their own) and,
+in the default invocation, `also` = acoustic configs[1] and the elastic survey on the 10 m grid
+350x1700 (per-step kernels, HBM-bound).
+
+`--dump-outputs DIR` writes what the last timed step returned (model gradients, loss, receiver
+traces) as DIR/<name>.npy; inputs are synthetic and seeded, so two builds compare output for output.
 """
 import argparse
 import contextlib
@@ -149,6 +157,7 @@ class AcousticMarmousi:
     nz, nx, h, dt, nt, freq = 174, 500, 10.0, 0.001, 2000, 8.0
     shots_per_gpu = 29
     pml = 10                                   # the width `Propagator({'vp': m}, dx)` gets (networks.py:5408: none passed)
+    model_names, trace_names = ("vp",), ("p",)       # --dump-outputs: gradient per model parameter, last_rec per component
     fwd_bytes, adj_bytes = 16.0, 20.0          # SURVEY.md 8d algorithmic B / cell-step, one launch per step
     # an LDS-resident time loop only has to move the snapshot stream (G^n, 4 B/cell-step out, 4 back in)
     resident_fwd_bytes, resident_adj_bytes = 4.0, 4.0
@@ -325,6 +334,7 @@ class ElasticMarmousi:
     nz, nx, h, dt, nt, freq = 100, 300, 20.0, 0.002, 3000, 5.0
     shots_per_gpu = 32
     pml = 10
+    model_names, trace_names = ("vp", "vs", "rho"), ("vx", "vz")
     fwd_bytes, adj_bytes = 60.0, 80.0    # fused forward 60 B, adjoint + correlation 80 B
     resident_fwd_bytes, resident_adj_bytes = 20.0, 20.0      # LDS-resident: the five snapshot planes only
     # acquisition (networks.py:7612-7631): sources every 80 m at z = 40 m, receivers every 20 m at z = 460 m
@@ -678,7 +688,29 @@ def cross_check(wl, name, dev, kw):
             "gradient_rel_l2": gr}
 
 
-def run_workload(name, args, dev, rank, world, want_cpu, grid=None, steps=None, warmup=None, nt=None, absorbing=None, pml=None):
+DUMP_MAX_ELEMS = 1 << 21      # per array (8 MiB of float32): at most 3 gradients + 2 trace components stay under 64 MB
+
+
+def dump_outputs(wl, grad, loss, path):
+    """What the last timed step returned to its caller, one float32 DIR/<name>.npy per array: grad_<parameter> (the
+    model gradient), loss, and traces_<component> (wl.last_rec, the seismograms of that step).  An array of more than
+    DUMP_MAX_ELEMS entries is cut to a sample of them at positions drawn once from a fixed seed: the same positions
+    for the same shape, run after run."""
+    import torch
+    os.makedirs(path, exist_ok=True)
+    grad, rec = grad.detach(), wl.last_rec               # [parameters][nz][nx], [components][nt][shots][nrec]
+    arrays = {"loss": loss.detach().reshape(1)}
+    arrays.update(("grad_" + n, g) for n, g in zip(wl.model_names, grad.reshape(-1, *grad.shape[-2:])))
+    arrays.update(("traces_" + n, r) for n, r in zip(wl.trace_names, rec.reshape(-1, *rec.shape[-3:])))
+    for name, a in arrays.items():
+        if a.numel() > DUMP_MAX_ELEMS:
+            idx = np.sort(np.random.default_rng(0).choice(a.numel(), DUMP_MAX_ELEMS, replace=False))
+            a = a.reshape(-1)[torch.from_numpy(idx).to(a.device)]
+        np.save(os.path.join(path, name + ".npy"), a.float().cpu().numpy())
+
+
+def run_workload(name, args, dev, rank, world, want_cpu, grid=None, steps=None, warmup=None, nt=None, absorbing=None, pml=None,
+                 dump=None):
     import copy
     import torch
     import torch.distributed as dist
@@ -750,6 +782,7 @@ def run_workload(name, args, dev, rank, world, want_cpu, grid=None, steps=None, 
     for grad, loss in kept:
         losses.append(loss)
         gsums.append(grad.abs().sum(dtype=torch.float64))
+    last_grad, last_loss = kept[-1]
     del kept
     # single-launch time loops that gave up inside the timed region and were re-run with one launch per step (rank 0's
     # count): must be 0 for `kernel_family` to describe what was timed
@@ -791,6 +824,8 @@ def run_workload(name, args, dev, rank, world, want_cpu, grid=None, steps=None, 
     if not args.timing_only and not (np.isfinite(losses[0]) and losses[0] > 1e-25 and gsums[0] > 1e-25):
         raise SystemExit("bench: the timed pass produced loss %.3g, |grad| sum %.3g - nothing reached the receivers, "
                          "the kernels were timed on zeros" % (losses[0], gsums[0]))
+    if dump:
+        dump_outputs(wl, last_grad, last_loss, dump)
     value = units_all * args.steps / el / 1e6
     t_f, t_b = wl.kernel_times()
     kernel_note = None
@@ -801,7 +836,10 @@ def run_workload(name, args, dev, rank, world, want_cpu, grid=None, steps=None, 
         kernel_note = ("snapshots of all %d steps fit for %d shots at a time: the gradient pass takes the shots in chunks "
                        "of %d, forward straight into adjoint (no time checkpoints, no second forward); per-kernel "
                        "durations = sums over the chunks" % (wl.nt, chunk, chunk))
-    if nt_res:
+    if nt_res and not args.full:
+        t_f = t_b = None
+        kernel_note = "time-checkpointed pass: per-kernel durations take a run of their own (--full)"
+    elif nt_res:
         # time-checkpointed run: the backward call re-runs the forward, so its events do not isolate the adjoint
         # kernels; the per-kernel durations come from a short run of the same workload with resident snapshots
         short = WORKLOADS[name](dev, rank, world, nt=nt_res, shots=args.shots or None, **kw)
@@ -813,17 +851,9 @@ def run_workload(name, args, dev, rank, world, want_cpu, grid=None, steps=None, 
         del short
         kernel_note = "per-kernel durations from a %d-step run of the same workload (snapshots resident)" % nt_res
     interior = wl.interior_cells              # the metric counts interior cells x user time steps
-    res_f, res_a = wl.resident()
-    kern = {
-        "forward+save": kernel_report(wl.profile_key, "forward+save", t_f, interior, wl.fwd_bytes,
-                                      wl.resident_fwd_bytes, res_f),
-        "adjoint+imaging": kernel_report(wl.profile_key, "adjoint+imaging", t_b, interior, wl.adj_bytes,
-                                         wl.resident_adj_bytes, res_a),
-    }
-    dom = "adjoint+imaging" if t_b >= t_f else "forward+save"
     check = {"loss": losses[0], "grad_abs_sum": gsums[0], "bitwise_repeatable": deterministic, "fallbacks": fallbacks,
              "agent_scope_relaunches": agent_tier, "slow_handoff_launches": slow_handoffs}
-    if not (args.no_verify or args.timing_only):
+    if args.full and not (args.no_verify or args.timing_only):
         check.update(cross_check(wl, name, dev, kw))
     out = {
         "metric": "grid-cells*timesteps/sec (forward+adjoint gradient pass)",
@@ -843,9 +873,17 @@ def run_workload(name, args, dev, rank, world, want_cpu, grid=None, steps=None, 
                    "peak_reserved_GiB": round(torch.cuda.max_memory_reserved(dev) / 2 ** 30, 2),
                    "note": "torch allocator, timed passes only (snapshots or checkpoints + work buffers + data)"},
         "ranks": ranks,
-        "roofline": roofline_of(kern, dom, interior),
-        "kernels": kern,
     }
+    if t_f is not None:
+        res_f, res_a = wl.resident()
+        kern = {
+            "forward+save": kernel_report(wl.profile_key, "forward+save", t_f, interior, wl.fwd_bytes,
+                                          wl.resident_fwd_bytes, res_f),
+            "adjoint+imaging": kernel_report(wl.profile_key, "adjoint+imaging", t_b, interior, wl.adj_bytes,
+                                             wl.resident_adj_bytes, res_a),
+        }
+        dom = "adjoint+imaging" if t_b >= t_f else "forward+save"
+        out["roofline"], out["kernels"] = roofline_of(kern, dom, interior), kern
     if getattr(wl, "sample_acquisition", False):
         out["config"]["acquisition"] = ("sample: %d of %d steps, sources 4 rows below the sea bed, receivers 3 rows "
                                         "further down, wavelet compressed into the run" % (wl.nt, wl.full_nt))
@@ -897,7 +935,7 @@ def compact_entry(e, headline):
     """What the final stdout line carries of one workload: the contract fields for the headline, a one-row summary
     (value, per-step kernel times, roofline fraction and traffic) for the secondary workloads."""
     kern = {}
-    for name, k in e["kernels"].items():
+    for name, k in e.get("kernels", {}).items():      # none for a time-checkpointed pass without --full
         kern[name] = {"us_per_step": k["avg_step_s"] * 1e6, "alg_B_per_cell": k["alg_bytes_per_cell_step"],
                       "frac_of_hbm_peak": k["alg_GBs"] / HBM_PEAK_GBS,
                       "hbm_B_per_cell_measured": k["hbm_bytes_per_cell_step_measured"]}
@@ -917,8 +955,9 @@ def compact_entry(e, headline):
         c["ranks"] = {k: rk[k] for k in ("world_size_seen", "backend", "shots_per_rank", "pass_ms_per_rank",
                                          "all_reduce_ms_per_rank")}
         c["memory_peak_GiB"] = e["memory"]["peak_allocated_GiB"]
-        c["roofline"] = compact_roofline(e["roofline"])
-        c["kernels"] = kern
+        if "roofline" in e:
+            c["roofline"] = compact_roofline(e["roofline"])
+            c["kernels"] = kern
         if "cpu_baseline" in e:
             c["cpu_baseline"] = e["cpu_baseline"]
         if "device" in e:
@@ -1053,10 +1092,18 @@ def main():
     ap.add_argument("--detail", default="", help="where the full report goes (default gpurun_out/bench_detail.json)")
     ap.add_argument("--no-also", action="store_true",
                     help="skip the secondary workloads of the default invocation")
+    ap.add_argument("--full", action="store_true",
+                    help="also what the headline figure does not need: CPU baseline, cross-check of the two kernel "
+                         "families, per-kernel durations of a time-checkpointed pass, the secondary workloads of the "
+                         "default invocation (each can be dropped again with its --no-... option)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write what the last timed step returned (gradients, loss, traces) as DIR/<name>.npy")
     args = ap.parse_args()
 
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("--steps must be >= 1 and --warmup >= 0")
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         sys.exit(self_launch(args, sys.argv[1:]))    # before anything here touches the GPU
 
@@ -1081,11 +1128,11 @@ def main():
         if dist.get_world_size() != args.gpus:
             raise SystemExit("process group has %d ranks, --gpus %d" % (dist.get_world_size(), args.gpus))
 
-    want_cpu = (not args.no_cpu_baseline) and world == 1
+    want_cpu = args.full and (not args.no_cpu_baseline) and world == 1
     primary = args.workload or "elastic_marmousi"
-    out = run_workload(primary, args, dev, rank, world, want_cpu)
+    out = run_workload(primary, args, dev, rank, world, want_cpu, dump=args.dump_outputs)
     also = []
-    if args.workload is None and not args.no_also:
+    if args.full and args.workload is None and not args.no_also:
         # C2 as the reference calls it: Propagator({'vp': m}, dx) - a PML of deepwave's default width (second-order C-PML,
         # 10 cells per side)
         also.append(run_workload("acoustic_marmousi", args, dev, rank, world, want_cpu, absorbing="cpml"))

@@ -198,6 +198,39 @@ def test_pmc_tool_knows_the_kernels_the_bench_runs():
         assert len(hits) == (1 if re.match(loop_re, n) else 0), (n, hits)
 
 
+def test_dump_outputs_writes_the_last_step_as_float32_with_a_fixed_sample(tmp_path, monkeypatch):
+    """--dump-outputs: one float32 .npy per gradient, the loss and one per trace component; arrays above the size cap
+    are cut to a sample whose positions depend on the shape alone (two runs - or two builds - compare entry for entry),
+    and the total stays under 64 MB for the largest gradients the bench knows."""
+    import numpy as np
+    import torch
+    cap = bench.DUMP_MAX_ELEMS
+    monkeypatch.setattr(bench, "DUMP_MAX_ELEMS", 1000)
+    for names, traces, gshape, rshape in ((("vp", "vs", "rho"), ("vx", "vz"), (3, 5, 7), (2, 30, 4, 10)),
+                                          (("vp",), ("p",), (5, 7), (30, 4, 10))):
+        class Wl:
+            model_names, trace_names = names, traces
+            last_rec = torch.arange(int(np.prod(rshape)), dtype=torch.float32).reshape(rshape)
+        grad, loss = torch.rand(gshape), torch.tensor(2.5)
+        root = tmp_path / traces[0]
+        for run in ("a", "b"):
+            bench.dump_outputs(Wl, grad, loss, str(root / run))
+        files = sorted(os.listdir(root / "a"))
+        assert files == sorted(["loss.npy"] + ["grad_%s.npy" % n for n in names] + ["traces_%s.npy" % n for n in traces])
+        for f in files:
+            a = np.load(root / "a" / f)
+            assert a.dtype == np.float32 and np.array_equal(a, np.load(root / "b" / f))
+        assert np.load(root / "a" / "loss.npy").tolist() == [2.5]
+        assert np.array_equal(np.load(root / "a" / ("grad_%s.npy" % names[-1])), grad.reshape(-1, 5, 7)[-1].numpy())
+        per = 30 * 4 * 10
+        t0 = np.load(root / "a" / ("traces_%s.npy" % traces[0]))
+        assert t0.shape == (1000,) and np.all(np.diff(t0) > 0) and t0[-1] < per       # sorted sample of component 0
+        for k, n in enumerate(traces):
+            assert np.array_equal(np.load(root / "a" / ("traces_%s.npy" % n)), t0 + k * per)    # same positions
+    seam = bench.ElasticSEAM
+    assert 4 * (len(seam.model_names) + len(seam.trace_names)) * cap < 64e6
+
+
 def test_gpus_without_a_launcher_starts_the_ranks_and_fails_loudly_when_one_fails():
     """`bench.py --gpus 2` with WORLD_SIZE unset spawns two ranks before touching the GPU; here (no GPU) every rank
     exits with an error and the parent must report it with a non-zero exit code instead of printing a line."""

@@ -1,6 +1,6 @@
 #!/bin/bash
 # usage: tools/c2_ab.sh "ENV=.." ...  - the C2 workload (acoustic 174x500 x 29 shots x 2000 steps) once per environment string
-ARGS="--workload acoustic_marmousi --no-cpu-baseline --no-also"
+ARGS="--workload acoustic_marmousi --full --no-cpu-baseline --no-also"
 timeout -k 10 200 python bench.py $ARGS --steps 2 --warmup 1 > /dev/null 2>&1
 for E in "$@"; do
   env $E timeout -k 10 300 python bench.py $ARGS --steps ${STEPS:-8} --warmup 3 2>gpurun_out/ab_err.log | tail -1 | python -c "

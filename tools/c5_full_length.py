@@ -4,7 +4,7 @@ MI355X; time-checkpointed: the 4.8 TB of f32 snapshot planes cannot be resident)
 
     python tools/c5_full_length.py [OUT.json]       (on the GPU box; ~1.5 minutes per snapshot format)
 
-Per format: the full report of `python bench.py --workload elastic_seam --steps 2 --warmup 1`, the per-kernel times of
+Per format: the full report of `python bench.py --workload elastic_seam --steps 2 --warmup 1 --full`, the per-kernel times of
 a short run with resident snapshots, resident_equivalent_ms = 5000 x (forward+save + adjoint) of that short run, and
 checkpointing_overhead = ms_per_step / resident_equivalent_ms - 1 (the second forward sweep of the checkpointed pass).
 """
@@ -23,7 +23,7 @@ def run(fmt):
     env = dict(os.environ, MIFWI_EL_SNAP=fmt)
     detail = tempfile.NamedTemporaryFile(suffix=".json", delete=False).name
     res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "elastic_seam", "--steps", "2", "--warmup", "1",
-                          "--no-cpu-baseline", "--detail", detail], env=env, capture_output=True, text=True, timeout=1100)
+                          "--full", "--no-cpu-baseline", "--detail", detail], env=env, capture_output=True, text=True, timeout=1100)
     if res.returncode != 0:
         raise SystemExit("bench failed (%s):\n%s" % (fmt, res.stderr[-2000:]))
     with open(detail) as fh:
@@ -43,7 +43,7 @@ def main():
     doc = {"csrc_sha16": bench.csrc_sha16(), "f32": run("f32"), "bf16": run("bf16"),
            "note": "BASELINE config 5's per-GPU share at its full length: elastic 1000x3000, free surface, 16 shots, 5000 steps, one "
                    "MI355X, time-checkpointed (the 4.8 TB of f32 snapshot planes cannot be resident): python bench.py --workload "
-                   "elastic_seam --steps 2 --warmup 1 [MIFWI_EL_SNAP=bf16].  resident_equivalent_ms = 5000 x (forward+save + adjoint) "
+                   "elastic_seam --steps 2 --warmup 1 --full [MIFWI_EL_SNAP=bf16].  resident_equivalent_ms = 5000 x (forward+save + adjoint) "
                    "kernel time of a short run with resident snapshots; the overhead is the second forward sweep of the checkpointed "
                    "backward pass."}
     with open(out, "w") as fh:

@@ -1,7 +1,7 @@
 #!/bin/bash
 # Round profile set, run on the GPU box (gpurun -- bash tools/profile_round.sh [r03]); results under gpurun_out/,
 # to be copied into profiles/:
-#   <R>_bench_default_output.json        python bench.py
+#   <R>_bench_default_output.json        python bench.py --full
 #   <R>_bench_default_kernel_stats.csv   rocprofv3 --kernel-trace --stats of the same command (no CPU baseline)
 #   <R>_pmc_traffic.json                 FETCH_SIZE / WRITE_SIZE passes of the four bench workloads (tools/pmc_traffic.py)
 #   <R>_latency_floor.json               tools/latency_floor.py (ablation build)
@@ -41,9 +41,9 @@ pmc ac174c --workload acoustic_marmousi -- --workload acoustic_marmousi --suffix
 pmc el350 --workload elastic_marmousi --grid 350x1700 --nt 60 -- --workload elastic_marmousi --grid 350x1700 --nt 60 &&
 pmc seam --workload elastic_seam --nt 24 -- --workload elastic_seam --nt 24 || exit 1
 cp $O/${R}_pmc_traffic.json profiles/${R}_pmc_traffic.json
-python bench.py --detail $O/${R}_bench_default_detail.json > $O/${R}_bench_default_output.json 2> $O/bench.err || { tail -5 $O/bench.err; exit 1; }
+python bench.py --full --detail $O/${R}_bench_default_detail.json > $O/${R}_bench_default_output.json 2> $O/bench.err || { tail -5 $O/bench.err; exit 1; }
 rm -rf $O/prof_default
-timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_default -- python bench.py --no-cpu-baseline > $O/prof.log 2>&1 || { tail -5 $O/prof.log; exit 1; }
+timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_default -- python bench.py --full --no-cpu-baseline > $O/prof.log 2>&1 || { tail -5 $O/prof.log; exit 1; }
 find $O/prof_default -name "*kernel_stats.csv" -exec cp {} $O/${R}_bench_default_kernel_stats.csv \;
 find $O/prof_default -name "*kernel_trace.csv" -delete
 rm -rf $O/prof_seam
