@@ -84,10 +84,6 @@ struct ElParams {
     const float *smp_w;
     float *smp_out0, *smp_out1;
     int tiles_z;
-    int walk_rows;               // el_adj_walk: rows of a column chunk (a multiple of 14)
-    float *trash;                // el_adj_walk: 1024 floats that lanes without an owned cell store to (stores stay branch-free)
-    long long *walk_trace;       // -DMIFWI_ABLATIONS builds: [block][8] cycles per phase (tools/walk_trace.sh)
-    int walk_dbg;                // -DMIFWI_ABLATIONS builds: streams switched off for traffic / timing experiments (wrong results)
     int xcd;                     // XCD-aware tile order (xcd_tile): 1 contiguous runs per shot, 2 whole shots, 3 tile-major over the shots
     FdK K;                       // stencil weights
 };
@@ -713,7 +709,7 @@ __global__ void el_build_tile_taps(const int *cell, int ntaps, int nx, int tx, i
 // S^T:  E = C^T sigma_bar through the transposed C-PML;  v_bar -= stencils(E);  all five material-gradient
 //       accumulators.  The adjoint sources of the tile's cells (v_bar += R^T g, which the oracle applies at the head
 //       of an adjoint step) are added to the loaded v_bar first, through the E planes while they are still empty
-//       (p.tile_start set), or have been applied to the state by el_inject_adjsrc.
+//       (p.tile_start set; null when the call has no receivers).
 // Every global load of a shot (own group, halo group, adjoint velocities, the five snapshot planes) is
 // requested before the first use: one memory round trip per shot instead of three.
 // Register budget pinned at three waves per SIMD (<= 168 VGPRs; 146 in use since the plane loads address as uniform
@@ -1017,7 +1013,6 @@ __global__ __launch_bounds__(kThreads) void el_adj_v(const ElParams p)
 }
 
 #include "mifwi_elastic_fused.h"
-#include "mifwi_elastic_walk.h"
 
 // receivers of the state in p.fields (the last step of a fused range)
 __global__ __launch_bounds__(kThreads) void el_sample_v(const ElParams p)
@@ -1104,28 +1099,6 @@ __global__ void el_inject_pressure(const ElParams p)
     atomicAdd(fl + F_SZZ * (long long)p.field_stride + off, a);
 }
 
-// adjoint of the velocity receivers: vx_bar, vz_bar [cell] += w g[n] at the head of adjoint step n, before S^T
-// (oracle/elastic.c, "a. receivers^T").  Receivers normally sit on distinct cells; taps that share a cell add
-// in hardware order.
-__global__ void el_inject_adjsrc(const ElParams p)
-{
-    const int per = p.ninj * p.ntap_inj;
-    const int idx = (int)(blockIdx.x * blockDim.x + threadIdx.x);
-    if (idx >= p.gs * per) return;
-    const int s = p.s0 + idx / per, r = idx % per;
-    if (s >= p.nshot) return;
-    const long long ee = (long long)s * per + r;
-    const int cell = p.inj_cell[ee];
-    if (cell < 0) return;
-    const int j = cell / p.nx, i = cell - j * p.nx;
-    const unsigned off = (unsigned)(j + 2) * p.pitch + 4 + i;
-    float *fl = p.fields + (long long)s * p.shot_stride;
-    const float w = p.inj_w[ee];
-    const long long ai = (long long)s * p.ninj + r / p.ntap_inj;
-    atomicAdd(fl + F_VX * (long long)p.field_stride + off, w * p.inj_amp0[ai]);
-    atomicAdd(fl + F_VZ * (long long)p.field_stride + off, w * p.inj_amp1[ai]);
-}
-
 __global__ void el_points_bbox(const int *cell, int npts_per_shot, int n1, int *bbox)
 {
     __shared__ int red[4][kThreads];
@@ -1196,9 +1169,6 @@ struct mifwi_elastic_plan {
     int pass_groups;       // adjoint per-step family: shot groups per pass
     int fused;             // forward V+S in one launch (second copy of the state in the work buffer)
     int fused_pass_shots;  // shots per pass of the fused forward (both copies of the state in the Infinity Cache)
-    int fused_adj;         // adjoint S^T+V^T in one launch (second copy of the adjoint fields in the work buffer):
-                           // 1 = el_adj_fused (16 x 64 tiles, recomputed z halo), 2 = el_adj_walk (column walk)
-    int walk_rows, walk_chunks;   // el_adj_walk: rows per column chunk, chunks per column
     long long field_stride, shot_stride, fields_elems, psix_elems, psiz_elems, coef_elems;
     long long psi_elems;  // psix+psiz rounded up to 64
     // cluster path (LDS-resident time loop); 0 when a shot does not fit
@@ -1553,9 +1523,6 @@ int mifwi_elastic_plan_create(mifwi_elastic_plan **plan, int device, const mifwi
     pl->sblk = (!pl->cluster && !pl->cl_adj && env_int("MIFWI_EL_SNAP_BLOCKED", 1) != 0) ? 1 : 0;
     pl->splane = pl->sblk ? 64LL * d->nz * mifwi::ceil_div(pl->ng, 16) : pl->coef_elems;
     pl->snap_shot = pl->snap_bf16 ? mifwi::round_up64(5 * pl->splane / 2, 4) : 5 * pl->splane;
-    pl->fused_adj = (!pl->cl_adj && d->source_type == 0 && !d->record_pressure) ? env_int("MIFWI_EL_FUSED_ADJ", 0) : 0;
-    if (pl->fused_adj < 0 || pl->fused_adj > 2) pl->fused_adj = 0;
-    pl->walk_rows = 0; pl->walk_chunks = 0;
     {
         // Infinity Cache residency (per-step family, large grids): a pass over the time range takes only as
         // many shots as keep state + materials (+ gradient accumulators) under kResident bytes; measured on
@@ -1574,7 +1541,7 @@ int mifwi_elastic_plan_create(mifwi_elastic_plan **plan, int device, const mifwi
         // adjoint: groups of gs shots share one accumulator set; when the groups do not all fit, smaller groups
         // (more accumulator traffic, 40/gs B per cell-step) can still pay: 1000x3000, gs 2, one group per pass
         // 0.87 ms against 0.98 ms for gs 4 over all shots
-        const double astate = (pl->fused_adj ? 8.0 : 4.0) * (double)pl->shot_stride + 2.0 * psi1, accg = 4.0 * 5.0 * cells;
+        const double astate = 4.0 * (double)pl->shot_stride + 2.0 * psi1, accg = 4.0 * 5.0 * cells;
         if (!pl->cl_adj && d->shots_per_group <= 0 && env_int("MIFWI_EL_GS", 0) <= 0 &&
             pl->ngroups * (pl->gs * astate + accg) + mats > kResident) {
             int g = pl->gs;
@@ -1610,34 +1577,6 @@ int mifwi_elastic_plan_create(mifwi_elastic_plan **plan, int device, const mifwi
     if (pl->cl_adj) {                    // the adjoint cluster kernel keeps one accumulator set per shot
         pl->gs = 1;
         pl->ngroups = d->nshot;
-    }
-    if (pl->fused_adj == 2) {
-        // el_adj_walk: columns of 16 groups are cut into chunks of rows; every chunk pays one start-up iteration (the
-        // rows above it that its first rows depend on), so as few chunks as still fill the chip a few times over
-        const size_t lds = walk_lds_bytes(pl->gs);
-        bool ok = lds <= 160 * 1024;
-        for (const void *fn : {(const void *)el_adj_walk<false>, (const void *)el_adj_walk<true>})
-            if (ok && hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) {
-                (void)hipGetLastError();
-                ok = false;
-            }
-        if (!ok) {
-            pl->fused_adj = 0;            // a group too large for the carry area: the two-launch form
-        } else {
-            int ncu = 256;
-            (void)hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, pl->device);
-            const int per_cu = std::max(1, std::min(MIFWI_WALK_WAVES, (int)(160 * 1024 / lds)));
-            const int cols = mifwi::ceil_div(pl->ng, WOG), tiles = mifwi::ceil_div(d->nz, WTZ);
-            const int launch_groups = std::min(pl->pass_groups, pl->ngroups);
-            const int want = mifwi::ceil_div(2 * per_cu * ncu, std::max(1, cols * launch_groups));
-            int chunks = std::min(tiles, std::max(1, want));
-            chunks = std::min(chunks, std::max(1, tiles / 2));          // at least two iterations per start-up iteration
-            int rows = mifwi::ceil_div(mifwi::ceil_div(d->nz, chunks), WTZ) * WTZ;
-            rows = env_int("MIFWI_EL_WALK_ROWS", rows);
-            rows = std::max(WTZ, rows / WTZ * WTZ);
-            pl->walk_rows = rows;
-            pl->walk_chunks = mifwi::ceil_div(d->nz, rows);
-        }
     }
     *plan = pl;
     return MIFWI_OK;
@@ -1682,7 +1621,7 @@ int mifwi_elastic_plan_layout(const mifwi_elastic_plan *pl, mifwi_elastic_layout
     out->snap_step_elems = pl->snap_shot * pl->d.nshot;
     out->snapshot_format = pl->snap_bf16 ? MIFWI_SNAPSHOT_BF16 : MIFWI_SNAPSHOT_F32;
     out->kernel_flags = (pl->cluster ? MIFWI_EL_KERNEL_FWD_SINGLE_LAUNCH : 0) | (pl->cl_adj ? MIFWI_EL_KERNEL_ADJ_SINGLE_LAUNCH : 0) |
-                        (pl->fused ? MIFWI_EL_KERNEL_FWD_FUSED_STEP : 0) | (pl->fused_adj ? MIFWI_EL_KERNEL_ADJ_FUSED_STEP : 0) |
+                        (pl->fused ? MIFWI_EL_KERNEL_FWD_FUSED_STEP : 0) |
                         (pl->cluster && pl->cl_xh ? MIFWI_EL_KERNEL_FWD_LANE_HALO : 0) |
                         (pl->cl_adj && pl->adj_xh ? MIFWI_EL_KERNEL_ADJ_LANE_HALO : 0);
     const long long psi = pl->psi_elems;
@@ -1693,7 +1632,7 @@ int mifwi_elastic_plan_layout(const mifwi_elastic_plan *pl, mifwi_elastic_layout
                               (pl->fused ? out->state_elems : 0);
     const long long adj_state = pl->fields_elems + 2 * psi + 5LL * pl->ngroups * pl->splane;
     out->work_backward_elems = adj_state + bbox + (pl->cl_adj ? pl->xbuf_elems + pl->list_elems + adj_state : 0) +
-                               (pl->fused_adj ? pl->fields_elems : 0) + pl->tile_elems;
+                               pl->tile_elems;
     return MIFWI_OK;
 }
 
@@ -1887,17 +1826,14 @@ int mifwi_elastic_backward(mifwi_elastic_plan *pl, const float *mat, const float
     float *acc = psiB + psi;
     const long long nacc = 5LL * pl->ngroups * pl->splane;          // accumulator planes: the snapshot planes' layout and size
     int *bbox = reinterpret_cast<int *>(acc + nacc);
-    float *fieldsB = reinterpret_cast<float *>(bbox) + mifwi::round_up64(4LL * d.nshot, 64);   // fused adjoint only
-    if (flags & MIFWI_ZERO_STATE) {
+    if (flags & MIFWI_ZERO_STATE)
         MIFWI_HIP_TRY(hipMemsetAsync(work, 0, sizeof(float) * (pl->fields_elems + 2 * psi + nacc), st));
-        if (pl->fused_adj) MIFWI_HIP_TRY(hipMemsetAsync(fieldsB, 0, sizeof(float) * pl->fields_elems, st));
-    }
     ElParams p = el_base(pl, mat, pz, px);
     p.fields = fields;
     p.acc = acc;
     ElParams ps = p;
     ps.gs = pl->gs;
-    ps.ninj = d.nrec; ps.ntap_inj = d.ntap; ps.inj_cell = rec_cell; ps.inj_w = rec_w;    // el_inject_adjsrc
+    ps.ninj = d.nrec; ps.ntap_inj = d.ntap; ps.inj_cell = rec_cell; ps.inj_w = rec_w;
     const bool want_f = grad_f != nullptr && d.nsrc > 0;
     ps.nsmp = want_f ? d.nsrc : 0; ps.ntap_smp = d.ntap; ps.smp_cell = src_cell; ps.smp_w = src_w;
     const long long snap_step = pl->snap_shot * d.nshot;
@@ -2012,10 +1948,8 @@ int mifwi_elastic_backward(mifwi_elastic_plan *pl, const float *mat, const float
             per_step = false;
         }
     }
-    // the two-launch form adds the adjoint sources inside el_adj_s (per-tile lists); the fused launch keeps the pre-pass
-    const bool inj_in_tile = per_step && !pl->fused_adj && d.nrec > 0 && n_hi >= n_lo &&
-                             env_int("MIFWI_EL_INJ_PREPASS", 0) == 0;
-    if (inj_in_tile) {
+    // el_adj_s adds the adjoint sources of its tile (per-tile lists)
+    if (per_step && d.nrec > 0 && n_hi >= n_lo) {
         build_tile_lists();
         ps.tile_start = tile_start; ps.tile_list = tile_list;
     }
@@ -2036,91 +1970,25 @@ int mifwi_elastic_backward(mifwi_elastic_plan *pl, const float *mat, const float
         const bool force = d.source_type != 0;        // grad_f of a point force: v_bar sampled between S^T and V^T
         ps.smp_out0 = (want_f && !force) ? grad_f + (long long)n * d.nshot * d.nsrc : nullptr;
         p.psix = ps.psix; p.psiz = ps.psiz; p.psix_out = ps.psix_out; p.psiz_out = ps.psiz_out;
-        if (pl->fused_adj) {
-            // S^T + V^T in one launch: the adjoint fields ping-pong like the memory variables (absolute in n)
-            ps.fields = par ? fieldsB : fields;
-            ps.fields_out = par ? fields : fieldsB;
-        }
-        if (d.nrec > 0 && !inj_in_tile) {
+        const int tx = mifwi::ceil_div(pl->ng, AGO), tz = mifwi::ceil_div(d.nz, ATZ);
+        ps.tiles_z = tz;
+        int ex = 0;
+        if (want_f && !force) ex = mifwi::ceil_div(mifwi::ceil_div(ps.gs * ps.nsmp, kThreads), tx);
+        if (pl->g_p && d.nrec > 0) {
             ElParams pq = ps;
-            pq.gs = cs;
-            hipLaunchKernelGGL(el_inject_adjsrc, dim3(mifwi::ceil_div(cs * d.nrec * d.ntap, 64)), dim3(64), 0, st, pq);
+            pq.gs = cs; pq.inj_amp0 = pl->g_p + (long long)n * d.nshot * d.nrec;
+            hipLaunchKernelGGL(el_inject_pressure, dim3(mifwi::ceil_div(cs * d.nrec * d.ntap, 64)), dim3(64), 0,
+                               st, pq);
         }
-        if (pl->fused_adj == 2) {
-            const int tx = mifwi::ceil_div(pl->ng, WOG);
-            ps.tiles_z = pl->walk_chunks;
-            ps.walk_rows = pl->walk_rows;
-            {   // the per-tile receiver lists of el_adj_s are not in use with this kernel: their room takes the dummy stores
-                mifwi_elastic_layout lay;
-                mifwi_elastic_plan_layout(pl, &lay);
-                ps.trash = work + lay.work_backward_elems - pl->tile_elems;
-            }
-#ifdef MIFWI_ABLATIONS
-            ps.walk_dbg = env_int("MIFWI_WALK_DBG", 0);
-#endif
-            const int ex = want_f ? mifwi::ceil_div(mifwi::ceil_div(ps.gs * ps.nsmp, kThreads), tx) : 0;
-            const size_t lds = walk_lds_bytes(ps.gs);
-#ifdef MIFWI_ABLATIONS
-            const char *trace_path = getenv("MIFWI_WALK_TRACE");
-            const size_t trace_n = (size_t)tx * pl->walk_chunks * cg * 8;
-            ps.walk_trace = nullptr;
-            if (trace_path && *trace_path && n == n_lo) {          // the last step of the range: caches warm
-                MIFWI_HIP_TRY(hipMalloc(&ps.walk_trace, trace_n * sizeof(long long)));
-                MIFWI_HIP_TRY(hipMemsetAsync(ps.walk_trace, 0, trace_n * sizeof(long long), st));
-            }
-#endif
-            if (pl->snap_bf16) hipLaunchKernelGGL(el_adj_walk<true>, dim3(tx, pl->walk_chunks + ex, cg), dim3(kThreads), lds, st, ps);
-            else hipLaunchKernelGGL(el_adj_walk<false>, dim3(tx, pl->walk_chunks + ex, cg), dim3(kThreads), lds, st, ps);
-#ifdef MIFWI_ABLATIONS
-            if (ps.walk_trace) {
-                std::vector<long long> h(trace_n);
-                MIFWI_HIP_TRY(hipStreamSynchronize(st));
-                MIFWI_HIP_TRY(hipMemcpy(h.data(), ps.walk_trace, trace_n * sizeof(long long), hipMemcpyDeviceToHost));
-                MIFWI_HIP_TRY(hipFree(ps.walk_trace));
-                double sum[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-                for (size_t i = 0; i < trace_n; ++i) sum[i & 7] += (double)h[i];
-                if (FILE *fp = fopen(trace_path, "a")) {
-                    // per item, mean over workgroups: A | barrier | B | barrier | C | barrier ; items ; whole kernel per workgroup
-                    const double items = sum[6] > 0 ? sum[6] : 1.0, wgs = (double)(trace_n / 8);
-                    fprintf(fp, "el_adj_walk wgs %.0f items/wg %.1f cycles/item: A %.0f bar %.0f B %.0f bar %.0f C %.0f bar %.0f | kernel cycles/wg %.0f\n",
-                            wgs, items / wgs, sum[0] / items, sum[1] / items, sum[2] / items, sum[3] / items, sum[4] / items,
-                            sum[5] / items, sum[7] / wgs);
-                    fclose(fp);
-                }
-                ps.walk_trace = nullptr;
-            }
-#endif
-            continue;
+        if (pl->snap_bf16) hipLaunchKernelGGL(el_adj_s<true>, dim3(tx, tz + ex, cg), dim3(kThreads), 0, st, ps);
+        else hipLaunchKernelGGL(el_adj_s<false>, dim3(tx, tz + ex, cg), dim3(kThreads), 0, st, ps);
+        if (want_f && force) {
+            ElParams pq = ps;
+            pq.gs = cs; pq.smp_out0 = grad_f + (long long)n * d.nshot * d.nsrc;
+            hipLaunchKernelGGL(el_sample_force, dim3(mifwi::ceil_div(cs * d.nsrc, 64)), dim3(64), 0, st, pq,
+                               d.source_type);
         }
-        if (pl->fused_adj) {
-            const int tx = mifwi::ceil_div(pl->ng, FTG), tz = mifwi::ceil_div(d.nz, FTZ);
-            ps.tiles_z = tz;
-            const int ex = want_f ? mifwi::ceil_div(mifwi::ceil_div(ps.gs * ps.nsmp, kThreads), tx) : 0;
-            if (pl->snap_bf16) hipLaunchKernelGGL(el_adj_fused<true>, dim3(tx, tz + ex, cg), dim3(kThreads), 0, st, ps);
-            else hipLaunchKernelGGL(el_adj_fused<false>, dim3(tx, tz + ex, cg), dim3(kThreads), 0, st, ps);
-            continue;
-        }
-        {
-            const int tx = mifwi::ceil_div(pl->ng, AGO), tz = mifwi::ceil_div(d.nz, ATZ);
-            ps.tiles_z = tz;
-            int ex = 0;
-            if (want_f && !force) ex = mifwi::ceil_div(mifwi::ceil_div(ps.gs * ps.nsmp, kThreads), tx);
-            if (pl->g_p && d.nrec > 0) {
-                ElParams pq = ps;
-                pq.gs = cs; pq.inj_amp0 = pl->g_p + (long long)n * d.nshot * d.nrec;
-                hipLaunchKernelGGL(el_inject_pressure, dim3(mifwi::ceil_div(cs * d.nrec * d.ntap, 64)), dim3(64), 0,
-                                   st, pq);
-            }
-            if (pl->snap_bf16) hipLaunchKernelGGL(el_adj_s<true>, dim3(tx, tz + ex, cg), dim3(kThreads), 0, st, ps);
-            else hipLaunchKernelGGL(el_adj_s<false>, dim3(tx, tz + ex, cg), dim3(kThreads), 0, st, ps);
-            if (want_f && force) {
-                ElParams pq = ps;
-                pq.gs = cs; pq.smp_out0 = grad_f + (long long)n * d.nshot * d.nsrc;
-                hipLaunchKernelGGL(el_sample_force, dim3(mifwi::ceil_div(cs * d.nsrc, 64)), dim3(64), 0, st, pq,
-                                   d.source_type);
-            }
-            hipLaunchKernelGGL(el_adj_v, dim3(tx, tz, cs), dim3(kThreads), 0, st, p);
-        }
+        hipLaunchKernelGGL(el_adj_v, dim3(tx, tz, cs), dim3(kThreads), 0, st, p);
     }
     if (flags & MIFWI_FINALIZE) {
         const long long n5 = 5LL * pl->coef_elems;

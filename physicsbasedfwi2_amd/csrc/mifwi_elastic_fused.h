@@ -1,21 +1,20 @@
-// Fused per-step kernels of the elastic propagator for grids that do not fit the LDS of a few CUs
+// Fused forward step of the elastic propagator for grids that do not fit the LDS of a few CUs
 // (HBM / Infinity-Cache-bound regime; included by mifwi_elastic.hip inside its anonymous namespace).
 //
 //   el_fwd_fused<SNAP> : V and S of one time step in ONE launch   (80 instead of 100 B per cell-step with f32
 //                        snapshot planes, 70 instead of 90 with bf16 planes)
-//   el_adj_fused<BF16> : S^T and V^T of one adjoint step in ONE launch (100 instead of 122 B; 90 instead of 112)
 //
 // A workgroup owns 16 rows x 64 cells (one 4-cell group per thread).  What the two-launch form exchanges through
-// memory between its launches (new velocities; new adjoint velocities) is recomputed on a two-row / one-group halo
-// and handed over through LDS, so a step reads its state once and writes it once.  Nothing is updated in place - a
-// neighbouring workgroup may still need the old value of a cell this one owns - so a launch reads one copy of the
-// state (fields + C-PML memory variables) and writes the other; the drivers ping-pong.
+// memory between its launches (the new velocities) is recomputed on a two-row / one-group halo and handed over
+// through LDS, so a step reads its state once and writes it once.  Nothing is updated in place - a neighbouring
+// workgroup may still need the old value of a cell this one owns - so a launch reads one copy of the state
+// (fields + C-PML memory variables) and writes the other; the driver ping-pongs.
 // What makes the form pay (the first version, round 1, did not): every stencil operand is staged ONCE in LDS by
 // plain 16-byte loads issued up front (13 per thread instead of 24 through per-thread z windows), the register
 // budget is capped at 128 so that four workgroups share a CU, and the time loop runs over as many shots at a time
 // as keep BOTH copies of their state inside the Infinity Cache.
-// Arithmetic: the same fmaf chains as el_step_v / el_step_s / el_adj_s / el_adj_v, term by term (bit-identical
-// results; tests/test_elastic_gpu.py::test_fused_* compare the two forms).
+// Arithmetic: the same fmaf chains as el_step_v / el_step_s, term by term (bit-identical results;
+// tests/test_full_size_gpu.py::test_fused_forward_matches_the_two_launch_form compares the two forms).
 
 constexpr int FTZ = 16;              // owned rows
 constexpr int FTG = 16;              // owned groups per row
@@ -305,274 +304,6 @@ __global__ __launch_bounds__(kThreads, 4) void el_fwd_fused(const ElParams p)
             float *Sp = p.S + (long long)s * p.snap_shot;
             bf_store2(Sp, snap_cell(p, oj, og) >> 2, e1, e2);
             bf_store1(Sp + bf_reg_c(p.splane), snap_cell(p, oj, og) >> 2, s3v);
-        }
-    }
-}
-
-// ================================================================================================================
-// fused adjoint step: S^T and V^T of one step in ONE launch.
-//   E = C^T sigma_bar (transposed C-PML) on the tile + 4 rows / 1 group  ->  LDS
-//   v_bar' = v_bar - stencils(E) on the tile + 2 rows / 1 group (recomputing what the neighbours own; R^T g has
-//            been added to the input state by el_inject_adjsrc);
-//            the five material-gradient accumulators from the snapshot planes;  D = B^T v_bar' (transposed C-PML)
-//   D -> LDS;  sigma_bar' = sigma_bar - stencils(D) on the tile
-// Reads one copy of the adjoint state, writes the other (the memory variables of the adjoint already ping-pong in
-// the two-launch form).  A workgroup walks the gs shots of its accumulator group with the accumulators in registers.
-// ================================================================================================================
-constexpr int kAFRows = 2 * FRS + 2 * FRV + 4 * FRV;       // E2, E3 (FRS rows), E1, E4 (FRV rows), D1..D4 (FRV rows)
-constexpr int kAFElems = kAFRows * FSW;
-// v_bar' of group (j, g) from the E planes: `lr` = row in the FRV-row planes, `lc` = first column
-template <int SW = FSW>      // floats per LDS row of the planes
-__device__ __forceinline__ void adj_v_update(const ElParams &p, int g, const float *E1, const float *E2, const float *E3,
-                                             const float *E4, int lr, int lc, const float4 &vxb, const float4 &vzb,
-                                             float *nvx, float *nvz)
-{
-    const FdK K = p.K;
-    const Row8 x1 = row8(E1 + lr * SW, lc), x4 = row8(E4 + lr * SW, lc);
-    const float4 z3a = lds4(E3 + (lr + 0) * SW + lc), z3b = lds4(E3 + (lr + 1) * SW + lc);
-    const float4 z3c = lds4(E3 + (lr + 2) * SW + lc), z3d = lds4(E3 + (lr + 3) * SW + lc);
-    const float4 z2a = lds4(E2 + (lr + 1) * SW + lc), z2b = lds4(E2 + (lr + 2) * SW + lc);
-    const float4 z2c = lds4(E2 + (lr + 3) * SW + lc), z2d = lds4(E2 + (lr + 4) * SW + lc);
-#pragma unroll
-    for (int c = 0; c < 4; ++c) {
-        const float dx1 = dfw(K, x1.v[c + 1], x1.v[c + 2], x1.v[c + 3], x1.v[c + 4]);
-        const float dz3 = dbw(K, comp(z3a, c), comp(z3b, c), comp(z3c, c), comp(z3d, c));
-        const float dz2 = dfw(K, comp(z2a, c), comp(z2b, c), comp(z2c, c), comp(z2d, c));
-        const float dx4 = dbw(K, x4.v[c], x4.v[c + 1], x4.v[c + 2], x4.v[c + 3]);
-        float ax = comp(vxb, c) - (dx1 + dz3);
-        float az = comp(vzb, c) - (dz2 + dx4);
-        if (4 * g + c >= p.nx) { ax = 0.f; az = 0.f; }
-        nvx[c] = ax; nvz[c] = az;
-    }
-}
-
-// index sets of a thread: its owned group, its halo item of the velocity region, its halo item of the stress region.
-// Recomputed from an opaque thread index at the head of every phase: derived once, the compiler keeps a few dozen
-// addresses alive across the whole step (and spills them).
-struct FOwn { int orow, ogrp, oj, og; bool ok; unsigned occ, oo; };
-struct FHalo { int r, g, j, gg; bool ok; unsigned cc, o; };
-__device__ __forceinline__ FOwn f_own(const ElParams &p, int t, int tile_j, int tile_g)
-{
-    FOwn o;
-    o.orow = t / FTG; o.ogrp = t % FTG;
-    o.oj = tile_j + o.orow; o.og = tile_g + o.ogrp;
-    o.ok = o.oj < p.nz && o.og < p.ng;
-    o.occ = (unsigned)o.oj * p.gp + 4 * o.og;
-    o.oo = (unsigned)(o.oj + 2) * p.pitch + 4 + 4 * o.og;
-    return o;
-}
-template <int HR>
-__device__ __forceinline__ FHalo f_halo(const ElParams &p, int t, int tile_j, int tile_g)
-{
-    FHalo h;
-    h.r = 0; h.g = 0;
-    constexpr int N = 2 * HR * (FTG + 2) + 2 * FTZ;
-    if (t < N) fhalo_item<HR>(t, h.r, h.g);
-    h.j = tile_j - HR + h.r; h.gg = tile_g - 1 + h.g;
-    h.ok = t < N && h.j >= 0 && h.j < p.nz && h.gg >= 0 && h.gg < p.ng;
-    h.cc = (unsigned)h.j * p.gp + 4 * h.gg;
-    h.o = (unsigned)(h.j + 2) * p.pitch + 4 + 4 * h.gg;
-    return h;
-}
-
-template <bool BF16>
-__global__ __launch_bounds__(kThreads, 3) void el_adj_fused(const ElParams p)
-{
-    const FdK K = p.K;
-    int bx, by, bz;
-    xcd_tile(p, bx, by, bz);
-    if (by >= p.tiles_z) {
-        sample_points<1>(p, bx, by, bz);
-        return;
-    }
-    __shared__ __attribute__((aligned(16))) float buf[kAFElems];      // 53,760 B: three workgroups per CU
-    float *E2 = buf, *E3 = buf + FRS * FSW, *E1 = buf + 2 * FRS * FSW, *E4 = E1 + FRV * FSW;
-    float *D1 = E4 + FRV * FSW, *D2 = D1 + FRV * FSW, *D3 = D2 + FRV * FSW, *D4 = D3 + FRV * FSW;
-    const int tile_j = by * FTZ, tile_g = bx * FTG;
-    const unsigned fs = p.field_stride;
-    const unsigned ncell = (unsigned)p.nz * p.gp;
-    const int t = (int)threadIdx.x;
-    const float4 zero4 = make_float4(0.f, 0.f, 0.f, 0.f);
-    float4 acc[5];
-    {
-        const FOwn o = f_own(p, t, tile_j, tile_g);
-        const long long acc_base = (long long)(p.s0 / p.gs + bz) * 5 * p.splane + snap_cell(p, o.oj, o.og);
-        if (o.ok) {
-#pragma unroll
-            for (int k = 0; k < 5; ++k) acc[k] = ld4(p.acc + acc_base + (long long)k * p.splane);
-        }
-    }
-    // margins of the LDS rows: zeros (they only ever feed lanes whose results are discarded)
-    for (int e = t; e < kAFRows; e += kThreads) {
-        sts4(buf + e * FSW, zero4);
-        sts4(buf + e * FSW + FSW - 4, zero4);
-    }
-    for (int si = 0; si < p.gs; ++si) {
-        const int s = p.s0 + bz * p.gs + si;
-        if (s >= p.nshot) break;
-        const float *fin = p.fields + (long long)s * p.shot_stride;
-        float *fout = p.fields_out + (long long)s * p.shot_stride;
-        float4 ovx = zero4, ovz = zero4, hvx = zero4, hvz = zero4, obx = zero4, obz = zero4, hbx = zero4, hbz = zero4;
-        float4 S1 = zero4, S2 = zero4, S3 = zero4, S4 = zero4, S5 = zero4;
-        BfPlanes packed;
-        packed.ab = packed.de = mifwi_u4{0u, 0u, 0u, 0u};
-        packed.c = mifwi_u2{0u, 0u};
-        float4 bxx = zero4, bzz = zero4, bxz = zero4;         // own adjoint stresses as S^T sees them
-        // ---- E on the tile + halo ---------------------------------------------------------------------------------
-        {
-            const int tq = f_opaque(t);
-            const FOwn o = f_own(p, tq, tile_j, tile_g);
-            const FHalo h = f_halo<4>(p, tq, tile_j, tile_g);
-            AdjIn own, halo;
-            own.a = own.b = own.c = own.m0 = own.m1 = own.m2 = zero4;
-            halo = own;
-            if (o.ok) {
-                own.a = ld4(fin + F_SXX * fs + o.oo); own.b = ld4(fin + F_SZZ * fs + o.oo); own.c = ld4(fin + F_SXZ * fs + o.oo);
-                own.m0 = ld4(p.mat + M_L * ncell + o.occ); own.m1 = ld4(p.mat + M_M * ncell + o.occ);
-                own.m2 = ld4(p.mat + M_MU * ncell + o.occ);
-            }
-            if (h.ok) {
-                halo.a = ld4(fin + F_SXX * fs + h.o); halo.b = ld4(fin + F_SZZ * fs + h.o); halo.c = ld4(fin + F_SXZ * fs + h.o);
-                halo.m0 = ld4(p.mat + M_L * ncell + h.cc); halo.m1 = ld4(p.mat + M_M * ncell + h.cc);
-                halo.m2 = ld4(p.mat + M_MU * ncell + h.cc);
-            }
-            if (p.fsurf && o.oj == 0) own.b = zero4;             // S^T: the adjoint of szz(0,.) is discarded
-            if (p.fsurf && h.j == 0) halo.b = zero4;
-            bxx = own.a; bzz = own.b; bxz = own.c;
-            {
-                float4 e1 = zero4, e2 = zero4, e3 = zero4, e4 = zero4;
-                if (o.ok) stage_E(p, s, o.oj, o.og, own, true, e1, e2, e3, e4);
-                const int x = 4 * (o.ogrp + 2);
-                sts4(E1 + (o.orow + 2) * FSW + x, e1); sts4(E4 + (o.orow + 2) * FSW + x, e4);
-                sts4(E2 + (o.orow + 4) * FSW + x, e2); sts4(E3 + (o.orow + 4) * FSW + x, e3);
-            }
-            if (tq < kFHaloS) {
-                float4 e1 = zero4, e2 = zero4, e3 = zero4, e4 = zero4;
-                if (h.ok) stage_E(p, s, h.j, h.gg, halo, false, e1, e2, e3, e4);
-                const int x = 4 * (h.g + 1);
-                sts4(E2 + h.r * FSW + x, e2); sts4(E3 + h.r * FSW + x, e3);
-                if (h.r >= 2 && h.r < FRS - 2) { sts4(E1 + (h.r - 2) * FSW + x, e1); sts4(E4 + (h.r - 2) * FSW + x, e4); }
-            }
-        }
-        // operands of the second half: requested before the barrier, used after it
-        {
-            const int tq = f_opaque(t);
-            const FOwn o = f_own(p, tq, tile_j, tile_g);
-            const FHalo h = f_halo<2>(p, tq, tile_j, tile_g);
-            if (o.ok) {
-                ovx = ld4(fin + F_VX * fs + o.oo); ovz = ld4(fin + F_VZ * fs + o.oo);
-                obx = ld4(p.mat + M_BX * ncell + o.occ); obz = ld4(p.mat + M_BZ * ncell + o.occ);
-            }
-            if (h.ok) {
-                hvx = ld4(fin + F_VX * fs + h.o); hvz = ld4(fin + F_VZ * fs + h.o);
-                hbx = ld4(p.mat + M_BX * ncell + h.cc); hbz = ld4(p.mat + M_BZ * ncell + h.cc);
-            }
-            if (o.ok && !BF16) {
-                const float *Sp = p.S + (long long)s * p.snap_shot + snap_cell(p, o.oj, o.og);
-                const long long sp = p.splane;
-                S1 = mifwi::ldnt4(Sp); S2 = mifwi::ldnt4(Sp + sp); S3 = mifwi::ldnt4(Sp + 2 * sp);
-                S4 = mifwi::ldnt4(Sp + 3 * sp); S5 = mifwi::ldnt4(Sp + 4 * sp);
-            } else if (o.ok) {
-                bf_request(p.S + (long long)s * p.snap_shot, p.splane, snap_cell(p, o.oj, o.og) >> 2, packed);
-            }
-        }
-        __syncthreads();
-        // ---- v_bar' (tile + halo), gradients, D ---------------------------------------------------------------------
-        {
-            const int tq = f_opaque(t);
-            const FOwn o = f_own(p, tq, tile_j, tile_g);
-            float4 oD1 = zero4, oD2 = zero4, oD3 = zero4, oD4 = zero4;
-            if (o.ok) {
-                float nvx[4], nvz[4];
-                adj_v_update(p, o.og, E1, E2, E3, E4, o.orow + 2, 4 * (o.ogrp + 2), ovx, ovz, nvx, nvz);
-                const float4 nx4 = make_float4(nvx[0], nvx[1], nvx[2], nvx[3]), nz4 = make_float4(nvz[0], nvz[1], nvz[2], nvz[3]);
-                st4(fout + F_VX * fs + o.oo, nx4);
-                st4(fout + F_VZ * fs + o.oo, nz4);
-                // gradients (oracle order): Ms, Ls, mus from sigma_bar; bxs, bzs from the new v_bar
-                if (BF16) {
-                    bf_pin(packed);
-                    bf_widen(packed, S1, S2, S3, S4, S5);
-                }
-#define ACC3(dst, a, b, c_, d) dst = fmaf(a, b, fmaf(c_, d, dst))
-                ACC3(acc[M_M].x, S1.x, bxx.x, S2.x, bzz.x); ACC3(acc[M_M].y, S1.y, bxx.y, S2.y, bzz.y);
-                ACC3(acc[M_M].z, S1.z, bxx.z, S2.z, bzz.z); ACC3(acc[M_M].w, S1.w, bxx.w, S2.w, bzz.w);
-                ACC3(acc[M_L].x, S2.x, bxx.x, S1.x, bzz.x); ACC3(acc[M_L].y, S2.y, bxx.y, S1.y, bzz.y);
-                ACC3(acc[M_L].z, S2.z, bxx.z, S1.z, bzz.z); ACC3(acc[M_L].w, S2.w, bxx.w, S1.w, bzz.w);
-#undef ACC3
-                acc[M_MU].x = fmaf(S3.x, bxz.x, acc[M_MU].x); acc[M_MU].y = fmaf(S3.y, bxz.y, acc[M_MU].y);
-                acc[M_MU].z = fmaf(S3.z, bxz.z, acc[M_MU].z); acc[M_MU].w = fmaf(S3.w, bxz.w, acc[M_MU].w);
-                acc[M_BX].x = fmaf(S4.x, nvx[0], acc[M_BX].x); acc[M_BX].y = fmaf(S4.y, nvx[1], acc[M_BX].y);
-                acc[M_BX].z = fmaf(S4.z, nvx[2], acc[M_BX].z); acc[M_BX].w = fmaf(S4.w, nvx[3], acc[M_BX].w);
-                acc[M_BZ].x = fmaf(S5.x, nvz[0], acc[M_BZ].x); acc[M_BZ].y = fmaf(S5.y, nvz[1], acc[M_BZ].y);
-                acc[M_BZ].z = fmaf(S5.z, nvz[2], acc[M_BZ].z); acc[M_BZ].w = fmaf(S5.w, nvz[3], acc[M_BZ].w);
-                stage_D(p, s, o.oj, o.og, nx4, nz4, obx, obz, true, oD1, oD2, oD3, oD4);
-            }
-            const int x = 4 * (o.ogrp + 2), r = o.orow + 2;
-            sts4(D1 + r * FSW + x, oD1); sts4(D2 + r * FSW + x, oD2); sts4(D3 + r * FSW + x, oD3); sts4(D4 + r * FSW + x, oD4);
-        }
-        {
-            const int tq = f_opaque(t);
-            if (tq < kFHaloV) {
-                const FHalo h = f_halo<2>(p, tq, tile_j, tile_g);
-                float4 hD1 = zero4, hD2 = zero4, hD3 = zero4, hD4 = zero4;
-                if (h.ok) {
-                    float nvx[4], nvz[4];
-                    adj_v_update(p, h.gg, E1, E2, E3, E4, h.r, 4 * (h.g + 1), hvx, hvz, nvx, nvz);
-                    stage_D(p, s, h.j, h.gg, make_float4(nvx[0], nvx[1], nvx[2], nvx[3]),
-                            make_float4(nvz[0], nvz[1], nvz[2], nvz[3]), hbx, hbz, false, hD1, hD2, hD3, hD4);
-                }
-                const int x = 4 * (h.g + 1);
-                sts4(D1 + h.r * FSW + x, hD1); sts4(D2 + h.r * FSW + x, hD2); sts4(D3 + h.r * FSW + x, hD3); sts4(D4 + h.r * FSW + x, hD4);
-            }
-        }
-        __syncthreads();
-        // ---- sigma_bar' of the tile -----------------------------------------------------------------------------------
-        {
-            const int tq = f_opaque(t);
-            const FOwn o = f_own(p, tq, tile_j, tile_g);
-            if (o.ok) {
-                const int r = o.orow + 2, cb = 4 * (o.ogrp + 2);
-                float nxx[4], nzz[4], nxz[4];
-                // the own adjoint stresses once more (cache hits): cheaper than registers held across the step;
-                // V^T updates the stored szz_bar(0,.) as it is (S^T discarded it)
-                const float4 sxx0 = ld4(fin + F_SXX * fs + o.oo), szz0 = ld4(fin + F_SZZ * fs + o.oo);
-                const float4 sxz0 = ld4(fin + F_SXZ * fs + o.oo);
-                const Row8 x1 = row8(D1 + r * FSW, cb), x3 = row8(D3 + r * FSW, cb);
-                const float4 z2a = lds4(D2 + (r - 1) * FSW + cb), z2b = lds4(D2 + r * FSW + cb);
-                const float4 z2c = lds4(D2 + (r + 1) * FSW + cb), z2d = lds4(D2 + (r + 2) * FSW + cb);
-                const float4 z4a = lds4(D4 + (r - 2) * FSW + cb), z4b = lds4(D4 + (r - 1) * FSW + cb);
-                const float4 z4c = lds4(D4 + r * FSW + cb), z4d = lds4(D4 + (r + 1) * FSW + cb);
-                float4 m12 = zero4, m13 = zero4, m32 = zero4;
-                if (p.fsurf && o.oj < 2) { m12 = lds4(D2 + 2 * FSW + cb); m13 = lds4(D2 + 3 * FSW + cb); m32 = lds4(D4 + 2 * FSW + cb); }
-#pragma unroll
-                for (int c = 0; c < 4; ++c) {
-                    const float dx1 = dbw(K, x1.v[c], x1.v[c + 1], x1.v[c + 2], x1.v[c + 3]);
-                    const float dz2 = dfw(K, comp(z2a, c), comp(z2b, c), comp(z2c, c), comp(z2d, c));
-                    const float dx3 = dfw(K, x3.v[c + 1], x3.v[c + 2], x3.v[c + 3], x3.v[c + 4]);
-                    const float dz4 = dbw(K, comp(z4a, c), comp(z4b, c), comp(z4c, c), comp(z4d, c));
-                    nxx[c] = comp(sxx0, c) - dx1;
-                    nxz[c] = comp(sxz0, c) - (dz2 + dx3);
-                    nzz[c] = comp(szz0, c) - dz4;
-                    if (p.fsurf && o.oj < 2) {
-                        // transposed odd mirroring (tile_j == 0 here: row 2 of the planes is grid row 0)
-                        if (o.oj == 0) nxz[c] = nxz[c] + fmaf(K.c1, comp(m12, c), K.c2 * comp(m13, c));
-                        else { nxz[c] = nxz[c] + K.c2 * comp(m12, c); nzz[c] = nzz[c] + K.c2 * comp(m32, c); }
-                    }
-                    if (4 * o.og + c >= p.nx) { nxx[c] = 0.f; nxz[c] = 0.f; nzz[c] = 0.f; }
-                }
-                st4(fout + F_SXX * fs + o.oo, make_float4(nxx[0], nxx[1], nxx[2], nxx[3]));
-                st4(fout + F_SZZ * fs + o.oo, make_float4(nzz[0], nzz[1], nzz[2], nzz[3]));
-                st4(fout + F_SXZ * fs + o.oo, make_float4(nxz[0], nxz[1], nxz[2], nxz[3]));
-            }
-        }
-        __syncthreads();          // the planes are reused by the next shot
-    }
-    {
-        const FOwn o = f_own(p, f_opaque(t), tile_j, tile_g);
-        const long long acc_base = (long long)(p.s0 / p.gs + bz) * 5 * p.splane + snap_cell(p, o.oj, o.og);
-        if (o.ok) {
-#pragma unroll
-            for (int k = 0; k < 5; ++k) st4(p.acc + acc_base + (long long)k * p.splane, acc[k]);
         }
     }
 }

@@ -43,8 +43,7 @@ def kernel_family(flags):
     """(forward, adjoint) description of the formulation a plan picked (``plan.layout.kernel_flags``)."""
     fwd = ("single-launch time loop" if flags & _lib.EL_KERNEL_FWD_SINGLE_LAUNCH else
            "one fused V+S launch per step" if flags & _lib.EL_KERNEL_FWD_FUSED_STEP else "one launch per half step")
-    adj = ("single-launch time loop" if flags & _lib.EL_KERNEL_ADJ_SINGLE_LAUNCH else
-           "one fused S^T+V^T launch per step" if flags & _lib.EL_KERNEL_ADJ_FUSED_STEP else "one launch per half step")
+    adj = "single-launch time loop" if flags & _lib.EL_KERNEL_ADJ_SINGLE_LAUNCH else "one launch per half step"
     return fwd, adj
 
 

@@ -419,7 +419,7 @@ def test_bf16_request_on_a_single_launch_plan_keeps_f32():
     {},                                                                                   # single-launch kernels
     {"MIFWI_EL_NW": "3"},                                                                 # ... with halo hand-off
     {"MIFWI_EL_CLUSTER": "0", "MIFWI_EL_CLUSTER_ADJ": "0"},                               # one launch per half step
-    {"MIFWI_EL_CLUSTER": "0", "MIFWI_EL_CLUSTER_ADJ": "0", "MIFWI_EL_FUSED": "1", "MIFWI_EL_FUSED_ADJ": "1"},
+    {"MIFWI_EL_CLUSTER": "0", "MIFWI_EL_CLUSTER_ADJ": "0", "MIFWI_EL_FUSED": "1"},        # ... fused forward
 ])
 def test_second_order_stencils(oracle32, monkeypatch, env):
     """fd_order = 2 (DENISE FD_ORDER; weights (1, 0) in the four-point form) through every kernel family, with the

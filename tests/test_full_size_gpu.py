@@ -342,12 +342,12 @@ def test_full_length_runs_agree_between_families(monkeypatch):
     assert rel_l2(outs[0][2].cpu().numpy(), outs[1][2].cpu().numpy()) <= 5e-5
 
 
-def test_fused_steps_match_the_two_launch_form(monkeypatch):
-    """MIFWI_EL_FUSED=1: V and S in one launch; MIFWI_EL_FUSED_ADJ=1: S^T and V^T in one launch (stencil operands
-    staged in LDS, recomputed halo, ping-pong state; large grids).  Same arithmetic term by term: traces and
-    gradients equal the two-launch kernels bit for bit, with the free surface, an odd number of steps, passes over
-    shot subsets (copy back of a pass that ends in the second copy), shot groups sharing one accumulator set,
-    checkpointed segments, bf16 snapshot planes and a grid wider and taller than one tile."""
+def test_fused_forward_matches_the_two_launch_form(monkeypatch):
+    """MIFWI_EL_FUSED=1: V and S of a forward step in one launch (stencil operands staged in LDS, recomputed halo,
+    ping-pong state; large grids).  Same arithmetic term by term: traces and gradients equal the two-launch kernels
+    bit for bit, with the free surface, an odd number of steps, passes over shot subsets (copy back of a pass that
+    ends in the second copy), shot groups sharing one accumulator set, checkpointed segments, bf16 snapshot planes
+    and a grid wider and taller than one tile."""
     monkeypatch.setenv("MIFWI_EL_CLUSTER", "0")
     monkeypatch.setenv("MIFWI_EL_CLUSTER_ADJ", "0")
     from physicsbasedfwi2_amd import elastic
@@ -355,19 +355,12 @@ def test_fused_steps_match_the_two_launch_form(monkeypatch):
     case = elastic_case(seed=61, nz=70, nx=150, fw=8, ns=3, nrec=40, nt=75)
     big = 1 << 40
     outs = []
-    for fused, adj, fsurf, budget, pass_shots, fmt, gs in (
-            ("0", "0", 0, big, None, "f32", 0), ("1", "0", 0, big, None, "f32", 0), ("1", "1", 0, big, 2, "f32", 0),
-            ("0", "0", 1, big, None, "f32", 2), ("0", "1", 1, big, None, "f32", 2), ("1", "1", 1, 3 << 20, 2, "f32", 2),
-            ("0", "0", 1, big, None, "bf16", 0), ("1", "1", 1, big, 2, "bf16", 0), ("1", "1", 1, 3 << 20, None, "bf16", 0),
-            # the column-walk adjoint (el_adj_walk): default chunking, one-iteration chunks, one chunk per column
-            ("1", "2", 0, big, 2, "f32", 0), ("0", "2:16", 1, big, None, "f32", 2), ("1", "2:80", 1, 3 << 20, 2, "f32", 2),
-            ("1", "2:32", 1, big, 2, "bf16", 0), ("0", "2", 1, 3 << 20, None, "bf16", 0)):
+    for fused, fsurf, budget, pass_shots, fmt, gs in (
+            ("0", 0, big, None, "f32", 0), ("1", 0, big, None, "f32", 0), ("1", 0, big, 2, "f32", 0),
+            ("0", 1, big, None, "f32", 2), ("1", 1, 3 << 20, 2, "f32", 2),
+            ("0", 1, big, None, "bf16", 0), ("1", 1, big, 2, "bf16", 0), ("1", 1, 3 << 20, None, "bf16", 0),
+            ("0", 1, 3 << 20, None, "bf16", 0)):
         monkeypatch.setenv("MIFWI_EL_FUSED", fused)
-        monkeypatch.setenv("MIFWI_EL_FUSED_ADJ", adj.split(":")[0])
-        if ":" in adj:
-            monkeypatch.setenv("MIFWI_EL_WALK_ROWS", adj.split(":")[1])
-        else:
-            monkeypatch.delenv("MIFWI_EL_WALK_ROWS", raising=False)
         if pass_shots:
             monkeypatch.setenv("MIFWI_EL_FUSED_PASS_SHOTS", str(pass_shots))
             monkeypatch.setenv("MIFWI_EL_PASS_GROUPS", "1")
@@ -385,12 +378,13 @@ def test_fused_steps_match_the_two_launch_form(monkeypatch):
         torch.autograd.backward([rvx, rvz], [torch.sign(rvx.detach()), torch.sign(rvz.detach())])
         outs.append((lay0.work_forward_elems, lay0.work_backward_elems, rvx.detach(), rvz.detach(), mat.grad.clone(),
                      f.grad.clone()))
-    assert outs[1][0] > outs[0][0] and outs[2][1] > outs[0][1]     # the fused plans carry a second copy of the state
+    # the fused forward carries a second copy of the state; the adjoint's work memory does not depend on it
+    assert outs[1][0] > outs[0][0] and outs[2][1] == outs[0][1]
     assert float(outs[0][2].abs().max()) > 0 and float(outs[0][4].abs().max()) > 0
-    for a, b in ((0, 1), (0, 2), (3, 4), (3, 5), (6, 7), (6, 8), (0, 9), (3, 10), (3, 11), (6, 12), (6, 13)):
+    for a, b in ((0, 1), (0, 2), (3, 4), (5, 6), (5, 7), (5, 8)):
         for x, y in zip(outs[a][2:], outs[b][2:]):
             assert torch.equal(x, y), (a, b)
-    assert not torch.equal(outs[3][4], outs[6][4])      # the bf16 planes were in use
+    assert not torch.equal(outs[3][4], outs[5][4])      # the bf16 planes were in use
 
 
 def test_passes_over_shot_subsets_change_nothing(monkeypatch):

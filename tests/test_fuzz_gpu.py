@@ -24,12 +24,11 @@ def _configs():
         opt = dict(source_type=int(rng.integers(0, 3)), pressure=bool(rng.integers(0, 2)),
                    gs=int(rng.integers(0, 4)), cluster=str(int(rng.integers(0, 2))),
                    pass_shots=str(int(rng.integers(1, 4))), pass_groups=str(int(rng.integers(1, 3))))
-        # round 4 (drawn from a generator of their own: the configurations above stay the ones of rounds 1-3): the fused
-        # adjoint forms (1 tiles, 2 column walk; explosive sources without pressure receivers only - the plan ignores the
-        # switch otherwise), rows per column chunk of the walk, plane layout, tile -> XCD order, fused forward
+        # round 4 (drawn from a generator of their own: the configurations above stay the ones of rounds 1-3): plane
+        # layout, tile -> XCD order, fused forward, snapshot format
         r4 = np.random.default_rng(4000 + k)
-        opt.update(fused_adj=str(int(r4.choice([0, 1, 2, 2]))), walk_rows=str(int(r4.choice([14, 28, 42, 70]))),
-                   blocked=str(int(r4.integers(0, 2))), xcd=str(int(r4.choice([0, 1, 2, 3]))), fused=str(int(r4.integers(0, 2))),
+        r4.choice([0, 1, 2, 2]), r4.choice([14, 28, 42, 70])   # options of removed adjoint forms: drawn, keep the sequence
+        opt.update(blocked=str(int(r4.integers(0, 2))), xcd=str(int(r4.choice([0, 1, 2, 3]))), fused=str(int(r4.integers(0, 2))),
                    fmt=str(r4.choice(["f32", "f32", "bf16"])))
         out.append((k, cfg, opt))
     return out
@@ -42,8 +41,6 @@ def test_random_elastic_configuration(oracle32, monkeypatch, k, cfg, opt):
     monkeypatch.setenv("MIFWI_EL_CLUSTER_ADJ", opt["cluster"])
     monkeypatch.setenv("MIFWI_EL_PASS_SHOTS", opt["pass_shots"])
     monkeypatch.setenv("MIFWI_EL_PASS_GROUPS", opt["pass_groups"])
-    monkeypatch.setenv("MIFWI_EL_FUSED_ADJ", opt["fused_adj"])
-    monkeypatch.setenv("MIFWI_EL_WALK_ROWS", opt["walk_rows"])
     monkeypatch.setenv("MIFWI_EL_SNAP_BLOCKED", opt["blocked"])
     monkeypatch.setenv("MIFWI_EL_XCD", opt["xcd"])
     monkeypatch.setenv("MIFWI_EL_FUSED", opt["fused"])

@@ -33,7 +33,7 @@ LABELS = {
     "elastic": {
         "forward+save": [r"^el_cluster_fwd<true", r"^el_step_v<\d+, \d+, [12]>", r"^el_step_s<\d+, \d+, [12]>",
                          r"^el_fwd_fused<[12]>"],
-        "adjoint+imaging": [r"^el_cluster_adj<", r"^el_adj_s<", r"^el_adj_v$", r"^el_adj_fused<", r"^el_adj_walk<", r"^el_inject_adjsrc$"],
+        "adjoint+imaging": [r"^el_cluster_adj<", r"^el_adj_s<", r"^el_adj_v$"],
     },
 }
 
