@@ -344,6 +344,10 @@ int mifwi_elastic_materials_vjp(int device, const float *vp, const float *vs, co
  *                              g_mu = g_vp / (rho Vp) + g_vs / (2 rho Vs)   (second term 0 where Vs = 0: a fluid has no mu to move),
  *                              g_rho' = g_rho - (Vp g_vp + Vs g_vs) / (2 rho)
  * i.e. the exact chain rule of the change of variables, cell by cell (a 3 x 3 Jacobian).  out_* may alias the inputs.
+ * A term whose divisor is zero contributes 0, so every output is finite:
+ *   IMPEDANCE, rho = 0:           g_Zp = g_Zs = 0, g_rho' = g_rho
+ *   LAME, rho = 0 or Vp = 0:      g_lambda = 0 and no g_vp term in g_mu
+ *   LAME, rho = 0 or Vs = 0:      no g_vs term in g_mu;   rho = 0: g_rho' = g_rho
  * n = number of cells; all arrays device. */
 #define MIFWI_PARAM_VELOCITY 1
 #define MIFWI_PARAM_IMPEDANCE 2

@@ -129,6 +129,8 @@ __global__ __launch_bounds__(kMT) void materials_vjp(const float *vp, const floa
 }
 
 // DENISE's INVMAT1: gradients with respect to (Vp, Vs, rho) -> (Zp, Zs, rho) or (lambda, mu, rho); include/mifwi.h
+// A term whose divisor is zero contributes 0 (rho = 0; vp = 0 or vs = 0 in the Lame form): every output stays finite.
+// All inputs of a cell are read before its outputs are written, so the outputs may alias the inputs.
 template <int MODE>
 __global__ __launch_bounds__(kMT) void reparam_vjp(const float *vp, const float *vs, const float *rho, const float *gvp,
                                                    const float *gvs, const float *grho, float *oa, float *ob, float *orho, long long n)
@@ -136,14 +138,16 @@ __global__ __launch_bounds__(kMT) void reparam_vjp(const float *vp, const float 
     const long long k = (long long)blockIdx.x * kMT + threadIdx.x;
     if (k >= n) return;
     const float p = vp[k], q = vs[k], r = rho[k], a = gvp[k], b = gvs[k], c = grho[k];
+    const bool r0 = r == 0.f;
     if (MODE == 2) {
-        oa[k] = a / r;
-        ob[k] = b / r;
-        orho[k] = c - (p * a + q * b) / r;
+        oa[k] = r0 ? 0.f : a / r;
+        ob[k] = r0 ? 0.f : b / r;
+        orho[k] = r0 ? c : c - (p * a + q * b) / r;
     } else {
-        oa[k] = a / (2.0f * r * p);
-        ob[k] = a / (r * p) + (q == 0.f ? 0.f : b / (2.0f * r * q));
-        orho[k] = c - (p * a + q * b) / (2.0f * r);
+        const bool p0 = r0 || p == 0.f, q0 = r0 || q == 0.f;
+        oa[k] = p0 ? 0.f : a / (2.0f * r * p);
+        ob[k] = (p0 ? 0.f : a / (r * p)) + (q0 ? 0.f : b / (2.0f * r * q));
+        orho[k] = r0 ? c : c - (p * a + q * b) / (2.0f * r);
     }
 }
 

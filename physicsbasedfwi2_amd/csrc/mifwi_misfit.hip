@@ -131,6 +131,9 @@ __global__ __launch_bounds__(kTr *kSl) void misfit_global_correlation(const floa
     if (threadIdx.x == 0) partial[blockIdx.x] = s_loss[0];
 }
 
+// VEC: pred, obs and adj are 16-byte aligned (decided on the host, mifwi_misfit); otherwise every group of four is
+// read one float at a time
+template <bool VEC>
 __global__ __launch_bounds__(256) void misfit_l2(const float *pred, const float *obs, long long n, float *adj,
                                                  double *partial)
 {
@@ -138,14 +141,15 @@ __global__ __launch_bounds__(256) void misfit_l2(const float *pred, const float 
     const long long stride = (long long)gridDim.x * blockDim.x * 4;
     double loss = 0.0;
     for (long long i = ((long long)blockIdx.x * blockDim.x + threadIdx.x) * 4; i < n; i += stride) {
-        if (i + 3 < n) {
+        if (VEC && i + 3 < n) {
             const float4 p = *reinterpret_cast<const float4 *>(pred + i);
             const float4 q = *reinterpret_cast<const float4 *>(obs + i);
             const float4 r = make_float4(p.x - q.x, p.y - q.y, p.z - q.z, p.w - q.w);
             loss += (double)(r.x * r.x) + (double)(r.y * r.y) + (double)(r.z * r.z) + (double)(r.w * r.w);
             if (adj) *reinterpret_cast<float4 *>(adj + i) = r;
         } else {
-            for (long long k = i; k < n; ++k) {
+            const long long e = VEC || i + 4 > n ? n : i + 4;      // VEC: only the tail of fewer than 4 lands here
+            for (long long k = i; k < e; ++k) {
                 const float r = pred[k] - obs[k];
                 loss += (double)(r * r);
                 if (adj) adj[k] = r;
@@ -222,7 +226,14 @@ int mifwi_misfit(int device, int32_t kind, const float *pred, const float *obs, 
         hipLaunchKernelGGL(misfit_finish, dim3(1), dim3(256), 0, st, partial, (int)blocks, 1.0, loss_out);
     } else {
         const int blocks = l2_blocks(n);
-        hipLaunchKernelGGL(misfit_l2, dim3(blocks), dim3(256), 0, st, pred, obs, n, adj_out, partial);
+        // float4 loads and stores only where all three pointers allow them: a view such as buf[1:] is contiguous but
+        // only 4-byte aligned, and the callers pass such views through unchanged
+        const bool vec = ((reinterpret_cast<uintptr_t>(pred) | reinterpret_cast<uintptr_t>(obs) |
+                           reinterpret_cast<uintptr_t>(adj_out)) & 15) == 0;
+        if (vec)
+            hipLaunchKernelGGL(misfit_l2<true>, dim3(blocks), dim3(256), 0, st, pred, obs, n, adj_out, partial);
+        else
+            hipLaunchKernelGGL(misfit_l2<false>, dim3(blocks), dim3(256), 0, st, pred, obs, n, adj_out, partial);
         hipLaunchKernelGGL(misfit_finish, dim3(1), dim3(256), 0, st, partial, blocks, 0.5, loss_out);
     }
     MIFWI_HIP_TRY(hipGetLastError());

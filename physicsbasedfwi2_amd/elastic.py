@@ -95,7 +95,10 @@ def gradient_parametrization(prm, grads, mode):
     """Gradients with respect to (Vp, Vs, rho) -> the parameter set DENISE calls INVMAT1 (``models/networks.py:11025``):
     1 unchanged, 2 (Zp = rho Vp, Zs = rho Vs, rho), 3 (lambda, mu, rho).  ``prm`` = (vp, vs, rho), ``grads`` = the three
     gradients, float32 tensors of one shape on a HIP device; returns three new tensors.  One launch
-    (``mifwi_elastic_gradient_parametrization``): the 3 x 3 Jacobian of the change of variables cell by cell."""
+    (``mifwi_elastic_gradient_parametrization``): the 3 x 3 Jacobian of the change of variables cell by cell.
+    A term whose divisor is zero contributes 0, so the result is finite everywhere: where rho = 0 the first two
+    gradients are 0 and the rho gradient passes unchanged; in the Lame form a cell with Vp = 0 has no lambda gradient
+    and no Vp term in the mu gradient, and a cell with Vs = 0 no Vs term."""
     vp, vs, rho = (t.detach().contiguous().float() for t in prm)
     gv, gs, gr = (t.detach().contiguous().float() for t in grads)
     if not vp.is_cuda:

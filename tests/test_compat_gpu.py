@@ -189,6 +189,35 @@ def test_denise_impedance_and_lame_parameterisations(tmp_path, monkeypatch):
         d.TIMEWIN = 1                            # changes the gradient, not built
 
 
+def test_denise_parameterisations_are_finite_at_a_zero_velocity_cell(tmp_path, monkeypatch):
+    """VPLOWERLIM defaults to 0, so a model may hold a cell with Vp = Vs = 0.  Its Vp / Vs gradients are 0, and the
+    Lame form used to divide 0 by 2 rho Vp = 0 there.  INVMAT1 = 2 and 3 return finite gradients; at that cell
+    lambda and mu get 0 and rho keeps its INVMAT1 = 1 gradient (include/mifwi.h)."""
+    api, d, (vp, vs, rho), dx, src, rec = _denise_setup(tmp_path)
+    monkeypatch.chdir(tmp_path)
+    cell = (30, 45)
+    vp, vs = vp.copy(), vs.copy()
+    vp[cell] = vs[cell] = 0.0
+    d.TIME = 0.3
+    ox, oy = d.forward(api.Model(np.flipud(vp * 1.03), np.flipud(vs * 0.98), np.flipud(rho), dx), src, rec)
+    grads = {}
+    for mode in (1, 2, 3):
+        dd = api.Denise(None, 0)
+        for k in ("TIME", "DT", "FREE_SURF", "FW", "FPML", "DAMPING"):
+            setattr(dd, k, getattr(d, k))
+        dd.INVMAT1 = mode
+        dd.set_observed(np.transpose(ox, (0, 2, 1)), np.transpose(oy, (0, 2, 1)))
+        dd.add_fwi_stage(fc_high=10)
+        dd.grad(api.Model(np.flipud(vp), np.flipud(vs), np.flipud(rho), dx), src, rec)
+        g_rho, g_a, g_b = (np.flipud(np.array(g)) for g in dd.get_fwi_gradients(["seis"]))
+        assert all(np.isfinite(g).all() for g in (g_rho, g_a, g_b)), mode
+        assert np.abs(g_a).max() > 0, mode
+        grads[mode] = (g_rho, g_a, g_b)
+    assert grads[1][1][cell] == 0.0 and grads[1][2][cell] == 0.0            # Vp = Vs = 0: lambda = mu = 0 there
+    assert grads[3][1][cell] == 0.0 and grads[3][2][cell] == 0.0
+    assert grads[3][0][cell] == grads[1][0][cell]
+
+
 def test_denise_free_surface_default_runs(oracle32, tmp_path):
     """pyapi default FREE_SURF=1 (what networks.py:7698-7731 leaves untouched, SEAM sets it at 9811)."""
     api, d, (vp, vs, rho), dx, src, rec = _denise_setup(tmp_path)
