@@ -11,6 +11,9 @@
 // {epoch,value} granules with agent-scope stores/loads (cdna_hip_programming.md, G16 form R2):
 // no flags, no fences, no grid barrier, every spin bounded.  The hand-off latency is hidden behind
 // the rows that do not need the halo: interior rows are updated before the poll, boundary rows after.
+// The adjoint publishes from its pointwise phases, ahead of the barrier in front of the interior pass, so
+// it also ASKS for the neighbours' granules in front of that pass (EA_EARLY_REQUEST) and only examines
+// them behind it; the forward kernel publishes stencil results and asks behind its interior pass.
 // Arithmetic per cell = el_step_v / el_step_s (bitwise identical seismograms).
 #pragma once
 
@@ -211,7 +214,8 @@ struct EcHandoff {
     //   request(): one pass of loads of ALL of this thread's granules, back to back (one memory round trip per
     //              pass, not one per granule), nothing waits;
     //   complete(): examine that pass; while a tag is missing, nap and sweep again (bounded: a time-out sets
-    //              `failed`); then hand every value to dest(lds_offset, value).
+    //              `failed`); then hand every value to dest(lds_offset, value).  EAGER: the pass under examination
+    //              was requested a phase ahead, so the second pass goes out without a nap in front of it.
     struct Pending {
         const unsigned long long *base;
         unsigned long long v[kEcGr];
@@ -235,7 +239,7 @@ struct EcHandoff {
         q.base = ec_at(xw, (unsigned)(kind * 2 + parity) * xs8) - 4 * (xs8 / 8);
         sweep(q);
     }
-    template <class Dest>
+    template <bool EAGER = false, class Dest>
     __device__ __forceinline__ void complete(Pending &q, unsigned epoch, Dest dest)
     {
         int lo[kEcGr];
@@ -257,7 +261,7 @@ struct EcHandoff {
                 failed = true;
                 break;
             }
-            mifwi::poll_nap(nap);
+            if (!(EAGER && spins == 0)) mifwi::poll_nap(nap);
             sweep(q);
         }
 #pragma unroll
@@ -1020,6 +1024,18 @@ __global__ void ec_build_slab_lists(const int *rec_cell, int nrec, int nz, int n
 #ifndef EA_S1
 #define EA_S1 2
 #endif
+// Where the first pass of granule loads of a hand-off is issued: 1 = right behind barriers 1 / 4, ahead of the interior
+// pass of B / D; 0 = behind that pass, with the poll.  The granules a slab reads here were published by its neighbours
+// in the pointwise phases A / C, before THEIR barrier 1 / 4, so unlike in the forward kernel (whose publish is a stencil
+// result) they are on their way when this slab passes its own barrier, and the round trip runs
+// beside the interior pass instead of behind it.  Nothing else is requested between the two points (EA_S0 = 0, EA_S1 =
+// 2), so the order in which loads retire is what it was.  A slab that runs ahead of a neighbour asks too early and finds
+// old tags; its second pass then goes out at once, where the first one used to (EcHandoff::complete<EAGER>) - with the plan's nap
+// in front of it the early request LOSES (100x300, adjoint us per step: 8.16-8.36 without, 8.72-8.83 with the nap,
+// 7.86-7.92 without it).  The slab that runs behind - the one the others wait for - finds its granules landed.
+#ifndef EA_EARLY_REQUEST
+#define EA_EARLY_REQUEST 1
+#endif
 
 struct EaGroup {
     int cls;                                      // 0: none, 1: interior rows of the slab, 2: boundary rows
@@ -1192,7 +1208,9 @@ __global__ __launch_bounds__(kEcThreads) void el_cluster_adj(const EaParams p)
     X.init(p.xbuf, s, p.NW, w, R, PL, p.gp, p.ng, t, p.err, false, p.nap, fsz);
     const bool do_x = p.NW > 1 && !(kDbg(p) & 1);
     EcHandoff::Pending P;
-    auto complete = [&](unsigned epoch) { X.complete(P, epoch, [&](int off, float v) { (pln + fsz)[off] = v; }); };
+    auto complete = [&](unsigned epoch) {
+        X.complete<EA_EARLY_REQUEST != 0>(P, epoch, [&](int off, float v) { (pln + fsz)[off] = v; });
+    };
     // byte offset of a group inside a [nz][gp] plane (snapshots, materials)
     auto cell_bytes = [&](int jq, int gq) { return 4u * (unsigned)(jq * p.gp + 4 * gq); };
     const float *S_shot = p.S + (long long)s * 5 * ncell;           // step n: S_shot + (n - s_first) * s_step
@@ -1474,7 +1492,9 @@ __global__ __launch_bounds__(kEcThreads) void el_cluster_adj(const EaParams p)
         }
         if (p.grad_f != nullptr && w == 0) {               // inactive source taps: slab 0 writes their zeros
             if (zero_tap) (p.grad_f + ((long long)n * p.nshot + s) * p.nsrc)[t] = 0.f;
-            for (int e = t + kEcThreads; e < p.nsrc; e += kEcThreads)
+            // (rare paths here and at the receivers below start from an opaque thread index: their per-lane 64-bit
+            // addresses are then formed where they are used, not carried through the whole time loop)
+            for (int e = ec_opaque(t) + kEcThreads; e < p.nsrc; e += kEcThreads)
                 if (p.src_cell[(long long)s * p.nsrc + e] < 0) p.grad_f[((long long)n * p.nshot + s) * p.nsrc + e] = 0.f;
         }
         if (direct) {                                      // this step's adjoint sources: read after barrier 3
@@ -1492,6 +1512,7 @@ __global__ __launch_bounds__(kEcThreads) void el_cluster_adj(const EaParams p)
             for (int q = 0; q < NG; ++q)
                 if ((q == 0 ? EA_S0 : EA_S1) == 1) request_S(G[q], n);
         }
+        if (EA_EARLY_REQUEST && do_x) X.request(P, 0, it & 1);          // in flight during the interior pass
         // ---- B ----------------------------------------------------------------------------------------
 #pragma unroll
         for (int q = 0; q < NG; ++q) {
@@ -1500,7 +1521,7 @@ __global__ __launch_bounds__(kEcThreads) void el_cluster_adj(const EaParams p)
         }
         EC_STAMP(3);
         if (do_x) {
-            X.request(P, 0, it & 1);
+            if (!EA_EARLY_REQUEST) X.request(P, 0, it & 1);
             complete((unsigned)(2 * it + 1));
         }
         EC_STAMP(4);
@@ -1552,7 +1573,7 @@ __global__ __launch_bounds__(kEcThreads) void el_cluster_adj(const EaParams p)
                 }
             } else {
                 const int *lst = p.slab_list + ((long long)s * p.NW + w) * p.nrec;
-                for (int e = t; e < cnt; e += kEcThreads) {
+                for (int e = ec_opaque(t); e < cnt; e += kEcThreads) {
                     const int id = lst[e];
                     const int cell = p.rec_cell[(long long)s * p.nrec + id];
                     const int i0 = cell / p.nx, i1 = cell - i0 * p.nx;
@@ -1595,6 +1616,7 @@ __global__ __launch_bounds__(kEcThreads) void el_cluster_adj(const EaParams p)
         EC_STAMP(9);
         __syncthreads();                                   // 4: D planes complete on the own rows
         EC_STAMP(10);
+        if (EA_EARLY_REQUEST && do_x) X.request(P, 1, it & 1);
         // ---- D ----------------------------------------------------------------------------------------
 #pragma unroll
         for (int q = 0; q < NG; ++q) {
@@ -1603,7 +1625,7 @@ __global__ __launch_bounds__(kEcThreads) void el_cluster_adj(const EaParams p)
         }
         EC_STAMP(11);
         if (do_x) {
-            X.request(P, 1, it & 1);
+            if (!EA_EARLY_REQUEST) X.request(P, 1, it & 1);
             complete((unsigned)(2 * it + 2));
         }
         EC_STAMP(12);

@@ -8,8 +8,9 @@ NAMES = ["V interior", "poll S halo", "wait barrier A", "V boundary", "wait barr
          "receivers", "wait barrier C", "S boundary", "wait barrier D"]
 NAMES_AC = ["sampling", "interior slots", "poll halo", "wait barrier A", "slot 0 (boundary rows)", "wait barrier B",
             "adjoint: inject + image", "publish", "snapshots + prefetch", "collective check"]
-NAMES_ADJ = ["A: E + publish", "wait barrier 1", "B interior", "poll E halo", "wait barrier 2", "B boundary",
-             "wait barrier 3", "receivers", "C: D + publish + grad", "wait barrier 4", "D interior", "poll D halo",
+# the adjoint asks for a hand-off's granules at the head of the interior pass and examines them in the poll
+NAMES_ADJ = ["A: E + publish", "wait barrier 1", "ask E + B interior", "poll E halo", "wait barrier 2", "B boundary",
+             "wait barrier 3", "receivers", "C: D + publish + grad", "wait barrier 4", "ask D + D interior", "poll D halo",
              "request S", "wait barrier 5", "D boundary"]
 
 
