@@ -19,12 +19,10 @@
 //     same launch (it reads the field the step only reads), so a step is ONE launch.
 // The arithmetic is the same explicit fmaf chain as oracle/acoustic.c (compile with
 // -ffp-contract=off) so wavefields can be compared bitwise.
-#include "mifwi_common.h"
+#include "mifwi_cluster_host.h"
 
 #include <atomic>
 
-#include <type_traits>
-#include <vector>
 
 #include <algorithm>
 #include <cmath>
@@ -1228,7 +1226,7 @@ struct mifwi_acoustic_plan {
     long long shot_stride, field_elems, coef_elems;
     // cluster path (LDS-resident time loop), 0 when the shot does not fit
     int cluster, NW, PL, cl_shots, cl_lds, rt;
-    long long xbuf_elems, list_elems;      // in floats
+    long long xbuf_elems, list_elems, xcc_elems;      // in floats
     // second-order C-PML (desc.cpml_width > 0; one launch per step family only)
     int pmlW;
     long long pml_persist, pml_scratch, zq_elems;      // floats, all shots: memory variables | scratch + e | zero q0, q1
@@ -1271,11 +1269,7 @@ void launch_step(const mifwi_acoustic_plan *pl, const AcParams &p, hipStream_t s
     }
 }
 
-int env_int(const char *name, int dflt)
-{
-    const char *v = getenv(name);
-    return (v && *v) ? atoi(v) : dflt;
-}
+using mifwi::env_int;
 
 AcParams base_params(const mifwi_acoustic_plan *pl, const float *r, const float *q0,
                      const float *q1)
@@ -1324,11 +1318,33 @@ void pml_step(const AcPml &m0, const float *cur, int shot0, int count, bool adjo
     }
 }
 
+// ---- the work buffer ---------------------------------------------------------------------------------
+// Offsets (in floats) of its regions, for a forward / Born call or for a backward call:
+//   [ua | ub | pml_persist | acc | pml_scratch | zq | bbox | xbuf | lists | backup]
+// The two time levels, the C-PML's memory variables and one gradient accumulator per shot group (backward only) are the
+// `state`: what a call hands to the call that resumes it, what MIFWI_ZERO_STATE zeroes and what a rolled-back single-launch
+// attempt gets back from `backup`.  pml_scratch (+ e) and zq (zero q0, q1): C-PML plans; xbuf (hand-off buffer), lists
+// (receivers per slab) and backup: single-launch plans.  Every region starts on a 16-byte boundary.
+struct AcWork { long long ua, ub, pml_persist, acc, pml_scratch, zq, bbox, xbuf, lists, backup, state, total; };
+AcWork work_map(const mifwi_acoustic_plan *pl, bool backward)
+{
+    AcWork m;
+    m.ua = 0; m.ub = pl->field_elems; m.pml_persist = 2 * pl->field_elems;
+    m.acc = m.pml_persist + pl->pml_persist;
+    m.state = m.acc + (backward ? pl->ngroups * pl->coef_elems : 0);
+    m.pml_scratch = m.state; m.zq = m.pml_scratch + pl->pml_scratch; m.bbox = m.zq + pl->zq_elems;
+    m.xbuf = m.bbox + mifwi::round_up64(4LL * pl->d.nshot, 64);
+    m.lists = m.xbuf + (pl->cluster ? pl->xbuf_elems : 0);
+    m.backup = m.lists + (pl->cluster ? pl->list_elems : 0);
+    m.total = m.backup + (pl->cluster ? m.state : 0);
+    return m;
+}
+
 // ---- cluster path helpers --------------------------------------------------------------------------
 void cluster_setup(mifwi_acoustic_plan *pl)
 {
     pl->cluster = 0; pl->NW = 0; pl->PL = 4 * (pl->ng + 2); pl->cl_shots = 0; pl->cl_lds = 0; pl->rt = 0;
-    pl->xbuf_elems = 0; pl->list_elems = 0;
+    pl->xbuf_elems = 0; pl->list_elems = 0; pl->xcc_elems = 0;
     if (env_int("MIFWI_AC_CLUSTER", 1) == 0 || pl->d.ntap != 1) return;
     if (pl->pmlW > 0 && env_int("MIFWI_AC_CLUSTER_PML", 1) == 0) return;
     int ncu = 0;
@@ -1391,8 +1407,8 @@ void cluster_setup(mifwi_acoustic_plan *pl)
     }
     if (!pl->cluster) return;
     // granules, the XCC_ID table of mifwi::same_xcd ([nshot][NW] ints), the block of the error word
-    pl->xbuf_elems = mifwi::round_up64(2LL * pl->d.nshot * pl->NW * 8 * pl->gp, 64) +
-                     mifwi::round_up64((long long)pl->d.nshot * pl->NW, 64) + 64;
+    pl->xcc_elems = mifwi::handoff_xcc_elems(pl->d.nshot, pl->NW);
+    pl->xbuf_elems = mifwi::handoff_elems(2LL * pl->d.nshot * pl->NW * 8 * pl->gp, pl->xcc_elems);
     pl->list_elems = mifwi::round_up64((long long)pl->d.nshot * pl->NW * (1 + (long long)pl->d.nrec), 64);
     // 28 function attributes: once per device and process, not once per plan (a plan is created on every propagate call)
     static std::atomic<unsigned> attr_done{0};
@@ -1422,7 +1438,7 @@ void cluster_setup(mifwi_acoustic_plan *pl)
 }
 
 ClParams cluster_params(const mifwi_acoustic_plan *pl, const float *r, const float *q0, const float *q1,
-                        float *ua, float *ub, float *xbuf)
+                        float *ua, float *ub, const mifwi::Handoff &h)
 {
     ClParams c;
     memset(&c, 0, sizeof(c));
@@ -1431,13 +1447,10 @@ ClParams cluster_params(const mifwi_acoustic_plan *pl, const float *r, const flo
     c.nt = pl->d.nt; c.c0 = pl->d.c0; c.c1 = pl->d.c1; c.r = r; c.q0 = q0; c.q1 = q1;
     c.ua = ua; c.ub = ub;
     c.nsrc = pl->d.nsrc; c.ntap = 1; c.nrec = pl->d.nrec;
-    c.xbuf = reinterpret_cast<unsigned long long *>(xbuf);
-    c.err = reinterpret_cast<int *>(xbuf + pl->xbuf_elems - 64);
-    c.xcc_tab = reinterpret_cast<int *>(xbuf + pl->xbuf_elems - 64 - mifwi::round_up64((long long)pl->d.nshot * pl->NW, 64));
+    c.xbuf = h.granules; c.err = h.err; c.xcc_tab = h.xcc_tab;
     c.dbg = env_int("MIFWI_AC_CL_DBG", 0);
     c.rcv_plain = env_int("MIFWI_AC_ADJ_PLAIN", 1);
-    // fat slabs nap long between poll passes, thin ones short (mifwi::poll_nap)
-    c.nap = env_int("MIFWI_POLL_NAP", mifwi::ceil_div(pl->d.n0, pl->NW) >= 16 ? 48 : 1);
+    c.nap = mifwi::poll_nap_default(mifwi::ceil_div(pl->d.n0, pl->NW), 16);
     c.pml_lds_floats = env_int("MIFWI_AC_PML_LDS", 1) ? pl->cl_lds / (int)sizeof(float) : 0;      // 0: every layer array through global memory
     // tests: pretend the launch has this many KB less LDS, so that pml_place keeps only a prefix of its list in LDS (every
     // partial placement must give the same bits)
@@ -1447,20 +1460,10 @@ ClParams cluster_params(const mifwi_acoustic_plan *pl, const float *r, const flo
     return c;
 }
 
+// the kernels of one single-launch attempt over the shot batches (AG: granules published at agent scope)
 template <int MODE, bool AG>
-int cluster_attempt(const mifwi_acoustic_plan *pl, ClParams c, float *xbuf, hipStream_t st)
+void cluster_launch(const mifwi_acoustic_plan *pl, ClParams c, hipStream_t st)
 {
-    if (mifwi::fake_timeout() == 1) return mifwi::kClusterTimedOut;
-    MIFWI_HIP_TRY(hipMemsetAsync(xbuf, 0, sizeof(float) * pl->xbuf_elems, st));
-#ifdef MIFWI_ABLATIONS
-    // MIFWI_AC_CL_TRACE=<file>: phase time stamps (CL_STAMP) of one workgroup, steps 64..127, appended as text
-    const char *trace_path = getenv("MIFWI_AC_CL_TRACE");
-    const size_t trace_n = 64 * 16 * 16;
-    if (trace_path && *trace_path) {
-        MIFWI_HIP_TRY(hipMalloc(&c.trace, trace_n * sizeof(long long)));
-        MIFWI_HIP_TRY(hipMemsetAsync(c.trace, 0, trace_n * sizeof(long long), st));
-    }
-#endif
     for (int s0 = 0; s0 < pl->d.nshot; s0 += pl->cl_shots) {
         c.shot0 = s0;
         c.shot1 = std::min(pl->d.nshot, s0 + pl->cl_shots);
@@ -1479,62 +1482,21 @@ int cluster_attempt(const mifwi_acoustic_plan *pl, ClParams c, float *xbuf, hipS
         if (general) hipLaunchKernelGGL((ac_cluster<MODE, true, AG>), grid, block, pl->cl_lds, st, c);
         else hipLaunchKernelGGL((ac_cluster<MODE, false, AG>), grid, block, pl->cl_lds, st, c);
     }
-    MIFWI_HIP_TRY(hipGetLastError());
-    int err[4] = {0, 0, 0, 0};
-    MIFWI_HIP_TRY(hipMemcpyAsync(err, c.err, sizeof(err), hipMemcpyDeviceToHost, st));
-    MIFWI_HIP_TRY(hipStreamSynchronize(st));
-#ifdef MIFWI_ABLATIONS
-    if (c.trace) {
-        std::vector<long long> h(trace_n);
-        MIFWI_HIP_TRY(hipMemcpy(h.data(), c.trace, trace_n * sizeof(long long), hipMemcpyDeviceToHost));
-        MIFWI_HIP_TRY(hipFree(c.trace));
-        if (FILE *fp = fopen(trace_path, "a")) {
-            fprintf(fp, "# ac_cluster mode=%d waves=16\n", MODE);
-            for (size_t i = 0; i < trace_n; i += 16) {
-                for (int k = 0; k < 16; ++k) fprintf(fp, "%lld ", h[i + k]);
-                fprintf(fp, "\n");
-            }
-            fclose(fp);
-        }
-    }
-#endif
-    const int verdict = mifwi::cluster_verdict(err, "acoustic");
-    return mifwi::fake_timeout() == 2 ? mifwi::kClusterTimedOut : verdict;
 }
 
-int cluster_restore(float *work, long long state_elems, const float *backup, int32_t flags, hipStream_t st);
-
-// The single-launch time loop with its middle tier: a failed placement check (the slabs of a shot were not dealt to one
-// XCD) restores the state and repeats the launch with granules published through the fabric; what comes back is OK,
-// an error, or kClusterTimedOut (the caller then restores the state and runs one launch per step).
+// mifwi::cluster_ladder over ac_cluster<MODE>: MIFWI_OK (range done), mifwi::kClusterFellBack (state restored: run one
+// launch per step) or an error
 template <int MODE>
-int cluster_run(const mifwi_acoustic_plan *pl, ClParams c, float *xbuf, hipStream_t st, float *work, long long state_elems,
-                const float *backup, int32_t flags)
+int cluster_run(const char *what, const mifwi_acoustic_plan *pl, const ClParams &c0, const mifwi::Handoff &h, hipStream_t st,
+                float *work, const AcWork &m, int32_t flags)
 {
-    int rc = cluster_attempt<MODE, false>(pl, c, xbuf, st);
-    if (rc != mifwi::kClusterMisplaced) return rc;
-    mifwi::note_agent_tier("acoustic");
-    rc = cluster_restore(work, state_elems, backup, flags, st);
-    if (rc) return rc;
-    rc = cluster_attempt<MODE, true>(pl, c, xbuf, st);
-    return rc == mifwi::kClusterMisplaced ? mifwi::kClusterTimedOut : rc;
-}
-
-// A single-launch attempt may time out (some workgroup was not resident in time) after it has advanced the state by
-// an unknown number of steps.  A call that starts from the zero state is simply zeroed again; a resumed call (time
-// checkpointing) keeps a copy of its input state behind the work buffer's other regions and gets it back.  Either
-// way the per-step family then runs the range.
-int cluster_backup(float *work, long long state_elems, float *backup, int32_t flags, hipStream_t st)
-{
-    if (flags & MIFWI_ZERO_STATE) return MIFWI_OK;
-    MIFWI_HIP_TRY(hipMemcpyAsync(backup, work, sizeof(float) * state_elems, hipMemcpyDeviceToDevice, st));
-    return MIFWI_OK;
-}
-int cluster_restore(float *work, long long state_elems, const float *backup, int32_t flags, hipStream_t st)
-{
-    if (flags & MIFWI_ZERO_STATE) MIFWI_HIP_TRY(hipMemsetAsync(work, 0, sizeof(float) * state_elems, st));
-    else MIFWI_HIP_TRY(hipMemcpyAsync(work, backup, sizeof(float) * state_elems, hipMemcpyDeviceToDevice, st));
-    return MIFWI_OK;
+    const mifwi::TraceSpec ts = {"MIFWI_AC_CL_TRACE", 64 * 16 * 16, "# ac_cluster mode=%d waves=16", MODE, 0};
+    return mifwi::cluster_ladder(what, work, m.state, work + m.backup, flags, st, h, ts, [&](bool agent, long long *trace) {
+        ClParams c = c0;
+        mifwi::set_trace(c, trace);
+        if (agent) cluster_launch<MODE, true>(pl, c, st);
+        else cluster_launch<MODE, false>(pl, c, st);
+    });
 }
 
 }  // namespace
@@ -1671,14 +1633,10 @@ int mifwi_acoustic_plan_layout(const mifwi_acoustic_plan *pl, mifwi_acoustic_lay
     out->shots_per_group = pl->gs;
     out->field_elems = pl->field_elems;
     out->coef_elems = pl->coef_elems;
-    const long long bbox = mifwi::round_up64(4LL * pl->d.nshot, 64);
-    const long long cl = pl->cluster ? pl->xbuf_elems + pl->list_elems : 0;
-    // single-launch plans: room for a copy of the input state of a resumed call (cluster_backup)
-    const long long pml = pl->pml_persist + pl->pml_scratch + pl->zq_elems;
-    out->work_forward_elems = 2 * pl->field_elems + pml + bbox + cl + (pl->cluster ? 2 * pl->field_elems + pl->pml_persist : 0);
-    out->work_backward_elems = 2 * pl->field_elems + pl->ngroups * pl->coef_elems + pml + bbox + cl +
-                               (pl->cluster ? 2 * pl->field_elems + pl->pml_persist + pl->ngroups * pl->coef_elems : 0);
-    out->state_elems = 2 * pl->field_elems + pl->pml_persist;
+    const AcWork fwd = work_map(pl, false);
+    out->work_forward_elems = fwd.total;
+    out->work_backward_elems = work_map(pl, true).total;
+    out->state_elems = fwd.state;
     return MIFWI_OK;
 }
 
@@ -1700,13 +1658,12 @@ int mifwi_acoustic_forward(mifwi_acoustic_plan *pl, const float *r, const float 
     if (rc) return rc;
     MIFWI_HIP_TRY(hipSetDevice(pl->device));
     hipStream_t st = (hipStream_t)stream;
-    float *ua = work, *ub = work + pl->field_elems;
-    // C-PML plans: [ua | ub | memory variables | scratch + e | zero q0, q1 | bbox]; q0 / q1 carry the a, b profiles
-    float *pml_persist = work + 2 * pl->field_elems, *pml_scratch = pml_persist + pl->pml_persist;
-    float *zq = pml_scratch + pl->pml_scratch;
-    int *bbox = reinterpret_cast<int *>(zq + pl->zq_elems);
-    if (flags & MIFWI_ZERO_STATE)
-        MIFWI_HIP_TRY(hipMemsetAsync(work, 0, sizeof(float) * (2 * pl->field_elems + pl->pml_persist), st));
+    const AcWork m = work_map(pl, false);
+    float *ua = work + m.ua, *ub = work + m.ub;
+    float *pml_persist = work + m.pml_persist, *pml_scratch = work + m.pml_scratch;
+    float *zq = work + m.zq;                                    // C-PML plans: q0 / q1 carry the a, b profiles
+    int *bbox = reinterpret_cast<int *>(work + m.bbox);
+    if (flags & MIFWI_ZERO_STATE) MIFWI_HIP_TRY(hipMemsetAsync(work, 0, sizeof(float) * m.state, st));
     AcPml pm;
     memset(&pm, 0, sizeof(pm));
     if (pl->pmlW > 0) {
@@ -1725,23 +1682,16 @@ int mifwi_acoustic_forward(mifwi_acoustic_plan *pl, const float *r, const float 
     p.smp_cell = rec_cell; p.smp_w = rec_w;
     const long long snap_step = (long long)d.nshot * pl->coef_elems;
     if (pl->cluster && n_end > n_begin) {
-        float *xbuf = reinterpret_cast<float *>(bbox) + mifwi::round_up64(4LL * d.nshot, 64);
-        ClParams c = cluster_params(pl, r, q0, q1, ua, ub, xbuf);
+        const mifwi::Handoff h = mifwi::cluster_handoff(pl, work, m);
+        ClParams c = cluster_params(pl, r, q0, q1, ua, ub, h);
         c.n_first = n_begin; c.n_last = n_end;
         c.src_cell = src_cell; c.src_w = src_w; c.f = f;
         c.rec_cell = rec_cell; c.rec_w = rec_w; c.rec_out = (rec_out && d.nrec > 0) ? rec_out : nullptr;
         c.G = snap; c.g_first = n_begin; c.g_step = snap_step;
         c.pml = pm;
-        const long long fstate = 2 * pl->field_elems + pl->pml_persist;       // fields + the layer's memory variables
-        float *backup = xbuf + pl->xbuf_elems + pl->list_elems;
-        rc = cluster_backup(work, fstate, backup, flags, st);
-        if (rc) return rc;
-        rc = snap ? cluster_run<1>(pl, c, xbuf, st, work, fstate, backup, flags)
-                  : cluster_run<0>(pl, c, xbuf, st, work, fstate, backup, flags);
-        if (rc != mifwi::kClusterTimedOut) return rc;
-        mifwi::note_fallback("acoustic");
-        rc = cluster_restore(work, fstate, backup, flags, st);
-        if (rc) return rc;
+        rc = snap ? cluster_run<1>("acoustic forward", pl, c, h, st, work, m, flags)
+                  : cluster_run<0>("acoustic forward", pl, c, h, st, work, m, flags);
+        if (rc != mifwi::kClusterFellBack) return rc;
     }
     // shot groups are independent: a few at a time keep wavefields and model inside the Infinity Cache
     for (int g0 = 0; g0 < pl->ngroups; g0 += pl->pass_fwd)
@@ -1780,11 +1730,11 @@ int mifwi_acoustic_born(mifwi_acoustic_plan *pl, const float *r, const float *q0
     if (rc) return rc;
     MIFWI_HIP_TRY(hipSetDevice(pl->device));
     hipStream_t st = (hipStream_t)stream;
-    float *ua = work, *ub = work + pl->field_elems;
-    float *pml_persist = work + 2 * pl->field_elems, *pml_scratch = pml_persist + pl->pml_persist;
-    float *zq = pml_scratch + pl->pml_scratch;
-    if (flags & MIFWI_ZERO_STATE)
-        MIFWI_HIP_TRY(hipMemsetAsync(work, 0, sizeof(float) * (2 * pl->field_elems + pl->pml_persist), st));
+    const AcWork m = work_map(pl, false);
+    float *ua = work + m.ua, *ub = work + m.ub;
+    float *pml_persist = work + m.pml_persist, *pml_scratch = work + m.pml_scratch;
+    float *zq = work + m.zq;
+    if (flags & MIFWI_ZERO_STATE) MIFWI_HIP_TRY(hipMemsetAsync(work, 0, sizeof(float) * m.state, st));
     AcPml pm;
     memset(&pm, 0, sizeof(pm));
     if (pl->pmlW > 0) {
@@ -1794,21 +1744,15 @@ int mifwi_acoustic_born(mifwi_acoustic_plan *pl, const float *r, const float *q0
     }
     const long long snap_step = (long long)d.nshot * pl->coef_elems;
     if (pl->cluster && pl->pmlW == 0 && n_end > n_begin) {          // (the Born pass of a C-PML plan runs one launch per step)
-        float *xbuf = zq + pl->zq_elems + mifwi::round_up64(4LL * d.nshot, 64);
-        ClParams c = cluster_params(pl, r, q0, q1, ua, ub, xbuf);
+        const mifwi::Handoff h = mifwi::cluster_handoff(pl, work, m);
+        ClParams c = cluster_params(pl, r, q0, q1, ua, ub, h);
         c.n_first = n_begin; c.n_last = n_end;
         c.nsrc = 0; c.src_cell = nullptr; c.src_w = nullptr; c.f = nullptr;      // no point source
         c.rec_cell = rec_cell; c.rec_w = rec_w; c.rec_out = d.nrec > 0 ? drec_out : nullptr;
         c.G = const_cast<float *>(snap); c.g_first = snap_first; c.g_step = snap_step;
         c.born_dr = dr;
-        float *backup = xbuf + pl->xbuf_elems + pl->list_elems;
-        rc = cluster_backup(work, 2 * pl->field_elems, backup, flags, st);
-        if (rc) return rc;
-        rc = cluster_run<3>(pl, c, xbuf, st, work, 2 * pl->field_elems, backup, flags);
-        if (rc != mifwi::kClusterTimedOut) return rc;
-        mifwi::note_fallback("acoustic");
-        rc = cluster_restore(work, 2 * pl->field_elems, backup, flags, st);
-        if (rc) return rc;
+        rc = cluster_run<3>("acoustic Born", pl, c, h, st, work, m, flags);      // (no layer here: the state is the two fields)
+        if (rc != mifwi::kClusterFellBack) return rc;
     }
     AcParams p = base_params(pl, r, q0, q1);
     p.ninj = 0;
@@ -1849,16 +1793,12 @@ int mifwi_acoustic_backward(mifwi_acoustic_plan *pl, const float *r, const float
     if (rc) return rc;
     MIFWI_HIP_TRY(hipSetDevice(pl->device));
     hipStream_t st = (hipStream_t)stream;
-    float *za = work, *zb = work + pl->field_elems;
-    // C-PML plans: [za | zb | adjoint memory variables | acc | scratch + e | zero q0, q1 | bbox]
-    float *pml_persist = work + 2 * pl->field_elems;
-    float *acc = pml_persist + pl->pml_persist;
-    float *pml_scratch = acc + (long long)pl->ngroups * pl->coef_elems;
-    float *zq = pml_scratch + pl->pml_scratch;
-    int *bbox = reinterpret_cast<int *>(zq + pl->zq_elems);
-    if (flags & MIFWI_ZERO_STATE)
-        MIFWI_HIP_TRY(hipMemsetAsync(
-            work, 0, sizeof(float) * (2 * pl->field_elems + pl->pml_persist + pl->ngroups * pl->coef_elems), st));
+    const AcWork m = work_map(pl, true);
+    float *za = work + m.ua, *zb = work + m.ub;
+    float *pml_persist = work + m.pml_persist;                  // C-PML plans: the adjoint memory variables
+    float *acc = work + m.acc, *pml_scratch = work + m.pml_scratch, *zq = work + m.zq;
+    int *bbox = reinterpret_cast<int *>(work + m.bbox);
+    if (flags & MIFWI_ZERO_STATE) MIFWI_HIP_TRY(hipMemsetAsync(work, 0, sizeof(float) * m.state, st));
     AcPml pm;
     memset(&pm, 0, sizeof(pm));
     if (pl->pmlW > 0) {
@@ -1881,11 +1821,11 @@ int mifwi_acoustic_backward(mifwi_acoustic_plan *pl, const float *r, const float
     // Buffer parity is absolute in k so that a range can be resumed by a later call.
     bool per_step = true;
     if (pl->cluster && k_hi >= k_lo) {
-        float *xbuf = reinterpret_cast<float *>(bbox) + mifwi::round_up64(4LL * d.nshot, 64);
-        int *lists = reinterpret_cast<int *>(xbuf + pl->xbuf_elems);
+        const mifwi::Handoff h = mifwi::cluster_handoff(pl, work, m);
+        int *lists = reinterpret_cast<int *>(work + m.lists);
         hipLaunchKernelGGL(cl_build_slab_lists, dim3(d.nshot), dim3(256), 0, st, rec_cell, d.nrec, d.n0, d.n1,
                            pl->NW, pl->rt, lists, lists + (long long)d.nshot * pl->NW);
-        ClParams c = cluster_params(pl, r, q0, q1, za, zb, xbuf);
+        ClParams c = cluster_params(pl, r, q0, q1, za, zb, h);
         c.n_first = k_hi; c.n_last = k_lo;
         c.src_cell = src_cell; c.src_w = src_w;
         c.rec_cell = rec_cell; c.rec_w = rec_w; c.grad_rec = grad_rec;
@@ -1894,19 +1834,9 @@ int mifwi_acoustic_backward(mifwi_acoustic_plan *pl, const float *r, const float
         c.acc = acc;
         c.slab_cnt = lists; c.slab_list = lists + (long long)d.nshot * pl->NW;
         c.pml = pm;
-        const long long state = 2 * pl->field_elems + pl->pml_persist + pl->ngroups * pl->coef_elems;     // adjoint fields (+ layer) + accumulators
-        float *backup = reinterpret_cast<float *>(lists) + pl->list_elems;
-        rc = cluster_backup(work, state, backup, flags, st);
-        if (rc) return rc;
-        rc = cluster_run<2>(pl, c, xbuf, st, work, state, backup, flags);
-        if (rc == mifwi::kClusterTimedOut) {
-            mifwi::note_fallback("acoustic");
-            rc = cluster_restore(work, state, backup, flags, st);
-            if (rc) return rc;
-        } else {
-            if (rc) return rc;
-            per_step = false;
-        }
+        rc = cluster_run<2>("acoustic adjoint", pl, c, h, st, work, m, flags);
+        if (rc != MIFWI_OK && rc != mifwi::kClusterFellBack) return rc;
+        per_step = rc == mifwi::kClusterFellBack;
     }
     for (int g0 = 0; per_step && g0 < pl->ngroups; g0 += pl->pass_adj)
     for (int k = k_hi; k >= k_lo; --k) {

@@ -24,9 +24,7 @@
 // the whole time loop in one launch instead (mifwi_elastic_cluster.h); point forces (source_type 1 / 2) and
 // the opt-in fused V+S launch (el_step_fused) live on the per-step path only.
 // Arithmetic = the explicit fmaf chain of oracle/elastic.c (build with -ffp-contract=off).
-#include "mifwi_common.h"
-
-#include <vector>
+#include "mifwi_cluster_host.h"
 
 #include <algorithm>
 #include <cmath>
@@ -1145,11 +1143,7 @@ __global__ void el_finalize(const float *acc, int ngroups, int nz, int gp, long 
 
 #include "mifwi_elastic_cluster.h"
 
-int env_int(const char *name, int dflt)
-{
-    const char *v = getenv(name);
-    return (v && *v) ? atoi(v) : dflt;
-}
+using mifwi::env_int;
 
 }  // namespace
 
@@ -1170,6 +1164,7 @@ struct mifwi_elastic_plan {
     int fused;             // forward V+S in one launch (second copy of the state in the work buffer)
     int fused_pass_shots;  // shots per pass of the fused forward (both copies of the state in the Infinity Cache)
     long long field_stride, shot_stride, fields_elems, psix_elems, psiz_elems, coef_elems;
+    long long psix_shot, psiz_shot;        // memory variables of one shot: x strips, z strips
     long long psi_elems;  // psix+psiz rounded up to 64
     // cluster path (LDS-resident time loop); 0 when a shot does not fit
     int cluster, NW, PL, fwd_PL, adj_PL, cl_shots, cl_lds, cl_ng;
@@ -1191,7 +1186,7 @@ ElParams el_base(const mifwi_elastic_plan *pl, const float *mat, const float *pz
     p.nshot = pl->d.nshot; p.gs = 1;
     p.W = pl->W; p.wl = pl->wl; p.xr0 = pl->xr0; p.wx = pl->wx;
     p.fsurf = pl->d.free_surface;
-    p.psix_shot = 4LL * pl->d.nz * pl->wx; p.psiz_shot = 4LL * 2 * pl->W * pl->gp;
+    p.psix_shot = pl->psix_shot; p.psiz_shot = pl->psiz_shot;
     p.mat = mat; p.pz = pz; p.px = px;
     p.xcd = pl->xcd;
     p.snap_shot = pl->snap_shot;
@@ -1231,6 +1226,53 @@ void launch_s(const mifwi_elastic_plan *pl, const ElParams &p0, int nshot, hipSt
     }
 }
 
+// Slab count (both loops): cost of a step ~ fixed part (barriers, two hand-off flights) + groups per
+// thread, times the launches the shot batch needs (measured on 100x300: 6 shots 8.7 us at 8 slabs,
+// 7.2 us at 20).  Few shots -> many thin slabs; a full batch -> the fewest slabs that fit.
+// lds_of(slabs, rows of the tallest, LDS row pitch): the loop's dynamic LDS in bytes, which must stay within `limit`;
+// where the wide (skewed) pitch does not fit a slab height, the plain one is tried.  NW == 0: nothing fits.
+struct SlabChoice { int NW, shots, lds, PL, ng; };
+template <class LdsOf>
+SlabChoice slab_search(const mifwi_elastic_plan *pl, int ncu, int forced, int PL_wide, int PL_plain, long long limit, LdsOf lds_of)
+{
+    SlabChoice best{0, 0, 0, 0, 0};
+    double best_cost = 1e30;
+    for (int nw = 1; nw <= 32; ++nw) {
+        if (forced > 0 && nw != forced) continue;
+        if (pl->d.nz / nw < 4) break;
+        const int rows = mifwi::ceil_div(pl->d.nz, nw);
+        int PLq = PL_wide;
+        long long lds = lds_of(nw, rows, PLq);
+        if (lds > limit && PLq != PL_plain) {          // the wider rows do not fit this slab height: plain pitch
+            PLq = PL_plain;
+            lds = lds_of(nw, rows, PLq);
+        }
+        if (lds > limit) continue;
+        if ((long long)rows * pl->ng > 2 * kEcThreads || kEcRowFields * pl->gp > kEcGr * kEcThreads) continue;
+        const int per_launch = 8 * (ncu / (8 * nw));
+        if (per_launch < 8) break;
+        const double cost = mifwi::ceil_div(pl->d.nshot, per_launch) * (4.8 + (double)rows * pl->ng / kEcThreads);
+        if (cost < best_cost - 1e-9) {
+            best_cost = cost;
+            best = {nw, per_launch, (int)lds, PLq, mifwi::ceil_div(rows * pl->ng, kEcThreads)};
+        }
+    }
+    return best;
+}
+// LDS rows the adjoint loop reserves for the z-strip memory variables: the most C-PML rows any slab holds
+int ea_zrows_max(const mifwi_elastic_plan *pl, int nw)
+{
+    int zmax = 0;
+    for (int w = 0; w < nw && pl->W > 0; ++w) {
+        int r0, R;
+        ec_slab_rows(pl->d.nz, nw, w, r0, R);
+        const int ntop = std::max(0, std::min(r0 + R, pl->W) - r0);
+        const int nbot = std::max(0, r0 + R - std::max(r0, pl->d.nz - pl->W));
+        zmax = std::max(zmax, ntop + nbot);
+    }
+    return zmax;
+}
+
 void el_cluster_setup(mifwi_elastic_plan *pl)
 {
     pl->cluster = 0; pl->NW = 0; pl->PL = 4 * (pl->ng + 2); pl->cl_shots = 0;
@@ -1258,30 +1300,12 @@ void el_cluster_setup(mifwi_elastic_plan *pl)
     int ncu = 0;
     if (hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, pl->device) != hipSuccess) return;
     const int forced = env_int("MIFWI_EL_NW", 0);
-    // Slab count (both loops): cost of a step ~ fixed part (barriers, two hand-off flights) + groups per
-    // thread, times the launches the shot batch needs (measured on 100x300: 6 shots 8.7 us at 8 slabs,
-    // 7.2 us at 20).  Few shots -> many thin slabs; a full batch -> the fewest slabs that fit.
-    double best = 1e30;
-    for (int nw = 1; nw <= 32 && want_fwd; ++nw) {
-        if (forced > 0 && nw != forced) continue;
-        const int rows = mifwi::ceil_div(pl->d.nz, nw);
-        if (pl->d.nz / nw < 4) break;
-        long long lds = (5LL * (rows + 4) * pl->PL + 6LL * pl->gp + 8LL * rows + 8) * sizeof(float);
-        int PLq = pl->PL;
-        if (lds > 150 * 1024 && pl->PL != PL_plain) {          // the wider rows do not fit this slab height: plain pitch
-            PLq = PL_plain;
-            lds = (5LL * (rows + 4) * PLq + 6LL * pl->gp + 8LL * rows + 8) * sizeof(float);
-        }
-        if (lds > 150 * 1024) continue;
-        if ((long long)rows * pl->ng > 2 * kEcThreads || kEcRowFields * pl->gp > kEcGr * kEcThreads) continue;
-        const int per_launch = 8 * (ncu / (8 * nw));
-        if (per_launch < 8) break;
-        const double cost = mifwi::ceil_div(pl->d.nshot, per_launch) * (4.8 + (double)rows * pl->ng / kEcThreads);
-        if (cost < best - 1e-9) {
-            best = cost;
-            pl->cluster = 1; pl->NW = nw; pl->cl_shots = per_launch; pl->cl_lds = (int)lds;
-            pl->cl_ng = mifwi::ceil_div(rows * pl->ng, kEcThreads);
-            pl->fwd_PL = PLq;
+    if (want_fwd) {
+        const SlabChoice f = slab_search(pl, ncu, forced, pl->PL, PL_plain, mifwi::kClusterLdsLimit, [&](int, int rows, int PLq) {
+            return (5LL * (rows + 4) * PLq + 6LL * pl->gp + 8LL * rows + 8) * (long long)sizeof(float);
+        });
+        if (f.NW > 0) {
+            pl->cluster = 1; pl->NW = f.NW; pl->cl_shots = f.shots; pl->cl_lds = f.lds; pl->cl_ng = f.ng; pl->fwd_PL = f.PL;
         }
     }
     // every slab's deal must suit the lane-shift form of the x-halo (ec_xhalo_deal_ok); MIFWI_EL_XHALO=0: plain LDS reads
@@ -1312,40 +1336,14 @@ void el_cluster_setup(mifwi_elastic_plan *pl)
     // asked for a group size)
     const int forced_adj = env_int("MIFWI_EL_ADJ_NW", forced);
     if (env_int("MIFWI_EL_CLUSTER_ADJ", 1) != 0 && pl->d.shots_per_group <= 0) {
-        double best_adj = 1e30;
-        const int adj_skewed = pl->adj_PL;             // the candidate pitch (MIFWI_EL_PL_SKEW bit 1); pl->adj_PL = what the chosen slabs use
-        for (int nw = 1; nw <= 32; ++nw) {
-            if (forced_adj > 0 && nw != forced_adj) continue;
-            if (pl->d.nz / nw < 4) break;
-            const int rows = mifwi::ceil_div(pl->d.nz, nw);
-            int zmax = 0;
-            for (int w = 0; w < nw && pl->W > 0; ++w) {
-                const int base = pl->d.nz / nw, rem = pl->d.nz - base * nw;
-                const int R = base + (w < rem ? 1 : 0), r0 = w * base + std::min(w, rem);
-                const int ntop = std::max(0, std::min(r0 + R, pl->W) - r0);
-                const int nbot = std::max(0, r0 + R - std::max(r0, pl->d.nz - pl->W));
-                zmax = std::max(zmax, ntop + nbot);
-            }
-            auto adj_lds = [&](int PLq) {
-                return (long long)((4LL * (rows + 4) * PLq + 6LL * pl->gp + 8LL * rows + 4LL * rows * pl->wx + 4LL * zmax * pl->gp +
-                                    (rows + 4) + 2LL * kEaRcvRows * PLq) * sizeof(float));   // + row map, receiver rows
-            };
-            int PLq = adj_skewed;
-            long long lds = adj_lds(PLq);
-            if (lds > kEaLdsLimit && PLq != PL_plain) {         // the wider rows do not fit this slab height: plain pitch
-                PLq = PL_plain;
-                lds = adj_lds(PLq);
-            }
-            if (lds > kEaLdsLimit) continue;
-            if ((long long)rows * pl->ng > 2 * kEcThreads || kEcRowFields * pl->gp > kEcGr * kEcThreads) continue;
-            const int per_launch = 8 * (ncu / (8 * nw));
-            if (per_launch < 8) break;
-            const double cost = mifwi::ceil_div(pl->d.nshot, per_launch) * (4.8 + (double)rows * pl->ng / kEcThreads);
-            if (cost < best_adj - 1e-9) {
-                best_adj = cost;
-                pl->cl_adj = 1; pl->adj_NW = nw; pl->adj_shots = per_launch; pl->adj_lds = (int)lds; pl->adj_PL = PLq;
-                pl->adj_ng = mifwi::ceil_div(rows * pl->ng, kEcThreads); pl->adj_zrows = zmax;
-            }
+        // (pl->adj_PL: the candidate pitch, MIFWI_EL_PL_SKEW bit 1, until the search says what the chosen slabs use)
+        const SlabChoice a = slab_search(pl, ncu, forced_adj, pl->adj_PL, PL_plain, kEaLdsLimit, [&](int nw, int rows, int PLq) {
+            return (4LL * (rows + 4) * PLq + 6LL * pl->gp + 8LL * rows + 4LL * rows * pl->wx + 4LL * ea_zrows_max(pl, nw) * pl->gp +
+                    (rows + 4) + 2LL * kEaRcvRows * PLq) * (long long)sizeof(float);   // + row map, receiver rows
+        });
+        if (a.NW > 0) {
+            pl->cl_adj = 1; pl->adj_NW = a.NW; pl->adj_shots = a.shots; pl->adj_lds = a.lds; pl->adj_PL = a.PL;
+            pl->adj_ng = a.ng; pl->adj_zrows = ea_zrows_max(pl, a.NW);
         }
         pl->adj_xh = pl->cl_adj ? xhalo_ok(pl->adj_NW, pl->adj_ng) : 0;
         if (pl->cl_adj)
@@ -1359,30 +1357,65 @@ void el_cluster_setup(mifwi_elastic_plan *pl)
     }
     const int nwmax = std::max(pl->cluster ? pl->NW : 0, pl->cl_adj ? pl->adj_NW : 0);
     // granules, the XCC_ID table of mifwi::same_xcd ([nshot][nwmax] ints) and the block of the error word
-    pl->xcc_elems = nwmax > 0 ? mifwi::round_up64((long long)pl->d.nshot * nwmax, 64) : 0;
+    pl->xcc_elems = nwmax > 0 ? mifwi::handoff_xcc_elems(pl->d.nshot, nwmax) : 0;
     if (nwmax > 0)
-        pl->xbuf_elems = mifwi::round_up64(2LL * pl->d.nshot * nwmax * 4 * kEcRowFields * pl->gp, 64) + pl->xcc_elems + 64;
+        pl->xbuf_elems = mifwi::handoff_elems(2LL * pl->d.nshot * nwmax * 4 * kEcRowFields * pl->gp, pl->xcc_elems);
     if (pl->cl_adj)
         pl->list_elems = mifwi::round_up64((long long)pl->d.nshot * pl->adj_NW * (1 + pl->d.nrec), 64);
 }
 
-template <bool SAVE, bool AG>
-int el_cluster_run(const mifwi_elastic_plan *pl, EcParams c, float *xbuf, hipStream_t st)
+// ---- the work buffer ---------------------------------------------------------------------------------
+// Offsets (in floats) of its regions.  Forward call:  [fields | psi | bbox | xbuf | backup]   or, fused plans,
+// [fields | psi | bbox | second];  backward call:  [fields | psi | psiB | acc | bbox | xbuf | lists | backup | tile].
+// fields, the C-PML memory variables (backward: two copies that ping-pong, absolute in n) and the gradient accumulators
+// (backward) are the `state`: what a call hands to the call that resumes it, what MIFWI_ZERO_STATE zeroes and what a
+// rolled-back single-launch attempt gets back from `backup`.  xbuf (hand-off buffer), lists (receivers per slab) and
+// backup exist only where the call's single-launch kernel does; tile: the per-tile receiver lists of el_adj_s.
+// second: the fused forward's other copy of the state.  It starts where xbuf does: a plan has one or the other (`fused`
+// needs `!cluster`), and the fused loop first touches it after a single-launch attempt has been given up and rolled
+// back, when nobody reads xbuf or backup any more; `total` counts room for both all the same.
+struct ElWork { long long fields, psi, psiB, acc, bbox, xbuf, lists, backup, second, tile, state, total; };
+ElWork work_map(const mifwi_elastic_plan *pl, bool backward)
 {
-    if (mifwi::fake_timeout() == 1) return mifwi::kClusterTimedOut;
-    MIFWI_HIP_TRY(hipMemsetAsync(xbuf, 0, sizeof(float) * pl->xbuf_elems, st));
-    c.xbuf = reinterpret_cast<unsigned long long *>(xbuf);
-    c.err = reinterpret_cast<int *>(xbuf + pl->xbuf_elems - 64);
-    c.xcc_tab = reinterpret_cast<int *>(xbuf + pl->xbuf_elems - 64 - pl->xcc_elems);
-#ifdef MIFWI_ABLATIONS
-    // MIFWI_EL_CL_TRACE=<file>: phase time stamps (EC_STAMP) of one workgroup, steps 64..127, appended as text
-    const char *trace_path = getenv("MIFWI_EL_CL_TRACE");
-    const size_t trace_n = 64 * 8 * 16;
-    if (trace_path && *trace_path) {
-        MIFWI_HIP_TRY(hipMalloc(&c.trace, trace_n * sizeof(long long)));
-        MIFWI_HIP_TRY(hipMemsetAsync(c.trace, 0, trace_n * sizeof(long long), st));
-    }
-#endif
+    const bool single = backward ? pl->cl_adj : pl->cluster;
+    ElWork m;
+    m.fields = 0; m.psi = pl->fields_elems; m.psiB = m.psi + pl->psi_elems;
+    m.acc = backward ? m.psiB + pl->psi_elems : m.psiB;
+    m.state = m.acc + (backward ? 5LL * pl->ngroups * pl->splane : 0);      // accumulator planes: the snapshot planes' layout and size
+    m.bbox = m.state; m.xbuf = m.bbox + mifwi::round_up64(4LL * pl->d.nshot, 64);
+    m.lists = m.xbuf + (single ? pl->xbuf_elems : 0);
+    m.backup = m.lists + (single && backward ? pl->list_elems : 0);
+    m.second = m.xbuf; m.tile = m.backup + (single ? m.state : 0);
+    m.total = backward ? m.tile + pl->tile_elems : m.tile + (pl->fused ? m.state : 0);
+    return m;
+}
+
+// what EcParams and EaParams share: geometry, strides, layer, materials, stencil weights, hand-off buffer, knobs
+template <class Params>
+Params cluster_base(const mifwi_elastic_plan *pl, int NW, int PL, const float *mat, const float *pz, const float *px,
+                    const mifwi::Handoff &h)
+{
+    Params c;
+    memset(&c, 0, sizeof(c));
+    const mifwi_elastic_desc &d = pl->d;
+    c.nz = d.nz; c.nx = d.nx; c.ng = pl->ng; c.gp = pl->gp; c.pitch = pl->pitch;
+    c.field_stride = (unsigned)pl->field_stride; c.shot_stride = pl->shot_stride;
+    c.nshot = d.nshot; c.NW = NW; c.PL = PL;
+    c.W = pl->W; c.wl = pl->wl; c.xr0 = pl->xr0; c.wx = pl->wx; c.fsurf = d.free_surface;
+    c.psix_shot = pl->psix_shot; c.psiz_shot = pl->psiz_shot;
+    c.mat = mat; c.pz = pz; c.px = px;
+    c.nsrc = d.nsrc; c.nrec = d.nrec;
+    c.xbuf = h.granules; c.err = h.err; c.xcc_tab = h.xcc_tab;
+    c.dbg = env_int("MIFWI_EL_CL_DBG", 0);
+    c.nap = mifwi::poll_nap_default(mifwi::ceil_div(d.nz, NW), 8);
+    c.K = fd_weights(d.fd_order);
+    return c;
+}
+
+// the kernels of one single-launch attempt over the shot batches (AG / agent: granules published at agent scope)
+template <bool SAVE, bool AG>
+void el_cluster_launch(const mifwi_elastic_plan *pl, EcParams c, hipStream_t st)
+{
     for (int s0 = 0; s0 < pl->d.nshot; s0 += pl->cl_shots) {
         c.shot0 = s0;
         c.shot1 = std::min(pl->d.nshot, s0 + pl->cl_shots);
@@ -1398,43 +1431,22 @@ int el_cluster_run(const mifwi_elastic_plan *pl, EcParams c, float *xbuf, hipStr
         if (pl->cl_ng == 1) hipLaunchKernelGGL((el_cluster_fwd<SAVE, 1, AG>), grid, block, pl->cl_lds, st, c);
         else hipLaunchKernelGGL((el_cluster_fwd<SAVE, 2, AG>), grid, block, pl->cl_lds, st, c);
     }
-    MIFWI_HIP_TRY(hipGetLastError());
-    int err[4] = {0, 0, 0, 0};
-    MIFWI_HIP_TRY(hipMemcpyAsync(err, c.err, sizeof(err), hipMemcpyDeviceToHost, st));
-    MIFWI_HIP_TRY(hipStreamSynchronize(st));
-#ifdef MIFWI_ABLATIONS
-    if (c.trace) {
-        std::vector<long long> h(trace_n);
-        MIFWI_HIP_TRY(hipMemcpy(h.data(), c.trace, trace_n * sizeof(long long), hipMemcpyDeviceToHost));
-        MIFWI_HIP_TRY(hipFree(c.trace));
-        if (FILE *fp = fopen(trace_path, "a")) {
-            fprintf(fp, "# el_cluster_fwd save=%d steps=%d\n", SAVE ? 1 : 0, c.n_last - c.n_first);
-            for (size_t i = 0; i < trace_n; i += 16) {
-                for (int k = 0; k < 16; ++k) fprintf(fp, "%lld ", h[i + k]);
-                fprintf(fp, "\n");
-            }
-            fclose(fp);
+}
+void ea_cluster_launch(const mifwi_elastic_plan *pl, EaParams c, bool agent, hipStream_t st)
+{
+    for (int s0 = 0; s0 < pl->d.nshot; s0 += pl->adj_shots) {
+        c.shot0 = s0;
+        c.shot1 = std::min(pl->d.nshot, s0 + pl->adj_shots);
+        const dim3 grid(8 * pl->adj_NW * mifwi::ceil_div(c.shot1 - s0, 8)), block(kEcThreads);
+        if (!agent && pl->adj_xh) {
+            if (pl->adj_ng == 1) hipLaunchKernelGGL((el_cluster_adj<1, false, true>), grid, block, pl->adj_lds, st, c);
+            else hipLaunchKernelGGL((el_cluster_adj<2, false, true>), grid, block, pl->adj_lds, st, c);
         }
+        else if (pl->adj_ng == 1 && !agent) hipLaunchKernelGGL((el_cluster_adj<1, false>), grid, block, pl->adj_lds, st, c);
+        else if (pl->adj_ng == 1) hipLaunchKernelGGL((el_cluster_adj<1, true>), grid, block, pl->adj_lds, st, c);
+        else if (!agent) hipLaunchKernelGGL((el_cluster_adj<2, false>), grid, block, pl->adj_lds, st, c);
+        else hipLaunchKernelGGL((el_cluster_adj<2, true>), grid, block, pl->adj_lds, st, c);
     }
-#endif
-    const int verdict = mifwi::cluster_verdict(err, "elastic forward");
-    return mifwi::fake_timeout() == 2 ? mifwi::kClusterTimedOut : verdict;
-}
-
-// A timed-out single-launch attempt has advanced the state by an unknown number of steps: a call that started from
-// the zero state is zeroed again, a resumed call (time checkpointing) gets back the copy of its input state taken
-// before the attempt; then the per-step kernels run the range.
-int el_cluster_backup(float *work, long long state_elems, float *backup, int32_t flags, hipStream_t st)
-{
-    if (flags & MIFWI_ZERO_STATE) return MIFWI_OK;
-    MIFWI_HIP_TRY(hipMemcpyAsync(backup, work, sizeof(float) * state_elems, hipMemcpyDeviceToDevice, st));
-    return MIFWI_OK;
-}
-int el_cluster_restore(float *work, long long state_elems, const float *backup, int32_t flags, hipStream_t st)
-{
-    if (flags & MIFWI_ZERO_STATE) MIFWI_HIP_TRY(hipMemsetAsync(work, 0, sizeof(float) * state_elems, st));
-    else MIFWI_HIP_TRY(hipMemcpyAsync(work, backup, sizeof(float) * state_elems, hipMemcpyDeviceToDevice, st));
-    return MIFWI_OK;
 }
 
 }  // namespace
@@ -1491,8 +1503,10 @@ int mifwi_elastic_plan_create(mifwi_elastic_plan **plan, int device, const mifwi
     } else {
         pl->wl = pl->xr0 = pl->wx = 0;
     }
-    pl->psix_elems = 4LL * d->nz * pl->wx * d->nshot;
-    pl->psiz_elems = 4LL * 2 * pl->W * pl->gp * d->nshot;
+    pl->psix_shot = 4LL * d->nz * pl->wx;
+    pl->psiz_shot = 4LL * 2 * pl->W * pl->gp;
+    pl->psix_elems = pl->psix_shot * d->nshot;
+    pl->psiz_elems = pl->psiz_shot * d->nshot;
     pl->lx = 16;
     for (int cand : {64, 32}) {
         const int padded = mifwi::ceil_div(pl->ng, cand) * cand;
@@ -1624,15 +1638,10 @@ int mifwi_elastic_plan_layout(const mifwi_elastic_plan *pl, mifwi_elastic_layout
                         (pl->fused ? MIFWI_EL_KERNEL_FWD_FUSED_STEP : 0) |
                         (pl->cluster && pl->cl_xh ? MIFWI_EL_KERNEL_FWD_LANE_HALO : 0) |
                         (pl->cl_adj && pl->adj_xh ? MIFWI_EL_KERNEL_ADJ_LANE_HALO : 0);
-    const long long psi = pl->psi_elems;
-    const long long bbox = mifwi::round_up64(4LL * pl->d.nshot, 64);
-    out->state_elems = pl->fields_elems + psi;
-    // single-launch plans: room for a copy of a resumed call's input state (el_cluster_backup)
-    out->work_forward_elems = out->state_elems + bbox + (pl->cluster ? pl->xbuf_elems + out->state_elems : 0) +
-                              (pl->fused ? out->state_elems : 0);
-    const long long adj_state = pl->fields_elems + 2 * psi + 5LL * pl->ngroups * pl->splane;
-    out->work_backward_elems = adj_state + bbox + (pl->cl_adj ? pl->xbuf_elems + pl->list_elems + adj_state : 0) +
-                               pl->tile_elems;
+    const ElWork fwd = work_map(pl, false);
+    out->state_elems = fwd.state;
+    out->work_forward_elems = fwd.total;
+    out->work_backward_elems = work_map(pl, true).total;
     return MIFWI_OK;
 }
 
@@ -1654,12 +1663,10 @@ int mifwi_elastic_forward(mifwi_elastic_plan *pl, const float *mat, const float 
     if (rc) return rc;
     MIFWI_HIP_TRY(hipSetDevice(pl->device));
     hipStream_t st = (hipStream_t)stream;
-    // state layout: [fields | psi | bbox], updated in place
-    const long long psi = pl->psi_elems;
-    float *fields = work, *psi_state = work + pl->fields_elems;
-    int *bbox = reinterpret_cast<int *>(work + pl->fields_elems + psi);
-    if (flags & MIFWI_ZERO_STATE)
-        MIFWI_HIP_TRY(hipMemsetAsync(work, 0, sizeof(float) * (pl->fields_elems + psi), st));
+    const ElWork m = work_map(pl, false);                 // the state is updated in place
+    float *fields = work + m.fields, *psi_state = work + m.psi;
+    int *bbox = reinterpret_cast<int *>(work + m.bbox);
+    if (flags & MIFWI_ZERO_STATE) MIFWI_HIP_TRY(hipMemsetAsync(work, 0, sizeof(float) * m.state, st));
     if (d.nsrc > 0)
         hipLaunchKernelGGL(el_points_bbox, dim3(d.nshot), dim3(kThreads), 0, st, src_cell,
                            d.nsrc * d.ntap, d.nx, bbox);
@@ -1668,46 +1675,31 @@ int mifwi_elastic_forward(mifwi_elastic_plan *pl, const float *mat, const float 
     const int save = !snap ? 0 : pl->snap_bf16 ? 2 : 1;
     const bool want_rec = rec_vx != nullptr && d.nrec > 0;
     if (pl->cluster && n_end > n_begin) {
-        float *xbuf = work + pl->fields_elems + psi + mifwi::round_up64(4LL * d.nshot, 64);
-        EcParams c;
-        memset(&c, 0, sizeof(c));
-        c.nz = d.nz; c.nx = d.nx; c.ng = pl->ng; c.gp = pl->gp; c.pitch = pl->pitch;
-        c.field_stride = (unsigned)pl->field_stride; c.shot_stride = pl->shot_stride;
-        c.nshot = d.nshot; c.NW = pl->NW; c.PL = pl->fwd_PL;
+        const mifwi::Handoff h = mifwi::cluster_handoff(pl, work, m);
+        EcParams c = cluster_base<EcParams>(pl, pl->NW, pl->fwd_PL, mat, pz, px, h);
         c.n_first = n_begin; c.n_last = n_end;
-        c.W = pl->W; c.wl = pl->wl; c.xr0 = pl->xr0; c.wx = pl->wx; c.fsurf = d.free_surface;
-        c.psix_shot = 4LL * d.nz * pl->wx; c.psiz_shot = 4LL * 2 * pl->W * pl->gp;
-        c.mat = mat; c.pz = pz; c.px = px;
         c.fields = fields; c.psix = psi_state; c.psiz = psi_state + pl->psix_elems;
         c.S = snap; c.s_first = n_begin; c.s_step = snap_step;
-        c.nsrc = d.nsrc; c.nrec = d.nrec; c.src_cell = src_cell; c.src_w = src_w; c.f = f;
+        c.src_cell = src_cell; c.src_w = src_w; c.f = f;
         c.rec_cell = rec_cell; c.rec_w = rec_w;
         c.rec_vx = want_rec ? rec_vx : nullptr; c.rec_vz = want_rec ? rec_vz : nullptr;
-        c.dbg = env_int("MIFWI_EL_CL_DBG", 0);
-        c.nap = env_int("MIFWI_POLL_NAP", mifwi::ceil_div(d.nz, c.NW) >= 8 ? 48 : 1);   // mifwi::poll_nap
-        c.K = fd_weights(d.fd_order);
-        float *backup = xbuf + pl->xbuf_elems;
-        rc = el_cluster_backup(work, pl->fields_elems + psi, backup, flags, st);
-        if (rc) return rc;
-        rc = snap ? el_cluster_run<true, false>(pl, c, xbuf, st) : el_cluster_run<false, false>(pl, c, xbuf, st);
-        if (rc == mifwi::kClusterMisplaced) {          // not on one XCD: once more with hand-offs through the fabric
-            mifwi::note_agent_tier("elastic forward");
-            rc = el_cluster_restore(work, pl->fields_elems + psi, backup, flags, st);
-            if (rc) return rc;
-            rc = snap ? el_cluster_run<true, true>(pl, c, xbuf, st) : el_cluster_run<false, true>(pl, c, xbuf, st);
-        }
-        if (rc != mifwi::kClusterTimedOut && rc != mifwi::kClusterMisplaced) return rc;
-        mifwi::note_fallback("elastic");
-        rc = el_cluster_restore(work, pl->fields_elems + psi, backup, flags, st);
-        if (rc) return rc;
+        const mifwi::TraceSpec ts = {"MIFWI_EL_CL_TRACE", 64 * 8 * 16, "# el_cluster_fwd save=%d steps=%d", snap ? 1 : 0, n_end - n_begin};
+        rc = mifwi::cluster_ladder("elastic forward", work, m.state, work + m.backup, flags, st, h, ts,
+                                   [&](bool agent, long long *trace) {
+            mifwi::set_trace(c, trace);
+            if (snap && agent) el_cluster_launch<true, true>(pl, c, st);
+            else if (snap) el_cluster_launch<true, false>(pl, c, st);
+            else if (agent) el_cluster_launch<false, true>(pl, c, st);
+            else el_cluster_launch<false, false>(pl, c, st);
+        });
+        if (rc != mifwi::kClusterFellBack) return rc;
     }
     if (pl->fused && n_end > n_begin) {
         // V+S in one launch: the state ping-pongs between the copy at the head of the work buffer and a second
         // one behind the bounding boxes.  Shots are taken a few at a time (both copies of their state stay in the
         // Infinity Cache); a pass with an odd number of steps ends with a copy back of its shots.
-        const long long state = pl->fields_elems + psi;
-        float *B = work + state + mifwi::round_up64(4LL * d.nshot, 64);
-        MIFWI_HIP_TRY(hipMemsetAsync(B, 0, sizeof(float) * state, st));     // its pad rows / columns stay zero
+        float *B = work + m.second;
+        MIFWI_HIP_TRY(hipMemsetAsync(B, 0, sizeof(float) * m.state, st));     // its pad rows / columns stay zero
         ElParams q = p;
         q.ninj = d.nsrc; q.ntap_inj = d.ntap; q.inj_cell = src_cell; q.inj_w = src_w; q.inj_bbox = bbox;
         q.nsmp = want_rec ? d.nrec : 0; q.ntap_smp = d.ntap; q.smp_cell = rec_cell; q.smp_w = rec_w;
@@ -1742,7 +1734,7 @@ int mifwi_elastic_forward(mifwi_elastic_plan *pl, const float *mat, const float 
                                    st, q);
             }
             if (last != work) {
-                const long long psix1 = 4LL * d.nz * pl->wx, psiz1 = 4LL * 2 * pl->W * pl->gp;
+                const long long psix1 = pl->psix_shot, psiz1 = pl->psiz_shot;
                 MIFWI_HIP_TRY(hipMemcpyAsync(work + s0 * pl->shot_stride, B + s0 * pl->shot_stride,
                                              sizeof(float) * cs * pl->shot_stride, hipMemcpyDeviceToDevice, st));
                 if (psix1 > 0)
@@ -1820,14 +1812,9 @@ int mifwi_elastic_backward(mifwi_elastic_plan *pl, const float *mat, const float
     if (rc) return rc;
     MIFWI_HIP_TRY(hipSetDevice(pl->device));
     hipStream_t st = (hipStream_t)stream;
-    const long long psi = pl->psi_elems;
-    float *fields = work;
-    float *psiA = work + pl->fields_elems, *psiB = psiA + psi;
-    float *acc = psiB + psi;
-    const long long nacc = 5LL * pl->ngroups * pl->splane;          // accumulator planes: the snapshot planes' layout and size
-    int *bbox = reinterpret_cast<int *>(acc + nacc);
-    if (flags & MIFWI_ZERO_STATE)
-        MIFWI_HIP_TRY(hipMemsetAsync(work, 0, sizeof(float) * (pl->fields_elems + 2 * psi + nacc), st));
+    const ElWork m = work_map(pl, true);
+    float *fields = work + m.fields, *psiA = work + m.psi, *psiB = work + m.psiB, *acc = work + m.acc;
+    if (flags & MIFWI_ZERO_STATE) MIFWI_HIP_TRY(hipMemsetAsync(work, 0, sizeof(float) * m.state, st));
     ElParams p = el_base(pl, mat, pz, px);
     p.fields = fields;
     p.acc = acc;
@@ -1837,13 +1824,11 @@ int mifwi_elastic_backward(mifwi_elastic_plan *pl, const float *mat, const float
     const bool want_f = grad_f != nullptr && d.nsrc > 0;
     ps.nsmp = want_f ? d.nsrc : 0; ps.ntap_smp = d.ntap; ps.smp_cell = src_cell; ps.smp_w = src_w;
     const long long snap_step = pl->snap_shot * d.nshot;
-    // per-tile receiver lists of el_adj_s, at the tail of the work buffer (mifwi_elastic_plan_layout)
+    // per-tile receiver lists of el_adj_s
     int *tile_start = nullptr, *tile_list = nullptr;
     const int tiles_x = mifwi::ceil_div(pl->ng, AGO), ntiles = tiles_x * mifwi::ceil_div(d.nz, ATZ);
     auto build_tile_lists = [&]() {
-        mifwi_elastic_layout lay;
-        mifwi_elastic_plan_layout(pl, &lay);
-        int *base = reinterpret_cast<int *>(work + lay.work_backward_elems - pl->tile_elems);
+        int *base = reinterpret_cast<int *>(work + m.tile);
         tile_start = base;
         int *cursor = base + (long long)d.nshot * (ntiles + 1);
         tile_list = cursor + (long long)d.nshot * ntiles;
@@ -1852,101 +1837,30 @@ int mifwi_elastic_backward(mifwi_elastic_plan *pl, const float *mat, const float
     };
     bool per_step = true;
     if (pl->cl_adj && n_hi >= n_lo) {
-        float *xbuf = reinterpret_cast<float *>(bbox) + mifwi::round_up64(4LL * d.nshot, 64);
-        int *lists = reinterpret_cast<int *>(xbuf + pl->xbuf_elems);
+        const mifwi::Handoff h = mifwi::cluster_handoff(pl, work, m);
+        int *lists = reinterpret_cast<int *>(work + m.lists);
         hipLaunchKernelGGL(ec_build_slab_lists, dim3(d.nshot), dim3(256), 0, st, rec_cell, d.nrec, d.nz, d.nx,
                            pl->adj_NW, lists, lists + (long long)d.nshot * pl->adj_NW);
-        EaParams c;
-        memset(&c, 0, sizeof(c));
-        c.nz = d.nz; c.nx = d.nx; c.ng = pl->ng; c.gp = pl->gp; c.pitch = pl->pitch;
-        c.field_stride = (unsigned)pl->field_stride; c.shot_stride = pl->shot_stride;
-        c.nshot = d.nshot; c.NW = pl->adj_NW; c.PL = pl->adj_PL;
+        EaParams c = cluster_base<EaParams>(pl, pl->adj_NW, pl->adj_PL, mat, pz, px, h);
         c.n_first = n_hi; c.n_last = n_lo; c.nt = d.nt;
-        c.W = pl->W; c.wl = pl->wl; c.xr0 = pl->xr0; c.wx = pl->wx; c.fsurf = d.free_surface;
         c.zrows_max = pl->adj_zrows;
-        c.psix_shot = 4LL * d.nz * pl->wx; c.psiz_shot = 4LL * 2 * pl->W * pl->gp; c.psix_elems = pl->psix_elems;
-        c.mat = mat; c.pz = pz; c.px = px;
+        c.psix_elems = pl->psix_elems;
         c.fields = fields; c.psiA = psiA; c.psiB = psiB;
         c.S = snap; c.s_first = snap_first; c.s_step = snap_step;
         c.acc = acc;
-        c.nsrc = d.nsrc; c.nrec = d.nrec; c.src_cell = src_cell; c.src_w = src_w;
+        c.src_cell = src_cell; c.src_w = src_w;
         c.grad_f = want_f ? grad_f : nullptr;
         c.rec_cell = rec_cell; c.rec_w = rec_w; c.g_vx = g_vx; c.g_vz = g_vz;
         c.slab_cnt = lists; c.slab_list = lists + (long long)d.nshot * pl->adj_NW;
         c.rcv_direct = env_int("MIFWI_EL_ADJ_DIRECT", 1);
-        c.dbg = env_int("MIFWI_EL_CL_DBG", 0);
-        c.nap = env_int("MIFWI_POLL_NAP", mifwi::ceil_div(d.nz, c.NW) >= 8 ? 48 : 1);   // mifwi::poll_nap
-        c.K = fd_weights(d.fd_order);
-        c.xbuf = reinterpret_cast<unsigned long long *>(xbuf);
-        c.err = reinterpret_cast<int *>(xbuf + pl->xbuf_elems - 64);
-        c.xcc_tab = reinterpret_cast<int *>(xbuf + pl->xbuf_elems - 64 - pl->xcc_elems);
-        const long long adj_state = pl->fields_elems + 2 * psi + nacc;
-        float *backup = reinterpret_cast<float *>(lists) + pl->list_elems;
-        rc = el_cluster_backup(work, adj_state, backup, flags, st);
-        if (rc) return rc;
-        // one attempt on the single-launch kernel; agent: granules published through the fabric (after a failed placement check)
-        auto attempt = [&](bool agent) -> int {
-            MIFWI_HIP_TRY(hipMemsetAsync(xbuf, 0, sizeof(float) * pl->xbuf_elems, st));
-#ifdef MIFWI_ABLATIONS
-            const char *trace_path = getenv("MIFWI_EL_CL_TRACE");
-            const size_t trace_n = 64 * 8 * 16;
-            c.trace = nullptr;
-            if (trace_path && *trace_path) {
-                MIFWI_HIP_TRY(hipMalloc(&c.trace, trace_n * sizeof(long long)));
-                MIFWI_HIP_TRY(hipMemsetAsync(c.trace, 0, trace_n * sizeof(long long), st));
-            }
-#endif
-            for (int s0 = 0; s0 < d.nshot && mifwi::fake_timeout() != 1; s0 += pl->adj_shots) {
-                c.shot0 = s0;
-                c.shot1 = std::min(d.nshot, s0 + pl->adj_shots);
-                const dim3 grid(8 * pl->adj_NW * mifwi::ceil_div(c.shot1 - s0, 8));
-                if (!agent && pl->adj_xh) {
-                    if (pl->adj_ng == 1) hipLaunchKernelGGL((el_cluster_adj<1, false, true>), grid, dim3(kEcThreads), pl->adj_lds, st, c);
-                    else hipLaunchKernelGGL((el_cluster_adj<2, false, true>), grid, dim3(kEcThreads), pl->adj_lds, st, c);
-                }
-                else if (pl->adj_ng == 1 && !agent) hipLaunchKernelGGL((el_cluster_adj<1, false>), grid, dim3(kEcThreads), pl->adj_lds, st, c);
-                else if (pl->adj_ng == 1) hipLaunchKernelGGL((el_cluster_adj<1, true>), grid, dim3(kEcThreads), pl->adj_lds, st, c);
-                else if (!agent) hipLaunchKernelGGL((el_cluster_adj<2, false>), grid, dim3(kEcThreads), pl->adj_lds, st, c);
-                else hipLaunchKernelGGL((el_cluster_adj<2, true>), grid, dim3(kEcThreads), pl->adj_lds, st, c);
-            }
-            MIFWI_HIP_TRY(hipGetLastError());
-            int err[4] = {0, 0, 0, 0};
-            MIFWI_HIP_TRY(hipMemcpyAsync(err, c.err, sizeof(err), hipMemcpyDeviceToHost, st));
-            MIFWI_HIP_TRY(hipStreamSynchronize(st));
-#ifdef MIFWI_ABLATIONS
-            if (c.trace) {
-                std::vector<long long> h(trace_n);
-                MIFWI_HIP_TRY(hipMemcpy(h.data(), c.trace, trace_n * sizeof(long long), hipMemcpyDeviceToHost));
-                MIFWI_HIP_TRY(hipFree(c.trace));
-                if (FILE *fp = fopen(trace_path, "a")) {
-                    fprintf(fp, "# el_cluster_adj steps=%d\n", n_hi - n_lo + 1);
-                    for (size_t i = 0; i < trace_n; i += 16) {
-                        for (int k = 0; k < 16; ++k) fprintf(fp, "%lld ", h[i + k]);
-                        fprintf(fp, "\n");
-                    }
-                    fclose(fp);
-                }
-            }
-#endif
-            const int verdict = mifwi::cluster_verdict(err, "elastic adjoint");
-            return mifwi::fake_timeout() ? mifwi::kClusterTimedOut : verdict;
-        };
-        rc = attempt(false);
-        if (rc == mifwi::kClusterMisplaced) {
-            mifwi::note_agent_tier("elastic adjoint");
-            rc = el_cluster_restore(work, adj_state, backup, flags, st);
-            if (rc) return rc;
-            rc = attempt(true);
-        }
-        if (rc == mifwi::kClusterTimedOut || rc == mifwi::kClusterMisplaced) {
-            mifwi::note_fallback("elastic adjoint");
-            rc = el_cluster_restore(work, adj_state, backup, flags, st);
-            if (rc) return rc;
-        } else if (rc != MIFWI_OK) {
-            return rc;
-        } else {
-            per_step = false;
-        }
+        const mifwi::TraceSpec ts = {"MIFWI_EL_CL_TRACE", 64 * 8 * 16, "# el_cluster_adj steps=%d", n_hi - n_lo + 1, 0};
+        rc = mifwi::cluster_ladder("elastic adjoint", work, m.state, work + m.backup, flags, st, h, ts,
+                                   [&](bool agent, long long *trace) {
+            mifwi::set_trace(c, trace);
+            ea_cluster_launch(pl, c, agent, st);
+        });
+        if (rc != MIFWI_OK && rc != mifwi::kClusterFellBack) return rc;
+        per_step = rc == mifwi::kClusterFellBack;
     }
     // el_adj_s adds the adjoint sources of its tile (per-tile lists)
     if (per_step && d.nrec > 0 && n_hi >= n_lo) {

@@ -1,9 +1,11 @@
 """The single-launch time loops hand halo rows between workgroups and give up (bounded spins) when
 a neighbour never shows up.  The call then re-runs with one launch per (half) step instead of failing:
 from the zero state when it started there, from a copy of its input state when it was a resumed
-(time-checkpointed) call.  MIFWI_TEST_FAKE_TIMEOUT=1 makes the host treat every single-launch attempt as
+(time-checkpointed) call.  All five entry points with a single-launch kernel go through one host routine for this
+(mifwi::cluster_ladder, csrc/mifwi_cluster_host.h).  MIFWI_TEST_FAKE_TIMEOUT=1 makes it treat every single-launch attempt as
 timed out before it runs, =2 after it has run (the state really has to be restored); the device side of
 the time-out (a workgroup that never shows up) is driven in an ablation build, in a child process."""
+import json
 import os
 import subprocess
 import sys
@@ -142,6 +144,69 @@ def test_cpml_calls_fall_back_too(monkeypatch, mode):
     assert float(ref[0].abs().max()) > 0 and torch.equal(ref[0], got[0]) and torch.equal(ref[0], got_ck[0])
     _same(ref[1:], got[1:])
     _same(ref[1:], got_ck[1:])
+
+
+# mifwi_fallback_count() increments of the calls below under MIFWI_TEST_FAKE_TIMEOUT = 1 and 2, recorded on an MI355X from
+# the library of commit 70b3316 (before the five copies of the ladder became one): {"acoustic/1": n, ...}
+with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "recorded_parent.json")) as _f:
+    _PARENT_FALLBACKS = json.load(_f)["fallbacks"]
+
+
+def _pinned_calls():
+    """name -> callable: one resident propagate + backward of each physics and one Born call, on the smallest grids that
+    still run the single-launch kernels (40x64 cells with the absorbing layers, 2 shots, 20 steps)."""
+    from physicsbasedfwi2_amd import acoustic
+    from physicsbasedfwi2_amd.acoustic import AcousticPlan
+    from physicsbasedfwi2_amd.elastic import ElasticPlan
+    ca = acoustic_case(seed=101, n0=28, n1=52, nb=6, nt=20, ns=2, nrec=7)
+    ce = elastic_case(seed=103, nz=40, nx=64, fw=6, nt=20, ns=2, nrec=9)
+    assert ca["shape"] == (40, 64)
+    assert AcousticPlan(40, 64, 20, 2, 1, 7, 1, ca["c0"], ca["c1"], 0).cluster_slabs() >= 1
+    pl = ElasticPlan(40, 64, 20, 2, 1, 9, 1, 6, 0)
+    assert pl.cluster_slabs(False) >= 1 and pl.cluster_slabs(True) >= 1
+    r = torch.tensor(ca["r"], dtype=torch.float32, device=DEV)
+    f = torch.tensor(ca["f"], dtype=torch.float32, device=DEV)
+    dr = 0.01 * torch.randn(r.shape, generator=torch.Generator().manual_seed(107)).to(DEV)
+    born_args = (r, f, dr, *_t(ca, "q0", "q1", "sc", "sw", "rc", "rw"), ca["c0"], ca["c1"])
+    return {"acoustic": lambda: _acoustic(ca), "elastic": lambda: _elastic(ce), "born": lambda: acoustic.born(*born_args)}
+
+
+def _counted(call):
+    """(results, fall-backs counted, agent-tier launches counted) of one call"""
+    from physicsbasedfwi2_amd import _lib
+    lib = _lib.load()
+    fb, ag = lib.mifwi_fallback_count(), lib.mifwi_agent_handoff_count()
+    out = call()
+    return out, lib.mifwi_fallback_count() - fb, lib.mifwi_agent_handoff_count() - ag
+
+
+@pytest.fixture(scope="module")
+def pinned_refs():
+    assert not os.environ.get("MIFWI_TEST_FAKE_TIMEOUT")
+    calls = _pinned_calls()
+    refs = {}
+    for name, call in calls.items():
+        refs[name], fb, ag = _counted(call)
+        assert (fb, ag) == (0, 0)
+    return calls, refs
+
+
+@pytest.mark.expects_fallback
+@pytest.mark.parametrize("mode", ["1", "2"])
+def test_a_call_that_gives_up_is_counted_once_per_time_loop(monkeypatch, pinned_refs, mode):
+    """The counters under both forms of the fake time-out: every entry-point call whose single-launch attempt gave up adds
+    exactly one fall-back (the increments the library before the shared ladder gave), no launch is repeated at agent scope,
+    traces are the bits of the undisturbed run and gradients agree to summation order."""
+    calls, refs = pinned_refs
+    monkeypatch.setenv("MIFWI_TEST_FAKE_TIMEOUT", mode)
+    for name, call in calls.items():
+        got, fb, ag = _counted(call)
+        print("%s mode %s: %d fall-back(s), %d agent-tier launch(es)" % (name, mode, fb, ag))
+        assert fb == _PARENT_FALLBACKS["%s/%s" % (name, mode)] and ag == 0
+        ntraces = {"acoustic": 1, "elastic": 2, "born": 2}[name]
+        for a, b in zip(refs[name][:ntraces], got[:ntraces]):
+            assert float(a.abs().max()) > 0 and torch.equal(a, b)
+        _same(refs[name][ntraces:], got[ntraces:])
 
 
 _CHILD = r"""
