@@ -29,7 +29,7 @@ extern "C" {
 #endif
 
 #define MIFWI_VERSION_MAJOR 0
-#define MIFWI_VERSION_MINOR 7   /* 3: elastic desc gained snapshot_format, fd_order; layout snap_step_elems, snapshot_format; 4: mifwi_fallback_count; 5: mifwi_agent_handoff_count, mifwi_slow_handoff_count; acoustic desc gained cpml_width, layout state_elems; 6: mifwi_elastic_materials(_vjp), mifwi_acoustic_coefficients(_vjp); 7: mifwi_elastic_gradient_parametrization; elastic snapshot planes column-blocked in plans without a single-launch kernel */
+#define MIFWI_VERSION_MINOR 7   /* 3: elastic desc gained snapshot_format, fd_order; layout snap_step_elems, snapshot_format; 4: mifwi_fallback_count; 5: mifwi_agent_handoff_count, mifwi_slow_handoff_count; acoustic desc gained cpml_width, layout state_elems; 6: mifwi_elastic_materials(_vjp), mifwi_acoustic_coefficients(_vjp); 7: mifwi_elastic_gradient_parametrization; elastic snapshot planes column-blocked in plans without a single-launch kernel; later additions that leave every existing call as it was keep 7: mifwi_elastic_snapshot_moments, mifwi_elastic_pseudo_hessian, mifwi_gradient_precondition */
 
 enum {
     MIFWI_OK = 0,
@@ -278,6 +278,48 @@ int mifwi_acoustic_plan_cluster_slabs(const mifwi_acoustic_plan *plan, int32_t a
 int mifwi_elastic_plan_cluster_slabs(const mifwi_elastic_plan *plan, int32_t adjoint);
 
 /* ======================================================================================
+ * Diagonal PSEUDO-HESSIAN of the elastic gradient (Shin's preconditioner)
+ *
+ * Serves: DENISE's EPRECOND = 1 / EPSILON_WE, reachable through pyapi_denise as every DENISE parameter is.  The
+ * reference's parameter blocks (models/networks.py:7698-7731, 9790-9833) never set the switch; what stands in its
+ * place there is the host heuristic of models/networks.py:7808-7862 (mute rows 0:25, rescale every plane to
+ * max(model)/max(gradient)), needed because the raw gradient is dominated by the cells around the sources.  The
+ * DENISE binary is not available to pin against: the definitions below are this library's documented choice.
+ *
+ * The five planes S0..S4 a forward step saves for the adjoint (exx', ezz', exz', the two force sums) are the virtual
+ * sources of the five material planes; the pseudo-Hessian is their energy summed over time and shots, so it needs no
+ * extra propagation, only one more read of the snapshot buffer.
+ *
+ * MOMENTS  [6][nz][gp], per cell summed over the plan's shots and the selected steps:
+ *   M0..M4 = sum Sk^2,   M5 = sum S0 S1
+ * A perturbation (dL, dM, dmu, db) of the collocated materials L = lambda s, M = (lambda + 2 mu) s, mu s, b = s / rho
+ * (s = dt/h) excites the virtual source (S1 dL + S0 dM, S0 dL + S1 dM, S2 dmu, S3 db, S4 db) in the sxx / szz / sxz /
+ * vx / vz equations; for a parameter p with pointwise partials (L_p, M_p, mu_p, b_p) the pseudo-Hessian is the summed
+ * squared norm of that vector:
+ *   H_p = (L_p^2 + M_p^2)(M0 + M1) + 4 L_p M_p M5 + mu_p^2 M2 + b_p^2 (M3 + M4)
+ * (the cross moment M5 because Vp, rho and lambda each move L and M together).  Partials:
+ *   VELOCITY   Vp:     (2 rho Vp s, 2 rho Vp s, 0, 0)    Vs: (-4 rho Vs s, 0, 2 rho Vs s, 0)
+ *              rho:    ((Vp^2 - 2 Vs^2) s, Vp^2 s, Vs^2 s, -s / rho^2)
+ *   IMPEDANCE  Zp:     (2 Vp s, 2 Vp s, 0, 0)            Zs: (-4 Vs s, 0, 2 Vs s, 0)
+ *              rho:    (-(Vp^2 - 2 Vs^2) s, -Vp^2 s, -Vs^2 s, -s / rho^2)
+ *   LAME       lambda: (s, s, 0, 0)                      mu: (0, 2 s, s, 0)
+ *              rho:    (0, 0, 0, -s / rho^2)
+ * A term whose divisor is zero contributes 0 (the convention of mifwi_elastic_gradient_parametrization).
+ * This is a COLLOCATED approximation: the staggered averages of the material planes, the harmonic mu_xz and the
+ * effective row 0 under a free surface are ignored.
+ * ==================================================================================== */
+int64_t mifwi_elastic_snapshot_moments_work_elems(const mifwi_elastic_plan *plan);
+/* steps n in [n_begin, n_end) with n % stride == 0 (absolute n: a range may be cut anywhere), each weighted by
+   stride; step n at snap + (n - snap_first) * layout.snap_step_elems; MIFWI_ZERO_STATE: overwrite, else add.
+   snap: as written by mifwi_elastic_forward of the same plan (any of its layouts).  moments [6][nz][gp] row-major,
+   columns >= nx written as 0.  work: mifwi_elastic_snapshot_moments_work_elems(plan) floats (partial planes of the
+   step range, added in a fixed order: no atomics, two identical calls give the same bits).  stride < 1, an empty or
+   reversed range: MIFWI_EINVAL. */
+int mifwi_elastic_snapshot_moments(mifwi_elastic_plan *plan, const float *snap, int32_t snap_first,
+                                   int32_t n_begin, int32_t n_end, int32_t stride, float *moments,
+                                   float *work, int32_t flags, void *stream);
+
+/* ======================================================================================
  * Fused data MISFIT + adjoint source (what sits between the propagator call and .backward())
  *
  * Replaces:
@@ -316,6 +358,14 @@ int64_t mifwi_gradient_condition_work_elems(int32_t nplane);
 int mifwi_gradient_condition(int device, const float *grad, const float *models, float *out, int32_t nplane,
                              int32_t nz, int32_t nx, const float *row_weight, float sigma, int32_t flip,
                              int32_t mute_rows, const float *factors, float *work, void *stream);
+
+/* Pseudo-Hessian preconditioning (DENISE EPRECOND = 1 with the water level EPSILON_WE; see the pseudo-Hessian block above):
+ *   out_k = grad_k / (hess_k / max(hess_k) + eps_k)      per plane; a plane whose maximum is not positive is copied.
+ * grad, hess, out [nplane][n] device (nplane 1..4; out may alias grad); eps HOST array [nplane], every entry > 0
+ * (else MIFWI_EINVAL); work: mifwi_gradient_precondition_work_elems(nplane) floats. */
+int64_t mifwi_gradient_precondition_work_elems(int32_t nplane);
+int mifwi_gradient_precondition(int device, const float *grad, const float *hess, float *out, int32_t nplane,
+                                int64_t n, const float *eps /* host [nplane], > 0 */, float *work, void *stream);
 
 /* ======================================================================================
  * MATERIAL PARAMETERISATION of the elastic kernels and its chain rule
@@ -356,6 +406,14 @@ int mifwi_elastic_gradient_parametrization(int device, int32_t parametrization, 
                                            const float *rho, const float *grad_vp, const float *grad_vs,
                                            const float *grad_rho, float *out_a, float *out_b, float *out_rho,
                                            int64_t n, void *stream);
+
+/* The pseudo-Hessian planes of one parameter set (MIFWI_PARAM_*) from the moments of mifwi_elastic_snapshot_moments:
+ * H_p of the formulas in the pseudo-Hessian block above, cell by cell, in the order of
+ * mifwi_elastic_gradient_parametrization (h_a, h_b: Vp, Vs / Zp, Zs / lambda, mu).  vp, vs, rho, h_* [nz][nx] device,
+ * no padding; moments [6][nz][gp].  Every output is finite and >= 0. */
+int mifwi_elastic_pseudo_hessian(int device, int32_t parametrization, const float *vp, const float *vs,
+                                 const float *rho, const float *moments, int32_t nz, int32_t nx, int32_t gp,
+                                 float dt_over_h, float *h_a, float *h_b, float *h_rho, void *stream);
 
 /* vp [nz][nx] (m/s) -> r [nz + 2 pad][nx + 2 pad] = (vp dt/h)^2 with the model edge-replicated into the absorbing
  * layer: the coefficient of the scalar scheme as the deepwave-shaped call protocol needs it per call

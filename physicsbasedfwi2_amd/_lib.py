@@ -97,6 +97,12 @@ SIGNATURES = {
     "mifwi_elastic_materials_vjp": (ctypes.c_int, [ctypes.c_int] + [_P] * 7 + [ctypes.c_int32] * 2 +
                                     [ctypes.c_float, ctypes.c_int32, _P]),
     "mifwi_elastic_gradient_parametrization": (ctypes.c_int, [ctypes.c_int, ctypes.c_int32] + [_P] * 9 + [ctypes.c_int64, _P]),
+    "mifwi_elastic_snapshot_moments_work_elems": (ctypes.c_int64, [_P]),
+    "mifwi_elastic_snapshot_moments": (ctypes.c_int, [_P] * 2 + [ctypes.c_int32] * 4 + [_P] * 2 + [ctypes.c_int32, _P]),
+    "mifwi_elastic_pseudo_hessian": (ctypes.c_int, [ctypes.c_int, ctypes.c_int32] + [_P] * 4 + [ctypes.c_int32] * 3 +
+                                     [ctypes.c_float] + [_P] * 4),
+    "mifwi_gradient_precondition_work_elems": (ctypes.c_int64, [ctypes.c_int32]),
+    "mifwi_gradient_precondition": (ctypes.c_int, [ctypes.c_int] + [_P] * 3 + [ctypes.c_int32, ctypes.c_int64] + [_P] * 3),
     "mifwi_acoustic_coefficients": (ctypes.c_int, [ctypes.c_int] + [_P] * 2 + [ctypes.c_int32] * 3 + [ctypes.c_float, _P]),
     "mifwi_acoustic_coefficients_vjp": (ctypes.c_int, [ctypes.c_int] + [_P] * 3 + [ctypes.c_int32] * 3 + [ctypes.c_float, _P]),
 }

@@ -240,7 +240,7 @@ _SERVED = frozenset((
     "root", "verbose", "device", "save_folder", "PHYSICS", "TIME", "DT", "FD_ORDER", "FW", "DAMPING", "FPML", "npower",
     "k_max_PML", "FREE_SURF", "QUELLART", "QUELLTYP", "QUELLTYPB", "FC_SPIKE_1", "FC_SPIKE_2", "ORDER_SPIKE", "SEISMO",
     "ITERMAX", "DATA_DIR", "SWS_TAPER_GRAD_HOR", "EXP_TAPER_GRAD_HOR", "GRADT1", "GRADT2", "GRADT3", "GRADT4", "INVMAT1",
-    "fwi_stages", "loss", "DT_used"))
+    "EPRECOND", "EPSILON_WE", "fwi_stages", "loss", "DT_used"))
 # DENISE parameters that cannot change what ONE gradient evaluation (ITERMAX = 1) returns: the MPI decomposition, names of
 # files this shim keeps in memory, logging, model bounds and line-search / optimiser settings that only act on model
 # updates, grid sizes that come from the Model object.  Accepted; one warning per name says so.
@@ -253,7 +253,7 @@ _INERT = frozenset((
 # parameters that DO change the result and are not built: only their neutral value is accepted
 _NEUTRAL = {"TIMEWIN": 0, "TRKILL": 0, "NORMALIZE": 0, "INV_STF": 0, "SPATFILTER": 0, "MODEL_FILTER": 0, "SWS_TAPER_GRAD_VERT": 0,
             "SWS_TAPER_GRAD_SOURCES": 0, "SWS_TAPER_CIRCULAR_PER_SHOT": 0, "SWS_TAPER_FILE": 0, "NDT": 1, "MAXRELERROR": 0,
-            "RTMOD": 0, "GRAVITY": 0, "INVMAT": 0, "EPRECOND": 0, "RUN_MULTIPLE_SHOTS": 1, "READREC": 0, "READMOD": 0,
+            "RTMOD": 0, "GRAVITY": 0, "INVMAT": 0, "RUN_MULTIPLE_SHOTS": 1, "READREC": 0, "READMOD": 0,
             "TW_IND": 0, "GAMMA": 0, "BOUNDARY": 0}
 _warned = set()
 
@@ -321,10 +321,16 @@ class Denise:
         self.SWS_TAPER_GRAD_HOR = 0
         self.EXP_TAPER_GRAD_HOR = 2.0
         self.GRADT1, self.GRADT2, self.GRADT3, self.GRADT4 = 21, 25, 490, 500
+        # EPRECOND: 0 off; 1 the diagonal pseudo-Hessian of the forward wavefields (Shin), grad / (H / max H + EPSILON_WE)
+        # per plane, in the parametrisation of INVMAT1; 3 (with the receiver-side term) is not built.  EPSILON_WE: the
+        # water level, DENISE.inp's 0.005, one value for all three planes
+        self.EPRECOND = 0
+        self.EPSILON_WE = 0.005
         self.fwi_stages = []
         self._observed = None
         self._gradients = None
         self._gradients_dev = None
+        self._pseudo_hessian = None        # the moments of the last grad() with EPRECOND = 1 (elastic.PseudoHessian)
         self._shots = None
         self._shots_p = None
         self._observed_p = None
@@ -438,13 +444,13 @@ class Denise:
                for a in (model.vp, vs, model.rho)]
         return prm, elastic.staggered_materials(prm[0], prm[1], prm[2], dt, h, free_surface=fsurf)
 
-    def _propagate(self, mat, f, pz, px, g, fw, fsurf, h):
+    def _propagate(self, mat, f, pz, px, g, fw, fsurf, h, pseudo_hessian=None):
         kind = {1: "explosive", 2: "fx", 3: "fz"}[self.QUELLTYP]
         if kind != "explosive":
             f = elastic.force_amplitude(f, mat, g["sc"], g["sw"], h, kind)
         out = elastic.propagate(mat, f, pz, px, g["sc"], g["sw"], g["rc"], g["rw"], fw,
                                 free_surface=fsurf, source_type=kind, record_pressure=self.SEISMO in (2, 4),
-                                fd_order=int(self.FD_ORDER))
+                                fd_order=int(self.FD_ORDER), pseudo_hessian=pseudo_hessian)
         # DENISE's pressure seismogram: p = -(sxx + syy) at the receiver node
         return (out[0], out[1], -out[2]) if len(out) == 3 else (out[0], out[1], None)
 
@@ -487,9 +493,15 @@ class Denise:
                              "own optimiser update the model)" % self.ITERMAX)
         if int(self.INVMAT1) not in (1, 2, 3):
             raise MifwiError("INVMAT1=%s not implemented (1: Vp, Vs, rho; 2: Zp, Zs, rho; 3: lambda, mu, rho)" % self.INVMAT1)
+        if int(self.EPRECOND) not in (0, 1):
+            raise MifwiError("EPRECOND=%s not implemented (0: off, 1: pseudo-Hessian of the forward wavefields; the "
+                             "receiver-side term of 3 is not built)" % self.EPRECOND)
+        if not float(self.EPSILON_WE) > 0:
+            raise MifwiError("EPSILON_WE=%s: the water level of the preconditioner must be > 0" % self.EPSILON_WE)
         dev, h, dt, nt, g, f, pz, px, fw, fsurf = self._setup(model, src, rec)
         prm, mat = self._materials(model, dev, dt, h, True, fsurf)
-        vx, vy, p = self._propagate(mat, f.to(dev), pz, px, g, fw, fsurf, h)
+        self._pseudo_hessian = elastic.PseudoHessian() if int(self.EPRECOND) == 1 else None
+        vx, vy, p = self._propagate(mat, f.to(dev), pz, px, g, fw, fsurf, h, self._pseudo_hessian)
         ox, oy = (o.to(dev).permute(1, 0, 2) for o in self._observed)     # -> [nt, ns, nrec]
         if ox.shape != vx.shape:
             raise MifwiError("observed data %s do not match modelled %s (nt, nshot, nrec)"
@@ -523,6 +535,11 @@ class Denise:
             # the same objective differentiated with respect to (Zp, Zs, rho) or (lambda, mu, rho): exact chain rule of
             # the change of variables, one launch (csrc/mifwi_materials.hip: mifwi_elastic_gradient_parametrization)
             grads = list(elastic.gradient_parametrization([q.detach() for q in prm], grads, int(self.INVMAT1)))
+        if self._pseudo_hessian is not None:
+            # after the change of variables, with the Hessian of the same parametrisation; before the depth taper
+            from .. import conditioning
+            hess = self._pseudo_hessian.hessian(prm[0], prm[1], prm[2], dt, h, int(self.INVMAT1))
+            grads = list(conditioning.precondition_gradients(torch.stack(grads), hess, float(self.EPSILON_WE)))
         if int(self.SWS_TAPER_GRAD_HOR) == 1:
             w = torch.tensor(gradient_taper(model.ny, h, self.GRADT1, self.GRADT2, self.GRADT3, self.GRADT4,
                                             self.EXP_TAPER_GRAD_HOR), device=dev)[:, None]

@@ -2,7 +2,8 @@
 ``prop()`` methods: trace normalisation and L1 misfit (models/networks.py:5418-5419,
 5467-5476), shot shuffle / strided mini-batch (5434-5440, 5454-5461), gradient conditioning
 (5329-5332, 5492-5493; 7808-7862).  Plain torch / numpy; the fused HIP misfit lives in misfit.py, the fused HIP
-gradient conditioning (:func:`condition_gradients`) in csrc/mifwi_gradient.hip.
+gradient conditioning (:func:`condition_gradients`) and the pseudo-Hessian preconditioning
+(:func:`precondition_gradients`) in csrc/mifwi_gradient.hip.
 """
 import numpy as np
 import torch
@@ -116,4 +117,35 @@ def condition_gradients(grads, models=None, row_weight=None, sigma=0.0, flip=Fal
                                                 _lib.ptr(w), float(sigma), int(bool(flip)), int(mute_rows),
                                                 ctypes.cast(fac, ctypes.c_void_p) if fac is not None else None,
                                                 _lib.ptr(work), torch.cuda.current_stream(dev).cuda_stream))
+    return out
+
+
+def precondition_gradients(grads, hess, eps):
+    """DENISE's ``EPRECOND = 1``: ``out_k = grads_k / (hess_k / max(hess_k) + eps_k)`` per plane, in one library call on
+    the device (``mifwi_gradient_precondition``; no CPU path).  grads, hess [k, nz, nx] (k <= 4) CUDA tensors - ``hess``
+    from :meth:`elastic.PseudoHessian.hessian` in the parametrisation of the gradients; eps: the water level
+    (``EPSILON_WE``), one float > 0 for all planes or k of them.  A plane whose Hessian is zero everywhere (Vs in a fluid)
+    is returned unchanged.  Returns a new [k, nz, nx] tensor."""
+    import ctypes
+    from . import _lib
+    if not grads.is_cuda:
+        raise _lib.MifwiError("precondition_gradients needs CUDA/HIP tensors (libmifwi has no CPU fallback)")
+    lib = _lib.load()
+    g = grads.detach().to(dtype=torch.float32).contiguous()
+    if g.dim() != 3 or not 1 <= g.shape[0] <= 4:
+        raise ValueError("grads must be [k, nz, nx] with k <= 4")
+    dev = g.device
+    hs = torch.as_tensor(hess).detach().to(device=dev, dtype=torch.float32).contiguous()
+    if tuple(hs.shape) != tuple(g.shape):
+        raise ValueError("hess must have the shape of grads")
+    k = g.shape[0]
+    e = [float(eps)] * k if np.isscalar(eps) else [float(v) for v in eps]
+    if len(e) != k:
+        raise ValueError("eps must be one float or one per plane")
+    out = torch.empty_like(g)
+    work = torch.empty(lib.mifwi_gradient_precondition_work_elems(k), device=dev, dtype=torch.float32)
+    with torch.cuda.device(dev):
+        _lib.check(lib.mifwi_gradient_precondition(dev.index or 0, _lib.ptr(g), _lib.ptr(hs), _lib.ptr(out), k,
+                                                   g[0].numel(), ctypes.cast((ctypes.c_float * k)(*e), ctypes.c_void_p),
+                                                   _lib.ptr(work), torch.cuda.current_stream(dev).cuda_stream))
     return out

@@ -1914,3 +1914,6 @@ int mifwi_elastic_backward(mifwi_elastic_plan *pl, const float *mat, const float
 }
 
 }  // extern "C"
+
+// snapshot second moments (pseudo-Hessian ingredient): reads the snapshot buffer the way the adjoint does
+#include "mifwi_elastic_moments.h"

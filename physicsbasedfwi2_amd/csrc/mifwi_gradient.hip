@@ -136,6 +136,20 @@ __global__ __launch_bounds__(kGT) void grad_scale(float *out, long long n, const
     for (long long i = (long long)blockIdx.x * kGT + threadIdx.x; i < n; i += (long long)gridDim.x * kGT) o[i] *= s;
 }
 
+// pseudo-Hessian preconditioning: out_k = grad_k / (H_k / max(H_k) + eps_k); a plane whose maximum is not positive is
+// copied.  Pointwise: out may alias grad.
+__global__ __launch_bounds__(kGT) void grad_precondition(const float *grad, const float *hess, float *out, long long n,
+                                                         const unsigned *keys, float e0, float e1, float e2, float e3)
+{
+    const int k = (int)blockIdx.y;
+    const float eps = k == 0 ? e0 : k == 1 ? e1 : k == 2 ? e2 : e3;
+    const float mx = key_f(keys[k]);
+    const float *g = grad + (long long)k * n, *h = hess + (long long)k * n;
+    float *o = out + (long long)k * n;
+    for (long long i = (long long)blockIdx.x * kGT + threadIdx.x; i < n; i += (long long)gridDim.x * kGT)
+        o[i] = mx > 0.f ? g[i] / (h[i] / mx + eps) : g[i];
+}
+
 }  // namespace
 
 extern "C" {
@@ -174,6 +188,31 @@ int mifwi_gradient_condition(int device, const float *grad, const float *models,
     if (any)
         hipLaunchKernelGGL(grad_scale, dim3((unsigned)std::min<long long>(256, (n + kGT - 1) / kGT), nplane), dim3(kGT), 0, st, out,
                            n, keys, nplane, models ? 1 : 0, f[0], f[1], f[2], f[3]);
+    MIFWI_HIP_TRY(hipGetLastError());
+    return MIFWI_OK;
+}
+
+int64_t mifwi_gradient_precondition_work_elems(int32_t nplane) { return mifwi::round_up64(std::max(nplane, 1), 64); }
+
+int mifwi_gradient_precondition(int device, const float *grad, const float *hess, float *out, int32_t nplane, int64_t n,
+                                const float *eps, float *work, void *stream)
+{
+    if (!grad || !hess || !out || !eps || !work) return mifwi::fail(MIFWI_EINVAL, "null argument");
+    if (nplane < 1 || nplane > 4 || n < 1) return mifwi::fail(MIFWI_EINVAL, "bad sizes: %d planes of %lld cells", nplane, (long long)n);
+    float e[4] = {1.f, 1.f, 1.f, 1.f};
+    for (int k = 0; k < nplane; ++k) {
+        if (!(eps[k] > 0.f)) return mifwi::fail(MIFWI_EINVAL, "eps[%d] = %g: the water level must be > 0", k, eps[k]);
+        e[k] = eps[k];
+    }
+    int rc = mifwi::check_device(device);
+    if (rc) return rc;
+    MIFWI_HIP_TRY(hipSetDevice(device));
+    hipStream_t st = (hipStream_t)stream;
+    unsigned *keys = reinterpret_cast<unsigned *>(work);
+    MIFWI_HIP_TRY(hipMemsetAsync(keys, 0, sizeof(unsigned) * nplane, st));
+    const dim3 grid((unsigned)std::min<long long>(256, (n + kGT - 1) / kGT), nplane), block(kGT);
+    hipLaunchKernelGGL(grad_model_max, grid, block, 0, st, hess, (long long)n, keys);          // the plane maxima of H
+    hipLaunchKernelGGL(grad_precondition, grid, block, 0, st, grad, hess, out, (long long)n, keys, e[0], e[1], e[2], e[3]);
     MIFWI_HIP_TRY(hipGetLastError());
     return MIFWI_OK;
 }

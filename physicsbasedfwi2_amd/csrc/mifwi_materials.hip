@@ -151,6 +151,44 @@ __global__ __launch_bounds__(kMT) void reparam_vjp(const float *vp, const float 
     }
 }
 
+// Shin's diagonal pseudo-Hessian of one parameter from the six snapshot moments (mifwi_elastic_moments.h; include/mifwi.h
+// has the derivation).  (L, M, mu, b) are the parameter's pointwise partials of the COLLOCATED materials L = lambda s,
+// M = (lambda + 2 mu) s, mu s, b = s / rho: the staggered averages, the harmonic mu_xz and the effective row 0 under a
+// free surface are ignored.  H is a sum of squared norms; rounding may leave it a hair below 0 where M5 = -sqrt(M0 M1)
+// cancels the first term, hence the max.
+__device__ __forceinline__ float hess_of(float L, float M, float mu, float b, float see, float m5, float m2, float m34)
+{
+    const float h = fmaf(fmaf(L, L, M * M), see, fmaf(4.0f * L * M, m5, fmaf(mu * mu, m2, b * b * m34)));
+    return fmaxf(h, 0.f);
+}
+template <int MODE>
+__global__ __launch_bounds__(kMT) void pseudo_hessian(const float *vp, const float *vs, const float *rho, const float *mom,
+                                                      int nz, int nx, int gp, float s, float *ha, float *hb, float *hrho)
+{
+    const long long k = (long long)blockIdx.x * kMT + threadIdx.x, n = (long long)nz * nx;
+    if (k >= n) return;
+    const int i = (int)(k / nx), j = (int)(k - (long long)i * nx);
+    const long long c = (long long)i * gp + j, pl = (long long)nz * gp;
+    const float see = mom[c] + mom[pl + c], m2 = mom[2 * pl + c], m34 = mom[3 * pl + c] + mom[4 * pl + c], m5 = mom[5 * pl + c];
+    const float p = vp[k], q = vs[k], r = rho[k];
+    const float brho = r == 0.f ? 0.f : -s / (r * r);          // a term whose divisor is zero contributes 0
+    if (MODE == MIFWI_PARAM_VELOCITY) {
+        const float a = 2.0f * r * p * s;
+        ha[k] = hess_of(a, a, 0.f, 0.f, see, m5, m2, m34);
+        hb[k] = hess_of(-4.0f * r * q * s, 0.f, 2.0f * r * q * s, 0.f, see, m5, m2, m34);
+        hrho[k] = hess_of((p * p - 2.0f * q * q) * s, p * p * s, q * q * s, brho, see, m5, m2, m34);
+    } else if (MODE == MIFWI_PARAM_IMPEDANCE) {
+        const float a = 2.0f * p * s;
+        ha[k] = hess_of(a, a, 0.f, 0.f, see, m5, m2, m34);
+        hb[k] = hess_of(-4.0f * q * s, 0.f, 2.0f * q * s, 0.f, see, m5, m2, m34);
+        hrho[k] = hess_of(-(p * p - 2.0f * q * q) * s, -(p * p) * s, -(q * q) * s, brho, see, m5, m2, m34);
+    } else {
+        ha[k] = hess_of(s, s, 0.f, 0.f, see, m5, m2, m34);
+        hb[k] = hess_of(0.f, 2.0f * s, s, 0.f, see, m5, m2, m34);
+        hrho[k] = hess_of(0.f, 0.f, 0.f, brho, see, m5, m2, m34);
+    }
+}
+
 // ---- scalar scheme: vp [nz][nx] -> r [nz + 2 pad][nx + 2 pad] = (vp dt / h)^2, the model replicated into the absorbing
 // layer (what the deepwave-shaped shim computes per call: compat/deepwave/scalar.py) ------------------------------------
 __global__ __launch_bounds__(kMT) void coef_fwd(const float *vp, float *r, int nz, int nx, int pad, float c)
@@ -229,6 +267,28 @@ int mifwi_elastic_gradient_parametrization(int device, int32_t parametrization, 
     } else {
         hipLaunchKernelGGL(reparam_vjp<3>, grid, block, 0, st, vp, vs, rho, grad_vp, grad_vs, grad_rho, out_a, out_b, out_rho, (long long)n);
     }
+    MIFWI_HIP_TRY(hipGetLastError());
+    return MIFWI_OK;
+}
+
+int mifwi_elastic_pseudo_hessian(int device, int32_t parametrization, const float *vp, const float *vs, const float *rho,
+                                 const float *moments, int32_t nz, int32_t nx, int32_t gp, float dt_over_h, float *h_a,
+                                 float *h_b, float *h_rho, void *stream)
+{
+    if (!vp || !vs || !rho || !moments || !h_a || !h_b || !h_rho || nz < 1 || nx < 1 || gp < nx)
+        return mifwi::fail(MIFWI_EINVAL, "mifwi_elastic_pseudo_hessian: bad argument");
+    if (parametrization < MIFWI_PARAM_VELOCITY || parametrization > MIFWI_PARAM_LAME)
+        return mifwi::fail(MIFWI_EINVAL, "parametrization %d: 1 = Vp/Vs/rho, 2 = Zp/Zs/rho, 3 = lambda/mu/rho", parametrization);
+    MIFWI_HIP_TRY(hipSetDevice(device));
+    hipStream_t st = (hipStream_t)stream;
+    const long long n = (long long)nz * nx;
+    const dim3 grid((unsigned)((n + kMT - 1) / kMT)), block(kMT);
+    if (parametrization == MIFWI_PARAM_VELOCITY)
+        hipLaunchKernelGGL(pseudo_hessian<MIFWI_PARAM_VELOCITY>, grid, block, 0, st, vp, vs, rho, moments, nz, nx, gp, dt_over_h, h_a, h_b, h_rho);
+    else if (parametrization == MIFWI_PARAM_IMPEDANCE)
+        hipLaunchKernelGGL(pseudo_hessian<MIFWI_PARAM_IMPEDANCE>, grid, block, 0, st, vp, vs, rho, moments, nz, nx, gp, dt_over_h, h_a, h_b, h_rho);
+    else
+        hipLaunchKernelGGL(pseudo_hessian<MIFWI_PARAM_LAME>, grid, block, 0, st, vp, vs, rho, moments, nz, nx, gp, dt_over_h, h_a, h_b, h_rho);
     MIFWI_HIP_TRY(hipGetLastError());
     return MIFWI_OK;
 }

@@ -193,6 +193,58 @@ class ElasticPlan:
             pass
 
 
+class PseudoHessian:
+    """Holder of the six snapshot second moments behind the diagonal pseudo-Hessian (Shin's preconditioner; DENISE's
+    ``EPRECOND = 1``): pass it to :func:`propagate` (``pseudo_hessian=``) and every backward pass through that call
+    adds ``M0..M4 = sum Sk^2, M5 = sum S0 S1`` of its forward snapshot planes - summed over its shots and over the
+    steps n with ``n % stride == 0``, each weighted by ``stride`` - into ``.moments`` [6, nz, nx] (None before the
+    first backward).  The holder accumulates over calls (shot chunks, ranks' shares); :meth:`reset` zeroes it.
+    The pass is one more read of the snapshot buffer the backward holds (``mifwi_elastic_snapshot_moments``), no
+    extra propagation; ``stride = 4`` reads a quarter of it."""
+
+    def __init__(self, stride=1):
+        if int(stride) < 1:
+            raise MifwiError("PseudoHessian: stride must be >= 1 (got %r)" % (stride,))
+        self.stride = int(stride)
+        self.moments = None
+
+    def reset(self):
+        if self.moments is not None:
+            self.moments.zero_()
+
+    def _add(self, m):
+        if self.moments is None:
+            self.moments = m.contiguous().clone()
+        elif self.moments.shape != m.shape or self.moments.device != m.device:
+            raise MifwiError("PseudoHessian holds moments of a %s grid, this run has %s"
+                             % (tuple(self.moments.shape[1:]), tuple(m.shape[1:])))
+        else:
+            self.moments.add_(m)
+
+    def hessian(self, vp, vs, rho, dt, h, parametrization=PARAM_VELOCITY):
+        """[3, nz, nx]: the pseudo-Hessian planes of (Vp, Vs, rho), (Zp, Zs, rho) or (lambda, mu, rho) - the order of
+        :func:`gradient_parametrization` - from the moments held and the model the run used:
+        ``H_p = (L_p^2 + M_p^2)(M0 + M1) + 4 L_p M_p M5 + mu_p^2 M2 + b_p^2 (M3 + M4)`` with the parameter's pointwise
+        partials of the collocated materials (include/mifwi.h has the table).  A collocated approximation: the
+        staggered averages, the harmonic mu_xz and the effective row 0 under a free surface are ignored.  Finite and
+        >= 0 everywhere (a term whose divisor is zero contributes 0)."""
+        if self.moments is None:
+            raise MifwiError("PseudoHessian.hessian: no moments yet - run a backward pass through "
+                             "propagate(..., pseudo_hessian=holder) first")
+        mom = self.moments.contiguous()
+        _, nz, nx = mom.shape
+        prm = [torch.as_tensor(t).detach().to(device=mom.device, dtype=torch.float32).contiguous() for t in (vp, vs, rho)]
+        if any(tuple(t.shape) != (nz, nx) for t in prm):
+            raise MifwiError("PseudoHessian.hessian: the model must be [%d, %d] like the moments" % (nz, nx))
+        out = torch.empty((3, nz, nx), device=mom.device, dtype=torch.float32)
+        with torch.cuda.device(mom.device):
+            _lib.check(_lib.load().mifwi_elastic_pseudo_hessian(
+                mom.device.index or 0, int(parametrization), _lib.ptr(prm[0]), _lib.ptr(prm[1]), _lib.ptr(prm[2]),
+                _lib.ptr(mom), nz, nx, nx, float(dt) / float(h), _lib.ptr(out[0]), _lib.ptr(out[1]), _lib.ptr(out[2]),
+                _stream()))
+        return out
+
+
 class _ArenaLease:
     """Held by the autograd node whose forward wrote the arena's tensor; dies with the node (a graph dropped without a
     backward frees the arena too)."""
@@ -243,7 +295,7 @@ class _SnapshotArena:
 class _ElasticFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, mat, f, pz, px, geom, pml_width, shots_per_group, snapshot_budget, free_surface,
-                source_type=0, record_pressure=0, snapshot_format=None, fd_order=4):
+                source_type=0, record_pressure=0, snapshot_format=None, fd_order=4, pseudo_hessian=None):
         _require_cuda(mat, "mat")
         dev = mat.device
         lib = _lib.load()
@@ -276,6 +328,9 @@ class _ElasticFn(torch.autograd.Function):
                 _lib.check(lib.mifwi_elastic_plan_bind_pressure(plan.handle, _lib.ptr(rp), None))
             work = torch.empty(lay.work_forward_elems, device=dev, dtype=torch.float32)
             need_grad = mat.requires_grad or f.requires_grad
+            if pseudo_hessian is not None and not need_grad:
+                raise MifwiError("pseudo_hessian: the moments are taken from the snapshots of a backward pass, and "
+                                 "neither mat nor f requires a gradient in this run")
             step_bytes = 4 * lay.snap_step_elems
             seg, snap, ckpt = nt, None, None
             arena = _SnapshotArena.current
@@ -317,6 +372,7 @@ class _ElasticFn(torch.autograd.Function):
                 ctx.dims = (nz, nx, nt, ns, nsrc, nrec)
                 ctx.need_f = f.requires_grad
                 ctx.record_pressure = record_pressure
+                ctx.hess = pseudo_hessian
                 ctx.save_for_backward(mat_p, pz_d, px_p, f_d)
             else:
                 plan.close()
@@ -346,6 +402,18 @@ class _ElasticFn(torch.autograd.Function):
             grad_f = (torch.zeros((nt, ns, nsrc), device=dev, dtype=torch.float32)
                       if ctx.need_f else None)
             work = torch.empty(lay.work_backward_elems, device=dev, dtype=torch.float32)
+            hess = ctx.hess
+            if hess is not None:
+                mom = torch.empty((6, nz, lay.gp), device=dev, dtype=torch.float32)
+                mwork = torch.empty(lib.mifwi_elastic_snapshot_moments_work_elems(plan.handle), device=dev,
+                                    dtype=torch.float32)
+
+            def moments(snap_t, b, e):
+                # one more read of a snapshot range this pass has in hand, each range once (absolute step numbers, so
+                # segments select the steps the resident buffer would); the range that ends the run comes first
+                _lib.check(lib.mifwi_elastic_snapshot_moments(
+                    plan.handle, _lib.ptr(snap_t), b, b, e, hess.stride, _lib.ptr(mom), _lib.ptr(mwork),
+                    _lib.ZERO_STATE if e == nt else 0, _stream()))
             common = (plan.handle, _lib.ptr(mat_p), _lib.ptr(pz_d), _lib.ptr(px_p),
                       _lib.ptr(geom.src_cell), _lib.ptr(geom.src_w), _lib.ptr(geom.rec_cell),
                       _lib.ptr(geom.rec_w), _lib.ptr(gx), _lib.ptr(gz))
@@ -353,6 +421,8 @@ class _ElasticFn(torch.autograd.Function):
                 _lib.check(lib.mifwi_elastic_backward(
                     *common, _lib.ptr(ctx.snap), 0, _lib.ptr(grad_mat), _lib.ptr(grad_f),
                     _lib.ptr(work), nt - 1, 0, _lib.ZERO_STATE | _lib.FINALIZE, _stream()))
+                if hess is not None:
+                    moments(ctx.snap, 0, nt)
             else:
                 seg = ctx.seg
                 fwork = torch.empty(lay.work_forward_elems, device=dev, dtype=torch.float32)
@@ -376,6 +446,11 @@ class _ElasticFn(torch.autograd.Function):
                     _lib.check(lib.mifwi_elastic_backward(
                         *common, _lib.ptr(snap), b, _lib.ptr(grad_mat), _lib.ptr(grad_f),
                         _lib.ptr(work), e - 1, b, flags, _stream()))
+                    if hess is not None:
+                        moments(snap, b, e)
+            if hess is not None:
+                hess._add(mom[:, :, :nx])
+                ctx.hess = None
             plan.close()
             ctx.plan = None
             ctx.snap = None
@@ -383,12 +458,12 @@ class _ElasticFn(torch.autograd.Function):
             if ctx.lease is not None:               # the arena's tensor may serve the next forward
                 ctx.lease.released = True
                 ctx.lease = None
-        return (grad_mat[:, :, :nx].contiguous(), grad_f) + (None,) * 11
+        return (grad_mat[:, :, :nx].contiguous(), grad_f) + (None,) * 12
 
 
 def propagate(mat, f, pz, px, src_cell, src_w, rec_cell, rec_w, pml_width,
               shots_per_group=0, snapshot_budget=DEFAULT_SNAPSHOT_BUDGET, free_surface=False,
-              source_type="explosive", record_pressure=False, snapshot_format=None, fd_order=4):
+              source_type="explosive", record_pressure=False, snapshot_format=None, fd_order=4, pseudo_hessian=None):
     """Elastic forward modelling, differentiable w.r.t. ``mat`` and ``f``.
 
     mat [5,nz,nx] from :func:`staggered_materials`;  f [nt,nshot,nsrc] (added to sxx and szz);
@@ -403,6 +478,10 @@ def propagate(mat, f, pz, px, src_cell, src_w, rec_cell, rec_w, pml_width,
     snapshot_format: "f32" (default; the gradient is the exact discrete adjoint) or "bf16": the forward snapshot
     planes are kept as bf16 (half the snapshot stream and memory; material gradients within 4e-3 rel-L2 of the
     f32 form in the worst case, seismograms unchanged) on grids that run the per-step kernels; None = MIFWI_EL_SNAP or "f32".
+    pseudo_hessian: a :class:`PseudoHessian` holder, or None.  The backward pass through this call then adds the second
+    moments of its snapshot planes into the holder (one more read of the snapshot buffer - resident, or every
+    regenerated checkpoint segment once); a run that needs no gradient has no such pass and raises.  Without a holder
+    nothing changes: the same launches, the same results.
     Returns (rec_vx, rec_vz), each [nt,nshot,nrec], sampled after the velocity update; with
     ``record_pressure`` also rec_p = sum w (sxx + szz) at the receivers after the stress update (DENISE's
     pressure seismogram is ``-rec_p``; such runs use the one-launch-per-half-step kernels)."""
@@ -415,9 +494,11 @@ def propagate(mat, f, pz, px, src_cell, src_w, rec_cell, rec_w, pml_width,
         raise MifwiError("source_type must be one of %s" % sorted(k for k in SOURCE_TYPES if isinstance(k, str)))
     if snapshot_format is not None and snapshot_format not in SNAPSHOT_FORMATS:
         raise MifwiError("snapshot_format must be one of %s" % sorted(SNAPSHOT_FORMATS))
+    if pseudo_hessian is not None and not isinstance(pseudo_hessian, PseudoHessian):
+        raise MifwiError("pseudo_hessian must be an elastic.PseudoHessian holder or None")
     rvx, rvz, rp = _ElasticFn.apply(mat, f, pz, px, geom, int(pml_width), int(shots_per_group),
                                     int(snapshot_budget), 1 if free_surface else 0, st,
-                                    1 if record_pressure else 0, snapshot_format, int(fd_order))
+                                    1 if record_pressure else 0, snapshot_format, int(fd_order), pseudo_hessian)
     return (rvx, rvz, rp) if record_pressure else (rvx, rvz)
 
 
