@@ -117,6 +117,19 @@ __device__ __forceinline__ unsigned ec_opaque(unsigned x)
     asm volatile("" : "+v"(x));
     return x;
 }
+// The same IN PLACE, for state that lives in a register of its own for the whole run (a group's offsets, class, strip
+// slots): ec_opaque() works on a copy - the original stays live, so every use costs a v_mov first (four to six per
+// group pass) - while here the register itself is declared rewritten and no instruction is emitted at all.
+__device__ __forceinline__ int ec_fresh(int &x)
+{
+    asm volatile("" : "+v"(x));
+    return x;
+}
+__device__ __forceinline__ unsigned ec_fresh(unsigned &x)
+{
+    asm volatile("" : "+v"(x));
+    return x;
+}
 
 // The same for a wave-uniform value (scalar register): every scalar derived from it (row pitches times k, plane
 // bases, table offsets) is then recomputed by two or three scalar instructions where it is used instead of being
@@ -157,6 +170,23 @@ __device__ __forceinline__ void ec_pin(float4 &a, float4 &b)
 __device__ __forceinline__ void ec_pin(float2 &a, float2 &b, float2 &c, float2 &d)
 {
     asm volatile("" : "+v"(a.x), "+v"(a.y), "+v"(b.x), "+v"(b.y), "+v"(c.x), "+v"(c.y), "+v"(d.x), "+v"(d.y));
+}
+
+// Two neighbouring cells of a group at once.  The stencils of the adjoint's phases B and D are written on these: left
+// to itself the compiler pairs an x-derivative with a z-derivative of the same cell in one packed instruction and
+// gathers their operands with one v_mov each (49 of the 148 vector instructions of a phase-B pass); paired by cell,
+// the z-stencils take their operands as the LDS reads deliver them and an x-stencil needs three register-pair
+// shuffles.  Per cell the operations and their order are those of dfw() / dbw().
+typedef float ec_f2 __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ ec_f2 ec_2(float a, float b) { ec_f2 r; r.x = a; r.y = b; return r; }
+__device__ __forceinline__ ec_f2 ec_2(const float4 &v, int h) { return h == 0 ? ec_2(v.x, v.y) : ec_2(v.z, v.w); }
+__device__ __forceinline__ ec_f2 dfw2(const FdK &K, ec_f2 fm1, ec_f2 f0, ec_f2 f1, ec_f2 f2)
+{
+    return __builtin_elementwise_fma(ec_2(K.c1, K.c1), f1 - f0, ec_2(K.c2, K.c2) * (f2 - fm1));
+}
+__device__ __forceinline__ ec_f2 dbw2(const FdK &K, ec_f2 fm2, ec_f2 fm1, ec_f2 f0, ec_f2 f1)
+{
+    return __builtin_elementwise_fma(ec_2(K.c1, K.c1), f0 - fm1, ec_2(K.c2, K.c2) * (f1 - fm2));
 }
 
 // nothing of the prologue is in flight when the time loop starts: without this the compiler carries the
@@ -226,13 +256,13 @@ struct EcHandoff {
             for (int k = 0; k < kEcGr; ++k) v[k] = 0;
         }
     };
-    __device__ __forceinline__ void sweep(Pending &q) const
+    __device__ __forceinline__ void sweep(Pending &q)
     {
 #pragma unroll
         for (int k = 0; k < kEcGr; ++k)       // lanes without a k-th granule read their own slot: no branches
-            q.v[k] = __hip_atomic_load(ec_at(q.base, ec_opaque(rcv_off[k])), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            q.v[k] = __hip_atomic_load(ec_at(q.base, ec_fresh(rcv_off[k])), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
-    __device__ __forceinline__ void request(Pending &q, int kind, int parity) const
+    __device__ __forceinline__ void request(Pending &q, int kind, int parity)
     {
         // (xw - 4 slots) + slot of (kind, parity): uniform base, per-lane byte offsets
         const unsigned xs8 = ec_su(xslot8);
@@ -245,7 +275,7 @@ struct EcHandoff {
         int lo[kEcGr];
         unsigned need[kEcGr];                  // all ones where this thread has a k-th granule
 #pragma unroll
-        for (int k = 0; k < kEcGr; ++k) { lo[k] = ec_opaque(rcv_lo[k]); need[k] = ~(unsigned)(lo[k] >> 31); }
+        for (int k = 0; k < kEcGr; ++k) { lo[k] = ec_fresh(rcv_lo[k]); need[k] = ~(unsigned)(lo[k] >> 31); }
         for (unsigned spins = 0;; ++spins) {
             unsigned bad = 0;
 #pragma unroll
@@ -406,26 +436,51 @@ __device__ __forceinline__ float ec_lane_above(float old, float x)          // x
 {
     return __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(old), __float_as_int(x), 0x130, 0xf, 0xf, false));
 }
-// the two cells left (L) and right (R) of a group (own four cells c, plane row at q); dummy = any 8-byte aligned LDS address
+// What a lane needs of ec_nb() in the time loop, worked out once and kept in ONE register per group (EcGroup::nb of
+// the XH kernels): bit 0 = the group is not the last of its grid row, bit 1 = not the first, bits 2.. = float offset,
+// relative to the group's own cells in a plane row, of the single LDS read: -2 without a lane below, +4 without a
+// lane above, minus the group's own offset for the others (the head of the plane: one address for all of them, a conflict-free broadcast whose
+// value is not used).  The loop then spends one shift and two bit-field extracts per group pass and one add and four
+// v_and per field, where selecting on the ec_nb() bits took four v_and + four v_cmp per pass and two adds and six
+// v_cndmask per field.
+__host__ __device__ __forceinline__ int ec_xh_word(int nb, int lo_floats)
+{
+    const int roff = !(nb & kNbL) ? -2 : !(nb & kNbR) ? 4 : -lo_floats;
+    return roff * 4 + ((nb & kNbFirst) ? 0 : 2) + ((nb & kNbLast) ? 0 : 1);
+}
+// the two cells left (L) and right (R) of a group (own four cells c, plane row at q); roff, keep_xy, keep_zw = the three
+// fields of the group's ec_xh_word(): offset of the LDS read, all ones unless first / last of the grid row
 template <bool XH>
-__device__ __forceinline__ void ec_xhalo(const float *q, const float4 &c, const int nb, const float *dummy, float2 &L, float2 &R)
+__device__ __forceinline__ void ec_xhalo(const float *q, const float4 &c, const int roff, const unsigned keep_xy,
+                                         const unsigned keep_zw, float2 &L, float2 &R)
 {
     if (!XH) {
         L = ld2(q - 2); R = ld2(q + 4);
         return;
     }
-    const float2 rd = ld2(!(nb & kNbL) ? q - 2 : !(nb & kNbR) ? q + 4 : dummy);
-    const float ez = (nb & kNbLast) ? 0.f : c.z, ew = (nb & kNbLast) ? 0.f : c.w;
-    const float ex = (nb & kNbFirst) ? 0.f : c.x, ey = (nb & kNbFirst) ? 0.f : c.y;
+    const float2 rd = ld2(q + roff);
+    // a lane at the end of a grid row exports zeros (bit pattern of +0.f) to the lane that starts the next row
+    const float ez = __uint_as_float(__float_as_uint(c.z) & keep_zw), ew = __uint_as_float(__float_as_uint(c.w) & keep_zw);
+    const float ex = __uint_as_float(__float_as_uint(c.x) & keep_xy), ey = __uint_as_float(__float_as_uint(c.y) & keep_xy);
     L.x = ec_lane_below(rd.x, ez); L.y = ec_lane_below(rd.y, ew);
     R.x = ec_lane_above(rd.x, ex); R.y = ec_lane_above(rd.y, ey);
+}
+__device__ __forceinline__ int ec_xh_roff(int xh) { return xh >> 2; }
+__device__ __forceinline__ unsigned ec_xh_keep_xy(int xh) { return (unsigned)((int)((unsigned)xh << 30) >> 31); }
+__device__ __forceinline__ unsigned ec_xh_keep_zw(int xh) { return (unsigned)((int)((unsigned)xh << 31) >> 31); }
+// from the word: one shift and two bit-field extracts per group pass (kept decoded in three registers per group the
+// forward kernel's scalar spills went from 74 to 100)
+template <bool XH>
+__device__ __forceinline__ void ec_xhalo(const float *q, const float4 &c, const int xh, float2 &L, float2 &R)
+{
+    ec_xhalo<XH>(q, c, ec_xh_roff(xh), ec_xh_keep_xy(xh), ec_xh_keep_zw(xh), L, R);
 }
 
 struct EcGroup {
     int cls;                                      // 0: none, 1: interior rows of the slab, 2: boundary rows (stencils reach the halo)
-    int nb;                                       // ec_nb: how the x-neighbours' cells reach this lane
+    int nb;                                       // ec_xh_word: how the x-neighbours' cells reach this lane
     int g, j;                                     // group in the row, grid row
-    int lo;                                       // LDS float offset of the group inside a field plane
+    int lo;                                       // LDS BYTE offset of the group inside a field plane (no shift per pass)
     unsigned gcb;                                 // byte offset of the group inside a [nz][gp] plane (snapshots, materials)
     int xtab, ztab;                               // LDS float offsets of its C-PML table entries (x strip / z strip), or -1
     float4 mL, mM, mMu, mBx, mBz;                 // materials
@@ -482,8 +537,8 @@ __device__ __forceinline__ void ec_update_v(EcGroup &G, const EcCtx &c, const in
 {
     const int PL = ec_su(c.PL);
     const FdK K = c.K;
-    const float *sxx = c.Lf[F_SXX] + lo, *szz = c.Lf[F_SZZ] + lo, *sxz = c.Lf[F_SXZ] + lo;
-    const int nb = XH ? ec_opaque(G.nb) : 0;
+    const float *sxx = ec_at(c.Lf[F_SXX], lo), *szz = ec_at(c.Lf[F_SZZ], lo), *sxz = ec_at(c.Lf[F_SXZ], lo);
+    const int nb = XH ? ec_fresh(G.nb) : 0;
     float4 cxx = ld4(sxx);
     float4 a2 = ld4(sxz);
     float2 Lxx, Rxx, Lxz, Rxz;
@@ -491,8 +546,8 @@ __device__ __forceinline__ void ec_update_v(EcGroup &G, const EcCtx &c, const in
     float4 a3 = ld4(sxz + PL);
     float4 b0 = ld4(szz - PL);
     float4 b1 = ld4(szz), b2 = ld4(szz + PL), b3 = ld4(szz + 2 * PL);
-    ec_xhalo<XH>(sxx, cxx, nb, c.Lf[0], Lxx, Rxx);
-    ec_xhalo<XH>(sxz, a2, nb, c.Lf[0], Lxz, Rxz);
+    ec_xhalo<XH>(sxx, cxx, nb, Lxx, Rxx);
+    ec_xhalo<XH>(sxz, a2, nb, Lxz, Rxz);
 #ifdef EC_PIN
     ec_pin(Lxx, Rxx, Lxz, Rxz);
     ec_pin(cxx, a2, a0, a1);
@@ -518,7 +573,7 @@ __device__ __forceinline__ void ec_update_v(EcGroup &G, const EcCtx &c, const in
         d3[k] = dbw(K, xz[k], xz[k + 1], xz[k + 2], xz[k + 3]);
         d4[k] = dfw(K, comp(b0, k), comp(b1, k), comp(b2, k), comp(b3, k));
     }
-    const int xtab = ec_opaque(G.xtab), ztab = ec_opaque(G.ztab);
+    const int xtab = ec_fresh(G.xtab), ztab = ec_fresh(G.ztab);
     if (xtab >= 0) {
         const EcTabX T = ec_tab_x(c.lpx, xtab);
         float t1[4] = {G.s1.x, G.s1.y, G.s1.z, G.s1.w}, t3[4] = {G.s3.x, G.s3.y, G.s3.z, G.s3.w};
@@ -539,15 +594,15 @@ __device__ __forceinline__ void ec_update_v(EcGroup &G, const EcCtx &c, const in
         }
         G.s2 = make_float4(t2[0], t2[1], t2[2], t2[3]); G.s4 = make_float4(t4[0], t4[1], t4[2], t4[3]);
     }
-    const float4 vxo = ld4(c.Lf[F_VX] + lo), vzo = ld4(c.Lf[F_VZ] + lo);
+    const float4 vxo = ld4(ec_at(c.Lf[F_VX], lo)), vzo = ld4(ec_at(c.Lf[F_VZ], lo));
     S4 = make_float4(d1[0] + d2[0], d1[1] + d2[1], d1[2] + d2[2], d1[3] + d2[3]);
     S5 = make_float4(d3[0] + d4[0], d3[1] + d4[1], d3[2] + d4[2], d3[3] + d4[3]);
     o0 = make_float4(fmaf(G.mBx.x, S4.x, vxo.x), fmaf(G.mBx.y, S4.y, vxo.y), fmaf(G.mBx.z, S4.z, vxo.z),
                      fmaf(G.mBx.w, S4.w, vxo.w));
     o1 = make_float4(fmaf(G.mBz.x, S5.x, vzo.x), fmaf(G.mBz.y, S5.y, vzo.y), fmaf(G.mBz.z, S5.z, vzo.z),
                      fmaf(G.mBz.w, S5.w, vzo.w));
-    st4(c.Lf[F_VX] + lo, o0);
-    st4(c.Lf[F_VZ] + lo, o1);
+    st4(ec_at(c.Lf[F_VX], lo), o0);
+    st4(ec_at(c.Lf[F_VZ], lo), o1);
 }
 
 // S update (reads velocities from LDS, writes the group's stresses in place); `amp` = source term
@@ -558,15 +613,15 @@ __device__ __forceinline__ void ec_update_s(EcGroup &G, const EcCtx &c, const in
 {
     const int PL = ec_su(c.PL);
     const FdK K = c.K;
-    const float *vx = c.Lf[F_VX] + lo, *vz = c.Lf[F_VZ] + lo;
-    const int nb = XH ? ec_opaque(G.nb) : 0;
+    const float *vx = ec_at(c.Lf[F_VX], lo), *vz = ec_at(c.Lf[F_VZ], lo);
+    const int nb = XH ? ec_fresh(G.nb) : 0;
     float4 b1 = ld4(vx);
     float4 a2 = ld4(vz);
     float2 Lvx, Rvx, Lvz, Rvz;
     float4 a0 = ld4(vz - 2 * PL), a1 = ld4(vz - PL), a3 = ld4(vz + PL);
     float4 b0 = ld4(vx - PL), b2 = ld4(vx + PL), b3 = ld4(vx + 2 * PL);
-    ec_xhalo<XH>(vx, b1, nb, c.Lf[0], Lvx, Rvx);
-    ec_xhalo<XH>(vz, a2, nb, c.Lf[0], Lvz, Rvz);
+    ec_xhalo<XH>(vx, b1, nb, Lvx, Rvx);
+    ec_xhalo<XH>(vz, a2, nb, Lvz, Rvz);
 #ifdef EC_PIN
     ec_pin(Lvx, Rvx, Lvz, Rvz);
     ec_pin(b1, a2, a0, a1);
@@ -582,7 +637,7 @@ __device__ __forceinline__ void ec_update_s(EcGroup &G, const EcCtx &c, const in
         e3[k] = dfw(K, comp(b0, k), comp(b1, k), comp(b2, k), comp(b3, k));
         e4[k] = dfw(K, zv[k + 1], zv[k + 2], zv[k + 3], zv[k + 4]);
     }
-    const int xtab = ec_opaque(G.xtab), ztab = ec_opaque(G.ztab);
+    const int xtab = ec_fresh(G.xtab), ztab = ec_fresh(G.ztab);
     if (xtab >= 0) {
         const EcTabX T = ec_tab_x(c.lpx, xtab);
         float t5[4] = {G.s5.x, G.s5.y, G.s5.z, G.s5.w}, t8[4] = {G.s8.x, G.s8.y, G.s8.z, G.s8.w};
@@ -603,7 +658,7 @@ __device__ __forceinline__ void ec_update_s(EcGroup &G, const EcCtx &c, const in
         }
         G.s6 = make_float4(t6[0], t6[1], t6[2], t6[3]); G.s7 = make_float4(t7[0], t7[1], t7[2], t7[3]);
     }
-    const float4 oxx = ld4(c.Lf[F_SXX] + lo), ozz = ld4(c.Lf[F_SZZ] + lo), oxz = ld4(c.Lf[F_SXZ] + lo);
+    const float4 oxx = ld4(ec_at(c.Lf[F_SXX], lo)), ozz = ld4(ec_at(c.Lf[F_SZZ], lo)), oxz = ld4(ec_at(c.Lf[F_SXZ], lo));
     float rxx[4], rzz[4], rxz[4], s3v[4];
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
@@ -618,9 +673,9 @@ __device__ __forceinline__ void ec_update_s(EcGroup &G, const EcCtx &c, const in
     S3 = make_float4(s3v[0], s3v[1], s3v[2], s3v[3]);
     o0 = make_float4(rzz[0], rzz[1], rzz[2], rzz[3]);            // published: szz, sxz
     o1 = make_float4(rxz[0], rxz[1], rxz[2], rxz[3]);
-    st4(c.Lf[F_SXX] + lo, make_float4(rxx[0], rxx[1], rxx[2], rxx[3]));
-    st4(c.Lf[F_SZZ] + lo, o0);
-    st4(c.Lf[F_SXZ] + lo, o1);
+    st4(ec_at(c.Lf[F_SXX], lo), make_float4(rxx[0], rxx[1], rxx[2], rxx[3]));
+    st4(ec_at(c.Lf[F_SZZ], lo), o0);
+    st4(ec_at(c.Lf[F_SXZ], lo), o1);
 }
 
 template <bool SAVE, int NG, bool AG, bool XH = false>
@@ -667,8 +722,8 @@ __global__ __launch_bounds__(kEcThreads) void el_cluster_fwd(const EcParams p)
         g.g = sl.g;
         g.j = r0 + lrw;
         g.cls = sl.cls;                      // 1, 3: stencils stay inside the own rows
-        g.nb = XH ? ec_nb(t + q * kEcThreads, R, p.ng, NG * kEcThreads) : 0;
-        g.lo = (lrw + 2) * PL + 4 + 4 * g.g;
+        g.lo = 4 * ((lrw + 2) * PL + 4 + 4 * g.g);
+        g.nb = XH ? ec_xh_word(ec_nb(t + q * kEcThreads, R, p.ng, NG * kEcThreads), g.lo / 4) : 0;
         const unsigned gcc = (unsigned)g.j * p.gp + 4 * g.g;
         g.gcb = 4u * gcc;
         g.mL = g.mM = g.mMu = g.mBx = g.mBz = zero4;
@@ -754,13 +809,13 @@ __global__ __launch_bounds__(kEcThreads) void el_cluster_fwd(const EcParams p)
     auto source_amp = [&](const EcGroup &g, int q, int n) -> float4 {
         float4 a = zero4;
         if (!slow) {
-            if (ec_opaque(tsq) == q) {
+            if (ec_fresh(tsq) == q) {
                 // f of this step arrived during the last one; request the next (a global load in the update
                 // itself would put a memory round trip on the workgroup's critical path every step)
                 const unsigned amp = __float_as_uint(tw * tnext);
                 a = make_float4(__uint_as_float(amp & tm0), __uint_as_float(amp & tm1), __uint_as_float(amp & tm2),
                                 __uint_as_float(amp & tm3));
-                if (n + 1 < p.n_last) tnext = *ec_at(f_shot + (n + 1) * f_step, ec_opaque(tsrc4));
+                if (n + 1 < p.n_last) tnext = *ec_at(f_shot + (n + 1) * f_step, ec_fresh(tsrc4));
             }
         } else if ((src_mask >> q) & 1) {   // several sources in this thread's cells: rescan the list every step
             float av[4] = {0.f, 0.f, 0.f, 0.f};
@@ -782,37 +837,39 @@ __global__ __launch_bounds__(kEcThreads) void el_cluster_fwd(const EcParams p)
     const int nsteps = p.n_last - p.n_first;
     // Snapshot terms are stored right after they are produced; the interior update that follows gives
     // them time to retire before the next poll is issued (vector memory operations retire in order).
-    float *S_shot = SAVE ? p.S + (long long)s * 5 * ncell : nullptr;   // step n: S_shot + (n - s_first) * s_step
+    // snapshots of the step under way: advanced by s_step at the end of a step (the product (n - s_first) * s_step, formed
+    // from spilled scalars twice per step, cost three v_readlane each time)
+    float *S_n = SAVE ? p.S + (long long)s * 5 * ncell + (long long)(p.n_first - p.s_first) * p.s_step : nullptr;
     auto do_v = [&](EcGroup &g, int n, int it, bool edge) {
         float4 S4, S5, o0, o1;
-        const int lo = ec_opaque(g.lo);
+        const int lo = ec_fresh(g.lo);
         if (edge) {
-            const int jq = ec_opaque(g.j);
+            const int jq = ec_fresh(g.j);
             ec_update_v<true, XH>(g, c, lo, jq, S4, S5, o0, o1);
-            if (do_x && !(kDbg(p) & 16)) X.template publish<AG>(jq - r0, ec_opaque(g.g), 0, (unsigned)(2 * it + 1), it & 1, o0, o1);
+            if (do_x && !(kDbg(p) & 16)) X.template publish<AG>(jq - r0, ec_fresh(g.g), 0, (unsigned)(2 * it + 1), it & 1, o0, o1);
         } else {
             ec_update_v<false, XH>(g, c, lo, 2, S4, S5, o0, o1);
         }
         if (SAVE && !(kDbg(p) & 2)) {
-            float *Sn = S_shot + (long long)(n - p.s_first) * p.s_step;
-            const unsigned gcb = ec_opaque(g.gcb), nc = ec_su(ncell);
+            float *Sn = S_n;
+            const unsigned gcb = ec_fresh(g.gcb), nc = ec_su(ncell);
             mifwi::stnt4(ec_at(Sn + 3 * (long long)nc, gcb), S4); mifwi::stnt4(ec_at(Sn + 4 * (long long)nc, gcb), S5);
         }
     };
     auto do_s = [&](EcGroup &g, int q, int n, int it, bool edge) {
         float4 S1, S2, S3, o0, o1;
-        const int lo = ec_opaque(g.lo);
+        const int lo = ec_fresh(g.lo);
         const float4 amp = source_amp(g, q, n);
         if (edge) {
-            const int jq = ec_opaque(g.j);
+            const int jq = ec_fresh(g.j);
             ec_update_s<true, XH>(g, c, lo, jq, amp, S1, S2, S3, o0, o1);
-            if (do_x && !(kDbg(p) & 16)) X.template publish<AG>(jq - r0, ec_opaque(g.g), 1, (unsigned)(2 * it + 2), it & 1, o0, o1);
+            if (do_x && !(kDbg(p) & 16)) X.template publish<AG>(jq - r0, ec_fresh(g.g), 1, (unsigned)(2 * it + 2), it & 1, o0, o1);
         } else {
             ec_update_s<false, XH>(g, c, lo, 2, amp, S1, S2, S3, o0, o1);
         }
         if (SAVE && !(kDbg(p) & 2)) {
-            float *Sn = S_shot + (long long)(n - p.s_first) * p.s_step;
-            const unsigned gcb = ec_opaque(g.gcb), nc = ec_su(ncell);
+            float *Sn = S_n;
+            const unsigned gcb = ec_fresh(g.gcb), nc = ec_su(ncell);
             mifwi::stnt4(ec_at(Sn, gcb), S1); mifwi::stnt4(ec_at(Sn + (long long)nc, gcb), S2);
             mifwi::stnt4(ec_at(Sn + 2 * (long long)nc, gcb), S3);
         }
@@ -829,7 +886,7 @@ __global__ __launch_bounds__(kEcThreads) void el_cluster_fwd(const EcParams p)
         const bool poll_s = do_x && it > 0 && !(kDbg(p) & 32);
 #pragma unroll
         for (int q = 0; q < NG; ++q) {
-            if ((!EC_LATE_INTERIOR || q == 0) && ec_opaque(G[q].cls) == 1) do_v(G[q], n, it, false);
+            if ((!EC_LATE_INTERIOR || q == 0) && ec_fresh(G[q].cls) == 1) do_v(G[q], n, it, false);
             __builtin_amdgcn_sched_barrier(0);             // one group at a time: bounds the register peak
         }
         EC_STAMP(1);
@@ -842,7 +899,7 @@ __global__ __launch_bounds__(kEcThreads) void el_cluster_fwd(const EcParams p)
         EC_STAMP(3);
 #pragma unroll
         for (int q = 0; q < NG; ++q) {
-            const int cls = ec_opaque(G[q].cls);
+            const int cls = ec_fresh(G[q].cls);
             if (cls == 2) do_v(G[q], n, it, true);
             else if (q > 0 && cls == 3) do_v(G[q], n, it, false);          // late interior (ec_slot)
             __builtin_amdgcn_sched_barrier(0);
@@ -854,7 +911,7 @@ __global__ __launch_bounds__(kEcThreads) void el_cluster_fwd(const EcParams p)
         const bool poll_v = do_x && !(kDbg(p) & 32);
 #pragma unroll
         for (int q = 0; q < NG; ++q) {
-            if ((!EC_LATE_INTERIOR || q == 0) && ec_opaque(G[q].cls) == 1) do_s(G[q], q, n, it, false);
+            if ((!EC_LATE_INTERIOR || q == 0) && ec_fresh(G[q].cls) == 1) do_s(G[q], q, n, it, false);
             __builtin_amdgcn_sched_barrier(0);
         }
         EC_STAMP(6);
@@ -867,7 +924,7 @@ __global__ __launch_bounds__(kEcThreads) void el_cluster_fwd(const EcParams p)
         if (p.rec_vx != nullptr && !(kDbg(p) & 8)) {
             if (!slow) {
                 const long long ro = ((long long)n * p.nshot + s) * p.nrec;
-                const int sl = ec_opaque(smp_lo);
+                const int sl = ec_fresh(smp_lo);
                 if (sl >= 0) {
                     *ec_at(p.rec_vx + ro, 4u * t) = fmaf(smp_w, c.Lf[F_VX][sl], 0.f);
                     *ec_at(p.rec_vz + ro, 4u * t) = fmaf(smp_w, c.Lf[F_VZ][sl], 0.f);
@@ -894,7 +951,7 @@ __global__ __launch_bounds__(kEcThreads) void el_cluster_fwd(const EcParams p)
         EC_STAMP(9);
 #pragma unroll
         for (int q = 0; q < NG; ++q) {
-            const int cls = ec_opaque(G[q].cls);
+            const int cls = ec_fresh(G[q].cls);
             if (cls == 2) do_s(G[q], q, n, it, true);
             else if (q > 0 && cls == 3) do_s(G[q], q, n, it, false);
             __builtin_amdgcn_sched_barrier(0);
@@ -909,6 +966,7 @@ __global__ __launch_bounds__(kEcThreads) void el_cluster_fwd(const EcParams p)
             __syncthreads();                               // D: all stresses of the slab are in LDS
         }
         EC_STAMP(11);
+        if (SAVE) S_n += p.s_step;
     }
 
     // ---- the own rows of the five fields and the memory variables go back to the global state -----
@@ -919,7 +977,7 @@ __global__ __launch_bounds__(kEcThreads) void el_cluster_fwd(const EcParams p)
         if (g.cls == 0) continue;
         const long long o = (long long)(g.j + 2) * p.pitch + 4 + 4 * g.g;
 #pragma unroll
-        for (int k = 0; k < 5; ++k) st4(gf + k * p.field_stride + o, ld4(c.Lf[k] + g.lo));
+        for (int k = 0; k < 5; ++k) st4(gf + k * p.field_stride + o, ld4(ec_at(c.Lf[k], g.lo)));
         const int xs_off = strip_x(g.g), zs = strip_z(g.j);
         if (xs_off >= 0) {
             float *q2 = p.psix + (long long)s * p.psix_shot + (long long)g.j * p.wx + xs_off;
@@ -1039,8 +1097,8 @@ __global__ void ec_build_slab_lists(const int *rec_cell, int nrec, int nz, int n
 
 struct EaGroup {
     int cls;                                      // 0: none, 1: interior rows of the slab, 2: boundary rows
-    int nb;                                       // ec_nb: how the x-neighbours' cells reach this lane
-    int g, j, lo;                                 // group in the row, grid row, LDS float offset inside a plane
+    int nb;                                       // ec_xh_word: how the x-neighbours' cells reach this lane
+    int g, j, lo;                                 // group in the row, grid row, LDS byte offset inside a plane
     int xsl, zsl;                                 // LDS float offset of the group's psi-bar slot, or -1
     float4 bxx, bzz, bxz, vx, vz;                 // adjoint fields
     float4 a0, a1, a2, a3, a4;                    // gradient accumulators (M_L, M_M, M_MU, M_BX, M_BZ order = index)
@@ -1100,9 +1158,9 @@ __global__ __launch_bounds__(kEcThreads) void el_cluster_adj(const EaParams p)
         const int lrw = sl.lrw;
         g.g = sl.g;
         g.j = r0 + lrw;
-        g.lo = (lrw + 2) * PL + 4 + 4 * g.g;
+        g.lo = 4 * ((lrw + 2) * PL + 4 + 4 * g.g);
         g.cls = sl.cls;
-        g.nb = XH ? ec_nb(t + q * kEcThreads, R, p.ng, NG * kEcThreads) : 0;
+        g.nb = XH ? ec_xh_word(ec_nb(t + q * kEcThreads, R, p.ng, NG * kEcThreads), g.lo / 4) : 0;
         g.bxx = g.bzz = g.bxz = g.vx = g.vz = zero4;
         g.a0 = g.a1 = g.a2 = g.a3 = g.a4 = zero4;
         g.S1 = g.S2 = g.S3 = g.S4 = g.S5 = zero4;
@@ -1215,19 +1273,19 @@ __global__ __launch_bounds__(kEcThreads) void el_cluster_adj(const EaParams p)
     auto cell_bytes = [&](int jq, int gq) { return 4u * (unsigned)(jq * p.gp + 4 * gq); };
     const float *S_shot = p.S + (long long)s * 5 * ncell;           // step n: S_shot + (n - s_first) * s_step
     auto request_S = [&](EaGroup &g, int n) {
-        if (ec_opaque(g.cls) == 0 || (kDbg(p) & 2)) return;
+        if (ec_fresh(g.cls) == 0 || (kDbg(p) & 2)) return;
         const unsigned ncell = ec_su(ncell_);
         const float *Sn = S_shot + (long long)(n - p.s_first) * p.s_step;
-        const unsigned gcb = cell_bytes(ec_opaque(g.j), ec_opaque(g.g));
+        const unsigned gcb = cell_bytes(ec_fresh(g.j), ec_fresh(g.g));
         g.S1 = mifwi::ldnt4(ec_at(Sn, gcb)); g.S2 = mifwi::ldnt4(ec_at(Sn + (long long)ncell, gcb));
         g.S3 = mifwi::ldnt4(ec_at(Sn + 2 * (long long)ncell, gcb));
         g.S4 = mifwi::ldnt4(ec_at(Sn + 3 * (long long)ncell, gcb)); g.S5 = mifwi::ldnt4(ec_at(Sn + 4 * (long long)ncell, gcb));
     };
     auto request_amp = [&](int n) {
-        if (ec_opaque(inj_lo) >= 0 && n >= p.n_last) {
+        if (ec_fresh(inj_lo) >= 0 && n >= p.n_last) {
             const long long o = ((long long)n * p.nshot + s) * p.nrec;
-            amp_x = *ec_at(p.g_vx + o, ec_opaque(inj_id4));
-            amp_z = *ec_at(p.g_vz + o, ec_opaque(inj_id4));
+            amp_x = *ec_at(p.g_vx + o, ec_fresh(inj_id4));
+            amp_z = *ec_at(p.g_vz + o, ec_fresh(inj_id4));
         }
     };
 
@@ -1237,24 +1295,24 @@ __global__ __launch_bounds__(kEcThreads) void el_cluster_adj(const EaParams p)
     // 600-800 clocks away, and a phase that loaded them group by group paid that twice per wave.
     auto mats_a = [&](EaGroup &g, float4 &Ls, float4 &Ms, float4 &mus) {
         const unsigned ncell = ec_su(ncell_);
-        const unsigned gcb = cell_bytes(ec_opaque(g.j), ec_opaque(g.g));
+        const unsigned gcb = cell_bytes(ec_fresh(g.j), ec_fresh(g.g));
         Ls = ld4(ec_at(p.mat + M_L * ncell, gcb)); Ms = ld4(ec_at(p.mat + M_M * ncell, gcb));
         mus = ld4(ec_at(p.mat + M_MU * ncell, gcb));
     };
     auto mats_c = [&](EaGroup &g, float4 &bxs, float4 &bzs) {
         const unsigned ncell = ec_su(ncell_);
-        const unsigned gcb = cell_bytes(ec_opaque(g.j), ec_opaque(g.g));
+        const unsigned gcb = cell_bytes(ec_fresh(g.j), ec_fresh(g.g));
         bxs = ld4(ec_at(p.mat + M_BX * ncell, gcb)); bzs = ld4(ec_at(p.mat + M_BZ * ncell, gcb));
     };
     auto phase_a = [&](EaGroup &g, int n, int it, const int cls, const float4 &Ls, const float4 &Ms, const float4 &mus) {
         const int fsz = ec_su(fsz_), xsz = ec_su(xsz_), zsz = ec_su(zsz_);
-        const int lo = ec_opaque(g.lo), gq = ec_opaque(g.g), jq = ec_opaque(g.j);
+        const int lo = ec_fresh(g.lo), gq = ec_fresh(g.g), jq = ec_fresh(g.j);
         // adjoint of szz(0,.) is discarded.  Component-wise selects: a whole-vector select was compiled
         // into a two-entry table in scratch memory (a vector-memory load per use)
         const bool top = p.fsurf && jq == 0;
         const float4 bzz = make_float4(top ? 0.f : g.bzz.x, top ? 0.f : g.bzz.y, top ? 0.f : g.bzz.z,
                                        top ? 0.f : g.bzz.w);
-        const int src = ec_opaque(g.src);
+        const int src = ec_fresh(g.src);
         if (p.grad_f != nullptr && src >= 0) {
             float *out = p.grad_f + ((long long)n * p.nshot + s) * p.nsrc;
             // sxx + szz of the four cells, selected with compile-time lane indices: a run-time index into a
@@ -1288,7 +1346,7 @@ __global__ __launch_bounds__(kEcThreads) void el_cluster_adj(const EaParams p)
             e3[c] = comp(mus, c) * comp(g.bxz, c);
             e4[c] = e3[c];
         }
-        const int xsl = ec_opaque(g.xsl), zsl = ec_opaque(g.zsl);
+        const int xsl = ec_fresh(g.xsl), zsl = ec_fresh(g.zsl);
         if (xsl >= 0) {
             const EcTabX T = ec_tab_x(lpx, 24 * gq);
             float *sl = lxs + xsl;
@@ -1316,37 +1374,44 @@ __global__ __launch_bounds__(kEcThreads) void el_cluster_adj(const EaParams p)
             st4(sl + 3 * zsz, make_float4(n7[0], n7[1], n7[2], n7[3]));
         }
         const float4 E2 = make_float4(e2[0], e2[1], e2[2], e2[3]), E3 = make_float4(e3[0], e3[1], e3[2], e3[3]);
-        st4(pln + lo, make_float4(e1[0], e1[1], e1[2], e1[3]));
-        st4(pln + fsz + lo, E2);
-        st4(pln + 2 * fsz + lo, E3);
-        st4(pln + 3 * fsz + lo, make_float4(e4[0], e4[1], e4[2], e4[3]));
+        st4(ec_at(pln, lo), make_float4(e1[0], e1[1], e1[2], e1[3]));
+        st4(ec_at(pln + fsz, lo), E2);
+        st4(ec_at(pln + 2 * fsz, lo), E3);
+        st4(ec_at(pln + 3 * fsz, lo), make_float4(e4[0], e4[1], e4[2], e4[3]));
         if (do_x && cls == 2) X.template publish<AG>(jq - r0, gq, 0, (unsigned)(2 * it + 1), it & 1, E2, E3);
     };
     // B: v_bar -= stencils(E)
     auto phase_b = [&](EaGroup &g) {
         const int fsz = ec_su(fsz_), PL = ec_su(PL_);
-        const int lo = ec_opaque(g.lo), gq = ec_opaque(g.g);
-        const float *E1 = pln + lo, *E2 = pln + fsz + lo, *E3 = pln + 2 * fsz + lo, *E4 = pln + 3 * fsz + lo;
-        const int nb = XH ? ec_opaque(g.nb) : 0;
+        const int lo = ec_fresh(g.lo), gq = ec_fresh(g.g);
+        const float *E1 = ec_at(pln, lo), *E2 = ec_at(pln + fsz, lo), *E3 = ec_at(pln + 2 * fsz, lo),
+                    *E4 = ec_at(pln + 3 * fsz, lo);
+        const int nb = XH ? ec_fresh(g.nb) : 0;
         const float4 c1 = ld4(E1);
         const float4 c4 = ld4(E4);
         const float4 t0 = ld4(E3 - 2 * PL), t1 = ld4(E3 - PL), t2 = ld4(E3), t3 = ld4(E3 + PL);
         const float4 u0 = ld4(E2 - PL), u1 = ld4(E2), u2 = ld4(E2 + PL), u3 = ld4(E2 + 2 * PL);
         float2 L1, R1, L4, R4;
-        ec_xhalo<XH>(E1, c1, nb, pln, L1, R1);
-        ec_xhalo<XH>(E4, c4, nb, pln, L4, R4);
+        ec_xhalo<XH>(E1, c1, nb, L1, R1);
+        ec_xhalo<XH>(E4, c4, nb, L4, R4);
         const float x1[8] = {L1.x, L1.y, c1.x, c1.y, c1.z, c1.w, R1.x, R1.y};
         const float x4[8] = {L4.x, L4.y, c4.x, c4.y, c4.z, c4.w, R4.x, R4.y};
         float nvx[4], nvz[4];
 #pragma unroll
-        for (int c = 0; c < 4; ++c) {
-            const float dx1 = dfw(K, x1[c + 1], x1[c + 2], x1[c + 3], x1[c + 4]);
-            const float dz3 = dbw(K, comp(t0, c), comp(t1, c), comp(t2, c), comp(t3, c));
-            const float dz2 = dfw(K, comp(u0, c), comp(u1, c), comp(u2, c), comp(u3, c));
-            const float dx4 = dbw(K, x4[c], x4[c + 1], x4[c + 2], x4[c + 3]);
-            nvx[c] = comp(g.vx, c) - (dx1 + dz3);
-            nvz[c] = comp(g.vz, c) - (dz2 + dx4);
-            if (4 * gq + c >= p.nx) { nvx[c] = 0.f; nvz[c] = 0.f; }
+        for (int h = 0; h < 4; h += 2) {
+            const ec_f2 dx1 = dfw2(K, ec_2(x1[h + 1], x1[h + 2]), ec_2(x1[h + 2], x1[h + 3]), ec_2(x1[h + 3], x1[h + 4]),
+                                   ec_2(x1[h + 4], x1[h + 5]));
+            const ec_f2 dz3 = dbw2(K, ec_2(t0, h), ec_2(t1, h), ec_2(t2, h), ec_2(t3, h));
+            const ec_f2 dz2 = dfw2(K, ec_2(u0, h), ec_2(u1, h), ec_2(u2, h), ec_2(u3, h));
+            const ec_f2 dx4 = dbw2(K, ec_2(x4[h], x4[h + 1]), ec_2(x4[h + 1], x4[h + 2]), ec_2(x4[h + 2], x4[h + 3]),
+                                   ec_2(x4[h + 3], x4[h + 4]));
+            const ec_f2 vx2 = ec_2(g.vx, h) - (dx1 + dz3), vz2 = ec_2(g.vz, h) - (dz2 + dx4);
+            nvx[h] = vx2.x; nvx[h + 1] = vx2.y; nvz[h] = vz2.x; nvz[h + 1] = vz2.y;
+        }
+        if (ec_su(p.nx & 3)) {                             // cells past the grid's last column (a group's first cell never is)
+#pragma unroll
+            for (int c = 1; c < 4; ++c)
+                if (4 * gq + c >= p.nx) { nvx[c] = 0.f; nvz[c] = 0.f; }
         }
         g.vx = make_float4(nvx[0], nvx[1], nvx[2], nvx[3]);
         g.vz = make_float4(nvz[0], nvz[1], nvz[2], nvz[3]);
@@ -1354,14 +1419,14 @@ __global__ __launch_bounds__(kEcThreads) void el_cluster_adj(const EaParams p)
     // C: D from the new v_bar -> planes [D1 D2 D4 D3]; boundary rows publish D2,D4; all five gradient accumulators
     auto phase_c = [&](EaGroup &g, int it, const int cls, const float4 &bxs, const float4 &bzs) {
         const int fsz = ec_su(fsz_), xsz = ec_su(xsz_), zsz = ec_su(zsz_);
-        const int lo = ec_opaque(g.lo), gq = ec_opaque(g.g), jq = ec_opaque(g.j);
+        const int lo = ec_fresh(g.lo), gq = ec_fresh(g.g), jq = ec_fresh(g.j);
         float d1[4], d2[4], d3[4], d4[4];
 #pragma unroll
         for (int c = 0; c < 4; ++c) {
             d1[c] = comp(bxs, c) * comp(g.vx, c); d2[c] = d1[c];
             d3[c] = comp(bzs, c) * comp(g.vz, c); d4[c] = d3[c];
         }
-        const int xsl = ec_opaque(g.xsl), zsl = ec_opaque(g.zsl);
+        const int xsl = ec_fresh(g.xsl), zsl = ec_fresh(g.zsl);
         if (xsl >= 0) {
             const EcTabX T = ec_tab_x(lpx, 24 * gq);
             float *sl = lxs + xsl;
@@ -1389,10 +1454,10 @@ __global__ __launch_bounds__(kEcThreads) void el_cluster_adj(const EaParams p)
             st4(sl + zsz, make_float4(n4[0], n4[1], n4[2], n4[3]));
         }
         const float4 D2 = make_float4(d2[0], d2[1], d2[2], d2[3]), D4 = make_float4(d4[0], d4[1], d4[2], d4[3]);
-        st4(pln + lo, make_float4(d1[0], d1[1], d1[2], d1[3]));
-        st4(pln + fsz + lo, D2);
-        st4(pln + 2 * fsz + lo, D4);
-        st4(pln + 3 * fsz + lo, make_float4(d3[0], d3[1], d3[2], d3[3]));
+        st4(ec_at(pln, lo), make_float4(d1[0], d1[1], d1[2], d1[3]));
+        st4(ec_at(pln + fsz, lo), D2);
+        st4(ec_at(pln + 2 * fsz, lo), D4);
+        st4(ec_at(pln + 3 * fsz, lo), make_float4(d3[0], d3[1], d3[2], d3[3]));
         if (do_x && cls == 2) X.template publish<AG>(jq - r0, gq, 1, (unsigned)(2 * it + 2), it & 1, D2, D4);
         // gradients (oracle order): Ms, Ls, mus from the old sigma_bar; bxs, bzs from the new v_bar
         const bool top = p.fsurf && jq == 0;
@@ -1414,31 +1479,33 @@ __global__ __launch_bounds__(kEcThreads) void el_cluster_adj(const EaParams p)
     // D: sigma_bar -= stencils(D) (+ transposed free-surface mirroring on grid rows 0 and 1)
     auto phase_d = [&](EaGroup &g, const bool edge) {
         const int fsz = ec_su(fsz_), PL = ec_su(PL_);
-        const int lo = ec_opaque(g.lo), gq = ec_opaque(g.g);
-        const float *D1 = pln + lo, *D2 = pln + fsz + lo, *D4 = pln + 2 * fsz + lo, *D3 = pln + 3 * fsz + lo;
-        const int nb = XH ? ec_opaque(g.nb) : 0;
+        const int lo = ec_fresh(g.lo), gq = ec_fresh(g.g);
+        const float *D1 = ec_at(pln, lo), *D2 = ec_at(pln + fsz, lo), *D4 = ec_at(pln + 2 * fsz, lo),
+                    *D3 = ec_at(pln + 3 * fsz, lo);
+        const int nb = XH ? ec_fresh(g.nb) : 0;
         const float4 c1 = ld4(D1);
         const float4 c3 = ld4(D3);
         const float4 u0 = ld4(D2 - PL), u1 = ld4(D2), u2 = ld4(D2 + PL), u3 = ld4(D2 + 2 * PL);
         const float4 t0 = ld4(D4 - 2 * PL), t1 = ld4(D4 - PL), t2 = ld4(D4), t3 = ld4(D4 + PL);
         float2 L1, R1, L3, R3;
-        ec_xhalo<XH>(D1, c1, nb, pln, L1, R1);
-        ec_xhalo<XH>(D3, c3, nb, pln, L3, R3);
+        ec_xhalo<XH>(D1, c1, nb, L1, R1);
+        ec_xhalo<XH>(D3, c3, nb, L3, R3);
         const float x1[8] = {L1.x, L1.y, c1.x, c1.y, c1.z, c1.w, R1.x, R1.y};
         const float x3[8] = {L3.x, L3.y, c3.x, c3.y, c3.z, c3.w, R3.x, R3.y};
         float nxx[4], nzz[4], nxz[4];
 #pragma unroll
-        for (int c = 0; c < 4; ++c) {
-            const float dx1 = dbw(K, x1[c], x1[c + 1], x1[c + 2], x1[c + 3]);
-            const float dz2 = dfw(K, comp(u0, c), comp(u1, c), comp(u2, c), comp(u3, c));
-            const float dx3 = dfw(K, x3[c + 1], x3[c + 2], x3[c + 3], x3[c + 4]);
-            const float dz4 = dbw(K, comp(t0, c), comp(t1, c), comp(t2, c), comp(t3, c));
-            nxx[c] = comp(g.bxx, c) - dx1;
-            nxz[c] = comp(g.bxz, c) - (dz2 + dx3);
-            nzz[c] = comp(g.bzz, c) - dz4;
+        for (int h = 0; h < 4; h += 2) {
+            const ec_f2 dx1 = dbw2(K, ec_2(x1[h], x1[h + 1]), ec_2(x1[h + 1], x1[h + 2]), ec_2(x1[h + 2], x1[h + 3]),
+                                   ec_2(x1[h + 3], x1[h + 4]));
+            const ec_f2 dz2 = dfw2(K, ec_2(u0, h), ec_2(u1, h), ec_2(u2, h), ec_2(u3, h));
+            const ec_f2 dx3 = dfw2(K, ec_2(x3[h + 1], x3[h + 2]), ec_2(x3[h + 2], x3[h + 3]), ec_2(x3[h + 3], x3[h + 4]),
+                                   ec_2(x3[h + 4], x3[h + 5]));
+            const ec_f2 dz4 = dbw2(K, ec_2(t0, h), ec_2(t1, h), ec_2(t2, h), ec_2(t3, h));
+            const ec_f2 xx2 = ec_2(g.bxx, h) - dx1, xz2 = ec_2(g.bxz, h) - (dz2 + dx3), zz2 = ec_2(g.bzz, h) - dz4;
+            nxx[h] = xx2.x; nxx[h + 1] = xx2.y; nxz[h] = xz2.x; nxz[h + 1] = xz2.y; nzz[h] = zz2.x; nzz[h + 1] = zz2.y;
         }
         if (edge && p.fsurf) {
-            const int jq = ec_opaque(g.j);
+            const int jq = ec_fresh(g.j);
             if (jq < 2) {
                 // grid rows 0 and 1 are local rows 2 and 3 of slab 0
                 const float4 r0d2 = ld4(pln + fsz + 2 * PL + 4 + 4 * gq), r1d2 = ld4(pln + fsz + 3 * PL + 4 + 4 * gq);
@@ -1450,9 +1517,11 @@ __global__ __launch_bounds__(kEcThreads) void el_cluster_adj(const EaParams p)
                 }
             }
         }
+        if (ec_su(p.nx & 3)) {                             // as in phase B
 #pragma unroll
-        for (int c = 0; c < 4; ++c)
-            if (4 * gq + c >= p.nx) { nxx[c] = 0.f; nxz[c] = 0.f; nzz[c] = 0.f; }
+            for (int c = 1; c < 4; ++c)
+                if (4 * gq + c >= p.nx) { nxx[c] = 0.f; nxz[c] = 0.f; nzz[c] = 0.f; }
+        }
         g.bxx = make_float4(nxx[0], nxx[1], nxx[2], nxx[3]);
         g.bzz = make_float4(nzz[0], nzz[1], nzz[2], nzz[3]);
         g.bxz = make_float4(nxz[0], nxz[1], nxz[2], nxz[3]);
@@ -1476,14 +1545,14 @@ __global__ __launch_bounds__(kEcThreads) void el_cluster_adj(const EaParams p)
 #pragma unroll
         for (int qq = 0; qq < NG; ++qq) {
             const int q = EA_PUBLISH_FIRST ? NG - 1 - qq : qq;
-            if (ec_opaque(G[q].cls) != 0) mats_a(G[q], mL[q], mM[q], mMu[q]);
+            if (ec_fresh(G[q].cls) != 0) mats_a(G[q], mL[q], mM[q], mMu[q]);
         }
         __builtin_amdgcn_sched_barrier(0);
 #endif
 #pragma unroll
         for (int qq = 0; qq < NG; ++qq) {
             const int q = EA_PUBLISH_FIRST ? NG - 1 - qq : qq;     // the second slot holds the rows that publish (ec_slot)
-            const int cls = ec_opaque(G[q].cls);
+            const int cls = ec_fresh(G[q].cls);
 #if !EA_MATS_AHEAD_A
             if (cls != 0) mats_a(G[q], mL[q], mM[q], mMu[q]);
 #endif
@@ -1498,7 +1567,7 @@ __global__ __launch_bounds__(kEcThreads) void el_cluster_adj(const EaParams p)
                 if (p.src_cell[(long long)s * p.nsrc + e] < 0) p.grad_f[((long long)n * p.nshot + s) * p.nsrc + e] = 0.f;
         }
         if (direct) {                                      // this step's adjoint sources: read after barrier 3
-            const int co = ec_opaque(inj_co);
+            const int co = ec_fresh(inj_co);
             if (co >= 0) {
                 rbuf[co] = inj_w * amp_x;
                 rbuf[kEaRcvRows * PL_ + co] = inj_w * amp_z;
@@ -1516,7 +1585,7 @@ __global__ __launch_bounds__(kEcThreads) void el_cluster_adj(const EaParams p)
         // ---- B ----------------------------------------------------------------------------------------
 #pragma unroll
         for (int q = 0; q < NG; ++q) {
-            if ((!EC_LATE_INTERIOR || q == 0) && ec_opaque(G[q].cls) == 1) phase_b(G[q]);
+            if ((!EC_LATE_INTERIOR || q == 0) && ec_fresh(G[q].cls) == 1) phase_b(G[q]);
             __builtin_amdgcn_sched_barrier(0);
         }
         EC_STAMP(3);
@@ -1541,7 +1610,7 @@ __global__ __launch_bounds__(kEcThreads) void el_cluster_adj(const EaParams p)
         }
 #pragma unroll
         for (int q = 0; q < NG; ++q) {
-            if (ec_opaque(G[q].cls) >= 2) phase_b(G[q]);                 // boundary + late interior (ec_slot)
+            if (ec_fresh(G[q].cls) >= 2) phase_b(G[q]);                 // boundary + late interior (ec_slot)
             __builtin_amdgcn_sched_barrier(0);
         }
         EC_STAMP(6);
@@ -1551,10 +1620,10 @@ __global__ __launch_bounds__(kEcThreads) void el_cluster_adj(const EaParams p)
         if (direct) {
 #pragma unroll
             for (int q = 0; q < NG; ++q)
-                if (ec_opaque(G[q].cls) != 0) {
-                    const int rr = rowmap[ec_opaque(G[q].j) - r0];
+                if (ec_fresh(G[q].cls) != 0) {
+                    const int rr = rowmap[ec_fresh(G[q].j) - r0];
                     if (rr >= 0) {
-                        const float *b = rbuf + rr * PL_ + 4 + 4 * ec_opaque(G[q].g);
+                        const float *b = rbuf + rr * PL_ + 4 + 4 * ec_fresh(G[q].g);
                         const float4 ix = ld4(b), iz = ld4(b + kEaRcvRows * PL_);
                         G[q].vx = make_float4(G[q].vx.x + ix.x, G[q].vx.y + ix.y, G[q].vx.z + ix.z, G[q].vx.w + ix.w);
                         G[q].vz = make_float4(G[q].vz.x + iz.x, G[q].vz.y + iz.y, G[q].vz.z + iz.z, G[q].vz.w + iz.w);
@@ -1563,10 +1632,10 @@ __global__ __launch_bounds__(kEcThreads) void el_cluster_adj(const EaParams p)
         } else if (cnt > 0) {
 #pragma unroll
             for (int q = 0; q < NG; ++q)
-                if (ec_opaque(G[q].cls) != 0) { st4(pln + ec_opaque(G[q].lo), zero4); st4(pln + fsz + ec_opaque(G[q].lo), zero4); }
+                if (ec_fresh(G[q].cls) != 0) { st4(ec_at(pln, ec_fresh(G[q].lo)), zero4); st4(ec_at(pln + fsz, ec_fresh(G[q].lo)), zero4); }
             __syncthreads();
             if (inj_fast) {
-                const int il = ec_opaque(inj_lo);
+                const int il = ec_fresh(inj_lo);
                 if (il >= 0) {
                     atomicAdd(pln + il, inj_w * amp_x);
                     atomicAdd(pln + fsz + il, inj_w * amp_z);
@@ -1586,8 +1655,8 @@ __global__ __launch_bounds__(kEcThreads) void el_cluster_adj(const EaParams p)
             __syncthreads();
 #pragma unroll
             for (int q = 0; q < NG; ++q)
-                if (ec_opaque(G[q].cls) != 0) {
-                    const float4 ix = ld4(pln + ec_opaque(G[q].lo)), iz = ld4(pln + fsz + ec_opaque(G[q].lo));
+                if (ec_fresh(G[q].cls) != 0) {
+                    const float4 ix = ld4(ec_at(pln, ec_fresh(G[q].lo))), iz = ld4(ec_at(pln + fsz, ec_fresh(G[q].lo)));
                     G[q].vx = make_float4(G[q].vx.x + ix.x, G[q].vx.y + ix.y, G[q].vx.z + ix.z, G[q].vx.w + ix.w);
                     G[q].vz = make_float4(G[q].vz.x + iz.x, G[q].vz.y + iz.y, G[q].vz.z + iz.z, G[q].vz.w + iz.w);
                 }
@@ -1599,14 +1668,14 @@ __global__ __launch_bounds__(kEcThreads) void el_cluster_adj(const EaParams p)
 #pragma unroll
         for (int qq = 0; qq < NG; ++qq) {
             const int q = EA_PUBLISH_FIRST ? NG - 1 - qq : qq;
-            if (ec_opaque(G[q].cls) != 0) mats_c(G[q], mBx[q], mBz[q]);
+            if (ec_fresh(G[q].cls) != 0) mats_c(G[q], mBx[q], mBz[q]);
         }
         __builtin_amdgcn_sched_barrier(0);
 #endif
 #pragma unroll
         for (int qq = 0; qq < NG; ++qq) {
             const int q = EA_PUBLISH_FIRST ? NG - 1 - qq : qq;
-            const int cls = ec_opaque(G[q].cls);
+            const int cls = ec_fresh(G[q].cls);
 #if !EA_MATS_AHEAD_C
             if (cls != 0) mats_c(G[q], mBx[q], mBz[q]);
 #endif
@@ -1620,7 +1689,7 @@ __global__ __launch_bounds__(kEcThreads) void el_cluster_adj(const EaParams p)
         // ---- D ----------------------------------------------------------------------------------------
 #pragma unroll
         for (int q = 0; q < NG; ++q) {
-            if ((!EC_LATE_INTERIOR || q == 0) && ec_opaque(G[q].cls) == 1) phase_d(G[q], false);
+            if ((!EC_LATE_INTERIOR || q == 0) && ec_fresh(G[q].cls) == 1) phase_d(G[q], false);
             __builtin_amdgcn_sched_barrier(0);
         }
         EC_STAMP(11);
@@ -1645,7 +1714,7 @@ __global__ __launch_bounds__(kEcThreads) void el_cluster_adj(const EaParams p)
         EC_STAMP(14);
 #pragma unroll
         for (int q = 0; q < NG; ++q) {
-            const int cls = ec_opaque(G[q].cls);
+            const int cls = ec_fresh(G[q].cls);
             if (cls == 2) phase_d(G[q], true);
             else if (q > 0 && cls == 3) phase_d(G[q], false);
             __builtin_amdgcn_sched_barrier(0);

@@ -1,0 +1,167 @@
+"""The instruction forms of the elastic single-launch time loops (csrc/mifwi_elastic_cluster.h) on the smallest shapes at
+which they can go wrong: the per-group word of the lane halo (ec_xh_word: offset of the one LDS read, zero export at the
+row ends), the stencils on pairs of cells (dfw2 / dbw2) with the zeroing of cells past the last column, byte offsets kept
+in place (ec_fresh), the snapshot base advanced per step.
+
+Every case forces the slab count (MIFWI_EL_NW; a shape the plan refuses is skipped), puts the source of the first shot
+in the first row of the second slab and that of the second shot in the row above it, the receivers in the last row of
+the first slab (first shot) and the first row of the second (second shot), and runs 2 shots for 40-60 steps three
+times: single launch, one launch per half step (MIFWI_EL_CLUSTER=0 MIFWI_EL_CLUSTER_ADJ=0) and single launch with the
+x-halo read from LDS (MIFWI_EL_XHALO=0).  Seismograms are the same bits in all three; gradients agree with the per-step
+kernels to 2e-5 relative L2 (they sum the snapshot correlations in another order) and are the same bits with and without
+the lane halo (data movement only).  mifwi_fallback_count() must not move: the shapes really run the single-launch kernels.
+"""
+import os
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+import torch
+
+from cases import elastic_case, rel_l2
+
+pytestmark = pytest.mark.gpu
+TOL_GRAD = 2e-5
+DEV = "cuda:0"
+
+# id -> (nz, nx, slabs, elastic_case keywords)
+CASES = {
+    # four-row slabs (no interior group: the classes share a wave's slot), 75 groups per row (a wave straddles one row
+    # break, some two), nx a multiple of 4, one group per thread, the first slab boundary (row 4) inside the top C-PML
+    "16x300/4": (16, 300, 4, dict(nt=40)),
+    # five-row slabs of 8 groups (a wave holds all of a slab's rows: seven row breaks); 30 columns: the last group of a
+    # row has two cells past the grid
+    "20x30/4": (20, 30, 4, dict(nt=48)),
+    # the same deal with nx a multiple of 4 (the zeroing is skipped by a uniform branch)
+    "20x32/4": (20, 32, 4, dict(nt=48)),
+    # uneven slabs (10, 10, 9 rows) of 21 groups, the last one partial (83 columns): waves straddle three row breaks
+    "29x83/3": (29, 83, 3, dict(nt=60)),
+    # two slabs of 13 rows x 25 groups with the free surface on: the top slab mirrors, sources on and below row 13
+    "26x100/2-free-surface": (26, 100, 2, dict(nt=60, free_surface=True)),
+    # the headline deal, two groups per thread: 13 rows x 75 groups, late-interior and boundary waves in the second slot
+    "52x300/4": (52, 300, 4, dict(nt=50)),
+}
+FAMILIES = {"single": {}, "per-step": {"MIFWI_EL_CLUSTER": "0", "MIFWI_EL_CLUSTER_ADJ": "0"}, "lds-halo": {"MIFWI_EL_XHALO": "0"}}
+
+
+def _case(cid):
+    nz, nx, nw, kw = CASES[cid]
+    kw = dict(dict(fw=6, ns=2, nrec=12), **kw)
+    case = elastic_case(seed=311 + nz + nx, nz=nz, nx=nx, **kw)
+    b = nz // nw + (1 if nz % nw else 0)                   # first row of the second slab (ec_slab_rows)
+    sz = np.array([[b], [b - 1]])                          # a boundary row of either slab
+    rx = np.linspace(1, nx - 2, kw["nrec"]).astype(int)    # first and last group of the row included
+    sx = np.array([[rx[kw["nrec"] // 3] + 2], [nx - 6]])    # two and four cells from a receiver
+    case["sc"] = (sz * nx + sx).astype(np.int32).reshape(case["sc"].shape)
+    rz = np.array([[b - 1], [b]])
+    case["rc"] = (rz * nx + rx[None, :]).astype(np.int32).reshape(case["rc"].shape)
+    case["rw"] = np.ones(case["rc"].shape, dtype=case["rw"].dtype)
+    return case, kw
+
+
+def _propagate(case, seeds=None):
+    from physicsbasedfwi2_amd import elastic
+    mat = torch.tensor(case["mat"], dtype=torch.float32, device=DEV, requires_grad=True)
+    f = torch.tensor(case["f"], dtype=torch.float32, device=DEV, requires_grad=True)
+    vx, vz = elastic.propagate(mat, f, *[torch.tensor(case[k]) for k in ("pz", "px", "sc", "sw", "rc", "rw")], case["fw"],
+                               free_surface=bool(case["fs"]))
+    hx, hz = vx.detach().cpu().numpy(), vz.detach().cpu().numpy()
+    if seeds is None:
+        rng = np.random.default_rng(12)
+        seeds = ((rng.standard_normal(hx.shape) * np.abs(hx).max()).astype(np.float32),
+                 (rng.standard_normal(hz.shape) * np.abs(hz).max()).astype(np.float32))
+    torch.autograd.backward([vx, vz], [torch.tensor(seeds[0], device=DEV), torch.tensor(seeds[1], device=DEV)])
+    return dict(vx=hx, vz=hz, gx=seeds[0], gz=seeds[1], gm=mat.grad.cpu().numpy(), gf=f.grad.cpu().numpy())
+
+
+_RUNS = {}
+
+
+def _runs(cid, monkeypatch):
+    """The three runs of one case, computed once per session and left unchanged."""
+    if cid in _RUNS:
+        return _RUNS[cid]
+    from physicsbasedfwi2_amd import _lib
+    from physicsbasedfwi2_amd.elastic import ElasticPlan
+    nz, nx, nw, _ = CASES[cid]
+    case, kw = _case(cid)
+    monkeypatch.setenv("MIFWI_EL_NW", str(nw))
+    pl = ElasticPlan(nz, nx, kw["nt"], 2, 1, kw["nrec"], 1, kw["fw"], 0, free_surface=case["fs"])
+    slabs = (pl.cluster_slabs(False), pl.cluster_slabs(True))
+    pl.close()
+    if slabs != (nw, nw):
+        _RUNS[cid] = None
+    else:
+        out, seeds = {}, None
+        for name, env in FAMILIES.items():
+            for k, v in env.items():
+                monkeypatch.setenv(k, v)
+            before = _lib.load().mifwi_fallback_count()
+            out[name] = _propagate(case, seeds)
+            out[name]["fallbacks"] = _lib.load().mifwi_fallback_count() - before
+            seeds = (out[name]["gx"], out[name]["gz"])
+            for k in env:
+                monkeypatch.delenv(k)
+        _RUNS[cid] = out
+    return _RUNS[cid]
+
+
+@pytest.mark.parametrize("cid", list(CASES))
+def test_loop_forms_against_the_other_families(monkeypatch, cid):
+    r = _runs(cid, monkeypatch)
+    if r is None:
+        pytest.skip("the plan does not take %d slabs for this shape" % CASES[cid][2])
+    one, step, lds = r["single"], r["per-step"], r["lds-halo"]
+    assert [x["fallbacks"] for x in (one, step, lds)] == [0, 0, 0]
+    assert np.isfinite(one["vx"]).all() and np.abs(one["vx"]).max() > 0 and np.abs(one["vz"]).max() > 0
+    assert np.abs(one["vx"][:, 0]).max() > 0 and np.abs(one["vx"][:, 1]).max() > 0        # both shots
+    for k in ("vx", "vz"):
+        assert np.array_equal(one[k], step[k]), k
+        assert np.array_equal(one[k], lds[k]), k
+    errs = [rel_l2(one["gm"][k], step["gm"][k]) for k in range(5)] + [rel_l2(one["gf"], step["gf"])]
+    print("gradient rel-L2 against the per-step kernels", " ".join("%.2e" % e for e in errs))
+    assert np.abs(one["gm"]).max() > 0 and np.abs(one["gf"]).max() > 0
+    assert max(errs) <= TOL_GRAD, errs
+    assert np.array_equal(one["gm"], lds["gm"]) and np.array_equal(one["gf"], lds["gf"])
+
+
+_CHILD = r"""
+import sys
+import numpy as np, torch
+sys.path.insert(0, %(tests)r); sys.path.insert(0, %(root)r)
+from test_elastic_loop_forms_gpu import _case, _propagate
+from physicsbasedfwi2_amd import _lib
+seeds = np.load(sys.argv[1])
+out = _propagate(_case(%(cid)r)[0], (seeds["gx"], seeds["gz"]))
+lib = _lib.load()
+np.savez(sys.argv[2], counts=np.array([lib.mifwi_fallback_count(), lib.mifwi_agent_handoff_count()]),
+         **{k: out[k] for k in ("vx", "vz", "gm", "gf")})
+"""
+
+
+def test_loop_forms_through_the_agent_scope_publish(monkeypatch, tmp_path):
+    """The AG kernel variants (granules published through the fabric), reached as tests/test_elastic_handoff_gpu.py
+    reaches them: debug bit 128 of the ablation build fails the placement check and the host repeats the launch.  Five-row
+    slabs with a partial last group, in a fresh process: the bits of the plain run, no fall-back."""
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    lib = os.path.join(root, "physicsbasedfwi2_amd", "libmifwi_ablations.so")
+    if not os.path.exists(lib):
+        pytest.skip("ablation build not present (python __graft_entry__.py builds it)")
+    cid = "20x30/4"
+    r = _runs(cid, monkeypatch)
+    if r is None:
+        pytest.skip("the plan does not take %d slabs for this shape" % CASES[cid][2])
+    ref = r["single"]
+    seeds, out, script = tmp_path / "seeds.npz", tmp_path / "ag.npz", tmp_path / "child.py"
+    np.savez(seeds, gx=ref["gx"], gz=ref["gz"])
+    script.write_text(_CHILD % {"tests": os.path.join(root, "tests"), "root": root, "cid": cid})
+    env = dict(os.environ, MIFWI_LIB=lib, MIFWI_EL_CL_DBG="128", MIFWI_EL_NW=str(CASES[cid][2]))
+    res = subprocess.run([sys.executable, str(script), str(seeds), str(out)], env=env, capture_output=True, text=True,
+                         timeout=300)
+    assert res.returncode == 0, res.stderr[-2000:]
+    ag = dict(np.load(out))
+    fb, n_ag = (int(v) for v in ag["counts"])
+    assert fb == 0 and n_ag > 0, (fb, n_ag)
+    for k in ("vx", "vz", "gm", "gf"):
+        assert np.array_equal(ref[k], ag[k]), k
