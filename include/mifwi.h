@@ -29,7 +29,7 @@ extern "C" {
 #endif
 
 #define MIFWI_VERSION_MAJOR 0
-#define MIFWI_VERSION_MINOR 7   /* 3: elastic desc gained snapshot_format, fd_order; layout snap_step_elems, snapshot_format; 4: mifwi_fallback_count; 5: mifwi_agent_handoff_count, mifwi_slow_handoff_count; acoustic desc gained cpml_width, layout state_elems; 6: mifwi_elastic_materials(_vjp), mifwi_acoustic_coefficients(_vjp); 7: mifwi_elastic_gradient_parametrization; elastic snapshot planes column-blocked in plans without a single-launch kernel; later additions that leave every existing call as it was keep 7: mifwi_elastic_snapshot_moments, mifwi_elastic_pseudo_hessian, mifwi_gradient_precondition */
+#define MIFWI_VERSION_MINOR 7   /* 3: elastic desc gained snapshot_format, fd_order; layout snap_step_elems, snapshot_format; 4: mifwi_fallback_count; 5: mifwi_agent_handoff_count, mifwi_slow_handoff_count; acoustic desc gained cpml_width, layout state_elems; 6: mifwi_elastic_materials(_vjp), mifwi_acoustic_coefficients(_vjp); 7: mifwi_elastic_gradient_parametrization; elastic snapshot planes column-blocked in plans without a single-launch kernel; later additions that leave every existing call as it was keep 7: mifwi_elastic_snapshot_moments, mifwi_elastic_pseudo_hessian, mifwi_gradient_precondition, mifwi_elastic_born */
 
 enum {
     MIFWI_OK = 0,
@@ -270,6 +270,28 @@ int mifwi_elastic_backward(mifwi_elastic_plan *plan, const float *mat, const flo
                            const float *g_vz, const float *snap, int32_t snap_first,
                            float *grad_mat, float *grad_f, float *work, int32_t n_hi, int32_t n_lo,
                            int32_t flags, void *stream);
+
+/* Born (linearised) modelling: drec = J (dmat, df), the first-order change of the velocity seismograms, steps
+ * n = n_begin .. n_end-1 - the JVP partner of mifwi_elastic_backward's (grad_mat, grad_f).  The perturbed state obeys
+ * the forward recursion (same materials, profiles, free surface, stencil order) without the point source; at step n the
+ * five snapshot planes S0..S4 of the background run's step n are its virtual sources:
+ *   after V:  dvx += dmat[3] S3,  dvz += dmat[4] S4
+ *   after S:  dsxx += dmat[1] S0 + dmat[0] S1,  dszz += dmat[0] S0 + dmat[1] S1,  dsxz += dmat[2] S2
+ *             (before row 0 of dszz is zeroed under a free surface)
+ *   dmat [5][nz][gp]: perturbation of `mat`, same layout (columns >= nx must be 0)
+ *   df   NULL or [nt][nshot][nsrc]: perturbation of f, injected as f is
+ *   snap: f32 planes as mifwi_elastic_forward of the same plan wrote them (either layout); step n at
+ *         snap + (n - snap_first) * layout.snap_step_elems
+ *   drec_vx, drec_vz [nt][nshot][nrec] or both NULL, sampled after V as the forward samples
+ *   work: layout.work_forward_elems floats; the perturbed state lives at its head (MIFWI_ZERO_STATE as in the forward)
+ * Runs on the one-launch-per-half-step kernels whatever family the plan's forward runs.  MIFWI_EINVAL: null dmat / snap /
+ * work, a bad step range, plans with bf16 snapshot planes, source_type != 0 (a force source needs df from the density
+ * at the source node) and record_pressure plans (pressure receivers are not sampled). */
+int mifwi_elastic_born(mifwi_elastic_plan *plan, const float *mat, const float *dmat, const float *pz, const float *px,
+                       const float *df, const int32_t *src_cell, const float *src_w,
+                       const int32_t *rec_cell, const float *rec_w,
+                       const float *snap, int32_t snap_first, float *drec_vx, float *drec_vz,
+                       float *work, int32_t n_begin, int32_t n_end, int32_t flags, void *stream);
 
 /* Which kernel family a plan selected: the number of row slabs a shot is cut
  * into by the single-launch "cluster" time loop, or 0 when the plan runs one launch per (half)

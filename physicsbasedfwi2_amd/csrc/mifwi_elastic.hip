@@ -13,6 +13,8 @@
 // row-aligned in z) so that interior tiles never touch them.  Source injection (LDS image of
 // the tile, only where the shot's bounding box intersects it) and receiver sampling (extra
 // workgroups) ride in the S launch.
+// Born (mifwi_elastic_born): the same two launches on the perturbed state; instead of writing the step's five snapshot
+// planes they read the background run's and add dmat times them (SAVE = kBorn), the JVP partner of the adjoint's gradients.
 // Adjoint: two launches per step (S^T then V^T).  The transposed C-PML acts on the
 // material-scaled adjoint fields BEFORE the spatial derivative, so each workgroup first
 // evaluates those four per-cell quantities on its tile + 2-cell halo into LDS, then applies the
@@ -84,6 +86,7 @@ struct ElParams {
     int tiles_z;
     int xcd;                     // XCD-aware tile order (xcd_tile): 1 contiguous runs per shot, 2 whole shots, 3 tile-major over the shots
     FdK K;                       // stencil weights
+    const float *dmat;           // Born step (SAVE 3): perturbation of the five material planes, [5][nz][gp] like mat
 };
 
 __device__ __forceinline__ float comp(const float4 &v, int c)
@@ -320,7 +323,10 @@ __device__ bool stage_injection(const ElParams &p, int s, int tile_j, int tile_i
 // ================================================================================================
 // forward V launch:  vx += bxs (Dp_x sxx' + Dm_z sxz'),  vz += bzs (Dm_x sxz' + Dp_z szz')
 // ================================================================================================
-template <int LX, int RZ, int SAVE>       // SAVE 0: no snapshots, 1: f32 planes, 2: bf16 planes
+// SAVE 0: no snapshots, 1: write f32 planes, 2: write bf16 planes, 3 (kBorn): the Born step - the state is the perturbed
+// field, and the f32 planes of the background run's step are READ: times dmat they are the step's virtual sources
+constexpr int kBorn = 3;
+template <int LX, int RZ, int SAVE>
 __global__ __launch_bounds__(kThreads, MIFWI_EL_MINWAVES) void el_step_v(const ElParams p)
 {
     const FdK K = p.K;
@@ -394,6 +400,12 @@ __global__ __launch_bounds__(kThreads, MIFWI_EL_MINWAVES) void el_step_v(const E
             const float2 Lxz = ld2(sxz + o - 2), Rxz = ld2(sxz + o + 4);
             float4 vxv = ld4(vx + o), vzv = ld4(vz + o);
             const float4 bxs = ld4(p.mat + M_BX * ncell + cc), bzs = ld4(p.mat + M_BZ * ncell + cc);
+            float4 B3 = zero4, B4 = zero4, dbx = zero4, dbz = zero4;
+            if (SAVE == kBorn) {
+                const float *Sp = p.S + (long long)s * p.snap_shot + snap_cell(p, j, g);
+                B3 = mifwi::ldnt4(Sp + 3 * (long long)p.splane); B4 = mifwi::ldnt4(Sp + 4 * (long long)p.splane);
+                dbx = ld4(p.dmat + M_BX * ncell + cc); dbz = ld4(p.dmat + M_BZ * ncell + cc);
+            }
             const float xx[8] = {Lxx.x, Lxx.y, cxx.x, cxx.y, cxx.z, cxx.w, Rxx.x, Rxx.y};
             const float xz[8] = {Lxz.x, Lxz.y, a2.x, a2.y, a2.z, a2.w, Rxz.x, Rxz.y};
             float d1[4], d2[4], d3[4], d4[4];
@@ -431,6 +443,12 @@ __global__ __launch_bounds__(kThreads, MIFWI_EL_MINWAVES) void el_step_v(const E
             vxv.z = fmaf(bxs.z, s4v[2], vxv.z); vxv.w = fmaf(bxs.w, s4v[3], vxv.w);
             vzv.x = fmaf(bzs.x, s5v[0], vzv.x); vzv.y = fmaf(bzs.y, s5v[1], vzv.y);
             vzv.z = fmaf(bzs.z, s5v[2], vzv.z); vzv.w = fmaf(bzs.w, s5v[3], vzv.w);
+            if (SAVE == kBorn) {
+                vxv.x = fmaf(dbx.x, B3.x, vxv.x); vxv.y = fmaf(dbx.y, B3.y, vxv.y);
+                vxv.z = fmaf(dbx.z, B3.z, vxv.z); vxv.w = fmaf(dbx.w, B3.w, vxv.w);
+                vzv.x = fmaf(dbz.x, B4.x, vzv.x); vzv.y = fmaf(dbz.y, B4.y, vzv.y);
+                vzv.z = fmaf(dbz.z, B4.z, vzv.z); vzv.w = fmaf(dbz.w, B4.w, vzv.w);
+            }
             st4(vx + o, vxv);
             st4(vz + o, vzv);
             if (SAVE == 1) {
@@ -505,6 +523,15 @@ __global__ __launch_bounds__(kThreads, MIFWI_EL_MINWAVES) void el_step_s(const E
                     float4 vxx = ld4(sxx + o), vzz = ld4(szz + o), vxz = ld4(sxz + o);
                     const float4 Ls = ld4(p.mat + M_L * ncell + cc), Ms = ld4(p.mat + M_M * ncell + cc);
                     const float4 mus = ld4(p.mat + M_MU * ncell + cc);
+                    const float4 zero4 = make_float4(0.f, 0.f, 0.f, 0.f);
+                    float4 B0 = zero4, B1 = zero4, B2 = zero4, dL = zero4, dM = zero4, dmu = zero4;
+                    if (SAVE == kBorn) {
+                        const float *Sp = p.S + (long long)s * p.snap_shot + snap_cell(p, j, g);
+                        B0 = mifwi::ldnt4(Sp); B1 = mifwi::ldnt4(Sp + (long long)p.splane);
+                        B2 = mifwi::ldnt4(Sp + 2 * (long long)p.splane);
+                        dL = ld4(p.dmat + M_L * ncell + cc); dM = ld4(p.dmat + M_M * ncell + cc);
+                        dmu = ld4(p.dmat + M_MU * ncell + cc);
+                    }
                     const float xv[8] = {Lvx.x, Lvx.y, b1.x, b1.y, b1.z, b1.w, Rvx.x, Rvx.y};
                     const float zv[8] = {Lvz.x, Lvz.y, a2.x, a2.y, a2.z, a2.w, Rvz.x, Rvz.y};
                     float e1[4], e2[4], e3[4], e4[4];
@@ -551,6 +578,11 @@ __global__ __launch_bounds__(kThreads, MIFWI_EL_MINWAVES) void el_step_s(const E
                         nxx[c] = fmaf(comp(Ms, c), e1[c], fmaf(comp(Ls, c), e2[c], comp(vxx, c)));
                         nzz[c] = fmaf(comp(Ls, c), e1[c], fmaf(comp(Ms, c), e2[c], comp(vzz, c)));
                         nxz[c] = fmaf(comp(mus, c), s3v[c], comp(vxz, c));
+                        if (SAVE == kBorn) {
+                            nxx[c] = fmaf(comp(dM, c), comp(B0, c), fmaf(comp(dL, c), comp(B1, c), nxx[c]));
+                            nzz[c] = fmaf(comp(dL, c), comp(B0, c), fmaf(comp(dM, c), comp(B1, c), nzz[c]));
+                            nxz[c] = fmaf(comp(dmu, c), comp(B2, c), nxz[c]);
+                        }
                         if (has_inj) {
                             const float a = inj[(j - tile_j) * TX + 4 * lx + c];
                             nxx[c] += a;
@@ -1449,6 +1481,57 @@ void ea_cluster_launch(const mifwi_elastic_plan *pl, EaParams c, bool agent, hip
     }
 }
 
+// The two-launch per-step time loop over the steps [n_begin, n_end): mifwi_elastic_forward's plain form (save 0, 1, 2:
+// `snap` is written) and the Born pass (save 3: `snap` is the background run's, read; p.dmat set; p.fields / psix / psiz
+// hold the perturbed state; f is the source perturbation or null).  The planes of step n are at
+// snap + (n - snap_first) * snap_step.  rec_vx null: no sampling.
+void el_two_launch_steps(const mifwi_elastic_plan *pl, ElParams p, int save, const float *f, const int32_t *src_cell,
+                         const float *src_w, const int *bbox, const int32_t *rec_cell, const float *rec_w, float *rec_vx,
+                         float *rec_vz, float *snap, int snap_first, int n_begin, int n_end, hipStream_t st)
+{
+    const mifwi_elastic_desc &d = pl->d;
+    const long long snap_step = pl->snap_shot * d.nshot;
+    const bool want_rec = rec_vx != nullptr;
+    ElParams ps = p;
+    const bool force = d.source_type != 0;       // point force: injected into vx / vz by a launch of its own
+    ps.ninj = (force || !f) ? 0 : d.nsrc; ps.ntap_inj = d.ntap; ps.inj_cell = src_cell; ps.inj_w = src_w;
+    ps.inj_bbox = bbox;
+    ElParams pf = p;
+    pf.ninj = d.nsrc; pf.ntap_inj = d.ntap; pf.inj_cell = src_cell; pf.inj_w = src_w;
+    ps.nsmp = want_rec ? d.nrec : 0; ps.ntap_smp = d.ntap; ps.smp_cell = rec_cell; ps.smp_w = rec_w;
+    // shots are independent: taken a few at a time, their state and the materials stay inside the
+    // 256 MiB Infinity Cache from one launch to the next (pl->pass_shots; all shots when they fit anyway)
+    for (int s0 = 0; s0 < d.nshot; s0 += pl->pass_shots) {
+        const int cs = std::min(pl->pass_shots, d.nshot - s0);
+        p.s0 = ps.s0 = s0;
+        for (int n = n_begin; n < n_end; ++n) {
+            float *Sn = snap ? snap + (long long)(n - snap_first) * snap_step : nullptr;
+            p.S = Sn; ps.S = Sn;
+            ps.inj_amp0 = f ? f + (long long)n * d.nshot * d.nsrc : nullptr;
+            ps.smp_out0 = want_rec ? rec_vx + (long long)n * d.nshot * d.nrec : nullptr;
+            ps.smp_out1 = want_rec ? rec_vz + (long long)n * d.nshot * d.nrec : nullptr;
+            if (save == kBorn) launch_v<kBorn>(pl, p, cs, st);
+            else if (save == 2) launch_v<2>(pl, p, cs, st);
+            else if (save == 1) launch_v<1>(pl, p, cs, st);
+            else launch_v<0>(pl, p, cs, st);
+            if (force && d.nsrc > 0 && f) {
+                pf.s0 = s0; pf.gs = cs; pf.inj_amp0 = ps.inj_amp0;
+                hipLaunchKernelGGL(el_inject_force, dim3(mifwi::ceil_div(cs, 64)), dim3(64), 0, st, pf,
+                                   d.source_type);
+            }
+            if (save == kBorn) launch_s<kBorn>(pl, ps, cs, st);
+            else if (save == 2) launch_s<2>(pl, ps, cs, st);
+            else if (save == 1) launch_s<1>(pl, ps, cs, st);
+            else launch_s<0>(pl, ps, cs, st);
+            if (pl->rec_p && want_rec) {
+                ElParams pq = ps;
+                pq.s0 = s0; pq.gs = cs; pq.smp_out0 = pl->rec_p + (long long)n * d.nshot * d.nrec;
+                hipLaunchKernelGGL(el_sample_pressure, dim3(mifwi::ceil_div(cs * d.nrec, 64)), dim3(64), 0, st, pq);
+            }
+        }
+    }
+}
+
 }  // namespace
 
 extern "C" {
@@ -1748,43 +1831,52 @@ int mifwi_elastic_forward(mifwi_elastic_plan *pl, const float *mat, const float 
         }
     } else {
         p.fields = fields; p.psix = psi_state; p.psiz = psi_state + pl->psix_elems;
-        ElParams ps = p;
-        const bool force = d.source_type != 0;       // point force: injected into vx / vz by a launch of its own
-        ps.ninj = force ? 0 : d.nsrc; ps.ntap_inj = d.ntap; ps.inj_cell = src_cell; ps.inj_w = src_w;
-        ps.inj_bbox = bbox;
-        ElParams pf = p;
-        pf.ninj = d.nsrc; pf.ntap_inj = d.ntap; pf.inj_cell = src_cell; pf.inj_w = src_w;
-        ps.nsmp = want_rec ? d.nrec : 0; ps.ntap_smp = d.ntap; ps.smp_cell = rec_cell; ps.smp_w = rec_w;
-        // shots are independent: taken a few at a time, their state and the materials stay inside the
-        // 256 MiB Infinity Cache from one launch to the next (pl->pass_shots; all shots when they fit anyway)
-        for (int s0 = 0; s0 < d.nshot; s0 += pl->pass_shots) {
-            const int cs = std::min(pl->pass_shots, d.nshot - s0);
-            p.s0 = ps.s0 = s0;
-            for (int n = n_begin; n < n_end; ++n) {
-                float *Sn = snap ? snap + (long long)(n - n_begin) * snap_step : nullptr;
-                p.S = Sn; ps.S = Sn;
-                ps.inj_amp0 = f ? f + (long long)n * d.nshot * d.nsrc : nullptr;
-                ps.smp_out0 = want_rec ? rec_vx + (long long)n * d.nshot * d.nrec : nullptr;
-                ps.smp_out1 = want_rec ? rec_vz + (long long)n * d.nshot * d.nrec : nullptr;
-                if (save == 2) launch_v<2>(pl, p, cs, st);
-                else if (save == 1) launch_v<1>(pl, p, cs, st);
-                else launch_v<0>(pl, p, cs, st);
-                if (force && d.nsrc > 0 && f) {
-                    pf.s0 = s0; pf.gs = cs; pf.inj_amp0 = ps.inj_amp0;
-                    hipLaunchKernelGGL(el_inject_force, dim3(mifwi::ceil_div(cs, 64)), dim3(64), 0, st, pf,
-                                       d.source_type);
-                }
-                if (save == 2) launch_s<2>(pl, ps, cs, st);
-                else if (save == 1) launch_s<1>(pl, ps, cs, st);
-                else launch_s<0>(pl, ps, cs, st);
-                if (pl->rec_p && want_rec) {
-                    ElParams pq = ps;
-                    pq.s0 = s0; pq.gs = cs; pq.smp_out0 = pl->rec_p + (long long)n * d.nshot * d.nrec;
-                    hipLaunchKernelGGL(el_sample_pressure, dim3(mifwi::ceil_div(cs * d.nrec, 64)), dim3(64), 0, st, pq);
-                }
-            }
-        }
+        el_two_launch_steps(pl, p, save, f, src_cell, src_w, bbox, rec_cell, rec_w, want_rec ? rec_vx : nullptr,
+                            want_rec ? rec_vz : nullptr, snap, n_begin, n_begin, n_end, st);
     }
+    MIFWI_HIP_TRY(hipGetLastError());
+    return MIFWI_OK;
+}
+
+int mifwi_elastic_born(mifwi_elastic_plan *pl, const float *mat, const float *dmat, const float *pz, const float *px,
+                       const float *df, const int32_t *src_cell, const float *src_w,
+                       const int32_t *rec_cell, const float *rec_w,
+                       const float *snap, int32_t snap_first, float *drec_vx, float *drec_vz,
+                       float *work, int32_t n_begin, int32_t n_end, int32_t flags, void *stream)
+{
+    if (!pl || !mat || !pz || !px) return mifwi::fail(MIFWI_EINVAL, "null argument");
+    if (!dmat || !snap || !work) return mifwi::fail(MIFWI_EINVAL, "born: dmat, snap and work must not be null");
+    const mifwi_elastic_desc &d = pl->d;
+    if (n_begin < 0 || n_end > d.nt || n_begin > n_end)
+        return mifwi::fail(MIFWI_EINVAL, "bad step range [%d,%d) for nt=%d", n_begin, n_end, d.nt);
+    if (snap_first > n_begin)
+        return mifwi::fail(MIFWI_EINVAL, "snapshots start at step %d but step %d is needed", snap_first, n_begin);
+    if (pl->snap_bf16)
+        return mifwi::fail(MIFWI_EINVAL, "born: the plan keeps bf16 snapshot planes; the Born step reads f32 planes");
+    if (d.source_type != 0)
+        return mifwi::fail(MIFWI_EINVAL, "born: point-force sources (source_type %d) are not served", d.source_type);
+    if (d.record_pressure) return mifwi::fail(MIFWI_EINVAL, "born: pressure receivers are not served");
+    if (df && d.nsrc > 0 && (!src_cell || !src_w))
+        return mifwi::fail(MIFWI_EINVAL, "df given but src_cell/src_w is null");
+    if ((drec_vx || drec_vz) && (!rec_cell || !rec_w || !drec_vx || !drec_vz))
+        return mifwi::fail(MIFWI_EINVAL, "receiver output needs rec_cell, rec_w, drec_vx and drec_vz");
+    int rc = mifwi::check_device(pl->device);
+    if (rc) return rc;
+    MIFWI_HIP_TRY(hipSetDevice(pl->device));
+    hipStream_t st = (hipStream_t)stream;
+    const ElWork m = work_map(pl, false);                 // the perturbed state: the forward's map of `work`
+    int *bbox = reinterpret_cast<int *>(work + m.bbox);
+    if (flags & MIFWI_ZERO_STATE) MIFWI_HIP_TRY(hipMemsetAsync(work, 0, sizeof(float) * m.state, st));
+    const bool inject = df != nullptr && d.nsrc > 0;
+    if (inject)
+        hipLaunchKernelGGL(el_points_bbox, dim3(d.nshot), dim3(kThreads), 0, st, src_cell, d.nsrc * d.ntap, d.nx, bbox);
+    ElParams p = el_base(pl, mat, pz, px);
+    p.dmat = dmat;
+    p.fields = work + m.fields; p.psix = work + m.psi; p.psiz = work + m.psi + pl->psix_elems;
+    const bool want_rec = drec_vx != nullptr && d.nrec > 0;
+    el_two_launch_steps(pl, p, kBorn, inject ? df : nullptr, src_cell, src_w, bbox, rec_cell, rec_w,
+                        want_rec ? drec_vx : nullptr, want_rec ? drec_vz : nullptr, const_cast<float *>(snap), snap_first,
+                        n_begin, n_end, st);
     MIFWI_HIP_TRY(hipGetLastError());
     return MIFWI_OK;
 }

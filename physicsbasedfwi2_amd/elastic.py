@@ -292,6 +292,24 @@ class _SnapshotArena:
         return self.buf[:need].view(nt, elems)
 
 
+def _padded_planes(t, gp):
+    """[5, nz, nx] -> float32 [5, nz, gp] on the same device, pad columns 0 (the layout of ``mat`` in include/mifwi.h)."""
+    out = torch.zeros(tuple(t.shape[:2]) + (gp,), device=t.device, dtype=torch.float32)
+    out[:, :, :t.shape[2]] = t.detach()
+    return out
+
+
+def _padded_inputs(mat, pz, px, gp):
+    """The material planes and C-PML tables as the C calls take them: on mat's device, rows padded to gp columns
+    (materials and a, b 0, 1/kappa 1 there)."""
+    dev = mat.device
+    px_p = torch.zeros((6, gp), device=dev, dtype=torch.float32)
+    px_p[2] = 1.0
+    px_p[5] = 1.0
+    px_p[:, :mat.shape[2]] = px.to(device=dev, dtype=torch.float32)
+    return _padded_planes(mat, gp), pz.to(device=dev, dtype=torch.float32).contiguous(), px_p
+
+
 class _ElasticFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, mat, f, pz, px, geom, pml_width, shots_per_group, snapshot_budget, free_surface,
@@ -312,13 +330,7 @@ class _ElasticFn(torch.autograd.Function):
                                fd_order)
             lay = plan.layout
             gp = lay.gp
-            mat_p = torch.zeros((5, nz, gp), device=dev, dtype=torch.float32)
-            mat_p[:, :, :nx] = mat.detach()
-            pz_d = pz.to(device=dev, dtype=torch.float32).contiguous()
-            px_p = torch.zeros((6, gp), device=dev, dtype=torch.float32)
-            px_p[2] = 1.0
-            px_p[5] = 1.0
-            px_p[:, :nx] = px.to(device=dev, dtype=torch.float32)
+            mat_p, pz_d, px_p = _padded_inputs(mat, pz, px, gp)
             f_d = f.detach().to(dtype=torch.float32).contiguous()
             rvx = torch.empty((nt, ns, nrec), device=dev, dtype=torch.float32)
             rvz = torch.empty((nt, ns, nrec), device=dev, dtype=torch.float32)
@@ -500,6 +512,146 @@ def propagate(mat, f, pz, px, src_cell, src_w, rec_cell, rec_w, pml_width,
                                     int(snapshot_budget), 1 if free_surface else 0, st,
                                     1 if record_pressure else 0, snapshot_format, int(fd_order), pseudo_hessian)
     return (rvx, rvz, rp) if record_pressure else (rvx, rvz)
+
+
+def materials_jvp(vp, vs, rho, dvp, dvs, drho, dt, h, free_surface=False):
+    """dmat [5, nz, nx]: the first-order change of :func:`staggered_materials` for the model perturbation
+    (dvp, dvs, drho) - the forward-mode derivative of the torch expression that defines the planes, on the tensors'
+    device and in their dtype; the transpose of the VJP autograd runs through ``staggered_materials``.  Finite where
+    Vs = 0 (keep ``dvs`` = 0 there: water stays water); under ``free_surface`` row 0 of plane 0 is 0."""
+    prm = [torch.as_tensor(t).detach() for t in (vp, vs, rho)]
+    tan = [torch.as_tensor(t).detach().to(device=prm[0].device, dtype=prm[0].dtype) for t in (dvp, dvs, drho)]
+    if any(t.shape != prm[0].shape for t in prm + tan) or prm[0].dim() != 2:
+        raise MifwiError("materials_jvp: vp, vs, rho and their perturbations must be [nz, nx] tensors of one shape")
+    return torch.func.jvp(lambda a, b, c: _staggered_materials_torch(a, b, c, dt, h, free_surface),
+                          tuple(prm), tuple(tan))[1]
+
+
+def _linearised(name, mat, dmat, f, pz, px, src_cell, src_w, rec_cell, rec_w, pml_width, df, free_surface, fd_order,
+                snapshot_budget, source_type, record_pressure, snapshot_format, adjoint, weight):
+    """born / gauss_newton_product: per shot chunk one plan, one background forward with resident f32 snapshots, the
+    Born pass over that buffer and - ``adjoint`` - the adjoint pass over it too."""
+    _require_cuda(mat, "mat")
+    dev = mat.device
+    lib = _lib.load()
+    geom = _Geometry.get(src_cell, src_w, rec_cell, rec_w, dev)
+    try:
+        st = SOURCE_TYPES[source_type]
+    except KeyError:
+        raise MifwiError("source_type must be one of %s" % sorted(k for k in SOURCE_TYPES if isinstance(k, str)))
+    if snapshot_format is not None and snapshot_format not in SNAPSHOT_FORMATS:
+        raise MifwiError("snapshot_format must be one of %s" % sorted(SNAPSHOT_FORMATS))
+    if st != 0 or record_pressure:
+        raise MifwiError("%s serves explosive sources and velocity receivers only (force sources need df from the "
+                         "density at the source node, pressure receivers a sampling pass of their own)" % name)
+    if mat.dim() != 3 or mat.shape[0] != 5:
+        raise MifwiError("mat must be [5, nz, nx]")
+    if tuple(dmat.shape) != tuple(mat.shape):
+        raise MifwiError("dmat must have the shape of mat, %s (got %s)" % (tuple(mat.shape), tuple(dmat.shape)))
+    _require_cuda(dmat, "dmat")
+    _, nz, nx = mat.shape
+    nt, ns, nsrc = f.shape
+    if geom.src_cell.shape[:2] != (ns, nsrc):
+        raise MifwiError("f is [nt,%d,%d] but src_cell is %s" % (ns, nsrc, tuple(geom.src_cell.shape)))
+    if df is not None and tuple(df.shape) != tuple(f.shape):
+        raise MifwiError("df must have the shape of f, %s (got %s)" % (tuple(f.shape), tuple(df.shape)))
+    nrec, ntap = geom.rec_cell.shape[1], geom.rec_cell.shape[2]
+    geom.check_cells(nz * nx, "%dx%d" % (nz, nx))
+    with torch.cuda.device(dev), torch.no_grad():
+        f_d = f.detach().to(device=dev, dtype=torch.float32).contiguous()
+        df_d = None if df is None else df.detach().to(device=dev, dtype=torch.float32).contiguous()
+        out = [torch.empty((nt, ns, nrec), device=dev, dtype=torch.float32) for _ in range(4)]
+        hv = torch.zeros((5, nz, nx), device=dev, dtype=torch.float32) if adjoint else None
+        budget = min(int(snapshot_budget), int(0.8 * _lib.free_device_bytes(dev)))
+        chunk = resident_shot_chunk(ns, nt, nz, nx, budget, "f32")
+        a = 0
+        while a < ns:
+            plan = None
+            for c in range(min(chunk, ns - a), 0, -1):     # the plan's own plane size decides (column-blocked planes are padded)
+                plan = ElasticPlan(nz, nx, nt, c, nsrc, nrec, ntap, int(pml_width), dev.index, 0,
+                                   1 if free_surface else 0, 0, 0, snapshot_format, int(fd_order))
+                if 4 * nt * plan.layout.snap_step_elems <= budget:
+                    break
+                plan.close()
+                plan = None
+            if plan is None:
+                raise MifwiError("%s keeps the forward snapshots of all %d steps resident, and not even one shot's fit "
+                                 "the snapshot budget; Born modelling across time checkpoints is not served" % (name, nt))
+            try:
+                lay = plan.layout
+                if lay.snapshot_format != _lib.SNAPSHOT_F32:
+                    raise MifwiError("%s reads f32 snapshot planes: this plan keeps them as bf16" % name)
+                sl = slice(a, a + c)
+                mat_p, pz_d, px_p = _padded_inputs(mat, pz, px, lay.gp)
+                dmat_p = _padded_planes(dmat.to(dev), lay.gp)
+                taps = [t[sl].contiguous() for t in (geom.src_cell, geom.src_w, geom.rec_cell, geom.rec_w)]
+                geo = [_lib.ptr(t) for t in taps]
+                fc = f_d[:, sl].contiguous()
+                dfc = None if df_d is None else df_d[:, sl].contiguous()
+                rec = [torch.empty((nt, c, nrec), device=dev, dtype=torch.float32) for _ in range(4)]
+                work = torch.empty(max(lay.work_forward_elems, lay.work_backward_elems if adjoint else 0), device=dev,
+                                   dtype=torch.float32)
+                snap = torch.empty((nt, lay.snap_step_elems), device=dev, dtype=torch.float32)
+                tabs = (_lib.ptr(pz_d), _lib.ptr(px_p))
+                _lib.check(lib.mifwi_elastic_forward(plan.handle, _lib.ptr(mat_p), *tabs, _lib.ptr(fc), *geo, _lib.ptr(rec[0]),
+                                                     _lib.ptr(rec[1]), _lib.ptr(snap), _lib.ptr(work), 0, nt,
+                                                     _lib.ZERO_STATE, _stream()))
+                _lib.check(lib.mifwi_elastic_born(plan.handle, _lib.ptr(mat_p), _lib.ptr(dmat_p), *tabs, _lib.ptr(dfc), *geo,
+                                                  _lib.ptr(snap), 0, _lib.ptr(rec[2]), _lib.ptr(rec[3]), _lib.ptr(work), 0, nt,
+                                                  _lib.ZERO_STATE, _stream()))
+                for o, r in zip(out, rec):
+                    o[:, sl] = r
+                if adjoint:
+                    g = (rec[2], rec[3]) if weight is None else weight(rec[2], rec[3])
+                    g = [t.detach().to(device=dev, dtype=torch.float32).contiguous() for t in g]
+                    if len(g) != 2 or any(t.shape != rec[2].shape for t in g):
+                        raise MifwiError("weight must return (g_vx, g_vz) of the shape of its arguments")
+                    grad = torch.empty((5, nz, lay.gp), device=dev, dtype=torch.float32)
+                    _lib.check(lib.mifwi_elastic_backward(plan.handle, _lib.ptr(mat_p), *tabs, *geo, _lib.ptr(g[0]),
+                                                          _lib.ptr(g[1]), _lib.ptr(snap), 0, _lib.ptr(grad), None,
+                                                          _lib.ptr(work), nt - 1, 0, _lib.ZERO_STATE | _lib.FINALIZE,
+                                                          _stream()))
+                    hv += grad[:, :, :nx]
+            finally:
+                plan.close()
+            a += c
+    return out, hv
+
+
+def born(mat, dmat, f, pz, px, src_cell, src_w, rec_cell, rec_w, pml_width, df=None, free_surface=False, fd_order=4,
+         snapshot_budget=DEFAULT_SNAPSHOT_BUDGET, source_type="explosive", record_pressure=False, snapshot_format=None):
+    """Born / linearised modelling: returns ``(rec_vx, rec_vz, drec_vx, drec_vz)`` - the seismograms of the background
+    ``mat`` (what :func:`propagate` returns, bit for bit) and ``drec = J (dmat, df)``, their first-order change for the
+    perturbation ``dmat`` [5, nz, nx] of the material planes (:func:`materials_jvp` maps (dVp, dVs, drho) to it) and,
+    optionally, ``df`` [nt, nshot, nsrc] of the source amplitudes.  ``J`` is the exact transpose partner of the
+    gradients autograd returns for :func:`propagate`.  No autograd through this call.
+
+    One plan runs the background forward with resident f32 snapshots, in whichever kernel family it picks; the Born
+    pass (``mifwi_elastic_born``, one launch per half step) then reads the same buffer.  When the snapshots of all shots
+    do not fit ``snapshot_budget`` the shots are taken a few at a time (they are independent: the same results); when
+    not even one shot fits, ``MifwiError`` - Born across time checkpoints is not served, nor are bf16 snapshot planes,
+    force sources and pressure receivers (``source_type``, ``record_pressure``, ``snapshot_format`` are accepted so
+    that a caller's propagate() arguments can be passed along, and refused)."""
+    out, _ = _linearised("born", mat, dmat, f, pz, px, src_cell, src_w, rec_cell, rec_w, pml_width, df, free_surface,
+                         fd_order, snapshot_budget, source_type, record_pressure, snapshot_format, False, None)
+    return tuple(out)
+
+
+def gauss_newton_product(mat, dmat, f, pz, px, src_cell, src_w, rec_cell, rec_w, pml_width, df=None, free_surface=False,
+                         fd_order=4, snapshot_budget=DEFAULT_SNAPSHOT_BUDGET, weight=None, source_type="explosive",
+                         record_pressure=False, snapshot_format=None):
+    """Gauss-Newton Hessian-vector product ``hv = J^T W J dmat`` [5, nz, nx] with ONE background forward, one Born pass
+    and one adjoint pass over the same resident snapshot buffer (composing :func:`born` and :func:`propagate` runs the
+    background twice).  Returns ``(hv, drec_vx, drec_vz)`` with ``drec = J (dmat, df)`` as :func:`born` gives it.
+
+    ``weight``: None - the L2 misfit's identity - or a callable ``(drec_vx, drec_vz) -> (g_vx, g_vz)``: a data weighting,
+    or the second derivative of another misfit.  Shots are taken a few at a time like :func:`born` when their
+    snapshots do not fit the budget; ``hv`` sums over the chunks and ``weight`` is then called once per chunk with that
+    chunk's [nt, shots, nrec] traces, so it must act shot by shot.  Other arguments and refusals as :func:`born`."""
+    out, hv = _linearised("gauss_newton_product", mat, dmat, f, pz, px, src_cell, src_w, rec_cell, rec_w, pml_width, df,
+                          free_surface, fd_order, snapshot_budget, source_type, record_pressure, snapshot_format, True,
+                          weight)
+    return hv, out[2], out[3]
 
 
 SOURCE_TYPES = {"explosive": 0, "fx": 1, "fz": 2, 0: 0, 1: 1, 2: 2}
