@@ -494,6 +494,12 @@ def propagate(mat, f, pz, px, src_cell, src_w, rec_cell, rec_w, pml_width,
     moments of its snapshot planes into the holder (one more read of the snapshot buffer - resident, or every
     regenerated checkpoint segment once); a run that needs no gradient has no such pass and raises.  Without a holder
     nothing changes: the same launches, the same results.
+    Cells may carry one tap of weight 1 or the four bilinear taps of a point ([nshot, npoint, 4], inactive taps -1;
+    such runs use the one-launch-per-half-step kernels).  Repeated calls return the same seismograms bit for bit; the
+    gradients are bit-repeatable while no cell receives more than two receiver taps of a shot.  With three or more
+    (bilinear receivers closer than a cell) the per-step adjoint adds them with LDS float atomics in hardware order:
+    the bits then differ from call to call (observed with four taps per cell), each call within 2e-5 rel-L2 of the
+    fixed-order sum.
     Returns (rec_vx, rec_vz), each [nt,nshot,nrec], sampled after the velocity update; with
     ``record_pressure`` also rec_p = sum w (sxx + szz) at the receivers after the stress update (DENISE's
     pressure seismogram is ``-rec_p``; such runs use the one-launch-per-half-step kernels)."""

@@ -77,3 +77,96 @@ def elastic_case(seed=0, nz=44, nx=60, fw=8, nt=120, ns=2, nsrc=1, nrec=9, h=20.
         rc[0], rw[0] = H.cell_taps(np.zeros((1, nrec), dtype=int), rx_[:1], nx)
     return dict(mat=mat, pz=pz, px=px, f=f, sc=sc, sw=sw, rc=rc, rw=rw, fw=fw, vp=vp, vs=vs,
                 rho=rho, dt=dt, h=h, fs=1 if free_surface else 0)
+
+
+ADJ_TILE = (16, 64)       # rows x columns of one el_adj_s tile (ATZ, 4 * AGO in csrc/mifwi_elastic.hip)
+
+
+def taps_per_cell(cells, ncell):
+    """[nshot, ncell]: how many active taps of each shot's points fall into each cell."""
+    cells = np.asarray(cells)
+    out = np.zeros((cells.shape[0], ncell), dtype=np.int64)
+    for s in range(cells.shape[0]):
+        c = cells[s].reshape(-1)
+        np.add.at(out[s], c[c >= 0], 1)
+    return out
+
+
+def elastic_case_taps4(geometry, seed, free_surface=False, rx0=40.25, src0=(15.4, 63.3), min_tiles=4, **kw):
+    """elastic_case with bilinear four-tap sources and receivers (oracle.helpers.bilinear_taps; positions in cells here,
+    (depth, x), handed over in metres).
+
+    "T" (tiles, many taps per cell): 70 receivers at depth 15.5 (rows 15|16: an adjoint tile boundary), x = rx0 + k / 2
+    (across column 63|64; 280 taps per shot, interior cells get four); source 0 of shot 0 at ``src0`` (its taps in four
+    adjoint tiles), every other source at a fractional depth in [2, 5) and x in [4, nx - 5); the last receiver of the last
+    shot exactly on the last cell, three of its taps inactive.  Under ``free_surface`` shot 0's receivers and source 1
+    of shot 0 sit at depth 0.3 (rows 0|1).
+    "U" (unshared enough for bit comparisons): 36 receivers at x = rx0 + k, at most two receiver taps of a shot per cell.
+    ``rx0``, ``src0`` move the line and the first source on other grids; ``min_tiles`` is the number of adjoint tiles the
+    receiver taps of some shot must reach (4 unless the grid has a single tile column).  The conditions the tests rely
+    on are asserted on the output."""
+    assert geometry in ("T", "U")
+    cfg = dict(nz=37, nx=133, fw=6, ns=2, nsrc=2, nrec=70 if geometry == "T" else 36, nt=80)
+    cfg.update(kw)
+    c = elastic_case(seed=seed, free_surface=free_surface, **cfg)
+    nz, nx, ns, nsrc, nrec, h = cfg["nz"], cfg["nx"], cfg["ns"], cfg["nsrc"], cfg["nrec"], c["h"]
+    rng = np.random.default_rng([seed, 4])
+    src = np.zeros((ns, nsrc, 2))
+    for s in range(ns):
+        for i in range(nsrc):
+            while True:                      # the sources of a shot at least two cells apart in x
+                z, x = 2.0 + 3.0 * rng.random(), 4.0 + (nx - 9.0) * rng.random()
+                if (s, i) == (0, 0):
+                    z, x = src0
+                if all(abs(x - src[s, k, 1]) >= 2.0 for k in range(i)) and min(z % 1.0, x % 1.0) > 0.0:
+                    break
+            src[s, i] = z, x
+    if free_surface and nsrc > 1:
+        src[0, 1, 0] = 0.3
+    rec = np.zeros((ns, nrec, 2))
+    rec[..., 0] = 15.5
+    rec[..., 1] = rx0 + (0.5 if geometry == "T" else 1.0) * np.arange(nrec)
+    if free_surface:
+        rec[0, :, 0] = 0.3
+    rec[-1, -1] = nz - 1, nx - 1
+    c["sc"], c["sw"] = H.bilinear_taps(src * h, (h, h), 0, (nz, nx))
+    c["rc"], c["rw"] = H.bilinear_taps(rec * h, (h, h), 0, (nz, nx))
+    c["src_zx"], c["rec_zx"] = src, rec
+    # ---- what the tests rely on -------------------------------------------------------------------------------
+    sc, sw, rc, rw = c["sc"], c["sw"], c["rc"], c["rw"]
+    assert sc.shape == (ns, nsrc, 4) and rc.shape == (ns, nrec, 4)
+    assert (sc >= 0).all() and ((sw > 0) & (sw < 1)).all()
+    assert taps_per_cell(sc, nz * nx).max() == 1                       # no cell with two source taps of a shot
+    corner = np.zeros(rc.shape, dtype=bool)
+    corner[-1, -1] = True
+    act = rc >= 0
+    assert act[~corner].all() and ((rw > 0) & (rw < 1))[~corner].all()
+    assert list(rc[-1, -1]) == [nz * nx - 1, -1, -1, -1] and list(rw[-1, -1]) == [1.0, 0.0, 0.0, 0.0]
+    per_cell = taps_per_cell(rc, nz * nx)
+    if geometry == "T":
+        assert 1 <= (~act).sum() <= 3
+        assert per_cell.max() >= 3
+        tiles = [len({(q // nx // ADJ_TILE[0], q % nx // ADJ_TILE[1]) for q in rc[s][rc[s] >= 0]}) for s in range(ns)]
+        assert max(tiles) >= min_tiles, tiles
+    else:
+        assert per_cell.max() <= 2
+        assert all(abs(src[s, a, 1] - src[s, b, 1]) >= 2.0 for s in range(ns) for a in range(nsrc) for b in range(a))
+    return c
+
+
+def flatten_taps(case):
+    """The same points as one-tap points: [ns, n, 4] -> [ns, 4 n, 1] (inactive taps stay -1, weight 0) and ``f``
+    repeated over a source's taps.  Traces and grad_f of such a run, summed over each point's four entries
+    (:func:`sum_taps`), are those of the four-tap run up to the order of a <= 4-term sum."""
+    out = dict(case)
+    for k in ("sc", "sw", "rc", "rw"):
+        a = np.asarray(case[k])
+        out[k] = a.reshape(a.shape[0], -1, 1)
+    out["f"] = np.repeat(np.asarray(case["f"]), 4, axis=2)
+    return out
+
+
+def sum_taps(a):
+    """[nt, ns, 4 n] of a flattened run -> [nt, ns, n]."""
+    a = np.asarray(a, dtype=np.float64)
+    return a.reshape(a.shape[0], a.shape[1], -1, 4).sum(axis=-1)
