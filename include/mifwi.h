@@ -29,7 +29,7 @@ extern "C" {
 #endif
 
 #define MIFWI_VERSION_MAJOR 0
-#define MIFWI_VERSION_MINOR 7   /* 3: elastic desc gained snapshot_format, fd_order; layout snap_step_elems, snapshot_format; 4: mifwi_fallback_count; 5: mifwi_agent_handoff_count, mifwi_slow_handoff_count; acoustic desc gained cpml_width, layout state_elems; 6: mifwi_elastic_materials(_vjp), mifwi_acoustic_coefficients(_vjp); 7: mifwi_elastic_gradient_parametrization; elastic snapshot planes column-blocked in plans without a single-launch kernel; later additions that leave every existing call as it was keep 7: mifwi_elastic_snapshot_moments, mifwi_elastic_pseudo_hessian, mifwi_gradient_precondition, mifwi_elastic_born */
+#define MIFWI_VERSION_MINOR 7   /* 3: elastic desc gained snapshot_format, fd_order; layout snap_step_elems, snapshot_format; 4: mifwi_fallback_count; 5: mifwi_agent_handoff_count, mifwi_slow_handoff_count; acoustic desc gained cpml_width, layout state_elems; 6: mifwi_elastic_materials(_vjp), mifwi_acoustic_coefficients(_vjp); 7: mifwi_elastic_gradient_parametrization; elastic snapshot planes column-blocked in plans without a single-launch kernel; later additions that leave every existing call as it was keep 7: mifwi_elastic_snapshot_moments, mifwi_elastic_pseudo_hessian, mifwi_gradient_precondition, mifwi_elastic_born, mifwi_acoustic_snapshot_moments, mifwi_acoustic_pseudo_hessian */
 
 enum {
     MIFWI_OK = 0,
@@ -445,6 +445,44 @@ int mifwi_acoustic_coefficients(int device, const float *vp, float *r, int32_t n
                                 float dt_over_h, void *stream);
 int mifwi_acoustic_coefficients_vjp(int device, const float *vp, const float *grad_r, float *grad_vp, int32_t nz,
                                     int32_t nx, int32_t pad, float dt_over_h, void *stream);
+
+/* ======================================================================================
+ * Diagonal PSEUDO-HESSIAN of the acoustic gradient (the scalar counterpart of the elastic block above)
+ *
+ * Serves the deepwave-shaped protocol (models/networks.py:5408-5491 and its prop() variants) and the square-slowness
+ * protocol of seisgan/fwi (layers.py:158-197), whose raw gradients are dominated by the cells around the sources.
+ *
+ * The plane G^n a forward step saves for the adjoint is the virtual source of the coefficient r (mifwi_acoustic_born
+ * injects G^n dr), so
+ *   MOMENT  M [n0][gp] = sum over the plan's shots and the selected steps of (G^n)^2
+ * is the pseudo-Hessian with respect to r: one more read of the snapshot buffer, no extra propagation.
+ * steps n in [n_begin, n_end) with n % stride == 0 (absolute n: a range may be cut anywhere), each weighted by stride;
+ * step n at snap + (n - snap_first) * nshot * n0 * gp as mifwi_acoustic_forward of the same plan wrote it (both kernel
+ * families, sponge and C-PML plans); MIFWI_ZERO_STATE: overwrite, else add.  Columns >= n1 are written as 0 whatever
+ * the snapshot pad holds.  work: mifwi_acoustic_snapshot_moments_work_elems(plan) floats (partial planes of the step
+ * range, added in a fixed order: no atomics, two identical calls give the same bits).  MIFWI_EINVAL: a null pointer,
+ * stride < 1, an empty or reversed range or one outside [0, nt), snap_first > n_begin, a pointer that is not 16-byte
+ * aligned.  (G^{nt-1} never reaches a recorded sample: a gradient's own Hessian takes [0, nt - 1).)
+ * ==================================================================================== */
+int64_t mifwi_acoustic_snapshot_moments_work_elems(const mifwi_acoustic_plan *plan);
+int mifwi_acoustic_snapshot_moments(mifwi_acoustic_plan *plan, const float *snap, int32_t snap_first,
+                                    int32_t n_begin, int32_t n_end, int32_t stride, float *moments,
+                                    float *work, int32_t flags, void *stream);
+
+/* The pseudo-Hessian plane of a model parameter from that moment:
+ *   MIFWI_AC_PARAM_VELOCITY  (1)  the deepwave protocol: model = vp [nz][nx], moments [nz + 2 pad][gp], scale = dt/h,
+ *                                 r = (edge-replicated vp * scale)^2 as mifwi_acoustic_coefficients forms it;
+ *                                 hess[i][j] = (2 vp scale^2)^2 * sum of M over the padded cells that replicate (i, j)
+ *                                 (the fold of mifwi_acoustic_coefficients_vjp; exact when J^T J is diagonal)
+ *   MIFWI_AC_PARAM_SLOWNESS2 (2)  the seisgan protocol: model = m = 1/vp^2 [nz][nx] on the padded grid itself, every
+ *                                 cell its own variable (pad must be 0), r = scale^2 / m with scale = s/h;
+ *                                 hess = (r / m)^2 * M
+ * hess [nz][nx] device, no padding.  Every output is finite and >= 0; a cell with vp = 0 or m <= 0 gives 0. */
+#define MIFWI_AC_PARAM_VELOCITY 1
+#define MIFWI_AC_PARAM_SLOWNESS2 2
+int mifwi_acoustic_pseudo_hessian(int device, int32_t parametrization, const float *model, const float *moments,
+                                  int32_t nz, int32_t nx, int32_t pad, int32_t gp, float scale, float *hess,
+                                  void *stream);
 
 #ifdef __cplusplus
 }

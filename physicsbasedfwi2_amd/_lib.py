@@ -106,7 +106,12 @@ SIGNATURES = {
     "mifwi_gradient_precondition": (ctypes.c_int, [ctypes.c_int] + [_P] * 3 + [ctypes.c_int32, ctypes.c_int64] + [_P] * 3),
     "mifwi_acoustic_coefficients": (ctypes.c_int, [ctypes.c_int] + [_P] * 2 + [ctypes.c_int32] * 3 + [ctypes.c_float, _P]),
     "mifwi_acoustic_coefficients_vjp": (ctypes.c_int, [ctypes.c_int] + [_P] * 3 + [ctypes.c_int32] * 3 + [ctypes.c_float, _P]),
+    "mifwi_acoustic_snapshot_moments_work_elems": (ctypes.c_int64, [_P]),
+    "mifwi_acoustic_snapshot_moments": (ctypes.c_int, [_P] * 2 + [ctypes.c_int32] * 4 + [_P] * 2 + [ctypes.c_int32, _P]),
+    "mifwi_acoustic_pseudo_hessian": (ctypes.c_int, [ctypes.c_int, ctypes.c_int32] + [_P] * 2 + [ctypes.c_int32] * 4 +
+                                      [ctypes.c_float] + [_P] * 2),
 }
+AC_PARAM_VELOCITY, AC_PARAM_SLOWNESS2 = 1, 2
 MISFIT_L1_TRACE_NORM = 0
 MISFIT_L2 = 1
 MISFIT_GLOBAL_CORRELATION = 2

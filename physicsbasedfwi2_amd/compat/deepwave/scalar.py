@@ -33,6 +33,11 @@ discretisation error inside the model); several times slower.
 of the fourth-order stencil; "deepwave": deepwave's own bound dt_max = 0.6 / (vp_max sqrt(sum 1/dx_i^2)) (SURVEY.md
 appendix C) - 1.4x tighter, so a caller that wants deepwave's sub-step ratio (2 above 4243 m/s at dx = 10 m,
 dt = 1 ms) gets it; a number = that fraction of the stability limit.
+
+``pseudo_hessian=holder`` (an ``acoustic.PseudoHessian``; not deepwave's): every backward pass through the propagator adds
+the snapshot second moments of its run to the holder, and ``prop.pseudo_hessian_vp()`` maps them to the diagonal
+pseudo-Hessian of ``vp`` with the ``pml_width`` and the internal ``dt / h`` the last call used
+(``holder.hessian_velocity``).  ``absorbing="cpml-staggered"`` runs on the elastic kernels and refuses the holder.
 """
 import functools
 import math
@@ -179,12 +184,19 @@ def _pml_velocity(vmax):
 
 class Propagator(torch.nn.Module):
     def __init__(self, model, dx, pml_width=None, survey_pad=None, vpmax=None, absorbing="cpml", pml_freq=None,
-                 cfl="stability"):
+                 cfl="stability", pseudo_hessian=None):
         super().__init__()
         if absorbing not in ("sponge", "cpml", "cpml-staggered"):
             raise MifwiError("absorbing must be 'sponge', 'cpml' or 'cpml-staggered'")
         if not (cfl in ("stability", "deepwave") or (isinstance(cfl, (int, float)) and 0 < cfl <= 1)):
             raise MifwiError("cfl must be 'stability', 'deepwave' or a fraction of the stability limit in (0, 1]")
+        if pseudo_hessian is not None and not isinstance(pseudo_hessian, acoustic.PseudoHessian):
+            raise MifwiError("pseudo_hessian must be an acoustic.PseudoHessian holder or None")
+        if pseudo_hessian is not None and absorbing == "cpml-staggered":
+            raise MifwiError("absorbing='cpml-staggered' runs on the elastic kernels, whose snapshot planes are not the "
+                             "scalar scheme's: an acoustic.PseudoHessian holder is served by 'cpml' and 'sponge' only")
+        self.pseudo_hessian = pseudo_hessian
+        self._hessian_pad_scale = None           # (pml_width, internal dt / h) of the last call
         self.absorbing = absorbing
         self.cfl = cfl
         self.pml_freq = pml_freq                 # C-PML only: dominant frequency (Hz) of the frequency shift
@@ -252,6 +264,7 @@ class Propagator(torch.nn.Module):
         dti = dt / ratio
 
         n0, n1 = vp.shape[0] + 2 * P, vp.shape[1] + 2 * P
+        self._hessian_pad_scale = (P, dti / h)
         if vp.dtype == torch.float32:
             r = _Coefficients.apply(vp, P, dti / h)
         else:
@@ -266,9 +279,20 @@ class Propagator(torch.nn.Module):
             vkey = float(self.vpmax) if self.vpmax is not None else _pml_velocity(vmax)
             ab0, ab1 = _cpml_ab(n0, P, dz, dti, vkey, fpml, str(dev)), _cpml_ab(n1, P, dx, dti, vkey, fpml, str(dev))
             rec = acoustic.propagate(r, f, ab0, ab1, sc, sw, rc, rw, (h / dz) ** 2, (h / dx) ** 2,
-                                     shots_per_group=self.shots_per_group, cpml_width=P)
+                                     shots_per_group=self.shots_per_group, cpml_width=P,
+                                     pseudo_hessian=self.pseudo_hessian)
             return rec[::ratio] if ratio > 1 else rec
         q0, q1 = _sponge(n0, P, dz, h, dti, str(dev)), _sponge(n1, P, dx, h, dti, str(dev))
         rec = acoustic.propagate(r, f, q0, q1, sc, sw, rc, rw, (h / dz) ** 2, (h / dx) ** 2,
-                                 shots_per_group=self.shots_per_group, edge_rows=P)
+                                 shots_per_group=self.shots_per_group, edge_rows=P, pseudo_hessian=self.pseudo_hessian)
         return rec[::ratio] if ratio > 1 else rec
+
+    def pseudo_hessian_vp(self):
+        """[nz, nx]: the diagonal pseudo-Hessian of ``self.vp`` from the moments the holder has gathered, with the
+        pad and the internal dt / h of the last call (``holder.hessian_velocity(vp, dt / h, pml_width)``)."""
+        if self.pseudo_hessian is None:
+            raise MifwiError("pseudo_hessian_vp: this Propagator was built without a pseudo_hessian holder")
+        if self._hessian_pad_scale is None:
+            raise MifwiError("pseudo_hessian_vp: call the propagator and run a backward pass first")
+        pad, scale = self._hessian_pad_scale
+        return self.pseudo_hessian.hessian_velocity(self.vp, scale, pad)

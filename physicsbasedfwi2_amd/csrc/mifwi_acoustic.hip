@@ -1876,3 +1876,6 @@ int mifwi_acoustic_backward(mifwi_acoustic_plan *pl, const float *r, const float
 }
 
 }  // extern "C"
+
+// snapshot second moment (pseudo-Hessian ingredient): reads the snapshot buffer the way the adjoint does
+#include "mifwi_acoustic_moments.h"

@@ -13,9 +13,10 @@
 // One thread owns one 4-cell group and keeps six float4 accumulators; it walks the shots, then its share of the selected
 // steps, in a fixed order, with 16-byte loads (every layout a plan writes: row-major f32, column-blocked f32,
 // column-blocked bf16).  The step range is split over blockIdx.y into partial planes (a 100x300 grid has 7.5 k groups,
-// far too few threads for the stream); a second launch adds the partials in index order.  The split depends on the plan
+// far too few threads for the stream); a second launch (mifwi_moments_sum.h) adds the partials in index order.  The split depends on the plan
 // and the range only, there is no atomic anywhere: two identical calls give the same bits.
 #pragma once
+#include "mifwi_moments_sum.h"
 
 namespace {
 
@@ -85,25 +86,6 @@ __global__ __launch_bounds__(kThreads) void el_snapshot_moments(const ElParams p
     st4(o + 5 * plane, M5);
 }
 
-// out [6][nz][gp] = (add ? out : 0) + w * (part[0] + part[1] + ...), columns >= nx written as 0
-__global__ __launch_bounds__(kThreads) void el_moments_sum(const float *part, int nsplit, long long n6, int gp, int nx, float w,
-                                                           int add, float *out)
-{
-    const long long e = 4 * ((long long)blockIdx.x * kThreads + threadIdx.x);
-    if (e >= n6) return;
-    float a[4] = {0.f, 0.f, 0.f, 0.f};
-    for (int c = 0; c < nsplit; ++c) {
-        const float4 v = ld4(part + (long long)c * n6 + e);
-        a[0] += v.x; a[1] += v.y; a[2] += v.z; a[3] += v.w;
-    }
-    const float4 old = add ? ld4(out + e) : make_float4(0.f, 0.f, 0.f, 0.f);
-    const int col = (int)(e % gp);
-    float r[4];
-#pragma unroll
-    for (int c = 0; c < 4; ++c) r[c] = col + c < nx ? fmaf(w, a[c], comp(old, c)) : 0.f;
-    st4(out + e, make_float4(r[0], r[1], r[2], r[3]));
-}
-
 }  // namespace
 
 extern "C" {
@@ -149,8 +131,7 @@ int mifwi_elastic_snapshot_moments(mifwi_elastic_plan *pl, const float *snap, in
         else hipLaunchKernelGGL(el_snapshot_moments<false>, grid, block, 0, st, p, m);
     }
     const long long n6 = 6LL * pl->coef_elems;
-    hipLaunchKernelGGL(el_moments_sum, dim3((unsigned)((n6 / 4 + kThreads - 1) / kThreads)), dim3(kThreads), 0, st, work, nsplit, n6,
-                       pl->gp, d.nx, (float)stride, (flags & MIFWI_ZERO_STATE) ? 0 : 1, moments);
+    launch_moments_sum(work, nsplit, n6, pl->gp, d.nx, (float)stride, (flags & MIFWI_ZERO_STATE) ? 0 : 1, moments, st);
     MIFWI_HIP_TRY(hipGetLastError());
     return MIFWI_OK;
 }

@@ -217,6 +217,36 @@ __global__ __launch_bounds__(kMT) void coef_vjp(const float *vp, const float *gr
     gvp[k] = sum * (2.0f * x) * c;
 }
 
+// diagonal pseudo-Hessian of the scalar scheme from the snapshot moment M = sum (G^n)^2 (mifwi_acoustic_moments.h), which
+// is the pseudo-Hessian with respect to the coefficient r itself.  VELOCITY: r = (edge-replicated vp * c)^2 - every padded
+// cell that replicates model cell (i, j) moves with it at the rate dr/dvp = 2 vp c^2, so H = (2 vp c^2)^2 * sum M over those
+// cells (the fold of coef_vjp, same order: exact when J^T J is diagonal).  One thread per model cell.
+__global__ __launch_bounds__(kMT) void ac_hess_velocity(const float *vp, const float *mom, float *hess, int nz, int nx, int pad,
+                                                        int gp, float c)
+{
+    const long long k = (long long)blockIdx.x * kMT + threadIdx.x;
+    if (k >= (long long)nz * nx) return;
+    const int i = (int)(k / nx), j = (int)(k - (long long)i * nx);
+    const int n0 = nz + 2 * pad, n1 = nx + 2 * pad;
+    const int a0 = i == 0 ? 0 : i + pad, a1 = i == nz - 1 ? n0 - 1 : i + pad;
+    const int b0 = j == 0 ? 0 : j + pad, b1 = j == nx - 1 ? n1 - 1 : j + pad;
+    float sum = 0.f;
+    for (int a = a0; a <= a1; ++a)
+        for (int b = b0; b <= b1; ++b) sum += mom[(long long)a * gp + b];
+    const float d = (2.0f * (vp[k] * c)) * c;
+    hess[k] = vp[k] == 0.f ? 0.f : fmaxf(d * d * sum, 0.f);
+}
+// SLOWNESS2: m = 1 / vp^2 on the padded grid itself, every cell its own variable; r = c^2 / m, dr/dm = -r / m
+__global__ __launch_bounds__(kMT) void ac_hess_slowness2(const float *m, const float *mom, float *hess, int nz, int nx, int gp, float c)
+{
+    const long long k = (long long)blockIdx.x * kMT + threadIdx.x;
+    if (k >= (long long)nz * nx) return;
+    const int i = (int)(k / nx), j = (int)(k - (long long)i * nx);
+    const float v = m[k];
+    const float d = v > 0.f ? (c * c / v) / v : 0.f;
+    hess[k] = v > 0.f ? fmaxf(d * d * mom[(long long)i * gp + j], 0.f) : 0.f;
+}
+
 }  // namespace
 
 extern "C" {
@@ -242,6 +272,29 @@ int mifwi_acoustic_coefficients_vjp(int device, const float *vp, const float *gr
     const long long n = (long long)nz * nx;
     hipLaunchKernelGGL(coef_vjp, dim3((unsigned)((n + kMT - 1) / kMT)), dim3(kMT), 0, (hipStream_t)stream, vp, grad_r, grad_vp, nz,
                        nx, pad, dt_over_h);
+    MIFWI_HIP_TRY(hipGetLastError());
+    return MIFWI_OK;
+}
+
+
+int mifwi_acoustic_pseudo_hessian(int device, int32_t parametrization, const float *model, const float *moments, int32_t nz,
+                                  int32_t nx, int32_t pad, int32_t gp, float scale, float *hess, void *stream)
+{
+    if (!model || !moments || !hess || nz < 1 || nx < 1 || pad < 0 || gp < nx + 2 * pad)
+        return mifwi::fail(MIFWI_EINVAL, "mifwi_acoustic_pseudo_hessian: bad argument");
+    if (parametrization != MIFWI_AC_PARAM_VELOCITY && parametrization != MIFWI_AC_PARAM_SLOWNESS2)
+        return mifwi::fail(MIFWI_EINVAL, "parametrization %d: 1 = vp (model edge-replicated into the layer), 2 = 1/vp^2 on the padded grid",
+                           parametrization);
+    if (parametrization == MIFWI_AC_PARAM_SLOWNESS2 && pad != 0)
+        return mifwi::fail(MIFWI_EINVAL, "the square-slowness model lives on the padded grid itself: pad must be 0 (got %d)", pad);
+    MIFWI_HIP_TRY(hipSetDevice(device));
+    hipStream_t st = (hipStream_t)stream;
+    const long long n = (long long)nz * nx;
+    const dim3 grid((unsigned)((n + kMT - 1) / kMT)), block(kMT);
+    if (parametrization == MIFWI_AC_PARAM_VELOCITY)
+        hipLaunchKernelGGL(ac_hess_velocity, grid, block, 0, st, model, moments, hess, nz, nx, pad, gp, scale);
+    else
+        hipLaunchKernelGGL(ac_hess_slowness2, grid, block, 0, st, model, moments, hess, nz, nx, gp, scale);
     MIFWI_HIP_TRY(hipGetLastError());
     return MIFWI_OK;
 }

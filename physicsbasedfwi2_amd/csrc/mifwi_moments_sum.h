@@ -1,0 +1,37 @@
+// Second launch of the snapshot-moments passes (mifwi_elastic_moments.h, mifwi_acoustic_moments.h): the partial planes
+// the first launch left in `work` are added in index order - a fixed order, no atomics.
+#pragma once
+
+namespace {
+
+constexpr int kMomSumThreads = 256;
+
+// out [n] = (add ? out : 0) + w * (part[0] + part[1] + ...); n floats = whole rows of gp columns, columns >= nx are
+// written as 0 whatever the partial planes hold there
+__global__ __launch_bounds__(kMomSumThreads) void moments_sum(const float *part, int nsplit, long long n, int gp, int nx, float w,
+                                                              int add, float *out)
+{
+    const long long e = 4 * ((long long)blockIdx.x * kMomSumThreads + threadIdx.x);
+    if (e >= n) return;
+    float a[4] = {0.f, 0.f, 0.f, 0.f};
+    for (int c = 0; c < nsplit; ++c) {
+        const float4 v = *reinterpret_cast<const float4 *>(part + (long long)c * n + e);
+        a[0] += v.x; a[1] += v.y; a[2] += v.z; a[3] += v.w;
+    }
+    const float4 old = add ? *reinterpret_cast<const float4 *>(out + e) : make_float4(0.f, 0.f, 0.f, 0.f);
+    const float o[4] = {old.x, old.y, old.z, old.w};
+    const int col = (int)(e % gp);
+    float r[4];
+#pragma unroll
+    for (int c = 0; c < 4; ++c) r[c] = col + c < nx ? fmaf(w, a[c], o[c]) : 0.f;
+    *reinterpret_cast<float4 *>(out + e) = make_float4(r[0], r[1], r[2], r[3]);
+}
+
+inline void launch_moments_sum(const float *part, int nsplit, long long n, int gp, int nx, float w, int add, float *out,
+                               hipStream_t st)
+{
+    hipLaunchKernelGGL(moments_sum, dim3((unsigned)((n / 4 + kMomSumThreads - 1) / kMomSumThreads)), dim3(kMomSumThreads), 0, st,
+                       part, nsplit, n, gp, nx, w, add, out);
+}
+
+}  // namespace

@@ -14,7 +14,7 @@ import torch
 
 from . import _lib
 from ._lib import MifwiError
-from .acoustic import _Geometry, _require_cuda, _stream
+from .acoustic import _Geometry, _MomentsHolder, _require_cuda, _stream
 
 # bytes of snapshot planes + time checkpoints a call may hold (288 GB of HBM per GPU; the rest is left to the caller's
 # network and data); MIFWI_EL_SNAPSHOT_BUDGET_GB overrides it (measurements of the checkpointed path on short runs)
@@ -193,7 +193,7 @@ class ElasticPlan:
             pass
 
 
-class PseudoHessian:
+class PseudoHessian(_MomentsHolder):
     """Holder of the six snapshot second moments behind the diagonal pseudo-Hessian (Shin's preconditioner; DENISE's
     ``EPRECOND = 1``): pass it to :func:`propagate` (``pseudo_hessian=``) and every backward pass through that call
     adds ``M0..M4 = sum Sk^2, M5 = sum S0 S1`` of its forward snapshot planes - summed over its shots and over the
@@ -201,25 +201,6 @@ class PseudoHessian:
     first backward).  The holder accumulates over calls (shot chunks, ranks' shares); :meth:`reset` zeroes it.
     The pass is one more read of the snapshot buffer the backward holds (``mifwi_elastic_snapshot_moments``), no
     extra propagation; ``stride = 4`` reads a quarter of it."""
-
-    def __init__(self, stride=1):
-        if int(stride) < 1:
-            raise MifwiError("PseudoHessian: stride must be >= 1 (got %r)" % (stride,))
-        self.stride = int(stride)
-        self.moments = None
-
-    def reset(self):
-        if self.moments is not None:
-            self.moments.zero_()
-
-    def _add(self, m):
-        if self.moments is None:
-            self.moments = m.contiguous().clone()
-        elif self.moments.shape != m.shape or self.moments.device != m.device:
-            raise MifwiError("PseudoHessian holds moments of a %s grid, this run has %s"
-                             % (tuple(self.moments.shape[1:]), tuple(m.shape[1:])))
-        else:
-            self.moments.add_(m)
 
     def hessian(self, vp, vs, rho, dt, h, parametrization=PARAM_VELOCITY):
         """[3, nz, nx]: the pseudo-Hessian planes of (Vp, Vs, rho), (Zp, Zs, rho) or (lambda, mu, rho) - the order of
