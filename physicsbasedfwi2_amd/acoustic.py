@@ -5,149 +5,25 @@ models/networks.py:5464/5491 and ``FWILoss`` does at seisgan/fwi/layers.py:158-1
 
 All arithmetic happens in libmifwi.so (HIP); there is no CPU path here.
 """
-import ctypes
-import os
-
 import torch
 
 from . import _lib
 from ._lib import MifwiError
+from ._driver import (_GEOMETRIES, _Geometry, _MomentsHolder, _Plan, _require_cuda, _stream,  # noqa: F401 (re-exported)
+                      pad_columns, ptrs, run_backward, run_forward, segment_length)
 
 # snapshots kept resident between forward and backward; above this the time axis is cut
 # into checkpointed segments that are re-propagated during the adjoint (exact, ~1 extra forward)
 DEFAULT_SNAPSHOT_BUDGET = 96 << 30
 
 
-class AcousticPlan:
-    """RAII wrapper of ``mifwi_acoustic_plan`` (include/mifwi.h)."""
+class AcousticPlan(_Plan):
+    PREFIX, LAYOUT = "acoustic", _lib.AcousticLayout
 
     def __init__(self, n0, n1, nt, nshot, nsrc, nrec, ntap, c0, c1, device_index,
                  shots_per_group=0, edge_rows=0, cpml_width=0):
-        self._lib = _lib.load()
-        self.desc = _lib.AcousticDesc(n0, n1, nt, nshot, nsrc, nrec, ntap, c0, c1,
-                                      shots_per_group, int(edge_rows), int(cpml_width))
-        self._h = ctypes.c_void_p()
-        _lib.check(self._lib.mifwi_acoustic_plan_create(ctypes.byref(self._h), device_index,
-                                                        ctypes.byref(self.desc)))
-        self.layout = _lib.AcousticLayout()
-        _lib.check(self._lib.mifwi_acoustic_plan_layout(self._h, ctypes.byref(self.layout)))
-
-    @property
-    def handle(self):
-        return self._h
-
-    def pass_sizes(self):
-        """(forward, adjoint) units per pass of the per-step kernels over the time range: shots / shot groups
-        (elastic), shot groups (acoustic) - what stays inside the Infinity Cache."""
-        a, b = ctypes.c_int32(0), ctypes.c_int32(0)
-        _lib.check(self._lib.mifwi_acoustic_plan_pass_sizes(self._h, ctypes.byref(a), ctypes.byref(b)))
-        return a.value, b.value
-
-    def cluster_slabs(self, adjoint=False):
-        """Row slabs per shot of the single-launch time loop (0: one launch per step)."""
-        return int(self._lib.mifwi_acoustic_plan_cluster_slabs(self._h, int(bool(adjoint))))
-
-    def close(self):
-        if self._h:
-            self._lib.mifwi_acoustic_plan_destroy(self._h)
-            self._h = ctypes.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:  # noqa: BLE001
-            pass
-
-
-def _require_cuda(t, name):
-    if not t.is_cuda:
-        raise MifwiError("%s must live on a HIP device (got %s): libmifwi has no CPU fallback"
-                         % (name, t.device))
-
-
-def _stream():
-    return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
-# Geometries already built from the caller's four tap tensors, when those live on the device (weak references + versions:
-# an entry is used only while the very same, unmodified tensor objects are passed again).  A training loop passes the same
-# acquisition every iteration: the validation of the cells (a host round trip that stalls the launch queue) is paid once.
-# What the key can see: the tensor OBJECT, its version counter, its storage address and shape.  What it cannot see: a
-# write that bypasses autograd's version counter (`t.data[...] = `, a kernel of another library writing through the raw
-# pointer) - a caller that edits an acquisition in place that way must pass a new tensor, or set MIFWI_NO_GEOM_CACHE=1
-# (every call then rebuilds and re-validates its geometry).  Negative cells are inactive taps by convention (the
-# kernels skip them), so the validation bounds the cells from above only.
-_GEOMETRIES = []
-
-
-def _geom_key(t):
-    return (t._version, t.data_ptr(), tuple(t.shape))
-
-
-class _Geometry:
-    """Device-resident sparse-point description shared by forward and backward."""
-
-    @classmethod
-    def get(cls, src_cell, src_w, rec_cell, rec_w, device):
-        import weakref
-        given = (src_cell, src_w, rec_cell, rec_w)
-        # host tensors may alias numpy buffers (no version counter there): rebuilt every call
-        if not all(t.is_cuda for t in given) or os.environ.get("MIFWI_NO_GEOM_CACHE", "0") not in ("", "0"):
-            return cls(src_cell, src_w, rec_cell, rec_w, device)
-        for refs, versions, dev, geom in _GEOMETRIES:
-            if dev == device and all(r() is t for r, t in zip(refs, given)) and versions == tuple(_geom_key(t) for t in given):
-                return geom
-        geom = cls(src_cell, src_w, rec_cell, rec_w, device)
-        _GEOMETRIES[:] = [e for e in _GEOMETRIES if all(r() is not None for r in e[0])][-15:]
-        _GEOMETRIES.append((tuple(weakref.ref(t) for t in given), tuple(_geom_key(t) for t in given), device, geom))
-        return geom
-
-    def check_cells(self, ncell, what):
-        """Every tap inside the grid (an out-of-grid cell would fault the kernels).  One host round trip, once per
-        geometry."""
-        if self._top is None:
-            tops = [c.max() for c in (self.src_cell, self.rec_cell) if c.numel()]
-            self._top = int(torch.stack(tops).max()) if tops else -1
-        if self._top >= ncell:
-            raise MifwiError("src_cell/rec_cell hold a cell outside the %s grid" % what)
-
-    def __init__(self, src_cell, src_w, rec_cell, rec_w, device):
-        self._top = None
-        self.src_cell = src_cell.to(device=device, dtype=torch.int32).contiguous()
-        self.src_w = src_w.to(device=device, dtype=torch.float32).contiguous()
-        self.rec_cell = rec_cell.to(device=device, dtype=torch.int32).contiguous()
-        self.rec_w = rec_w.to(device=device, dtype=torch.float32).contiguous()
-        if self.src_cell.dim() != 3 or self.rec_cell.dim() != 3:
-            raise MifwiError("src_cell/rec_cell must be [nshot, npoint, ntap]")
-        if self.src_cell.shape != self.src_w.shape or self.rec_cell.shape != self.rec_w.shape:
-            raise MifwiError("cell/weight shape mismatch")
-        if self.src_cell.shape[0] != self.rec_cell.shape[0]:
-            raise MifwiError("source and receiver shot counts differ")
-        if self.src_cell.shape[2] != self.rec_cell.shape[2]:
-            raise MifwiError("sources and receivers must use the same number of taps")
-
-
-class _MomentsHolder:
-    """What the pseudo-Hessian holders of the two propagators share: the stride, the accumulated moments of one grid."""
-
-    def __init__(self, stride=1):
-        if int(stride) < 1:
-            raise MifwiError("PseudoHessian: stride must be >= 1 (got %r)" % (stride,))
-        self.stride = int(stride)
-        self.moments = None
-
-    def reset(self):
-        if self.moments is not None:
-            self.moments.zero_()
-
-    def _add(self, m):
-        if self.moments is None:
-            self.moments = m.contiguous().clone()
-        elif self.moments.shape != m.shape or self.moments.device != m.device:
-            raise MifwiError("PseudoHessian holds moments of a %s grid, this run has %s"
-                             % (tuple(self.moments.shape[-2:]), tuple(m.shape[-2:])))
-        else:
-            self.moments.add_(m)
+        self._create(_lib.AcousticDesc(n0, n1, nt, nshot, nsrc, nrec, ntap, c0, c1,
+                                       shots_per_group, int(edge_rows), int(cpml_width)), device_index)
 
 
 class PseudoHessian(_MomentsHolder):
@@ -199,37 +75,51 @@ class PseudoHessian(_MomentsHolder):
         return conditioning.precondition_gradients(grad[None], torch.as_tensor(hess)[None], eps)[0]
 
 
+def _acoustic_inputs(r, q0, q1, cpml_width, gp):
+    """r, q0, q1 as the C calls take them: float32 on r's device, the rows of r and q1 padded with 0 to gp columns."""
+    n0, n1 = r.shape
+    if cpml_width > 0 and (tuple(q0.shape) != (2, n0) or tuple(q1.shape) != (2, n1)):
+        # q0 / q1 carry the layer's a, b profiles: [2, n0], [2, n1] -> [2, gp]
+        raise MifwiError("cpml_width > 0: q0 / q1 must be the [2, n0] / [2, n1] C-PML profiles (a, b)")
+    dev = r.device
+    return (pad_columns(r, gp), q0.to(device=dev, dtype=torch.float32).contiguous(),
+            pad_columns(q1.to(device=dev, dtype=torch.float32), gp))
+
+
+def _forward_call(plan, coef, f_d, geo, rec):
+    """``forward(snap_ptr, work_ptr, b, e, flags)`` as the drivers take it; ``rec`` None: a re-run that samples nothing."""
+    lib = _lib.load()
+    args = (plan.handle, *coef, _lib.ptr(f_d), *geo, _lib.ptr(rec))
+    return lambda snap, work, b, e, flags: _lib.check(
+        lib.mifwi_acoustic_forward(*args, snap, work, b, e, flags, _stream()))
+
+
+def _adjoint_call(plan, coef, geo, g, grad_r, grad_f, work):
+    """``adjoint(snap_ptr, snap_first, hi, lo, flags)`` as the backward driver takes it."""
+    lib = _lib.load()
+    return lambda snap, first, hi, lo, flags: _lib.check(lib.mifwi_acoustic_backward(
+        plan.handle, *coef, *geo, _lib.ptr(g), snap, first, _lib.ptr(grad_r), _lib.ptr(grad_f), _lib.ptr(work), hi, lo,
+        flags, _stream()))
+
+
 class _AcousticFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, r, f, q0, q1, geom, c0, c1, shots_per_group, snapshot_budget, edge_rows, cpml_width=0,
                 pseudo_hessian=None):
         _require_cuda(r, "r")
         dev = r.device
-        lib = _lib.load()
         n0, n1 = r.shape
         nt, ns, nsrc = f.shape
         if geom.src_cell.shape[:2] != (ns, nsrc):
             raise MifwiError("f is [nt,%d,%d] but src_cell is %s" % (ns, nsrc,
                                                                       tuple(geom.src_cell.shape)))
         nrec, ntap = geom.rec_cell.shape[1], geom.rec_cell.shape[2]
-        ncell = n0 * n1
-        geom.check_cells(ncell, "%dx%d" % (n0, n1))
+        geom.check_cells(n0 * n1, "%dx%d" % (n0, n1))
         with torch.cuda.device(dev):
             plan = AcousticPlan(n0, n1, nt, ns, nsrc, nrec, ntap, c0, c1, dev.index,
                                 shots_per_group, edge_rows, cpml_width)
             lay = plan.layout
-            gp = lay.gp
-            r_p = torch.zeros((n0, gp), device=dev, dtype=torch.float32)
-            r_p[:, :n1] = r.detach()
-            q0_d = q0.to(device=dev, dtype=torch.float32).contiguous()
-            if cpml_width > 0:                   # q0 / q1 carry the layer's a, b profiles: [2, n0], [2, n1] -> [2, gp]
-                if tuple(q0.shape) != (2, n0) or tuple(q1.shape) != (2, n1):
-                    raise MifwiError("cpml_width > 0: q0 / q1 must be the [2, n0] / [2, n1] C-PML profiles (a, b)")
-                q1_p = torch.zeros((2, gp), device=dev, dtype=torch.float32)
-                q1_p[:, :n1] = q1.to(device=dev, dtype=torch.float32)
-            else:
-                q1_p = torch.zeros(gp, device=dev, dtype=torch.float32)
-                q1_p[:n1] = q1.to(device=dev, dtype=torch.float32)
+            r_p, q0_d, q1_p = _acoustic_inputs(r, q0, q1, cpml_width, lay.gp)
             f_d = f.detach().to(dtype=torch.float32).contiguous()
             rec = torch.empty((nt, ns, nrec), device=dev, dtype=torch.float32)
             work = torch.empty(lay.work_forward_elems, device=dev, dtype=torch.float32)
@@ -237,35 +127,14 @@ class _AcousticFn(torch.autograd.Function):
             if pseudo_hessian is not None and not need_grad:
                 raise MifwiError("pseudo_hessian: the moments are taken from the snapshots of a backward pass, and "
                                  "neither r nor f requires a gradient in this run")
-            step_bytes = 4 * ns * lay.coef_elems
-            seg = nt
-            snap = None
-            ckpt = None
+            seg, snap = nt, None
             if need_grad:
-                # never plan for more than most of the memory that is free right now (other tensors of
-                # the training loop share the device); segmentation does not change the results
-                snapshot_budget = min(snapshot_budget, int(0.8 * _lib.free_device_bytes(dev)))
-                if nt * step_bytes > snapshot_budget:
-                    seg = max(1, int(snapshot_budget // (2 * step_bytes)))
-                if seg >= nt:
-                    seg = nt
-                    snap = torch.empty((nt, ns, n0, gp), device=dev, dtype=torch.float32)
-            args = (plan.handle, _lib.ptr(r_p), _lib.ptr(q0_d), _lib.ptr(q1_p), _lib.ptr(f_d),
-                    _lib.ptr(geom.src_cell), _lib.ptr(geom.src_w), _lib.ptr(geom.rec_cell),
-                    _lib.ptr(geom.rec_w), _lib.ptr(rec))
-            if not need_grad or seg == nt:
-                _lib.check(lib.mifwi_acoustic_forward(*args, _lib.ptr(snap), _lib.ptr(work), 0, nt,
-                                                      _lib.ZERO_STATE, _stream()))
-            else:
-                # checkpoint the state (two time levels + C-PML memory variables) at every segment start, no snapshots yet
-                ckpt = []
-                state_elems = lay.state_elems
-                for b in range(0, nt, seg):
-                    flags = _lib.ZERO_STATE if b == 0 else 0
-                    if b > 0:
-                        ckpt.append(work[:state_elems].clone())
-                    _lib.check(lib.mifwi_acoustic_forward(*args, None, _lib.ptr(work), b,
-                                                          min(b + seg, nt), flags, _stream()))
+                seg = segment_length(snapshot_budget, dev, 4 * ns * lay.coef_elems, nt)
+                if seg == nt:
+                    snap = torch.empty((nt, ns, n0, lay.gp), device=dev, dtype=torch.float32)
+            geo = ptrs(geom.src_cell, geom.src_w, geom.rec_cell, geom.rec_w)
+            ckpt = run_forward(_forward_call(plan, ptrs(r_p, q0_d, q1_p), f_d, geo, rec), nt, seg, work,
+                               lay.state_elems, snap)
             if need_grad:
                 ctx.plan = plan
                 ctx.geom = geom
@@ -298,57 +167,23 @@ class _AcousticFn(torch.autograd.Function):
                       if ctx.need_f else None)
             work = torch.empty(lay.work_backward_elems, device=dev, dtype=torch.float32)
             hess = ctx.hess
+            moments = None
             if hess is not None:
                 mom = torch.zeros((n0, lay.gp), device=dev, dtype=torch.float32)
                 mwork = torch.empty(lib.mifwi_acoustic_snapshot_moments_work_elems(plan.handle), device=dev,
                                     dtype=torch.float32)
 
-            def moments(snap_t, b, e):
-                # one more read of a snapshot range this pass has in hand, each range once (absolute step numbers, so
-                # segments select the steps the resident buffer would); G^{nt-1} never reaches a recorded sample
-                _lib.check(lib.mifwi_acoustic_snapshot_moments(
-                    plan.handle, _lib.ptr(snap_t), b, b, e, hess.stride, _lib.ptr(mom), _lib.ptr(mwork), 0, _stream()))
-            common = (plan.handle, _lib.ptr(r_p), _lib.ptr(q0_d), _lib.ptr(q1_p),
-                      _lib.ptr(geom.src_cell), _lib.ptr(geom.src_w), _lib.ptr(geom.rec_cell),
-                      _lib.ptr(geom.rec_w), _lib.ptr(g))
-            if nt < 2:
+                def moments(snap, first, b, e):
+                    # one more read of a snapshot range this pass has in hand, each range once (absolute step numbers, so
+                    # segments select the steps the resident buffer would); G^{nt-1} never reaches a recorded sample
+                    _lib.check(lib.mifwi_acoustic_snapshot_moments(
+                        plan.handle, snap, first, b, e, hess.stride, _lib.ptr(mom), _lib.ptr(mwork), 0, _stream()))
+            coef = ptrs(r_p, q0_d, q1_p)
+            geo = ptrs(geom.src_cell, geom.src_w, geom.rec_cell, geom.rec_w)
+            if nt < 2:                           # no adjoint step, so no visit: nothing writes the gradient
                 grad_r.zero_()
-            elif ctx.snap is not None:
-                _lib.check(lib.mifwi_acoustic_backward(
-                    *common, _lib.ptr(ctx.snap), 0, _lib.ptr(grad_r), _lib.ptr(grad_f),
-                    _lib.ptr(work), nt - 1, 1, _lib.ZERO_STATE | _lib.FINALIZE, _stream()))
-                if hess is not None:
-                    moments(ctx.snap, 0, nt - 1)
-            else:
-                seg = ctx.seg
-                fwork = torch.empty(lay.work_forward_elems, device=dev, dtype=torch.float32)
-                snap = torch.empty((seg, ns, n0, lay.gp), device=dev, dtype=torch.float32)
-                state_elems = lay.state_elems
-                starts = list(range(0, nt, seg))
-                first = True
-                for si in reversed(range(len(starts))):
-                    b, e = starts[si], min(starts[si] + seg, nt)
-                    # snapshots G^b..G^{e-1} serve adjoint steps k = e .. b+1
-                    k_hi, k_lo = min(e, nt - 1), b + 1
-                    if k_hi < k_lo:
-                        continue
-                    if b == 0:
-                        fflags = _lib.ZERO_STATE
-                    else:
-                        fwork[:state_elems].copy_(ctx.ckpt[si - 1])
-                        fflags = 0
-                    _lib.check(lib.mifwi_acoustic_forward(
-                        plan.handle, _lib.ptr(r_p), _lib.ptr(q0_d), _lib.ptr(q1_p), _lib.ptr(f_d),
-                        _lib.ptr(geom.src_cell), _lib.ptr(geom.src_w), _lib.ptr(geom.rec_cell),
-                        _lib.ptr(geom.rec_w), None, _lib.ptr(snap), _lib.ptr(fwork), b, e, fflags,
-                        _stream()))
-                    flags = (_lib.ZERO_STATE if first else 0) | (_lib.FINALIZE if b == 0 else 0)
-                    first = False
-                    _lib.check(lib.mifwi_acoustic_backward(
-                        *common, _lib.ptr(snap), b, _lib.ptr(grad_r), _lib.ptr(grad_f),
-                        _lib.ptr(work), k_hi, k_lo, flags, _stream()))
-                    if hess is not None:
-                        moments(snap, b, k_hi)
+            run_backward("acoustic", nt, ctx.seg, ctx.snap, _adjoint_call(plan, coef, geo, g, grad_r, grad_f, work), moments,
+                         _forward_call(plan, coef, f_d, geo, None), ctx.ckpt, lay, (ns, n0, lay.gp))
             if hess is not None:
                 hess._add(mom[:, :n1])
                 ctx.hess = None
@@ -418,55 +253,87 @@ def _flatten_taps_pays(r, f, geom, c0, c1, edge_rows):
     return ok
 
 
-def born(r, f, dr, q0, q1, src_cell, src_w, rec_cell, rec_w, c0=1.0, c1=1.0,
-         snapshot_budget=DEFAULT_SNAPSHOT_BUDGET, cpml_width=0):
-    """Born / linearised modelling (``AcousticWaveSolver.born``, wavesolver.py:174-209;
-    ``BornOperator``, operators.py:168-207): returns ``(rec, drec)`` where ``rec`` are the seismograms
-    of the background model ``r`` and ``drec = J dr`` their first-order change for the perturbation
-    ``dr`` (same parametrisation and shape as ``r``).  ``J`` is the exact transpose partner of the
-    gradient autograd returns for :func:`propagate`.  No autograd through this call."""
+def _linearised(name, r, dr, f, q0, q1, src_cell, src_w, rec_cell, rec_w, c0, c1, cpml_width, snapshot_budget, adjoint,
+                weight):
+    """born / gauss_newton_product: per shot chunk one plan, one background forward with resident snapshots, the Born
+    pass over that buffer and - ``adjoint`` - the adjoint pass over it too.  Returns (rec, drec, hv); rec is None with
+    ``adjoint``, hv without."""
     _require_cuda(r, "r")
     dev = r.device
     lib = _lib.load()
     geom = _Geometry.get(src_cell, src_w, rec_cell, rec_w, dev)
     n0, n1 = r.shape
     nt, ns, nsrc = f.shape
+    if geom.src_cell.shape[:2] != (ns, nsrc):
+        raise MifwiError("f is [nt,%d,%d] but src_cell is %s" % (ns, nsrc, tuple(geom.src_cell.shape)))
     nrec, ntap = geom.rec_cell.shape[1], geom.rec_cell.shape[2]
     if tuple(dr.shape) != (n0, n1):
         raise MifwiError("dr must have the shape of r")
     geom.check_cells(n0 * n1, "%dx%d" % (n0, n1))
     with torch.cuda.device(dev), torch.no_grad():
-        plan = AcousticPlan(n0, n1, nt, ns, nsrc, nrec, ntap, float(c0), float(c1), dev.index, 0, 0, int(cpml_width))
-        lay = plan.layout
-        gp = lay.gp
-        if 4 * nt * ns * lay.coef_elems > snapshot_budget:
-            plan.close()
-            raise MifwiError("born() keeps the forward snapshots resident: %d steps do not fit the budget" % nt)
-        r_p = torch.zeros((n0, gp), device=dev, dtype=torch.float32)
-        r_p[:, :n1] = r.detach()
-        dr_p = torch.zeros((n0, gp), device=dev, dtype=torch.float32)
-        dr_p[:, :n1] = dr.detach().to(dev)
-        q0_d = q0.to(device=dev, dtype=torch.float32).contiguous()
-        if cpml_width:
-            q1_p = torch.zeros((2, gp), device=dev, dtype=torch.float32)
-            q1_p[:, :n1] = q1.to(device=dev, dtype=torch.float32)
-        else:
-            q1_p = torch.zeros(gp, device=dev, dtype=torch.float32)
-            q1_p[:n1] = q1.to(device=dev, dtype=torch.float32)
+        gp = 4 * ((n1 + 3) // 4)
+        budget = min(int(snapshot_budget), int(0.8 * _lib.free_device_bytes(dev)))
+        chunk = min(ns, budget // (4 * nt * n0 * gp))
+        if chunk < 1:
+            raise MifwiError("%s keeps the forward snapshots of all %d steps resident, and not even one shot's fit the "
+                             "snapshot budget; products across time checkpoints are not served" % (name, nt))
+        r_p, q0_d, q1_p = _acoustic_inputs(r, q0, q1, cpml_width, gp)
+        dr_p = pad_columns(dr.to(dev), gp)
         f_d = f.detach().to(device=dev, dtype=torch.float32).contiguous()
-        rec = torch.empty((nt, ns, nrec), device=dev, dtype=torch.float32)
+        rec = None if adjoint else torch.empty((nt, ns, nrec), device=dev, dtype=torch.float32)
         drec = torch.empty((nt, ns, nrec), device=dev, dtype=torch.float32)
-        work = torch.empty(lay.work_forward_elems, device=dev, dtype=torch.float32)
-        snap = torch.empty((nt, ns, n0, gp), device=dev, dtype=torch.float32)
-        _lib.check(lib.mifwi_acoustic_forward(plan.handle, _lib.ptr(r_p), _lib.ptr(q0_d), _lib.ptr(q1_p),
-                                              _lib.ptr(f_d), _lib.ptr(geom.src_cell), _lib.ptr(geom.src_w),
-                                              _lib.ptr(geom.rec_cell), _lib.ptr(geom.rec_w), _lib.ptr(rec),
-                                              _lib.ptr(snap), _lib.ptr(work), 0, nt, _lib.ZERO_STATE, _stream()))
-        _lib.check(lib.mifwi_acoustic_born(plan.handle, _lib.ptr(r_p), _lib.ptr(q0_d), _lib.ptr(q1_p),
-                                           _lib.ptr(dr_p), _lib.ptr(geom.rec_cell), _lib.ptr(geom.rec_w),
-                                           _lib.ptr(snap), 0, _lib.ptr(drec), _lib.ptr(work), 0, nt,
-                                           _lib.ZERO_STATE, _stream()))
-        plan.close()
+        hv = torch.zeros((n0, n1), device=dev, dtype=torch.float32) if adjoint else None
+        coef = ptrs(r_p, q0_d, q1_p)
+        # Born modelling of all shots at once writes its outputs in place; a product's traces stay the chunk's own tensor,
+        # which is what the caller's weight() gets
+        in_place = chunk == ns and not adjoint
+        for a in range(0, ns, chunk):
+            c = min(chunk, ns - a)
+            sl = slice(a, a + c)
+            plan = AcousticPlan(n0, n1, nt, c, nsrc, nrec, ntap, float(c0), float(c1), dev.index, 0, 0, int(cpml_width))
+            try:
+                lay = plan.layout
+                taps = [t[sl].contiguous() for t in (geom.src_cell, geom.src_w, geom.rec_cell, geom.rec_w)]
+                geo = ptrs(*taps)
+                fc = f_d[:, sl].contiguous()
+                rec_c, drc = (rec, drec) if in_place else (
+                    torch.empty((nt, c, nrec), device=dev, dtype=torch.float32) for _ in range(2))
+                work = torch.empty(max(lay.work_forward_elems, lay.work_backward_elems if adjoint else 0), device=dev,
+                                   dtype=torch.float32)
+                snap = torch.empty((nt, c, n0, gp), device=dev, dtype=torch.float32)
+                run_forward(_forward_call(plan, coef, fc, geo, rec_c), nt, nt, work, lay.state_elems, snap)
+                _lib.check(lib.mifwi_acoustic_born(plan.handle, *coef, _lib.ptr(dr_p), geo[2], geo[3], _lib.ptr(snap), 0,
+                                                   _lib.ptr(drc), _lib.ptr(work), 0, nt, _lib.ZERO_STATE, _stream()))
+                if not in_place:
+                    drec[:, sl] = drc
+                    if rec is not None:
+                        rec[:, sl] = rec_c
+                if adjoint and nt >= 2:
+                    g = drc if weight is None else weight(drc)
+                    g = g.detach().to(device=dev, dtype=torch.float32).contiguous()
+                    if g.shape != drc.shape:
+                        raise MifwiError("weight must return a tensor of the shape of its argument")
+                    grad = torch.empty((n0, gp), device=dev, dtype=torch.float32)
+                    run_backward("acoustic", nt, nt, snap, _adjoint_call(plan, coef, geo, g, grad, None, work))
+                    hv += grad[:, :n1]
+            finally:
+                plan.close()
+    return rec, drec, hv
+
+
+def born(r, f, dr, q0, q1, src_cell, src_w, rec_cell, rec_w, c0=1.0, c1=1.0,
+         snapshot_budget=DEFAULT_SNAPSHOT_BUDGET, cpml_width=0):
+    """Born / linearised modelling (``AcousticWaveSolver.born``, wavesolver.py:174-209;
+    ``BornOperator``, operators.py:168-207): returns ``(rec, drec)`` where ``rec`` are the seismograms
+    of the background model ``r`` and ``drec = J dr`` their first-order change for the perturbation
+    ``dr`` (same parametrisation and shape as ``r``).  ``J`` is the exact transpose partner of the
+    gradient autograd returns for :func:`propagate`.  No autograd through this call.
+
+    The forward snapshots of all steps stay resident, within ``snapshot_budget`` and 80 % of the memory that is free.
+    When the snapshots of all shots do not fit, the shots are taken a few at a time (they are independent: the same
+    bits); when not even one shot fits, ``MifwiError`` - Born across time checkpoints is not served."""
+    rec, drec, _ = _linearised("born", r, dr, f, q0, q1, src_cell, src_w, rec_cell, rec_w, c0, c1, cpml_width,
+                               snapshot_budget, False, None)
     return rec, drec
 
 
@@ -482,66 +349,6 @@ def gauss_newton_product(r, dr, f, q0, q1, src_cell, src_w, rec_cell, rec_w, c0=
     few at a time (they are independent); ``hv`` sums over the chunks and ``weight`` is then called once per chunk with
     that chunk's [nt, shots, nrec] traces, so it must act shot by shot.  When not even one shot fits, ``MifwiError``:
     Gauss-Newton products across time checkpoints are not served."""
-    _require_cuda(r, "r")
-    dev = r.device
-    lib = _lib.load()
-    geom = _Geometry.get(src_cell, src_w, rec_cell, rec_w, dev)
-    n0, n1 = r.shape
-    nt, ns, nsrc = f.shape
-    if geom.src_cell.shape[:2] != (ns, nsrc):
-        raise MifwiError("f is [nt,%d,%d] but src_cell is %s" % (ns, nsrc, tuple(geom.src_cell.shape)))
-    nrec, ntap = geom.rec_cell.shape[1], geom.rec_cell.shape[2]
-    if tuple(dr.shape) != (n0, n1):
-        raise MifwiError("dr must have the shape of r")
-    if cpml_width and (tuple(q0.shape) != (2, n0) or tuple(q1.shape) != (2, n1)):
-        raise MifwiError("cpml_width > 0: q0 / q1 must be the [2, n0] / [2, n1] C-PML profiles (a, b)")
-    geom.check_cells(n0 * n1, "%dx%d" % (n0, n1))
-    with torch.cuda.device(dev), torch.no_grad():
-        gp = 4 * ((n1 + 3) // 4)
-        budget = min(int(snapshot_budget), int(0.8 * _lib.free_device_bytes(dev)))
-        chunk = min(ns, budget // (4 * nt * n0 * gp))
-        if chunk < 1:
-            raise MifwiError("gauss_newton_product keeps the forward snapshots of all %d steps resident, and not even one "
-                             "shot's fit the snapshot budget; products across time checkpoints are not served" % nt)
-        r_p = torch.zeros((n0, gp), device=dev, dtype=torch.float32)
-        r_p[:, :n1] = r.detach()
-        dr_p = torch.zeros((n0, gp), device=dev, dtype=torch.float32)
-        dr_p[:, :n1] = dr.detach().to(dev)
-        q0_d = q0.to(device=dev, dtype=torch.float32).contiguous()
-        q1_p = torch.zeros((2, gp) if cpml_width else (gp,), device=dev, dtype=torch.float32)
-        q1_p[..., :n1] = q1.to(device=dev, dtype=torch.float32)
-        f_d = f.detach().to(device=dev, dtype=torch.float32).contiguous()
-        drec = torch.empty((nt, ns, nrec), device=dev, dtype=torch.float32)
-        hv = torch.zeros((n0, n1), device=dev, dtype=torch.float32)
-        coef = (_lib.ptr(r_p), _lib.ptr(q0_d), _lib.ptr(q1_p))
-        for a in range(0, ns, chunk):
-            c = min(chunk, ns - a)
-            sl = slice(a, a + c)
-            plan = AcousticPlan(n0, n1, nt, c, nsrc, nrec, ntap, float(c0), float(c1), dev.index, 0, 0, int(cpml_width))
-            try:
-                lay = plan.layout
-                taps = [t[sl].contiguous() for t in (geom.src_cell, geom.src_w, geom.rec_cell, geom.rec_w)]
-                geo = [_lib.ptr(t) for t in taps]
-                fc = f_d[:, sl].contiguous()
-                rec = torch.empty((nt, c, nrec), device=dev, dtype=torch.float32)
-                drc = torch.empty((nt, c, nrec), device=dev, dtype=torch.float32)
-                work = torch.empty(max(lay.work_forward_elems, lay.work_backward_elems), device=dev, dtype=torch.float32)
-                snap = torch.empty((nt, c, n0, gp), device=dev, dtype=torch.float32)
-                _lib.check(lib.mifwi_acoustic_forward(plan.handle, *coef, _lib.ptr(fc), *geo, _lib.ptr(rec), _lib.ptr(snap),
-                                                      _lib.ptr(work), 0, nt, _lib.ZERO_STATE, _stream()))
-                _lib.check(lib.mifwi_acoustic_born(plan.handle, *coef, _lib.ptr(dr_p), geo[2], geo[3], _lib.ptr(snap), 0,
-                                                   _lib.ptr(drc), _lib.ptr(work), 0, nt, _lib.ZERO_STATE, _stream()))
-                drec[:, sl] = drc
-                if nt >= 2:
-                    g = drc if weight is None else weight(drc)
-                    g = g.detach().to(device=dev, dtype=torch.float32).contiguous()
-                    if g.shape != drc.shape:
-                        raise MifwiError("weight must return a tensor of the shape of its argument")
-                    grad = torch.empty((n0, gp), device=dev, dtype=torch.float32)
-                    _lib.check(lib.mifwi_acoustic_backward(plan.handle, *coef, *geo, _lib.ptr(g), _lib.ptr(snap), 0,
-                                                           _lib.ptr(grad), None, _lib.ptr(work), nt - 1, 1,
-                                                           _lib.ZERO_STATE | _lib.FINALIZE, _stream()))
-                    hv += grad[:, :n1]
-            finally:
-                plan.close()
+    _, drec, hv = _linearised("gauss_newton_product", r, dr, f, q0, q1, src_cell, src_w, rec_cell, rec_w, c0, c1, cpml_width,
+                              snapshot_budget, True, weight)
     return hv, drec

@@ -6,7 +6,6 @@ Stands where ``d.forward`` / ``d.grad`` of pyapi_denise stand in the reference
 (models/networks.py:7752-7802): models in, vx/vz seismograms and Vp/Vs/rho gradients out,
 with no mpirun and no files.  All wave arithmetic is in libmifwi.so; there is no CPU path.
 """
-import ctypes
 import os
 import weakref
 
@@ -14,7 +13,8 @@ import torch
 
 from . import _lib
 from ._lib import MifwiError
-from .acoustic import _Geometry, _MomentsHolder, _require_cuda, _stream
+from ._driver import (_Geometry, _MomentsHolder, _Plan, _require_cuda, _stream, pad_columns, ptrs, run_backward,
+                      run_forward, segment_length)
 
 # bytes of snapshot planes + time checkpoints a call may hold (288 GB of HBM per GPU; the rest is left to the caller's
 # network and data); MIFWI_EL_SNAPSHOT_BUDGET_GB overrides it (measurements of the checkpointed path on short runs)
@@ -152,45 +152,16 @@ def _staggered_materials_torch(vp, vs, rho, dt, h, free_surface=False):
     return torch.stack([Ls, Ms, muxz * s, s / rx, s / rz])
 
 
-class ElasticPlan:
+class ElasticPlan(_Plan):
+    PREFIX, LAYOUT = "elastic", _lib.ElasticLayout
+
     def __init__(self, nz, nx, nt, nshot, nsrc, nrec, ntap, pml_width, device_index,
                  shots_per_group=0, free_surface=0, source_type=0, record_pressure=0, snapshot_format=None,
                  fd_order=4):
-        self._lib = _lib.load()
         fmt = SNAPSHOT_FORMATS[snapshot_format or snapshot_mode()]
-        self.desc = _lib.ElasticDesc(nz, nx, nt, nshot, nsrc, nrec, ntap, pml_width,
-                                     free_surface, shots_per_group, source_type, record_pressure, fmt, fd_order)
-        self._h = ctypes.c_void_p()
-        _lib.check(self._lib.mifwi_elastic_plan_create(ctypes.byref(self._h), device_index,
-                                                       ctypes.byref(self.desc)))
-        self.layout = _lib.ElasticLayout()
-        _lib.check(self._lib.mifwi_elastic_plan_layout(self._h, ctypes.byref(self.layout)))
-
-    @property
-    def handle(self):
-        return self._h
-
-    def pass_sizes(self):
-        """(forward, adjoint) units per pass of the per-step kernels over the time range: shots / shot groups
-        (elastic), shot groups (acoustic) - what stays inside the Infinity Cache."""
-        a, b = ctypes.c_int32(0), ctypes.c_int32(0)
-        _lib.check(self._lib.mifwi_elastic_plan_pass_sizes(self._h, ctypes.byref(a), ctypes.byref(b)))
-        return a.value, b.value
-
-    def cluster_slabs(self, adjoint=False):
-        """Row slabs per shot of the single-launch time loop (0: one launch per half step)."""
-        return int(self._lib.mifwi_elastic_plan_cluster_slabs(self._h, int(bool(adjoint))))
-
-    def close(self):
-        if self._h:
-            self._lib.mifwi_elastic_plan_destroy(self._h)
-            self._h = ctypes.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:  # noqa: BLE001
-            pass
+        self._create(_lib.ElasticDesc(nz, nx, nt, nshot, nsrc, nrec, ntap, pml_width,
+                                      free_surface, shots_per_group, source_type, record_pressure, fmt, fd_order),
+                     device_index)
 
 
 class PseudoHessian(_MomentsHolder):
@@ -275,20 +246,32 @@ class _SnapshotArena:
 
 def _padded_planes(t, gp):
     """[5, nz, nx] -> float32 [5, nz, gp] on the same device, pad columns 0 (the layout of ``mat`` in include/mifwi.h)."""
-    out = torch.zeros(tuple(t.shape[:2]) + (gp,), device=t.device, dtype=torch.float32)
-    out[:, :, :t.shape[2]] = t.detach()
-    return out
+    return pad_columns(t, gp)
 
 
 def _padded_inputs(mat, pz, px, gp):
     """The material planes and C-PML tables as the C calls take them: on mat's device, rows padded to gp columns
-    (materials and a, b 0, 1/kappa 1 there)."""
+    (materials and a, b 0, 1/kappa - rows 2 and 5 of the table - 1 there)."""
     dev = mat.device
-    px_p = torch.zeros((6, gp), device=dev, dtype=torch.float32)
-    px_p[2] = 1.0
-    px_p[5] = 1.0
-    px_p[:, :mat.shape[2]] = px.to(device=dev, dtype=torch.float32)
-    return _padded_planes(mat, gp), pz.to(device=dev, dtype=torch.float32).contiguous(), px_p
+    px_p = pad_columns(px.to(device=dev, dtype=torch.float32), gp)
+    px_p[2::3, mat.shape[2]:] = 1.0
+    return pad_columns(mat, gp), pz.to(device=dev, dtype=torch.float32).contiguous(), px_p
+
+
+def _forward_call(plan, coef, f_d, geo, rvx, rvz):
+    """``forward(snap_ptr, work_ptr, b, e, flags)`` as the drivers take it; rvx, rvz None: a re-run that samples nothing."""
+    lib = _lib.load()
+    args = (plan.handle, *coef, _lib.ptr(f_d), *geo, _lib.ptr(rvx), _lib.ptr(rvz))
+    return lambda snap, work, b, e, flags: _lib.check(
+        lib.mifwi_elastic_forward(*args, snap, work, b, e, flags, _stream()))
+
+
+def _adjoint_call(plan, coef, geo, gx, gz, grad_mat, grad_f, work):
+    """``adjoint(snap_ptr, snap_first, hi, lo, flags)`` as the backward driver takes it."""
+    lib = _lib.load()
+    return lambda snap, first, hi, lo, flags: _lib.check(lib.mifwi_elastic_backward(
+        plan.handle, *coef, *geo, _lib.ptr(gx), _lib.ptr(gz), snap, first, _lib.ptr(grad_mat), _lib.ptr(grad_f),
+        _lib.ptr(work), hi, lo, flags, _stream()))
 
 
 class _ElasticFn(torch.autograd.Function):
@@ -324,8 +307,7 @@ class _ElasticFn(torch.autograd.Function):
             if pseudo_hessian is not None and not need_grad:
                 raise MifwiError("pseudo_hessian: the moments are taken from the snapshots of a backward pass, and "
                                  "neither mat nor f requires a gradient in this run")
-            step_bytes = 4 * lay.snap_step_elems
-            seg, snap, ckpt = nt, None, None
+            seg, snap = nt, None
             arena = _SnapshotArena.current
             lease = None
             if need_grad and arena is not None:
@@ -333,32 +315,15 @@ class _ElasticFn(torch.autograd.Function):
                 if snap is not None:
                     lease = arena.lease()
             if need_grad and snap is None:
-                # never plan for more than most of the memory that is free right now (other tensors of
-                # the training loop share the device); segmentation does not change the results
-                snapshot_budget = min(snapshot_budget, int(0.8 * _lib.free_device_bytes(dev)))
-                if nt * step_bytes > snapshot_budget:
-                    seg = max(1, int(snapshot_budget // (2 * step_bytes)))
-                if seg >= nt:
-                    seg = nt
+                seg = segment_length(snapshot_budget, dev, 4 * lay.snap_step_elems, nt)
+                if seg == nt:
                     snap = torch.empty((nt, lay.snap_step_elems), device=dev, dtype=torch.float32)
                     if arena is not None and arena.buf is None:
                         arena.buf = snap.view(-1)
                         lease = arena.lease()
-            args = (plan.handle, _lib.ptr(mat_p), _lib.ptr(pz_d), _lib.ptr(px_p), _lib.ptr(f_d),
-                    _lib.ptr(geom.src_cell), _lib.ptr(geom.src_w), _lib.ptr(geom.rec_cell),
-                    _lib.ptr(geom.rec_w), _lib.ptr(rvx), _lib.ptr(rvz))
-            if not need_grad or seg == nt:
-                _lib.check(lib.mifwi_elastic_forward(*args, _lib.ptr(snap), _lib.ptr(work), 0, nt,
-                                                     _lib.ZERO_STATE, _stream()))
-            else:
-                ckpt = []
-                for b in range(0, nt, seg):
-                    if b > 0:
-                        ckpt.append(work[:lay.state_elems].clone())
-                    _lib.check(lib.mifwi_elastic_forward(*args, None, _lib.ptr(work), b,
-                                                         min(b + seg, nt),
-                                                         _lib.ZERO_STATE if b == 0 else 0,
-                                                         _stream()))
+            geo = ptrs(geom.src_cell, geom.src_w, geom.rec_cell, geom.rec_w)
+            ckpt = run_forward(_forward_call(plan, ptrs(mat_p, pz_d, px_p), f_d, geo, rvx, rvz), nt, seg, work,
+                               lay.state_elems, snap)
             if need_grad:
                 ctx.plan, ctx.geom, ctx.seg, ctx.ckpt, ctx.snap = plan, geom, seg, ckpt, snap
                 ctx.lease = lease
@@ -396,51 +361,22 @@ class _ElasticFn(torch.autograd.Function):
                       if ctx.need_f else None)
             work = torch.empty(lay.work_backward_elems, device=dev, dtype=torch.float32)
             hess = ctx.hess
+            moments = None
             if hess is not None:
                 mom = torch.empty((6, nz, lay.gp), device=dev, dtype=torch.float32)
                 mwork = torch.empty(lib.mifwi_elastic_snapshot_moments_work_elems(plan.handle), device=dev,
                                     dtype=torch.float32)
 
-            def moments(snap_t, b, e):
-                # one more read of a snapshot range this pass has in hand, each range once (absolute step numbers, so
-                # segments select the steps the resident buffer would); the range that ends the run comes first
-                _lib.check(lib.mifwi_elastic_snapshot_moments(
-                    plan.handle, _lib.ptr(snap_t), b, b, e, hess.stride, _lib.ptr(mom), _lib.ptr(mwork),
-                    _lib.ZERO_STATE if e == nt else 0, _stream()))
-            common = (plan.handle, _lib.ptr(mat_p), _lib.ptr(pz_d), _lib.ptr(px_p),
-                      _lib.ptr(geom.src_cell), _lib.ptr(geom.src_w), _lib.ptr(geom.rec_cell),
-                      _lib.ptr(geom.rec_w), _lib.ptr(gx), _lib.ptr(gz))
-            if ctx.snap is not None:
-                _lib.check(lib.mifwi_elastic_backward(
-                    *common, _lib.ptr(ctx.snap), 0, _lib.ptr(grad_mat), _lib.ptr(grad_f),
-                    _lib.ptr(work), nt - 1, 0, _lib.ZERO_STATE | _lib.FINALIZE, _stream()))
-                if hess is not None:
-                    moments(ctx.snap, 0, nt)
-            else:
-                seg = ctx.seg
-                fwork = torch.empty(lay.work_forward_elems, device=dev, dtype=torch.float32)
-                snap = torch.empty((seg, lay.snap_step_elems), device=dev, dtype=torch.float32)
-                starts = list(range(0, nt, seg))
-                first = True
-                for si in reversed(range(len(starts))):
-                    b, e = starts[si], min(starts[si] + seg, nt)
-                    if b == 0:
-                        fflags = _lib.ZERO_STATE
-                    else:
-                        fwork[:lay.state_elems].copy_(ctx.ckpt[si - 1])
-                        fflags = 0
-                    _lib.check(lib.mifwi_elastic_forward(
-                        plan.handle, _lib.ptr(mat_p), _lib.ptr(pz_d), _lib.ptr(px_p),
-                        _lib.ptr(f_d), _lib.ptr(geom.src_cell), _lib.ptr(geom.src_w),
-                        _lib.ptr(geom.rec_cell), _lib.ptr(geom.rec_w), None, None,
-                        _lib.ptr(snap), _lib.ptr(fwork), b, e, fflags, _stream()))
-                    flags = (_lib.ZERO_STATE if first else 0) | (_lib.FINALIZE if b == 0 else 0)
-                    first = False
-                    _lib.check(lib.mifwi_elastic_backward(
-                        *common, _lib.ptr(snap), b, _lib.ptr(grad_mat), _lib.ptr(grad_f),
-                        _lib.ptr(work), e - 1, b, flags, _stream()))
-                    if hess is not None:
-                        moments(snap, b, e)
+                def moments(snap, first, b, e):
+                    # one more read of a snapshot range this pass has in hand, each range once (absolute step numbers, so
+                    # segments select the steps the resident buffer would); the range that ends the run comes first
+                    _lib.check(lib.mifwi_elastic_snapshot_moments(
+                        plan.handle, snap, first, b, e, hess.stride, _lib.ptr(mom), _lib.ptr(mwork),
+                        _lib.ZERO_STATE if e == nt else 0, _stream()))
+            coef = ptrs(mat_p, pz_d, px_p)
+            geo = ptrs(geom.src_cell, geom.src_w, geom.rec_cell, geom.rec_w)
+            run_backward("elastic", nt, ctx.seg, ctx.snap, _adjoint_call(plan, coef, geo, gx, gz, grad_mat, grad_f, work),
+                         moments, _forward_call(plan, coef, f_d, geo, None, None), ctx.ckpt, lay, (lay.snap_step_elems,))
             if hess is not None:
                 hess._add(mom[:, :, :nx])
                 ctx.hess = None
@@ -570,20 +506,18 @@ def _linearised(name, mat, dmat, f, pz, px, src_cell, src_w, rec_cell, rec_w, pm
                     raise MifwiError("%s reads f32 snapshot planes: this plan keeps them as bf16" % name)
                 sl = slice(a, a + c)
                 mat_p, pz_d, px_p = _padded_inputs(mat, pz, px, lay.gp)
-                dmat_p = _padded_planes(dmat.to(dev), lay.gp)
+                dmat_p = pad_columns(dmat.to(dev), lay.gp)
                 taps = [t[sl].contiguous() for t in (geom.src_cell, geom.src_w, geom.rec_cell, geom.rec_w)]
-                geo = [_lib.ptr(t) for t in taps]
+                geo = ptrs(*taps)
                 fc = f_d[:, sl].contiguous()
                 dfc = None if df_d is None else df_d[:, sl].contiguous()
                 rec = [torch.empty((nt, c, nrec), device=dev, dtype=torch.float32) for _ in range(4)]
                 work = torch.empty(max(lay.work_forward_elems, lay.work_backward_elems if adjoint else 0), device=dev,
                                    dtype=torch.float32)
                 snap = torch.empty((nt, lay.snap_step_elems), device=dev, dtype=torch.float32)
-                tabs = (_lib.ptr(pz_d), _lib.ptr(px_p))
-                _lib.check(lib.mifwi_elastic_forward(plan.handle, _lib.ptr(mat_p), *tabs, _lib.ptr(fc), *geo, _lib.ptr(rec[0]),
-                                                     _lib.ptr(rec[1]), _lib.ptr(snap), _lib.ptr(work), 0, nt,
-                                                     _lib.ZERO_STATE, _stream()))
-                _lib.check(lib.mifwi_elastic_born(plan.handle, _lib.ptr(mat_p), _lib.ptr(dmat_p), *tabs, _lib.ptr(dfc), *geo,
+                coef = ptrs(mat_p, pz_d, px_p)
+                run_forward(_forward_call(plan, coef, fc, geo, rec[0], rec[1]), nt, nt, work, lay.state_elems, snap)
+                _lib.check(lib.mifwi_elastic_born(plan.handle, coef[0], _lib.ptr(dmat_p), *coef[1:], _lib.ptr(dfc), *geo,
                                                   _lib.ptr(snap), 0, _lib.ptr(rec[2]), _lib.ptr(rec[3]), _lib.ptr(work), 0, nt,
                                                   _lib.ZERO_STATE, _stream()))
                 for o, r in zip(out, rec):
@@ -594,10 +528,7 @@ def _linearised(name, mat, dmat, f, pz, px, src_cell, src_w, rec_cell, rec_w, pm
                     if len(g) != 2 or any(t.shape != rec[2].shape for t in g):
                         raise MifwiError("weight must return (g_vx, g_vz) of the shape of its arguments")
                     grad = torch.empty((5, nz, lay.gp), device=dev, dtype=torch.float32)
-                    _lib.check(lib.mifwi_elastic_backward(plan.handle, _lib.ptr(mat_p), *tabs, *geo, _lib.ptr(g[0]),
-                                                          _lib.ptr(g[1]), _lib.ptr(snap), 0, _lib.ptr(grad), None,
-                                                          _lib.ptr(work), nt - 1, 0, _lib.ZERO_STATE | _lib.FINALIZE,
-                                                          _stream()))
+                    run_backward("elastic", nt, nt, snap, _adjoint_call(plan, coef, geo, g[0], g[1], grad, None, work))
                     hv += grad[:, :, :nx]
             finally:
                 plan.close()

@@ -271,6 +271,41 @@ def test_born_operator_matches_oracle_and_transposes_the_gradient(oracle32, monk
     assert abs(lhs - rhs) <= 2e-5 * max(abs(lhs), abs(rhs))
 
 
+def _born_in_chunks_case():
+    case = acoustic_case(seed=29, nt=40, ns=3)
+    dev = torch.device("cuda:0")
+    dr = np.random.default_rng(6).standard_normal(case["r"].shape) * case["r"] * 0.05
+    args = [torch.tensor(case[k], dtype=torch.float32, device=dev) for k in ("r", "f")]
+    args.append(torch.tensor(dr, dtype=torch.float32, device=dev))
+    args += [torch.tensor(case[k]) for k in ("q0", "q1", "sc", "sw", "rc", "rw")]
+    return case, args + [case["c0"], case["c1"]]
+
+
+@pytest.mark.parametrize("family", ["1", "0"])
+def test_born_in_shot_chunks_equals_born_of_all_shots(monkeypatch, family):
+    """A budget that holds one shot's snapshots: three chunks, the bits of the run that holds all three; not even one
+    shot's: refused."""
+    from physicsbasedfwi2_amd import acoustic
+    monkeypatch.setenv("MIFWI_AC_CLUSTER", family)
+    case, args = _born_in_chunks_case()
+    rec, drec = acoustic.born(*args)
+    assert float(rec.abs().max()) > 0 and float(drec.abs().max()) > 0
+    N0, N1 = case["shape"]
+    one_shot = 4 * case["f"].shape[0] * N0 * ((N1 + 3) // 4 * 4)
+    rec1, drec1 = acoustic.born(*args, snapshot_budget=one_shot + 64)
+    assert torch.equal(rec1, rec) and torch.equal(drec1, drec)
+    with pytest.raises(acoustic.MifwiError):
+        acoustic.born(*args, snapshot_budget=one_shot - 4)
+
+
+def test_born_refuses_cpml_profiles_of_the_wrong_shape():
+    from physicsbasedfwi2_amd import acoustic
+    case, args = _born_in_chunks_case()
+    assert tuple(args[4].shape) == (case["shape"][1],)                  # the sponge's q1 [n1], not the [2, n1] a, b
+    with pytest.raises(acoustic.MifwiError, match="C-PML profiles"):
+        acoustic.born(*args, cpml_width=8)
+
+
 def test_deepwave_shim_substeps_when_dt_exceeds_the_stability_limit(oracle32):
     """dt = 4 ms on a 10 m grid with 3.5 km/s needs an internal step of dt/ratio: the wavelet is
     resampled band-limited, the propagator runs ratio*nt steps and the traces are decimated."""
