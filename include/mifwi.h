@@ -363,6 +363,39 @@ int mifwi_misfit(int device, int32_t kind, const float *pred, const float *obs, 
                  int64_t nt, int64_t ntrace, float *loss_out, float *adj_out, float *work, void *stream);
 
 /* ======================================================================================
+ * STAGE FILTER of the elastic protocol, alone and fused with the objective that follows it
+ *
+ * Replaces what DENISE does with the corners of the last frequency stage: every prop() that calls d.grad() first calls
+ * add_fwi_stage(fc_high=...) or add_fwi_stage(fc_low=..., fc_high=...) (models/networks.py:6374, 6738, 7116, 7761, 8432,
+ * 9147, 9863, 10503, 11070, 11676); the modelled and the observed traces are filtered along time with a causal recursive
+ * Butterworth filter F before the misfit, and the adjoint sources with its transpose.
+ * F: a cascade of nsec second-order sections run with zero initial state in transposed direct form II,
+ *     y = b0 x + s1;  s1 = b1 x - a1 y + s2;  s2 = b2 x - a2 y;   (x of the next section = y)
+ * i.e. scipy.signal.sosfilt; F^T is the same recurrence from the last sample to the first.  Coefficients and state are
+ * double, traces float.  sos: HOST array [nsec][6], rows b0 b1 b2 a0 a1 a2 as scipy.signal.butter(..., output="sos") emits
+ * them; a0 must be 1; a first-order section is a row with b2 = a2 = 0 (an odd order's rows with a2 = 0 or b2 = 0
+ * need no special case).  Every other pointer is a device pointer.
+ *   mifwi_trace_filter     y = F x (transpose != 0: y = F^T x); x, y [nt][ntrace]; y == x allowed
+ *   mifwi_misfit_filtered  one launch for loss and adjoint source of the filtered traces:
+ *     L2                  r = F(pred - obs) rounded to float;  loss = 1/2 sum r^2;  adj_out = F^T r
+ *     GLOBAL_CORRELATION  s = F pred, o = F obs rounded to float;  loss = - sum_traces <s, o> / (|s| |o|);
+ *                         adj_out = F^T(dloss/ds)  (a trace with |s| = 0 or |o| = 0 contributes nothing, adj_out 0)
+ *     pred, obs, adj_out (NULL = loss only, the same bits), loss_out as for mifwi_misfit; no atomics, fixed summation
+ *     order: two identical calls give the same bits.  work: mifwi_misfit_filtered_work_elems(kind, nt, ntrace) floats,
+ *     8-byte aligned (GLOBAL_CORRELATION keeps F obs there between its two sweeps).
+ * MIFWI_EINVAL: a null argument, nsec < 1 or > MIFWI_FILTER_MAX_SECTIONS, a0 != 1, a coefficient that is not finite,
+ * kind L1_TRACE_NORM (the acoustic protocol has no stage), work not 8-byte aligned, sizes as mifwi_misfit rejects them.
+ * ==================================================================================== */
+enum { MIFWI_FILTER_MAX_SECTIONS = 8 };
+
+int mifwi_trace_filter(int device, const float *x, float *y, int64_t nt, int64_t ntrace, const double *sos,
+                       int32_t nsec, int32_t transpose, void *stream);
+int64_t mifwi_misfit_filtered_work_elems(int32_t kind, int64_t nt, int64_t ntrace);
+int mifwi_misfit_filtered(int device, int32_t kind, const float *pred, const float *obs, int64_t nt,
+                          int64_t ntrace, const double *sos, int32_t nsec, float *loss_out, float *adj_out,
+                          float *work, void *stream);
+
+/* ======================================================================================
  * GRADIENT CONDITIONING on the device (what sits between d.get_fwi_gradients(...) and fake_Vp.backward(grad))
  *
  * Replaces the numpy / scipy post-processing of the model gradients in the elastic prop() methods:

@@ -91,6 +91,10 @@ SIGNATURES = {
     "mifwi_misfit_work_elems": (ctypes.c_int64, [ctypes.c_int32, ctypes.c_int64, ctypes.c_int64]),
     "mifwi_misfit": (ctypes.c_int, [ctypes.c_int, ctypes.c_int32] + [_P] * 3 + [ctypes.c_int64] * 2 +
                      [_P] * 4),
+    "mifwi_trace_filter": (ctypes.c_int, [ctypes.c_int] + [_P] * 2 + [ctypes.c_int64] * 2 + [_P] + [ctypes.c_int32] * 2 + [_P]),
+    "mifwi_misfit_filtered_work_elems": (ctypes.c_int64, [ctypes.c_int32, ctypes.c_int64, ctypes.c_int64]),
+    "mifwi_misfit_filtered": (ctypes.c_int, [ctypes.c_int, ctypes.c_int32] + [_P] * 2 + [ctypes.c_int64] * 2 +
+                              [_P, ctypes.c_int32] + [_P] * 4),
     "mifwi_gradient_condition_work_elems": (ctypes.c_int64, [ctypes.c_int32]),
     "mifwi_gradient_condition": (ctypes.c_int, [ctypes.c_int] + [_P] * 3 + [ctypes.c_int32] * 3 + [_P, ctypes.c_float] +
                                  [ctypes.c_int32] * 2 + [_P] * 3),
@@ -115,6 +119,7 @@ AC_PARAM_VELOCITY, AC_PARAM_SLOWNESS2 = 1, 2
 MISFIT_L1_TRACE_NORM = 0
 MISFIT_L2 = 1
 MISFIT_GLOBAL_CORRELATION = 2
+FILTER_MAX_SECTIONS = 8
 
 _lib = None
 

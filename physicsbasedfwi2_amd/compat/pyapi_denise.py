@@ -507,15 +507,24 @@ class Denise:
             raise MifwiError("observed data %s do not match modelled %s (nt, nshot, nrec)"
                              % (tuple(ox.shape), tuple(vx.shape)))
         st = self.fwi_stages[-1] if self.fwi_stages else dict(fc_low=0.0, fc_high=0.0, order=6, lnorm=2)
-        fl = lambda a: butterworth(a, dt, st.get("fc_low", 0.0), st.get("fc_high", 0.0),
-                                   st.get("order", 6))
+        # the stage: the causal recursive Butterworth filter, fused with the objective (one launch reads the unfiltered
+        # traces and delivers the loss of the filtered ones and the adjoint source through the transposed filter,
+        # csrc/mifwi_misfit_filter.h).  MIFWI_STAGE_FILTER=fft (read per call): the same filter as its frequency response
+        # on padded spectra (butterworth(), through autograd) followed by the unfiltered kernels, kept for comparison
+        corners = (st.get("fc_low", 0.0), st.get("fc_high", 0.0), st.get("order", 6))
+        mode = os.environ.get("MIFWI_STAGE_FILTER", "recursive")
+        if mode not in ("recursive", "fft"):
+            raise MifwiError("MIFWI_STAGE_FILTER=%s (recursive: the fused kernels, fft: the frequency-domain form)" % mode)
+        sos = misfit.butterworth_sos(dt, *corners) if mode == "recursive" else None
+        fl = (lambda a: butterworth(a, dt, *corners)) if mode == "fft" else (lambda a: a)
         # objective and adjoint sources in one fused pass per component (csrc/mifwi_misfit.hip): lnorm = 2 is the
         # L2 norm every stage of the reference asks for (networks.py:7761, 9863, 10503); 5 is DENISE's
         # global-correlation norm (numbering as in the DENISE manual; DENISE itself is not in the reference tree)
         lnorm = int(st.get("lnorm", 2))
         if lnorm not in (2, 5):
             raise MifwiError("lnorm=%s not implemented (2: L2, 5: global correlation)" % lnorm)
-        objective = misfit.l2_half if lnorm == 2 else misfit.global_correlation
+        kernel = misfit.l2_half if lnorm == 2 else misfit.global_correlation
+        objective = (lambda v, o: kernel(v, o, sos=sos)) if sos is not None else kernel
         loss = 0.0
         if self.QUELLTYPB in (1, 2):
             loss = loss + objective(fl(vy), fl(oy))

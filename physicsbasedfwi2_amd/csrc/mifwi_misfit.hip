@@ -181,6 +181,8 @@ int l2_blocks(long long n) { return (int)std::min<long long>(2048, (n / 4 + 255)
 
 }  // namespace
 
+#include "mifwi_misfit_filter.h"
+
 extern "C" {
 
 int64_t mifwi_misfit_work_elems(int32_t kind, int64_t nt, int64_t ntrace)
@@ -235,6 +237,59 @@ int mifwi_misfit(int device, int32_t kind, const float *pred, const float *obs, 
         else
             hipLaunchKernelGGL(misfit_l2<false>, dim3(blocks), dim3(256), 0, st, pred, obs, n, adj_out, partial);
         hipLaunchKernelGGL(misfit_finish, dim3(1), dim3(256), 0, st, partial, blocks, 0.5, loss_out);
+    }
+    MIFWI_HIP_TRY(hipGetLastError());
+    return MIFWI_OK;
+}
+
+int mifwi_trace_filter(int device, const float *x, float *y, int64_t nt, int64_t ntrace, const double *sos,
+                       int32_t nsec, int32_t transpose, void *stream)
+{
+    if (!x || !y || !sos) return mifwi::fail(MIFWI_EINVAL, "null argument");
+    mifwi_filter::Sos c;
+    int rc = mifwi_filter::check(nt, ntrace, sos, nsec, &c);
+    if (rc) return rc;
+    rc = mifwi::check_device(device);
+    if (rc) return rc;
+    MIFWI_HIP_TRY(hipSetDevice(device));
+    mifwi_filter::launch_plain(nsec, transpose != 0, (unsigned)mifwi_filter::blocks(ntrace), (hipStream_t)stream, c, x, y,
+                               (int)nt, (long long)ntrace);
+    MIFWI_HIP_TRY(hipGetLastError());
+    return MIFWI_OK;
+}
+
+int64_t mifwi_misfit_filtered_work_elems(int32_t kind, int64_t nt, int64_t ntrace)
+{
+    if (nt < 1 || ntrace < 1) return 0;
+    const int64_t partials = mifwi::round_up64(2 * mifwi_filter::blocks(ntrace) + 2, 64);      // doubles, counted in floats
+    return kind == MIFWI_MISFIT_GLOBAL_CORRELATION ? partials + nt * ntrace : partials;        // + the filtered obs
+}
+
+int mifwi_misfit_filtered(int device, int32_t kind, const float *pred, const float *obs, int64_t nt, int64_t ntrace,
+                          const double *sos, int32_t nsec, float *loss_out, float *adj_out, float *work, void *stream)
+{
+    if (!pred || !obs || !sos || !loss_out || !work) return mifwi::fail(MIFWI_EINVAL, "null argument");
+    if (kind == MIFWI_MISFIT_L1_TRACE_NORM)
+        return mifwi::fail(MIFWI_EINVAL, "the trace-normalised L1 misfit has no stage filter (the acoustic protocol has no stage)");
+    if (kind != MIFWI_MISFIT_L2 && kind != MIFWI_MISFIT_GLOBAL_CORRELATION)
+        return mifwi::fail(MIFWI_EINVAL, "unknown misfit kind %d", kind);
+    if ((reinterpret_cast<uintptr_t>(work) & 7) != 0) return mifwi::fail(MIFWI_EINVAL, "work must be 8-byte aligned");
+    mifwi_filter::Sos c;
+    int rc = mifwi_filter::check(nt, ntrace, sos, nsec, &c);
+    if (rc) return rc;
+    rc = mifwi::check_device(device);
+    if (rc) return rc;
+    MIFWI_HIP_TRY(hipSetDevice(device));
+    hipStream_t st = (hipStream_t)stream;
+    const long long nblk = mifwi_filter::blocks(ntrace);
+    double *partial = reinterpret_cast<double *>(work);
+    if (kind == MIFWI_MISFIT_L2) {
+        mifwi_filter::launch_l2(nsec, (unsigned)nblk, st, c, pred, obs, (int)nt, (long long)ntrace, adj_out, partial);
+        hipLaunchKernelGGL(misfit_finish, dim3(1), dim3(256), 0, st, partial, (int)nblk, 0.5, loss_out);
+    } else {
+        float *fobs = work + mifwi::round_up64(2 * nblk + 2, 64);
+        mifwi_filter::launch_gc(nsec, (unsigned)nblk, st, c, pred, obs, (int)nt, (long long)ntrace, adj_out, fobs, partial);
+        hipLaunchKernelGGL(misfit_finish, dim3(1), dim3(256), 0, st, partial, (int)nblk, 1.0, loss_out);
     }
     MIFWI_HIP_TRY(hipGetLastError());
     return MIFWI_OK;
