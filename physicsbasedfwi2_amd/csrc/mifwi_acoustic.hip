@@ -20,9 +20,7 @@
 // The arithmetic is the same explicit fmaf chain as oracle/acoustic.c (compile with
 // -ffp-contract=off) so wavefields can be compared bitwise.
 #include "mifwi_cluster_host.h"
-
-#include <atomic>
-
+#include "mifwi_host.h"
 
 #include <algorithm>
 #include <cmath>
@@ -298,36 +296,6 @@ __global__ __launch_bounds__(kThreads) void ac_step(const AcParams p)
     }
 }
 
-// ---- per-shot bounding box of a point set ------------------------------------------------------
-__global__ void points_bbox(const int *cell, int npts_per_shot, int n1, int *bbox)
-{
-    __shared__ int red[4][kThreads];
-    const int s = blockIdx.x;
-    int a0 = 0x7fffffff, a1 = -1, b0 = 0x7fffffff, b1 = -1;
-    for (int e = threadIdx.x; e < npts_per_shot; e += kThreads) {
-        const int c = cell[(long long)s * npts_per_shot + e];
-        if (c < 0) continue;
-        const int i0 = c / n1, i1 = c - i0 * n1;
-        a0 = min(a0, i0); a1 = max(a1, i0); b0 = min(b0, i1); b1 = max(b1, i1);
-    }
-    red[0][threadIdx.x] = a0; red[1][threadIdx.x] = a1;
-    red[2][threadIdx.x] = b0; red[3][threadIdx.x] = b1;
-    __syncthreads();
-    for (int st = kThreads / 2; st > 0; st >>= 1) {
-        if ((int)threadIdx.x < st) {
-            red[0][threadIdx.x] = min(red[0][threadIdx.x], red[0][threadIdx.x + st]);
-            red[1][threadIdx.x] = max(red[1][threadIdx.x], red[1][threadIdx.x + st]);
-            red[2][threadIdx.x] = min(red[2][threadIdx.x], red[2][threadIdx.x + st]);
-            red[3][threadIdx.x] = max(red[3][threadIdx.x], red[3][threadIdx.x + st]);
-        }
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) {
-        bbox[4 * s + 0] = red[0][0]; bbox[4 * s + 1] = red[1][0];
-        bbox[4 * s + 2] = red[2][0]; bbox[4 * s + 3] = red[3][0];
-    }
-}
-
 // ---- grad_r = (sum over shot groups of acc) * (1 + q r)/r --------------------------------------
 __global__ void ac_finalize(const float *acc, int ngroups, int n0, int n1, int gp, const float *r,
                             const float *q0, const float *q1, float *grad)
@@ -440,56 +408,6 @@ struct ClParams {
     long long *trace;                    // phase time stamps of one workgroup (MIFWI_AC_CL_TRACE), see CL_STAMP
 #endif
 };
-
-// Row slabs of a shot.  rt == 0: n0 rows split evenly over NW slabs.  rt > 0 (NW >= 3): the first and
-// the last slab hold rt rows each - the absorbing layer, whose cells cost an IEEE division per step -
-// and the other NW-2 slabs share the rest evenly, so that the all-sponge slabs do not set the pace.
-__host__ __device__ __forceinline__ void slab_rows(int n0, int NW, int rt, int w, int &r0, int &rows)
-{
-    if (rt > 0) {
-        if (w == 0) { r0 = 0; rows = rt; return; }
-        if (w == NW - 1) { r0 = n0 - rt; rows = rt; return; }
-        const int m = n0 - 2 * rt, k = NW - 2, v = w - 1;
-        const int base = m / k, rem = m - base * k;
-        rows = base + (v < rem ? 1 : 0);
-        r0 = rt + v * base + (v < rem ? v : rem);
-        return;
-    }
-    const int base = n0 / NW, rem = n0 - base * NW;
-    rows = base + (w < rem ? 1 : 0);
-    r0 = w * base + (w < rem ? w : rem);
-}
-
-__host__ __device__ __forceinline__ int slab_of_row(int n0, int NW, int rt, int i0)
-{
-    int m = n0, k = NW, off = 0, first = 0;
-    if (rt > 0) {
-        if (i0 < rt) return 0;
-        if (i0 >= n0 - rt) return NW - 1;
-        m = n0 - 2 * rt; k = NW - 2; off = rt; first = 1;
-    }
-    const int base = m / k, rem = m - base * k, i = i0 - off;
-    return first + ((i < rem * (base + 1)) ? i / (base + 1) : rem + (i - rem * (base + 1)) / base);
-}
-
-// lists of the receiver taps that fall into each slab (adjoint injection), one block per shot
-__global__ void cl_build_slab_lists(const int *rec_cell, int ntaps, int n0, int n1, int NW, int rt,
-                                    int *slab_cnt, int *slab_list)
-{
-    const int s = blockIdx.x;
-    __shared__ int cnt[64];
-    if ((int)threadIdx.x < NW) cnt[threadIdx.x] = 0;
-    __syncthreads();
-    for (int e = threadIdx.x; e < ntaps; e += blockDim.x) {
-        const int cell = rec_cell[(long long)s * ntaps + e];
-        if (cell < 0) continue;
-        const int w = slab_of_row(n0, NW, rt, cell / n1);
-        const int pos = atomicAdd(&cnt[w], 1);
-        slab_list[((long long)s * NW + w) * ntaps + pos] = e;
-    }
-    __syncthreads();
-    if ((int)threadIdx.x < NW) slab_cnt[s * NW + threadIdx.x] = cnt[threadIdx.x];
-}
 
 // one stencil update of a group of 4 cells whose operands sit in LDS.  Same fmaf chain as ac_step,
 // written on 2-wide vectors so that hipcc emits packed fp32 VALU (v_pk_fma/mul/add_f32: two cells
@@ -1234,24 +1152,44 @@ struct mifwi_acoustic_plan {
 
 namespace {
 
-template <int LX, bool SAVE, bool IMAGE>
-void launch_rz(const mifwi_acoustic_plan *pl, dim3 grid, const AcParams &q, hipStream_t st)
+using mifwi::with_bool;
+using mifwi::with_int;
+
+// ---- variant tables (mifwi_host.h) ----------------------------------------------------------------
+// ac_step<LX, RZ, SAVE, IMAGE, PML>: lanes per row 64 | 32 | 16, rows per thread 8 | 2 | 1 | 4 (C-PML plans: 2 only, the
+// layer's variant is built for two rows per thread), and snapshot store, imaging or neither (never both: null)
+using AcStepKernel = void (*)(AcParams);
+AcStepKernel ac_step_variant(int lx, int rz, bool save, bool image, bool pml)
 {
-    dim3 block(kThreads);
-    if (q.pmlW > 0) {                  // C-PML plans march two rows per thread (plan_create pins rz)
-        hipLaunchKernelGGL((ac_step<LX, 2, SAVE, IMAGE, true>), grid, block, 0, st, q);
-        return;
-    }
-    switch (pl->rz) {
-        case 8: hipLaunchKernelGGL((ac_step<LX, 8, SAVE, IMAGE>), grid, block, 0, st, q); break;
-        case 2: hipLaunchKernelGGL((ac_step<LX, 2, SAVE, IMAGE>), grid, block, 0, st, q); break;
-        case 1: hipLaunchKernelGGL((ac_step<LX, 1, SAVE, IMAGE>), grid, block, 0, st, q); break;
-        default: hipLaunchKernelGGL((ac_step<LX, 4, SAVE, IMAGE>), grid, block, 0, st, q); break;
-    }
+    return with_int<64, 32, 16>(lx, [&](auto LX) {
+    return with_int<8, 2, 1, 4>(pml ? 2 : rz, [&](auto RZ) {
+    return with_bool(save, [&](auto SAVE) {
+    return with_bool(image, [&](auto IMAGE) {
+    return with_bool(pml, [&](auto PML) -> AcStepKernel {
+        constexpr bool S = decltype(SAVE)::value, I = decltype(IMAGE)::value, P = decltype(PML)::value;
+        if constexpr ((S && I) || (P && decltype(RZ)::value != 2)) return nullptr;
+        else return ac_step<decltype(LX)::value, decltype(RZ)::value, S, I, P>;
+    }); }); }); }); });
 }
 
-template <bool SAVE, bool IMAGE>
-void launch_step(const mifwi_acoustic_plan *pl, const AcParams &p, hipStream_t st, int ngroups = -1)
+// ac_cluster<MODE, SLOW, AG, PML>: forward, forward + snapshots, adjoint, Born; the rescanning form (a thread may own
+// several sparse points); granules published at agent scope; C-PML.  The Born loop has no C-PML form (null): that pass of
+// a C-PML plan runs one launch per step.
+using ClKernel = void (*)(ClParams);
+ClKernel ac_cluster_variant(int mode, bool slow, bool agent, bool pml)
+{
+    return with_int<0, 1, 2, 3>(mode, [&](auto MODE) {
+    return with_bool(slow, [&](auto SLOW) {
+    return with_bool(agent, [&](auto AG) {
+    return with_bool(pml, [&](auto PML) -> ClKernel {
+        constexpr int M = decltype(MODE)::value;
+        constexpr bool P = decltype(PML)::value;
+        if constexpr (M == 3 && P) return nullptr;
+        else return ac_cluster<M, decltype(SLOW)::value, decltype(AG)::value, P>;
+    }); }); }); });
+}
+
+void launch_step(const mifwi_acoustic_plan *pl, bool save, bool image, const AcParams &p, hipStream_t st, int ngroups = -1)
 {
     const int lz = kThreads / pl->lx;
     const int tiles_x = mifwi::ceil_div(pl->ng, pl->lx);
@@ -1262,11 +1200,7 @@ void launch_step(const mifwi_acoustic_plan *pl, const AcParams &p, hipStream_t s
     if (p.smp_out != nullptr && p.nsmp > 0)
         extra = mifwi::ceil_div(mifwi::ceil_div(pl->gs * p.nsmp, kThreads), tiles_x);
     dim3 grid(tiles_x, tiles_z + extra, ngroups > 0 ? ngroups : pl->ngroups);
-    switch (pl->lx) {
-        case 64: launch_rz<64, SAVE, IMAGE>(pl, grid, q, st); break;
-        case 32: launch_rz<32, SAVE, IMAGE>(pl, grid, q, st); break;
-        default: launch_rz<16, SAVE, IMAGE>(pl, grid, q, st); break;
-    }
+    hipLaunchKernelGGL(ac_step_variant(pl->lx, pl->rz, save, image, q.pmlW > 0), grid, dim3(kThreads), 0, st, q);
 }
 
 using mifwi::env_int;
@@ -1340,6 +1274,20 @@ AcWork work_map(const mifwi_acoustic_plan *pl, bool backward)
     return m;
 }
 
+// C-PML plans: the caller's q0 / q1 carry the layer's a, b profiles (`pm` gets them and the layer's arrays in `work`); the
+// sponge terms of the kernels read the zero vectors instead.  Other plans: `pm` zeroed, q0 / q1 as they came.
+int pml_open(const mifwi_acoustic_plan *pl, float *work, const AcWork &m, hipStream_t st, const float *&q0, const float *&q1,
+             AcPml &pm)
+{
+    memset(&pm, 0, sizeof(pm));
+    if (pl->pmlW == 0) return MIFWI_OK;
+    float *zq = work + m.zq;
+    MIFWI_HIP_TRY(hipMemsetAsync(zq, 0, sizeof(float) * pl->zq_elems, st));
+    pm = pml_params(pl, q0, q1, work + m.pml_persist, work + m.pml_scratch);
+    q0 = zq; q1 = zq + mifwi::round_up64(pl->d.n0, 4);      // q1 is read with 16-byte loads
+    return MIFWI_OK;
+}
+
 // ---- cluster path helpers --------------------------------------------------------------------------
 void cluster_setup(mifwi_acoustic_plan *pl)
 {
@@ -1410,31 +1358,12 @@ void cluster_setup(mifwi_acoustic_plan *pl)
     pl->xcc_elems = mifwi::handoff_xcc_elems(pl->d.nshot, pl->NW);
     pl->xbuf_elems = mifwi::handoff_elems(2LL * pl->d.nshot * pl->NW * 8 * pl->gp, pl->xcc_elems);
     pl->list_elems = mifwi::round_up64((long long)pl->d.nshot * pl->NW * (1 + (long long)pl->d.nrec), 64);
-    // 28 function attributes: once per device and process, not once per plan (a plan is created on every propagate call)
+    // one cap for every variant (the attribute is per function and plans of both kinds coexist): C-PML plans ask for up
+    // to kClPmlLdsLimit, the others never for more than kClusterLdsLimit.  A failure: the plan uses one launch per step.
     static std::atomic<unsigned> attr_done{0};
-    if (pl->device < 32 && (attr_done.load() >> pl->device & 1u)) return;
-    for (const void *fn : {(const void *)ac_cluster<0, false, false>, (const void *)ac_cluster<1, false, false>,
-                           (const void *)ac_cluster<2, false, false>, (const void *)ac_cluster<3, false, false>,
-                           (const void *)ac_cluster<0, true, false>, (const void *)ac_cluster<1, true, false>,
-                           (const void *)ac_cluster<2, true, false>, (const void *)ac_cluster<3, true, false>,
-                           (const void *)ac_cluster<0, false, true>, (const void *)ac_cluster<1, false, true>,
-                           (const void *)ac_cluster<2, false, true>, (const void *)ac_cluster<3, false, true>,
-                           (const void *)ac_cluster<0, true, true>, (const void *)ac_cluster<1, true, true>,
-                           (const void *)ac_cluster<2, true, true>, (const void *)ac_cluster<3, true, true>,
-                           (const void *)ac_cluster<0, false, false, true>, (const void *)ac_cluster<1, false, false, true>,
-                           (const void *)ac_cluster<2, false, false, true>, (const void *)ac_cluster<0, true, false, true>,
-                           (const void *)ac_cluster<1, true, false, true>, (const void *)ac_cluster<2, true, false, true>,
-                           (const void *)ac_cluster<0, false, true, true>, (const void *)ac_cluster<1, false, true, true>,
-                           (const void *)ac_cluster<2, false, true, true>, (const void *)ac_cluster<0, true, true, true>,
-                           (const void *)ac_cluster<1, true, true, true>, (const void *)ac_cluster<2, true, true, true>})
-        // one cap for every variant (the attribute is per function and plans of both kinds coexist): C-PML plans ask for up
-        // to kClPmlLdsLimit, the others never for more than kClusterLdsLimit
-        if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, kClPmlLdsLimit) != hipSuccess) {
-            (void)hipGetLastError();           // not sticky: the plan simply uses one launch per step
-            pl->cluster = 0;
-            return;
-        }
-    if (pl->device < 32) attr_done.fetch_or(1u << pl->device);
+    if (!mifwi::lds_cap_once(attr_done, pl->device, kClPmlLdsLimit, 32,
+                             [](int v) { return ac_cluster_variant(v >> 3, v & 4, v & 2, v & 1); }))
+        pl->cluster = 0;
 }
 
 ClParams cluster_params(const mifwi_acoustic_plan *pl, const float *r, const float *q0, const float *q1,
@@ -1461,41 +1390,29 @@ ClParams cluster_params(const mifwi_acoustic_plan *pl, const float *r, const flo
 }
 
 // the kernels of one single-launch attempt over the shot batches (AG: granules published at agent scope)
-template <int MODE, bool AG>
-void cluster_launch(const mifwi_acoustic_plan *pl, ClParams c, hipStream_t st)
+void cluster_launch(const mifwi_acoustic_plan *pl, int mode, bool agent, ClParams c, hipStream_t st)
 {
+    // the rescanning variant only when a thread may own several sparse points
+    const bool slow = mode == 2 ? (c.nrec > kClThreads || c.nsrc > kClThreads) : (c.nsrc > 1 || c.nrec > kClThreads);
+    const ClKernel kernel = ac_cluster_variant(mode, slow, agent, pl->pmlW > 0);
     for (int s0 = 0; s0 < pl->d.nshot; s0 += pl->cl_shots) {
         c.shot0 = s0;
         c.shot1 = std::min(pl->d.nshot, s0 + pl->cl_shots);
         const int nsl8 = mifwi::ceil_div(c.shot1 - s0, 8);
-        // general (rescanning) variant only when a thread may own several sparse points
-        const bool general = MODE == 2 ? (c.nrec > kClThreads || c.nsrc > kClThreads)
-                                       : (c.nsrc > 1 || c.nrec > kClThreads);
-        const dim3 grid(8 * pl->NW * nsl8), block(kClThreads);
-        if constexpr (MODE != 3) {
-            if (pl->pmlW > 0) {
-                if (general) hipLaunchKernelGGL((ac_cluster<MODE, true, AG, true>), grid, block, pl->cl_lds, st, c);
-                else hipLaunchKernelGGL((ac_cluster<MODE, false, AG, true>), grid, block, pl->cl_lds, st, c);
-                continue;
-            }
-        }
-        if (general) hipLaunchKernelGGL((ac_cluster<MODE, true, AG>), grid, block, pl->cl_lds, st, c);
-        else hipLaunchKernelGGL((ac_cluster<MODE, false, AG>), grid, block, pl->cl_lds, st, c);
+        hipLaunchKernelGGL(kernel, dim3(8 * pl->NW * nsl8), dim3(kClThreads), pl->cl_lds, st, c);
     }
 }
 
-// mifwi::cluster_ladder over ac_cluster<MODE>: MIFWI_OK (range done), mifwi::kClusterFellBack (state restored: run one
-// launch per step) or an error
-template <int MODE>
-int cluster_run(const char *what, const mifwi_acoustic_plan *pl, const ClParams &c0, const mifwi::Handoff &h, hipStream_t st,
-                float *work, const AcWork &m, int32_t flags)
+// mifwi::cluster_ladder over ac_cluster (mode: its MODE): MIFWI_OK (range done), mifwi::kClusterFellBack (state restored:
+// run one launch per step) or an error
+int cluster_run(const char *what, const mifwi_acoustic_plan *pl, int mode, const ClParams &c0, const mifwi::Handoff &h,
+                hipStream_t st, float *work, const AcWork &m, int32_t flags)
 {
-    const mifwi::TraceSpec ts = {"MIFWI_AC_CL_TRACE", 64 * 16 * 16, "# ac_cluster mode=%d waves=16", MODE, 0};
+    const mifwi::TraceSpec ts = {"MIFWI_AC_CL_TRACE", 64 * 16 * 16, "# ac_cluster mode=%d waves=16", mode, 0};
     return mifwi::cluster_ladder(what, work, m.state, work + m.backup, flags, st, h, ts, [&](bool agent, long long *trace) {
         ClParams c = c0;
         mifwi::set_trace(c, trace);
-        if (agent) cluster_launch<MODE, true>(pl, c, st);
-        else cluster_launch<MODE, false>(pl, c, st);
+        cluster_launch(pl, mode, agent, c, st);
     });
 }
 
@@ -1559,12 +1476,7 @@ int mifwi_acoustic_plan_create(mifwi_acoustic_plan **plan, int device,
     pl->shot_stride = (long long)(d->n0 + 4) * pl->pitch;
     pl->field_elems = pl->shot_stride * d->nshot;
     pl->coef_elems = (long long)d->n0 * pl->gp;
-    // lanes per row: widest tile whose padding waste stays small
-    pl->lx = 16;
-    for (int cand : {64, 32}) {
-        const int padded = mifwi::ceil_div(pl->ng, cand) * cand;
-        if (padded * 10 <= pl->ng * 12) { pl->lx = cand; break; }
-    }
+    pl->lx = mifwi::pick_lx(pl->ng);
     pl->rz = 2;
     pl->xcd = env_int("MIFWI_AC_XCD", 1) != 0;
     // tuning overrides (benchmarks only)
@@ -1589,16 +1501,11 @@ int mifwi_acoustic_plan_create(mifwi_acoustic_plan **plan, int device,
         // 4 groups = 216 MB between 119 and 141 us, all 8 groups 165-200 us); adjoint: 250 MB as in the elastic plan
         const double model = 4.0 * (double)pl->coef_elems;
         const double gstate = 4.0 * 2.0 * (double)pl->shot_stride * pl->gs;
-        auto fit = [&](double per_group, double resident) {
-            int k = pl->ngroups;
-            if (pl->ngroups * per_group + model > resident) {
-                k = (int)std::floor((resident - model) / per_group);
-                if (k < 1) k = pl->ngroups;
-            }
-            return k;
-        };
-        pl->pass_fwd = std::min(pl->ngroups, std::max(1, env_int("MIFWI_AC_PASS_GROUPS", fit(gstate, 200e6))));
-        pl->pass_adj = std::min(pl->ngroups, std::max(1, env_int("MIFWI_AC_PASS_GROUPS", fit(gstate + model, 250e6))));
+        // (no group fits: one pass over all of them)
+        const int fwd = mifwi::units_per_pass(pl->ngroups, gstate, model, 200e6, 200e6, pl->ngroups);
+        const int adj = mifwi::units_per_pass(pl->ngroups, gstate + model, model, 250e6, 250e6, pl->ngroups);
+        pl->pass_fwd = std::min(pl->ngroups, std::max(1, env_int("MIFWI_AC_PASS_GROUPS", fwd)));
+        pl->pass_adj = std::min(pl->ngroups, std::max(1, env_int("MIFWI_AC_PASS_GROUPS", adj)));
     }
     *plan = pl;
     return MIFWI_OK;
@@ -1648,32 +1555,20 @@ int mifwi_acoustic_forward(mifwi_acoustic_plan *pl, const float *r, const float 
 {
     if (!pl || !r || !q0 || !q1 || !work) return mifwi::fail(MIFWI_EINVAL, "null argument");
     const mifwi_acoustic_desc &d = pl->d;
-    if (n_begin < 0 || n_end > d.nt || n_begin > n_end)
-        return mifwi::fail(MIFWI_EINVAL, "bad step range [%d,%d) for nt=%d", n_begin, n_end, d.nt);
+    int rc = mifwi::check_steps(n_begin, n_end, d.nt);
+    if (rc) return rc;
     if (d.nsrc > 0 && (!f || !src_cell || !src_w))
         return mifwi::fail(MIFWI_EINVAL, "sources declared but f/src_cell/src_w is null");
     if (rec_out && (!rec_cell || !rec_w))
         return mifwi::fail(MIFWI_EINVAL, "rec_out given but rec_cell/rec_w is null");
-    int rc = mifwi::check_device(pl->device);
-    if (rc) return rc;
-    MIFWI_HIP_TRY(hipSetDevice(pl->device));
-    hipStream_t st = (hipStream_t)stream;
     const AcWork m = work_map(pl, false);
+    hipStream_t st;
+    if ((rc = mifwi::open_call(pl->device, stream, work, m, flags, &st))) return rc;
     float *ua = work + m.ua, *ub = work + m.ub;
-    float *pml_persist = work + m.pml_persist, *pml_scratch = work + m.pml_scratch;
-    float *zq = work + m.zq;                                    // C-PML plans: q0 / q1 carry the a, b profiles
     int *bbox = reinterpret_cast<int *>(work + m.bbox);
-    if (flags & MIFWI_ZERO_STATE) MIFWI_HIP_TRY(hipMemsetAsync(work, 0, sizeof(float) * m.state, st));
     AcPml pm;
-    memset(&pm, 0, sizeof(pm));
-    if (pl->pmlW > 0) {
-        MIFWI_HIP_TRY(hipMemsetAsync(zq, 0, sizeof(float) * pl->zq_elems, st));
-        pm = pml_params(pl, q0, q1, pml_persist, pml_scratch);
-        q0 = zq; q1 = zq + mifwi::round_up64(d.n0, 4);      // q1 is read with 16-byte loads
-    }
-    if (d.nsrc > 0)
-        hipLaunchKernelGGL(points_bbox, dim3(d.nshot), dim3(kThreads), 0, st, src_cell,
-                           d.nsrc * d.ntap, d.n1, bbox);
+    if ((rc = pml_open(pl, work, m, st, q0, q1, pm))) return rc;
+    if (d.nsrc > 0) launch_points_bbox(src_cell, d.nshot, d.nsrc * d.ntap, d.n1, bbox, st);
     AcParams p = base_params(pl, r, q0, q1);
     p.pmlW = pl->pmlW; p.pml_adj = 0; p.pe0 = pm.e0; p.pe1 = pm.e1;
     p.ninj = d.nsrc; p.ntap_inj = d.ntap; p.inj_mode = 0;
@@ -1689,8 +1584,7 @@ int mifwi_acoustic_forward(mifwi_acoustic_plan *pl, const float *r, const float 
         c.rec_cell = rec_cell; c.rec_w = rec_w; c.rec_out = (rec_out && d.nrec > 0) ? rec_out : nullptr;
         c.G = snap; c.g_first = n_begin; c.g_step = snap_step;
         c.pml = pm;
-        rc = snap ? cluster_run<1>("acoustic forward", pl, c, h, st, work, m, flags)
-                  : cluster_run<0>("acoustic forward", pl, c, h, st, work, m, flags);
+        rc = cluster_run("acoustic forward", pl, snap ? 1 : 0, c, h, st, work, m, flags);
         if (rc != mifwi::kClusterFellBack) return rc;
     }
     // shot groups are independent: a few at a time keep wavefields and model inside the Infinity Cache
@@ -1703,12 +1597,8 @@ int mifwi_acoustic_forward(mifwi_acoustic_plan *pl, const float *r, const float 
         p.inj_amp = f ? f + (long long)n * d.nshot * d.nsrc : nullptr;
         p.smp_out = (rec_out && d.nrec > 0) ? rec_out + (long long)n * d.nshot * d.nrec : nullptr;
         if (pl->pmlW > 0) pml_step(pm, p.cur, g0 * pl->gs, std::min(cg * pl->gs, d.nshot - g0 * pl->gs), false, st);
-        if (snap) {
-            p.G = snap + (long long)(n - n_begin) * snap_step;
-            launch_step<true, false>(pl, p, st, cg);
-        } else {
-            launch_step<false, false>(pl, p, st, cg);
-        }
+        if (snap) p.G = snap + (long long)(n - n_begin) * snap_step;
+        launch_step(pl, snap != nullptr, false, p, st, cg);
     }
     MIFWI_HIP_TRY(hipGetLastError());
     return MIFWI_OK;
@@ -1722,28 +1612,18 @@ int mifwi_acoustic_born(mifwi_acoustic_plan *pl, const float *r, const float *q0
     if (!pl || !r || !q0 || !q1 || !dr || !snap || !work || !drec_out || !rec_cell || !rec_w)
         return mifwi::fail(MIFWI_EINVAL, "null argument");
     const mifwi_acoustic_desc &d = pl->d;
-    if (n_begin < 0 || n_end > d.nt || n_begin > n_end)
-        return mifwi::fail(MIFWI_EINVAL, "bad step range [%d,%d) for nt=%d", n_begin, n_end, d.nt);
-    if (snap_first > n_begin)
-        return mifwi::fail(MIFWI_EINVAL, "snapshots start at step %d but step %d is needed", snap_first, n_begin);
-    int rc = mifwi::check_device(pl->device);
+    int rc = mifwi::check_steps(n_begin, n_end, d.nt);
+    if (!rc) rc = mifwi::check_snapshots(snap_first, n_begin);
     if (rc) return rc;
-    MIFWI_HIP_TRY(hipSetDevice(pl->device));
-    hipStream_t st = (hipStream_t)stream;
     const AcWork m = work_map(pl, false);
+    hipStream_t st;
+    if ((rc = mifwi::open_call(pl->device, stream, work, m, flags, &st))) return rc;
     float *ua = work + m.ua, *ub = work + m.ub;
-    float *pml_persist = work + m.pml_persist, *pml_scratch = work + m.pml_scratch;
-    float *zq = work + m.zq;
-    if (flags & MIFWI_ZERO_STATE) MIFWI_HIP_TRY(hipMemsetAsync(work, 0, sizeof(float) * m.state, st));
     AcPml pm;
-    memset(&pm, 0, sizeof(pm));
-    if (pl->pmlW > 0) {
-        MIFWI_HIP_TRY(hipMemsetAsync(zq, 0, sizeof(float) * pl->zq_elems, st));
-        pm = pml_params(pl, q0, q1, pml_persist, pml_scratch);
-        q0 = zq; q1 = zq + mifwi::round_up64(d.n0, 4);      // q1 is read with 16-byte loads
-    }
+    if ((rc = pml_open(pl, work, m, st, q0, q1, pm))) return rc;
     const long long snap_step = (long long)d.nshot * pl->coef_elems;
-    if (pl->cluster && pl->pmlW == 0 && n_end > n_begin) {          // (the Born pass of a C-PML plan runs one launch per step)
+    // (the Born pass of a C-PML plan runs one launch per step: ac_cluster_variant has no such loop)
+    if (pl->cluster && ac_cluster_variant(3, false, false, pl->pmlW > 0) && n_end > n_begin) {
         const mifwi::Handoff h = mifwi::cluster_handoff(pl, work, m);
         ClParams c = cluster_params(pl, r, q0, q1, ua, ub, h);
         c.n_first = n_begin; c.n_last = n_end;
@@ -1751,7 +1631,7 @@ int mifwi_acoustic_born(mifwi_acoustic_plan *pl, const float *r, const float *q0
         c.rec_cell = rec_cell; c.rec_w = rec_w; c.rec_out = d.nrec > 0 ? drec_out : nullptr;
         c.G = const_cast<float *>(snap); c.g_first = snap_first; c.g_step = snap_step;
         c.born_dr = dr;
-        rc = cluster_run<3>("acoustic Born", pl, c, h, st, work, m, flags);      // (no layer here: the state is the two fields)
+        rc = cluster_run("acoustic Born", pl, 3, c, h, st, work, m, flags);      // (no layer here: the state is the two fields)
         if (rc != mifwi::kClusterFellBack) return rc;
     }
     AcParams p = base_params(pl, r, q0, q1);
@@ -1765,7 +1645,7 @@ int mifwi_acoustic_born(mifwi_acoustic_plan *pl, const float *r, const float *q0
         p.smp_out = d.nrec > 0 ? drec_out + (long long)n * d.nshot * d.nrec : nullptr;
         p.G = const_cast<float *>(snap) + (long long)(n - snap_first) * snap_step;
         if (pl->pmlW > 0) pml_step(pm, p.cur, 0, d.nshot, false, st);
-        launch_step<false, true>(pl, p, st);
+        launch_step(pl, false, true, p, st);
     }
     MIFWI_HIP_TRY(hipGetLastError());
     return MIFWI_OK;
@@ -1780,34 +1660,21 @@ int mifwi_acoustic_backward(mifwi_acoustic_plan *pl, const float *r, const float
     if (!pl || !r || !q0 || !q1 || !work || !snap || !grad_rec || !rec_cell || !rec_w)
         return mifwi::fail(MIFWI_EINVAL, "null argument");
     const mifwi_acoustic_desc &d = pl->d;
-    if (k_lo < 1 || k_hi > d.nt - 1 || k_lo > k_hi + 1)
-        return mifwi::fail(MIFWI_EINVAL, "bad adjoint range k=%d..%d for nt=%d", k_hi, k_lo, d.nt);
-    if (snap_first > k_lo - 1)
-        return mifwi::fail(MIFWI_EINVAL, "snapshots start at step %d but step %d is needed",
-                           snap_first, k_lo - 1);
+    int rc = mifwi::check_adjoint_steps('k', 1, k_hi, k_lo, d.nt);
+    if (!rc) rc = mifwi::check_snapshots(snap_first, k_lo - 1);
+    if (rc) return rc;
     if (grad_f && (!src_cell || !src_w))
         return mifwi::fail(MIFWI_EINVAL, "grad_f requested but src_cell/src_w is null");
     if ((flags & MIFWI_FINALIZE) && !grad_r)
         return mifwi::fail(MIFWI_EINVAL, "finalize requested but grad_r is null");
-    int rc = mifwi::check_device(pl->device);
-    if (rc) return rc;
-    MIFWI_HIP_TRY(hipSetDevice(pl->device));
-    hipStream_t st = (hipStream_t)stream;
     const AcWork m = work_map(pl, true);
-    float *za = work + m.ua, *zb = work + m.ub;
-    float *pml_persist = work + m.pml_persist;                  // C-PML plans: the adjoint memory variables
-    float *acc = work + m.acc, *pml_scratch = work + m.pml_scratch, *zq = work + m.zq;
+    hipStream_t st;
+    if ((rc = mifwi::open_call(pl->device, stream, work, m, flags, &st))) return rc;
+    float *za = work + m.ua, *zb = work + m.ub, *acc = work + m.acc;
     int *bbox = reinterpret_cast<int *>(work + m.bbox);
-    if (flags & MIFWI_ZERO_STATE) MIFWI_HIP_TRY(hipMemsetAsync(work, 0, sizeof(float) * m.state, st));
-    AcPml pm;
-    memset(&pm, 0, sizeof(pm));
-    if (pl->pmlW > 0) {
-        MIFWI_HIP_TRY(hipMemsetAsync(zq, 0, sizeof(float) * pl->zq_elems, st));
-        pm = pml_params(pl, q0, q1, pml_persist, pml_scratch);
-        q0 = zq; q1 = zq + mifwi::round_up64(d.n0, 4);      // q1 is read with 16-byte loads
-    }
-    hipLaunchKernelGGL(points_bbox, dim3(d.nshot), dim3(kThreads), 0, st, rec_cell,
-                       d.nrec * d.ntap, d.n1, bbox);
+    AcPml pm;                                                   // (its persistent arrays: the adjoint memory variables)
+    if ((rc = pml_open(pl, work, m, st, q0, q1, pm))) return rc;
+    launch_points_bbox(rec_cell, d.nshot, d.nrec * d.ntap, d.n1, bbox, st);
     AcParams p = base_params(pl, r, q0, q1);
     p.pmlW = pl->pmlW; p.pml_adj = 1; p.pe0 = pm.e0; p.pe1 = pm.e1;
     p.acc = acc;
@@ -1823,8 +1690,7 @@ int mifwi_acoustic_backward(mifwi_acoustic_plan *pl, const float *r, const float
     if (pl->cluster && k_hi >= k_lo) {
         const mifwi::Handoff h = mifwi::cluster_handoff(pl, work, m);
         int *lists = reinterpret_cast<int *>(work + m.lists);
-        hipLaunchKernelGGL(cl_build_slab_lists, dim3(d.nshot), dim3(256), 0, st, rec_cell, d.nrec, d.n0, d.n1,
-                           pl->NW, pl->rt, lists, lists + (long long)d.nshot * pl->NW);
+        launch_build_slab_lists(rec_cell, d.nshot, d.nrec, d.n0, d.n1, pl->NW, pl->rt, lists, st);
         ClParams c = cluster_params(pl, r, q0, q1, za, zb, h);
         c.n_first = k_hi; c.n_last = k_lo;
         c.src_cell = src_cell; c.src_w = src_w;
@@ -1834,7 +1700,7 @@ int mifwi_acoustic_backward(mifwi_acoustic_plan *pl, const float *r, const float
         c.acc = acc;
         c.slab_cnt = lists; c.slab_list = lists + (long long)d.nshot * pl->NW;
         c.pml = pm;
-        rc = cluster_run<2>("acoustic adjoint", pl, c, h, st, work, m, flags);
+        rc = cluster_run("acoustic adjoint", pl, 2, c, h, st, work, m, flags);
         if (rc != MIFWI_OK && rc != mifwi::kClusterFellBack) return rc;
         per_step = rc == mifwi::kClusterFellBack;
     }
@@ -1849,7 +1715,7 @@ int mifwi_acoustic_backward(mifwi_acoustic_plan *pl, const float *r, const float
         p.smp_out = want_f ? grad_f + (long long)k * d.nshot * d.nsrc : nullptr;
         const int cg = std::min(pl->pass_adj, pl->ngroups - g0);
         if (pl->pmlW > 0) pml_step(pm, p.cur, g0 * pl->gs, std::min(cg * pl->gs, d.nshot - g0 * pl->gs), true, st);
-        launch_step<false, true>(pl, p, st, cg);
+        launch_step(pl, false, true, p, st, cg);
     }
     p.g0 = 0;
     if (flags & MIFWI_FINALIZE) {
@@ -1865,7 +1731,7 @@ int mifwi_acoustic_backward(mifwi_acoustic_plan *pl, const float *r, const float
                 mifwi::ceil_div(mifwi::ceil_div(pl->gs * s.nsmp, kThreads), tiles_x);
             dim3 grid(tiles_x, extra, pl->ngroups), block(kThreads);
             s.pmlW = 0;                                         // sampling workgroups only: no stencil, no layer term
-            hipLaunchKernelGGL((ac_step<16, 4, false, false>), grid, block, 0, st, s);
+            hipLaunchKernelGGL(ac_step_variant(16, 4, false, false, false), grid, block, 0, st, s);
         }
         const long long ncoef = pl->coef_elems;
         hipLaunchKernelGGL(ac_finalize, dim3((unsigned)((ncoef + 255) / 256)), dim3(256), 0, st,

@@ -1,5 +1,6 @@
-// Host-side driver of the single-launch ("cluster") time loops of both physics: hand-off buffer view, copy of a resumed
-// call's state, phase trace, and the ladder single launch -> agent-scope publishes -> one launch per step.  No device code.
+// Host-side driver of the single-launch ("cluster") time loops of both physics: LDS attribute of a kernel family, hand-off
+// buffer view, copy of a resumed call's state, phase trace, and the ladder single launch -> agent-scope publishes -> one
+// launch per step.  No device code.
 #pragma once
 #include "mifwi_common.h"
 #include <vector>
@@ -17,6 +18,26 @@ inline int env_int(const char *name, int dflt)
 inline int poll_nap_default(int rows_per_slab, int fat_rows)
 {
     return env_int("MIFWI_POLL_NAP", rows_per_slab >= fat_rows ? 48 : 1);
+}
+
+// Dynamic-LDS cap of a single-launch kernel family: entry(0 .. entries-1) walks the whole domain of the family's variant
+// table (the selectors packed into the index; null: no such variant).  The attribute is per function, so it is set once
+// per device and process (`done`: the family's guard, one bit per device), not once per plan - a plan is created on every
+// propagate call.  False: a call failed (not sticky) - this plan does without the family, and the guard stays unset, so
+// the next plan tries again.
+template <class Entry>
+bool lds_cap_once(std::atomic<unsigned> &done, int device, int bytes, int entries, Entry &&entry)
+{
+    if (device < 32 && (done.load() >> device & 1u)) return true;
+    for (int v = 0; v < entries; ++v) {
+        const void *fn = (const void *)entry(v);
+        if (fn && hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, bytes) != hipSuccess) {
+            (void)hipGetLastError();
+            return false;
+        }
+    }
+    if (device < 32) done.fetch_or(1u << device);
+    return true;
 }
 
 // A single-launch attempt may give up (some workgroup was not resident in time, or the slabs of a shot were not dealt to

@@ -27,6 +27,7 @@
 // the opt-in fused V+S launch (el_step_fused) live on the per-step path only.
 // Arithmetic = the explicit fmaf chain of oracle/elastic.c (build with -ffp-contract=off).
 #include "mifwi_cluster_host.h"
+#include "mifwi_host.h"
 
 #include <algorithm>
 #include <cmath>
@@ -1129,35 +1130,6 @@ __global__ void el_inject_pressure(const ElParams p)
     atomicAdd(fl + F_SZZ * (long long)p.field_stride + off, a);
 }
 
-__global__ void el_points_bbox(const int *cell, int npts_per_shot, int n1, int *bbox)
-{
-    __shared__ int red[4][kThreads];
-    const int s = blockIdx.x;
-    int a0 = 0x7fffffff, a1 = -1, b0 = 0x7fffffff, b1 = -1;
-    for (int e = threadIdx.x; e < npts_per_shot; e += kThreads) {
-        const int c = cell[(long long)s * npts_per_shot + e];
-        if (c < 0) continue;
-        const int i0 = c / n1, i1 = c - i0 * n1;
-        a0 = min(a0, i0); a1 = max(a1, i0); b0 = min(b0, i1); b1 = max(b1, i1);
-    }
-    red[0][threadIdx.x] = a0; red[1][threadIdx.x] = a1;
-    red[2][threadIdx.x] = b0; red[3][threadIdx.x] = b1;
-    __syncthreads();
-    for (int st = kThreads / 2; st > 0; st >>= 1) {
-        if ((int)threadIdx.x < st) {
-            red[0][threadIdx.x] = min(red[0][threadIdx.x], red[0][threadIdx.x + st]);
-            red[1][threadIdx.x] = max(red[1][threadIdx.x], red[1][threadIdx.x + st]);
-            red[2][threadIdx.x] = min(red[2][threadIdx.x], red[2][threadIdx.x + st]);
-            red[3][threadIdx.x] = max(red[3][threadIdx.x], red[3][threadIdx.x + st]);
-        }
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) {
-        bbox[4 * s + 0] = red[0][0]; bbox[4 * s + 1] = red[1][0];
-        bbox[4 * s + 2] = red[2][0]; bbox[4 * s + 3] = red[3][0];
-    }
-}
-
 // grad[k][cell] = sum over shot groups of acc[group][k][cell]; grad is row-major [5][nz][gp] (the C-ABI's layout), the
 // accumulator planes are `aplane` floats apart and column-blocked when sblk (snap_cell)
 __global__ void el_finalize(const float *acc, int ngroups, int nz, int gp, long long aplane, int sblk, float *grad)
@@ -1227,21 +1199,60 @@ ElParams el_base(const mifwi_elastic_plan *pl, const float *mat, const float *pz
     return p;
 }
 
-template <int SAVE>
-void launch_v(const mifwi_elastic_plan *pl, const ElParams &p, int nshot, hipStream_t st)
+using mifwi::with_bool;
+using mifwi::with_int;
+
+// ---- variant tables (mifwi_host.h) ----------------------------------------------------------------
+// the two launches of a per-step forward step, el_step_v / el_step_s<LX, 1, SAVE>: lanes per row 64 | 32 | 16; save
+// kBorn | 2 (bf16 planes) | 1 (f32 planes) | 0
+using ElKernel = void (*)(ElParams);
+struct ElStepKernels { ElKernel v, s; };
+ElStepKernels el_step_variant(int lx, int save)
+{
+    return with_int<64, 32, 16>(lx, [&](auto LX) {
+    return with_int<kBorn, 2, 1, 0>(save, [&](auto SAVE) {
+        return ElStepKernels{el_step_v<decltype(LX)::value, 1, decltype(SAVE)::value>,
+                             el_step_s<decltype(LX)::value, 1, decltype(SAVE)::value>};
+    }); });
+}
+// el_fwd_fused<SAVE>: save 2 | 1 | 0 (no Born form: that pass runs the two launches)
+ElKernel el_fwd_fused_variant(int save)
+{
+    return with_int<2, 1, 0>(save, [](auto SAVE) -> ElKernel { return el_fwd_fused<decltype(SAVE)::value>; });
+}
+// el_cluster_fwd<SAVE, NG, AG, XH>: snapshots; one | two groups per thread; granules published at agent scope; x-halo from
+// the neighbouring lanes.  The agent-scope tier keeps the plain reads (one variant less to build): AG takes XH off.
+using EcKernel = void (*)(EcParams);
+EcKernel el_cluster_fwd_variant(bool save, int ng, bool agent, bool xh)
+{
+    return with_bool(save, [&](auto SAVE) {
+    return with_int<1, 2>(ng, [&](auto NG) {
+    return with_bool(agent, [&](auto AG) {
+    return with_bool(xh, [&](auto XH) -> EcKernel {
+        constexpr bool A = decltype(AG)::value;
+        return el_cluster_fwd<decltype(SAVE)::value, decltype(NG)::value, A, decltype(XH)::value && !A>;
+    }); }); }); });
+}
+// el_cluster_adj<NG, AG, XH>: as above
+using EaKernel = void (*)(EaParams);
+EaKernel el_cluster_adj_variant(int ng, bool agent, bool xh)
+{
+    return with_int<1, 2>(ng, [&](auto NG) {
+    return with_bool(agent, [&](auto AG) {
+    return with_bool(xh, [&](auto XH) -> EaKernel {
+        constexpr bool A = decltype(AG)::value;
+        return el_cluster_adj<decltype(NG)::value, A, decltype(XH)::value && !A>;
+    }); }); });
+}
+
+void launch_v(const mifwi_elastic_plan *pl, ElKernel kernel, const ElParams &p, int nshot, hipStream_t st)
 {
     const int lz = kThreads / pl->lx;
     dim3 grid(mifwi::ceil_div(pl->ng, pl->lx), mifwi::ceil_div(pl->d.nz, lz), nshot);
-    dim3 block(kThreads);
-    switch (pl->lx) {
-        case 64: hipLaunchKernelGGL((el_step_v<64, 1, SAVE>), grid, block, 0, st, p); break;
-        case 32: hipLaunchKernelGGL((el_step_v<32, 1, SAVE>), grid, block, 0, st, p); break;
-        default: hipLaunchKernelGGL((el_step_v<16, 1, SAVE>), grid, block, 0, st, p); break;
-    }
+    hipLaunchKernelGGL(kernel, grid, dim3(kThreads), 0, st, p);
 }
 
-template <int SAVE>
-void launch_s(const mifwi_elastic_plan *pl, const ElParams &p0, int nshot, hipStream_t st)
+void launch_s(const mifwi_elastic_plan *pl, ElKernel kernel, const ElParams &p0, int nshot, hipStream_t st)
 {
     const int lz = kThreads / pl->lx;
     const int tiles_x = mifwi::ceil_div(pl->ng, pl->lx);
@@ -1250,12 +1261,8 @@ void launch_s(const mifwi_elastic_plan *pl, const ElParams &p0, int nshot, hipSt
     int extra = 0;
     if (p.smp_out0 != nullptr && p.nsmp > 0)
         extra = mifwi::ceil_div(mifwi::ceil_div(p.gs * p.nsmp, kThreads), tiles_x);
-    dim3 grid(tiles_x, p.tiles_z + extra, mifwi::ceil_div(nshot, p.gs)), block(kThreads);
-    switch (pl->lx) {
-        case 64: hipLaunchKernelGGL((el_step_s<64, 1, SAVE>), grid, block, 0, st, p); break;
-        case 32: hipLaunchKernelGGL((el_step_s<32, 1, SAVE>), grid, block, 0, st, p); break;
-        default: hipLaunchKernelGGL((el_step_s<16, 1, SAVE>), grid, block, 0, st, p); break;
-    }
+    dim3 grid(tiles_x, p.tiles_z + extra, mifwi::ceil_div(nshot, p.gs));
+    hipLaunchKernelGGL(kernel, grid, dim3(kThreads), 0, st, p);
 }
 
 // Slab count (both loops): cost of a step ~ fixed part (barriers, two hand-off flights) + groups per
@@ -1297,7 +1304,7 @@ int ea_zrows_max(const mifwi_elastic_plan *pl, int nw)
     int zmax = 0;
     for (int w = 0; w < nw && pl->W > 0; ++w) {
         int r0, R;
-        ec_slab_rows(pl->d.nz, nw, w, r0, R);
+        slab_rows(pl->d.nz, nw, 0, w, r0, R);
         const int ntop = std::max(0, std::min(r0 + R, pl->W) - r0);
         const int nbot = std::max(0, r0 + R - std::max(r0, pl->d.nz - pl->W));
         zmax = std::max(zmax, ntop + nbot);
@@ -1345,24 +1352,17 @@ void el_cluster_setup(mifwi_elastic_plan *pl)
         if (env_int("MIFWI_EL_XHALO", 1) == 0) return 0;
         for (int w = 0; w < nw; ++w) {
             int r0, R;
-            ec_slab_rows(pl->d.nz, nw, w, r0, R);
+            slab_rows(pl->d.nz, nw, 0, w, r0, R);
             if (!ec_xhalo_deal_ok(R, pl->ng, ngq * kEcThreads)) return 0;
         }
         return 1;
     };
     pl->cl_xh = pl->cluster ? xhalo_ok(pl->NW, pl->cl_ng) : 0;
-    if (pl->cluster) {
-        for (const void *fn : {(const void *)el_cluster_fwd<false, 1, false>, (const void *)el_cluster_fwd<true, 1, false>,
-                               (const void *)el_cluster_fwd<false, 2, false>, (const void *)el_cluster_fwd<true, 2, false>,
-                               (const void *)el_cluster_fwd<false, 1, true>, (const void *)el_cluster_fwd<true, 1, true>,
-                               (const void *)el_cluster_fwd<false, 2, true>, (const void *)el_cluster_fwd<true, 2, true>,
-                               (const void *)el_cluster_fwd<false, 1, false, true>, (const void *)el_cluster_fwd<true, 1, false, true>,
-                               (const void *)el_cluster_fwd<false, 2, false, true>, (const void *)el_cluster_fwd<true, 2, false, true>})
-            if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, mifwi::kClusterLdsLimit) != hipSuccess) {
-                (void)hipGetLastError();       // not sticky: fall back to one launch per half step
-                pl->cluster = 0;
-            }
-    }
+    // (a failed attribute call: one launch per half step)
+    static std::atomic<unsigned> fwd_attr_done{0}, adj_attr_done{0};
+    if (pl->cluster && !mifwi::lds_cap_once(fwd_attr_done, pl->device, mifwi::kClusterLdsLimit, 16, [](int v) {
+            return el_cluster_fwd_variant(v & 8, 1 + (v >> 2 & 1), v & 2, v & 1); }))
+        pl->cluster = 0;
     // adjoint: four E/D planes + the adjoint memory variables of the slab's C-PML cells in LDS; the
     // gradient accumulators are per shot, so it needs shot groups of one (not used when the caller
     // asked for a group size)
@@ -1378,14 +1378,9 @@ void el_cluster_setup(mifwi_elastic_plan *pl)
             pl->adj_ng = a.ng; pl->adj_zrows = ea_zrows_max(pl, a.NW);
         }
         pl->adj_xh = pl->cl_adj ? xhalo_ok(pl->adj_NW, pl->adj_ng) : 0;
-        if (pl->cl_adj)
-            for (const void *fn : {(const void *)el_cluster_adj<1, false>, (const void *)el_cluster_adj<2, false>,
-                                   (const void *)el_cluster_adj<1, true>, (const void *)el_cluster_adj<2, true>,
-                                   (const void *)el_cluster_adj<1, false, true>, (const void *)el_cluster_adj<2, false, true>})
-                if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, kEaLdsLimit) != hipSuccess) {
-                    (void)hipGetLastError();
-                    pl->cl_adj = 0;
-                }
+        if (pl->cl_adj && !mifwi::lds_cap_once(adj_attr_done, pl->device, kEaLdsLimit, 8, [](int v) {
+                return el_cluster_adj_variant(1 + (v >> 2 & 1), v & 2, v & 1); }))
+            pl->cl_adj = 0;
     }
     const int nwmax = std::max(pl->cluster ? pl->NW : 0, pl->cl_adj ? pl->adj_NW : 0);
     // granules, the XCC_ID table of mifwi::same_xcd ([nshot][nwmax] ints) and the block of the error word
@@ -1445,39 +1440,15 @@ Params cluster_base(const mifwi_elastic_plan *pl, int NW, int PL, const float *m
 }
 
 // the kernels of one single-launch attempt over the shot batches (AG / agent: granules published at agent scope)
-template <bool SAVE, bool AG>
-void el_cluster_launch(const mifwi_elastic_plan *pl, EcParams c, hipStream_t st)
+// (EcParams and an el_cluster_fwd, or EaParams and an el_cluster_adj; NW, shots, lds: that loop's slab count, batch, LDS)
+template <class Params>
+void el_cluster_launch(const mifwi_elastic_plan *pl, void (*kernel)(Params), int NW, int shots, int lds, Params c, hipStream_t st)
 {
-    for (int s0 = 0; s0 < pl->d.nshot; s0 += pl->cl_shots) {
+    for (int s0 = 0; s0 < pl->d.nshot; s0 += shots) {
         c.shot0 = s0;
-        c.shot1 = std::min(pl->d.nshot, s0 + pl->cl_shots);
+        c.shot1 = std::min(pl->d.nshot, s0 + shots);
         const int nsl8 = mifwi::ceil_div(c.shot1 - s0, 8);
-        const dim3 grid(8 * pl->NW * nsl8), block(kEcThreads);
-        if constexpr (!AG) {                 // (the agent-scope tier keeps the plain reads: one variant less to build)
-            if (pl->cl_xh) {
-                if (pl->cl_ng == 1) hipLaunchKernelGGL((el_cluster_fwd<SAVE, 1, false, true>), grid, block, pl->cl_lds, st, c);
-                else hipLaunchKernelGGL((el_cluster_fwd<SAVE, 2, false, true>), grid, block, pl->cl_lds, st, c);
-                continue;
-            }
-        }
-        if (pl->cl_ng == 1) hipLaunchKernelGGL((el_cluster_fwd<SAVE, 1, AG>), grid, block, pl->cl_lds, st, c);
-        else hipLaunchKernelGGL((el_cluster_fwd<SAVE, 2, AG>), grid, block, pl->cl_lds, st, c);
-    }
-}
-void ea_cluster_launch(const mifwi_elastic_plan *pl, EaParams c, bool agent, hipStream_t st)
-{
-    for (int s0 = 0; s0 < pl->d.nshot; s0 += pl->adj_shots) {
-        c.shot0 = s0;
-        c.shot1 = std::min(pl->d.nshot, s0 + pl->adj_shots);
-        const dim3 grid(8 * pl->adj_NW * mifwi::ceil_div(c.shot1 - s0, 8)), block(kEcThreads);
-        if (!agent && pl->adj_xh) {
-            if (pl->adj_ng == 1) hipLaunchKernelGGL((el_cluster_adj<1, false, true>), grid, block, pl->adj_lds, st, c);
-            else hipLaunchKernelGGL((el_cluster_adj<2, false, true>), grid, block, pl->adj_lds, st, c);
-        }
-        else if (pl->adj_ng == 1 && !agent) hipLaunchKernelGGL((el_cluster_adj<1, false>), grid, block, pl->adj_lds, st, c);
-        else if (pl->adj_ng == 1) hipLaunchKernelGGL((el_cluster_adj<1, true>), grid, block, pl->adj_lds, st, c);
-        else if (!agent) hipLaunchKernelGGL((el_cluster_adj<2, false>), grid, block, pl->adj_lds, st, c);
-        else hipLaunchKernelGGL((el_cluster_adj<2, true>), grid, block, pl->adj_lds, st, c);
+        hipLaunchKernelGGL(kernel, dim3(8 * NW * nsl8), dim3(kEcThreads), lds, st, c);
     }
 }
 
@@ -1492,8 +1463,9 @@ void el_two_launch_steps(const mifwi_elastic_plan *pl, ElParams p, int save, con
     const mifwi_elastic_desc &d = pl->d;
     const long long snap_step = pl->snap_shot * d.nshot;
     const bool want_rec = rec_vx != nullptr;
+    const ElStepKernels step = el_step_variant(pl->lx, save);
     ElParams ps = p;
-    const bool force = d.source_type != 0;       // point force: injected into vx / vz by a launch of its own
+    const bool force = d.source_type != 0;      // point force: injected into vx / vz by a launch of its own
     ps.ninj = (force || !f) ? 0 : d.nsrc; ps.ntap_inj = d.ntap; ps.inj_cell = src_cell; ps.inj_w = src_w;
     ps.inj_bbox = bbox;
     ElParams pf = p;
@@ -1510,19 +1482,13 @@ void el_two_launch_steps(const mifwi_elastic_plan *pl, ElParams p, int save, con
             ps.inj_amp0 = f ? f + (long long)n * d.nshot * d.nsrc : nullptr;
             ps.smp_out0 = want_rec ? rec_vx + (long long)n * d.nshot * d.nrec : nullptr;
             ps.smp_out1 = want_rec ? rec_vz + (long long)n * d.nshot * d.nrec : nullptr;
-            if (save == kBorn) launch_v<kBorn>(pl, p, cs, st);
-            else if (save == 2) launch_v<2>(pl, p, cs, st);
-            else if (save == 1) launch_v<1>(pl, p, cs, st);
-            else launch_v<0>(pl, p, cs, st);
+            launch_v(pl, step.v, p, cs, st);
             if (force && d.nsrc > 0 && f) {
                 pf.s0 = s0; pf.gs = cs; pf.inj_amp0 = ps.inj_amp0;
                 hipLaunchKernelGGL(el_inject_force, dim3(mifwi::ceil_div(cs, 64)), dim3(64), 0, st, pf,
                                    d.source_type);
             }
-            if (save == kBorn) launch_s<kBorn>(pl, ps, cs, st);
-            else if (save == 2) launch_s<2>(pl, ps, cs, st);
-            else if (save == 1) launch_s<1>(pl, ps, cs, st);
-            else launch_s<0>(pl, ps, cs, st);
+            launch_s(pl, step.s, ps, cs, st);
             if (pl->rec_p && want_rec) {
                 ElParams pq = ps;
                 pq.s0 = s0; pq.gs = cs; pq.smp_out0 = pl->rec_p + (long long)n * d.nshot * d.nrec;
@@ -1590,11 +1556,7 @@ int mifwi_elastic_plan_create(mifwi_elastic_plan **plan, int device, const mifwi
     pl->psiz_shot = 4LL * 2 * pl->W * pl->gp;
     pl->psix_elems = pl->psix_shot * d->nshot;
     pl->psiz_elems = pl->psiz_shot * d->nshot;
-    pl->lx = 16;
-    for (int cand : {64, 32}) {
-        const int padded = mifwi::ceil_div(pl->ng, cand) * cand;
-        if (padded * 10 <= pl->ng * 12) { pl->lx = cand; break; }
-    }
+    pl->lx = mifwi::pick_lx(pl->ng);
     { const int v = env_int("MIFWI_EL_LX", 0); if (v == 16 || v == 32 || v == 64) pl->lx = v; }
     pl->rz = 1;
     // 3: tile-major, shots of the launch back to back through every tile (xcd_tile); 1: every XCD walks one contiguous run of
@@ -1629,11 +1591,9 @@ int mifwi_elastic_plan_create(mifwi_elastic_plan **plan, int device, const mifwi
         const double mats = 4.0 * 5.0 * cells;
         const double psi1 = 4.0 * (double)(pl->psix_elems + pl->psiz_elems) / d->nshot;
         const double fstate = 4.0 * (double)pl->shot_stride + psi1;
-        int ps = d->nshot;
         // forward a little below the adjoint's bound: 1000x3000 runs 0.61 ms with 3 shots (240 MB) and 0.62 ms with 2
         // (180 MB), but a set that close to the cache size fell back to the all-shots time on some boxes (acoustic plan)
-        if (d->nshot * fstate + mats > kResident) ps = (int)std::max(1.0, std::floor((230e6 - mats) / fstate));
-        ps = env_int("MIFWI_EL_PASS_SHOTS", ps);
+        const int ps = env_int("MIFWI_EL_PASS_SHOTS", mifwi::units_per_pass(d->nshot, fstate, mats, kResident, 230e6, 1));
         pl->pass_shots = std::min(d->nshot, std::max(1, ps));
         // adjoint: groups of gs shots share one accumulator set; when the groups do not all fit, smaller groups
         // (more accumulator traffic, 40/gs B per cell-step) can still pay: 1000x3000, gs 2, one group per pass
@@ -1648,13 +1608,9 @@ int mifwi_elastic_plan_create(mifwi_elastic_plan **plan, int device, const mifwi
                 pl->ngroups = mifwi::ceil_div(d->nshot, g);
             }
         }
-        const double group = pl->gs * astate + accg;
-        int k = pl->ngroups;
-        if (pl->ngroups * group + mats > kResident) {
-            k = (int)std::floor((kResident - mats) / group);
-            if (k < 1) k = pl->ngroups;                 // nothing fits: one pass over all groups
-        }
-        k = env_int("MIFWI_EL_PASS_GROUPS", k);
+        // (nothing fits: one pass over all groups)
+        const int k = env_int("MIFWI_EL_PASS_GROUPS", mifwi::units_per_pass(pl->ngroups, pl->gs * astate + accg, mats, kResident,
+                                                                             kResident, pl->ngroups));
         pl->pass_groups = std::min(pl->ngroups, std::max(1, k));
     }
     // V+S in one launch pays where the time loop has to be cut into Infinity-Cache-sized passes anyway (measured,
@@ -1666,9 +1622,8 @@ int mifwi_elastic_plan_create(mifwi_elastic_plan **plan, int device, const mifwi
     {
         const double cells = (double)pl->coef_elems, mats = 4.0 * 5.0 * cells;
         const double fstate = 4.0 * (double)pl->shot_stride + 4.0 * (double)(pl->psix_elems + pl->psiz_elems) / d->nshot;
-        int ps = d->nshot;
-        if (d->nshot * 2.0 * fstate + mats > 250e6) ps = (int)std::max(1.0, std::floor((230e6 - mats) / (2.0 * fstate)));
-        ps = env_int("MIFWI_EL_FUSED_PASS_SHOTS", ps);
+        // (both copies of a shot's state; the bounds of pass_shots)
+        const int ps = env_int("MIFWI_EL_FUSED_PASS_SHOTS", mifwi::units_per_pass(d->nshot, 2.0 * fstate, mats, 250e6, 230e6, 1));
         pl->fused_pass_shots = std::min(d->nshot, std::max(1, ps));
     }
     if (pl->cl_adj) {                    // the adjoint cluster kernel keeps one accumulator set per shot
@@ -1736,23 +1691,18 @@ int mifwi_elastic_forward(mifwi_elastic_plan *pl, const float *mat, const float 
 {
     if (!pl || !mat || !pz || !px || !work) return mifwi::fail(MIFWI_EINVAL, "null argument");
     const mifwi_elastic_desc &d = pl->d;
-    if (n_begin < 0 || n_end > d.nt || n_begin > n_end)
-        return mifwi::fail(MIFWI_EINVAL, "bad step range [%d,%d) for nt=%d", n_begin, n_end, d.nt);
+    int rc = mifwi::check_steps(n_begin, n_end, d.nt);
+    if (rc) return rc;
     if (d.nsrc > 0 && (!f || !src_cell || !src_w))
         return mifwi::fail(MIFWI_EINVAL, "sources declared but f/src_cell/src_w is null");
     if ((rec_vx || rec_vz) && (!rec_cell || !rec_w || !rec_vx || !rec_vz))
         return mifwi::fail(MIFWI_EINVAL, "receiver output needs rec_cell, rec_w, rec_vx and rec_vz");
-    int rc = mifwi::check_device(pl->device);
-    if (rc) return rc;
-    MIFWI_HIP_TRY(hipSetDevice(pl->device));
-    hipStream_t st = (hipStream_t)stream;
     const ElWork m = work_map(pl, false);                 // the state is updated in place
+    hipStream_t st;
+    if ((rc = mifwi::open_call(pl->device, stream, work, m, flags, &st))) return rc;
     float *fields = work + m.fields, *psi_state = work + m.psi;
     int *bbox = reinterpret_cast<int *>(work + m.bbox);
-    if (flags & MIFWI_ZERO_STATE) MIFWI_HIP_TRY(hipMemsetAsync(work, 0, sizeof(float) * m.state, st));
-    if (d.nsrc > 0)
-        hipLaunchKernelGGL(el_points_bbox, dim3(d.nshot), dim3(kThreads), 0, st, src_cell,
-                           d.nsrc * d.ntap, d.nx, bbox);
+    if (d.nsrc > 0) launch_points_bbox(src_cell, d.nshot, d.nsrc * d.ntap, d.nx, bbox, st);
     ElParams p = el_base(pl, mat, pz, px);
     const long long snap_step = pl->snap_shot * d.nshot;
     const int save = !snap ? 0 : pl->snap_bf16 ? 2 : 1;
@@ -1770,10 +1720,8 @@ int mifwi_elastic_forward(mifwi_elastic_plan *pl, const float *mat, const float 
         rc = mifwi::cluster_ladder("elastic forward", work, m.state, work + m.backup, flags, st, h, ts,
                                    [&](bool agent, long long *trace) {
             mifwi::set_trace(c, trace);
-            if (snap && agent) el_cluster_launch<true, true>(pl, c, st);
-            else if (snap) el_cluster_launch<true, false>(pl, c, st);
-            else if (agent) el_cluster_launch<false, true>(pl, c, st);
-            else el_cluster_launch<false, false>(pl, c, st);
+            el_cluster_launch(pl, el_cluster_fwd_variant(snap != nullptr, pl->cl_ng, agent, pl->cl_xh), pl->NW, pl->cl_shots,
+                              pl->cl_lds, c, st);
         });
         if (rc != mifwi::kClusterFellBack) return rc;
     }
@@ -1788,6 +1736,7 @@ int mifwi_elastic_forward(mifwi_elastic_plan *pl, const float *mat, const float 
         q.nsmp = want_rec ? d.nrec : 0; q.ntap_smp = d.ntap; q.smp_cell = rec_cell; q.smp_w = rec_w;
         const int tx = mifwi::ceil_div(pl->ng, FTG), tz = mifwi::ceil_div(d.nz, FTZ);
         const int ex = want_rec ? mifwi::ceil_div(mifwi::ceil_div(d.nrec, kThreads), tx) : 0;
+        const ElKernel fused = el_fwd_fused_variant(save);
         for (int s0 = 0; s0 < d.nshot; s0 += pl->fused_pass_shots) {
             const int cs = std::min(pl->fused_pass_shots, d.nshot - s0);
             q.s0 = s0;
@@ -1804,9 +1753,7 @@ int mifwi_elastic_forward(mifwi_elastic_plan *pl, const float *mat, const float 
                 q.smp_out0 = smp ? rec_vx + (long long)(n - 1) * d.nshot * d.nrec : nullptr;
                 q.smp_out1 = smp ? rec_vz + (long long)(n - 1) * d.nshot * d.nrec : nullptr;
                 const dim3 grid(tx, tz + (smp ? ex : 0), cs);
-                if (save == 2) hipLaunchKernelGGL(el_fwd_fused<2>, grid, dim3(kThreads), 0, st, q);
-                else if (save == 1) hipLaunchKernelGGL(el_fwd_fused<1>, grid, dim3(kThreads), 0, st, q);
-                else hipLaunchKernelGGL(el_fwd_fused<0>, grid, dim3(kThreads), 0, st, q);
+                hipLaunchKernelGGL(fused, grid, dim3(kThreads), 0, st, q);
             }
             float *last = ((n_end - n_begin) & 1) ? B : work;
             if (want_rec) {
@@ -1847,10 +1794,9 @@ int mifwi_elastic_born(mifwi_elastic_plan *pl, const float *mat, const float *dm
     if (!pl || !mat || !pz || !px) return mifwi::fail(MIFWI_EINVAL, "null argument");
     if (!dmat || !snap || !work) return mifwi::fail(MIFWI_EINVAL, "born: dmat, snap and work must not be null");
     const mifwi_elastic_desc &d = pl->d;
-    if (n_begin < 0 || n_end > d.nt || n_begin > n_end)
-        return mifwi::fail(MIFWI_EINVAL, "bad step range [%d,%d) for nt=%d", n_begin, n_end, d.nt);
-    if (snap_first > n_begin)
-        return mifwi::fail(MIFWI_EINVAL, "snapshots start at step %d but step %d is needed", snap_first, n_begin);
+    int rc = mifwi::check_steps(n_begin, n_end, d.nt);
+    if (!rc) rc = mifwi::check_snapshots(snap_first, n_begin);
+    if (rc) return rc;
     if (pl->snap_bf16)
         return mifwi::fail(MIFWI_EINVAL, "born: the plan keeps bf16 snapshot planes; the Born step reads f32 planes");
     if (d.source_type != 0)
@@ -1860,16 +1806,12 @@ int mifwi_elastic_born(mifwi_elastic_plan *pl, const float *mat, const float *dm
         return mifwi::fail(MIFWI_EINVAL, "df given but src_cell/src_w is null");
     if ((drec_vx || drec_vz) && (!rec_cell || !rec_w || !drec_vx || !drec_vz))
         return mifwi::fail(MIFWI_EINVAL, "receiver output needs rec_cell, rec_w, drec_vx and drec_vz");
-    int rc = mifwi::check_device(pl->device);
-    if (rc) return rc;
-    MIFWI_HIP_TRY(hipSetDevice(pl->device));
-    hipStream_t st = (hipStream_t)stream;
     const ElWork m = work_map(pl, false);                 // the perturbed state: the forward's map of `work`
+    hipStream_t st;
+    if ((rc = mifwi::open_call(pl->device, stream, work, m, flags, &st))) return rc;
     int *bbox = reinterpret_cast<int *>(work + m.bbox);
-    if (flags & MIFWI_ZERO_STATE) MIFWI_HIP_TRY(hipMemsetAsync(work, 0, sizeof(float) * m.state, st));
     const bool inject = df != nullptr && d.nsrc > 0;
-    if (inject)
-        hipLaunchKernelGGL(el_points_bbox, dim3(d.nshot), dim3(kThreads), 0, st, src_cell, d.nsrc * d.ntap, d.nx, bbox);
+    if (inject) launch_points_bbox(src_cell, d.nshot, d.nsrc * d.ntap, d.nx, bbox, st);
     ElParams p = el_base(pl, mat, pz, px);
     p.dmat = dmat;
     p.fields = work + m.fields; p.psix = work + m.psi; p.psiz = work + m.psi + pl->psix_elems;
@@ -1891,22 +1833,17 @@ int mifwi_elastic_backward(mifwi_elastic_plan *pl, const float *mat, const float
     if (!pl || !mat || !pz || !px || !work || !snap || !g_vx || !g_vz || !rec_cell || !rec_w)
         return mifwi::fail(MIFWI_EINVAL, "null argument");
     const mifwi_elastic_desc &d = pl->d;
-    if (n_lo < 0 || n_hi > d.nt - 1 || n_lo > n_hi + 1)
-        return mifwi::fail(MIFWI_EINVAL, "bad adjoint range n=%d..%d for nt=%d", n_hi, n_lo, d.nt);
-    if (snap_first > n_lo)
-        return mifwi::fail(MIFWI_EINVAL, "snapshots start at step %d but step %d is needed",
-                           snap_first, n_lo);
+    int rc = mifwi::check_adjoint_steps('n', 0, n_hi, n_lo, d.nt);
+    if (!rc) rc = mifwi::check_snapshots(snap_first, n_lo);
+    if (rc) return rc;
     if (grad_f && (!src_cell || !src_w))
         return mifwi::fail(MIFWI_EINVAL, "grad_f requested but src_cell/src_w is null");
     if ((flags & MIFWI_FINALIZE) && !grad_mat)
         return mifwi::fail(MIFWI_EINVAL, "finalize requested but grad_mat is null");
-    int rc = mifwi::check_device(pl->device);
-    if (rc) return rc;
-    MIFWI_HIP_TRY(hipSetDevice(pl->device));
-    hipStream_t st = (hipStream_t)stream;
     const ElWork m = work_map(pl, true);
+    hipStream_t st;
+    if ((rc = mifwi::open_call(pl->device, stream, work, m, flags, &st))) return rc;
     float *fields = work + m.fields, *psiA = work + m.psi, *psiB = work + m.psiB, *acc = work + m.acc;
-    if (flags & MIFWI_ZERO_STATE) MIFWI_HIP_TRY(hipMemsetAsync(work, 0, sizeof(float) * m.state, st));
     ElParams p = el_base(pl, mat, pz, px);
     p.fields = fields;
     p.acc = acc;
@@ -1931,8 +1868,7 @@ int mifwi_elastic_backward(mifwi_elastic_plan *pl, const float *mat, const float
     if (pl->cl_adj && n_hi >= n_lo) {
         const mifwi::Handoff h = mifwi::cluster_handoff(pl, work, m);
         int *lists = reinterpret_cast<int *>(work + m.lists);
-        hipLaunchKernelGGL(ec_build_slab_lists, dim3(d.nshot), dim3(256), 0, st, rec_cell, d.nrec, d.nz, d.nx,
-                           pl->adj_NW, lists, lists + (long long)d.nshot * pl->adj_NW);
+        launch_build_slab_lists(rec_cell, d.nshot, d.nrec, d.nz, d.nx, pl->adj_NW, 0, lists, st);
         EaParams c = cluster_base<EaParams>(pl, pl->adj_NW, pl->adj_PL, mat, pz, px, h);
         c.n_first = n_hi; c.n_last = n_lo; c.nt = d.nt;
         c.zrows_max = pl->adj_zrows;
@@ -1949,7 +1885,7 @@ int mifwi_elastic_backward(mifwi_elastic_plan *pl, const float *mat, const float
         rc = mifwi::cluster_ladder("elastic adjoint", work, m.state, work + m.backup, flags, st, h, ts,
                                    [&](bool agent, long long *trace) {
             mifwi::set_trace(c, trace);
-            ea_cluster_launch(pl, c, agent, st);
+            el_cluster_launch(pl, el_cluster_adj_variant(pl->adj_ng, agent, pl->adj_xh), pl->adj_NW, pl->adj_shots, pl->adj_lds, c, st);
         });
         if (rc != MIFWI_OK && rc != mifwi::kClusterFellBack) return rc;
         per_step = rc == mifwi::kClusterFellBack;

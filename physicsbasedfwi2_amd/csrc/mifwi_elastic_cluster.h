@@ -71,13 +71,6 @@ struct EcParams {
 #define EC_LAGGARD() do { } while (0)
 #endif
 
-__host__ __device__ __forceinline__ void ec_slab_rows(int nz, int NW, int w, int &r0, int &rows)
-{
-    const int base = nz / NW, rem = nz - base * NW;
-    rows = base + (w < rem ? 1 : 0);
-    r0 = w * base + (w < rem ? w : rem);
-}
-
 // One exchange slot = kEcRowFields rows of gp granules.  A z-stencil reads the backward-differenced
 // field (vz, sxz; adjoint E3, D4: "A") on rows j-2..j+1 and the forward-differenced one (vx, szz;
 // adjoint E2, D2: "B") on rows j-1..j+2, so a slab needs A on 2 rows above / 1 below and B on 1 row
@@ -691,7 +684,7 @@ __global__ __launch_bounds__(kEcThreads) void el_cluster_fwd(const EcParams p)
     const int t = (int)threadIdx.x;
     if (!AG && !mifwi::same_xcd(p.xcc_tab, s, p.NW, w, t, p.err, kEcMaxSpin, kDbg(p) & 128)) return;
     int r0, R;
-    ec_slab_rows(p.nz, p.NW, w, r0, R);
+    slab_rows(p.nz, p.NW, 0, w, r0, R);
     const int PL = p.PL, LR = R + 4;
     const int fsz = LR * PL;
     EcCtx c;
@@ -1050,27 +1043,6 @@ struct EaParams {
 #endif
 };
 
-// receivers of each slab (adjoint sources), one block per shot
-__global__ void ec_build_slab_lists(const int *rec_cell, int nrec, int nz, int nx, int NW, int *slab_cnt,
-                                    int *slab_list)
-{
-    const int s = blockIdx.x;
-    __shared__ int cnt[64];
-    if ((int)threadIdx.x < NW) cnt[threadIdx.x] = 0;
-    __syncthreads();
-    const int base = nz / NW, rem = nz - base * NW;
-    for (int e = threadIdx.x; e < nrec; e += blockDim.x) {
-        const int cell = rec_cell[(long long)s * nrec + e];
-        if (cell < 0) continue;
-        const int i0 = cell / nx;
-        const int w = (i0 < rem * (base + 1)) ? i0 / (base + 1) : rem + (i0 - rem * (base + 1)) / base;
-        const int pos = atomicAdd(&cnt[w], 1);
-        slab_list[((long long)s * NW + w) * nrec + pos] = e;
-    }
-    __syncthreads();
-    if ((int)threadIdx.x < NW) slab_cnt[s * NW + threadIdx.x] = cnt[threadIdx.x];
-}
-
 // Where the snapshot planes of the coming phase C are requested (80 KB per workgroup and step, from HBM): slot 0 right
 // after the poll of the previous step's phase D (0), the other slots at the head of the B boundary update (2) - half
 // the burst at either point.  All of it after the poll, as in round 1, kept the wave's memory queue busy for 3800 clocks
@@ -1121,7 +1093,7 @@ __global__ __launch_bounds__(kEcThreads) void el_cluster_adj(const EaParams p)
     const int t = (int)threadIdx.x;
     if (!AG && !mifwi::same_xcd(p.xcc_tab, s, p.NW, w, t, p.err, kEcMaxSpin, kDbg(p) & 128)) return;
     int r0, R;
-    ec_slab_rows(p.nz, p.NW, w, r0, R);
+    slab_rows(p.nz, p.NW, 0, w, r0, R);
     const int PL = p.PL, LR = R + 4;
     const int fsz = LR * PL;
     // 4 planes [LR][PL]: E1 E2 E3 E4 in the S^T half, D1 D2 D4 D3 in the V^T half - in both the plane a

@@ -100,17 +100,10 @@ int mifwi_elastic_snapshot_moments(mifwi_elastic_plan *pl, const float *snap, in
 {
     if (!pl || !snap || !moments || !work) return mifwi::fail(MIFWI_EINVAL, "null argument");
     const mifwi_elastic_desc &d = pl->d;
-    if (stride < 1) return mifwi::fail(MIFWI_EINVAL, "stride %d: must be >= 1", stride);
-    if (n_begin < 0 || n_end > d.nt || n_begin >= n_end)
-        return mifwi::fail(MIFWI_EINVAL, "bad step range [%d,%d) for nt=%d", n_begin, n_end, d.nt);
-    if (snap_first < 0 || snap_first > n_begin)
-        return mifwi::fail(MIFWI_EINVAL, "snap_first %d lies behind the range [%d,%d)", snap_first, n_begin, n_end);
-    if (((uintptr_t)snap | (uintptr_t)moments | (uintptr_t)work) & 15)
-        return mifwi::fail(MIFWI_EINVAL, "snap, moments and work must be 16-byte aligned");
-    int rc = mifwi::check_device(pl->device);
+    int rc = moments_check(d.nt, snap, moments, work, snap_first, n_begin, n_end, stride);
     if (rc) return rc;
-    MIFWI_HIP_TRY(hipSetDevice(pl->device));
-    hipStream_t st = (hipStream_t)stream;
+    hipStream_t st;
+    if ((rc = mifwi::select_device(pl->device, stream, &st))) return rc;
     // selected steps: the multiples of stride inside the range (absolute n, so a run cut into ranges anywhere selects
     // the same steps as the whole run)
     const long long first = ((long long)n_begin + stride - 1) / stride * stride;

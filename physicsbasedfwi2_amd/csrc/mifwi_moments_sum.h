@@ -1,8 +1,23 @@
-// Second launch of the snapshot-moments passes (mifwi_elastic_moments.h, mifwi_acoustic_moments.h): the partial planes
-// the first launch left in `work` are added in index order - a fixed order, no atomics.
+// What the two snapshot-moments passes share (mifwi_elastic_moments.h, mifwi_acoustic_moments.h): the argument checks of
+// their entry points, and their second launch - the partial planes the first launch left in `work` are added in index
+// order, a fixed order, no atomics.
 #pragma once
 
 namespace {
+
+// the argument checks both snapshot-moments entry points open with (behind their null checks)
+inline int moments_check(int nt, const void *snap, const void *moments, const void *work, int snap_first, int n_begin,
+                         int n_end, int stride)
+{
+    if (stride < 1) return mifwi::fail(MIFWI_EINVAL, "stride %d: must be >= 1", stride);
+    if (n_begin < 0 || n_end > nt || n_begin >= n_end)
+        return mifwi::fail(MIFWI_EINVAL, "bad step range [%d,%d) for nt=%d", n_begin, n_end, nt);
+    if (snap_first < 0 || snap_first > n_begin)
+        return mifwi::fail(MIFWI_EINVAL, "snap_first %d lies behind the range [%d,%d)", snap_first, n_begin, n_end);
+    if (((uintptr_t)snap | (uintptr_t)moments | (uintptr_t)work) & 15)
+        return mifwi::fail(MIFWI_EINVAL, "snap, moments and work must be 16-byte aligned");
+    return MIFWI_OK;
+}
 
 constexpr int kMomSumThreads = 256;
 

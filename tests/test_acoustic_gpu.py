@@ -514,6 +514,109 @@ def test_cpml_single_launch_and_per_step_families_agree(oracle32, monkeypatch):
     assert rel_l2(r2.grad.cpu().numpy(), outs[1][1].cpu().numpy()) <= 2e-5
 
 
+@pytest.mark.parametrize("kind,nsrc,nrec,w,nw", [
+    ("sources", 2, 7, 0, 2),            # two sources per shot: forward loops rescan (ac_cluster<0 | 1, SLOW>)
+    ("receivers", 1, 1100, 0, 2),       # more receivers than threads: forward + snapshots, adjoint and Born loops rescan
+    ("cpml sources", 2, 7, 6, 3),       # the same with the C-PML inside the loop (edge slabs of W + 2 rows: three slabs)
+    ("cpml receivers", 1, 1100, 6, 3),
+])
+def test_rescanning_single_launch_variants_agree_with_the_per_step_kernels(monkeypatch, kind, nsrc, nrec, w, nw):
+    """The SLOW variants of ac_cluster (a thread may own several sparse points: nsrc > 1, or more receivers than the
+    workgroup has threads) on the smallest grid that is still cut into slabs, 40x64 x 2 shots x 20 steps: forward without
+    and with snapshots, adjoint and (sponge plans) Born.  Traces are the bits of the per-step kernels, gradients agree to
+    summation order (2e-5, as everywhere in this file)."""
+    from physicsbasedfwi2_amd import acoustic
+    from physicsbasedfwi2_amd.acoustic import AcousticPlan
+    c = _cpml_case(seed=43, n0=28, n1=52, w=w, nt=20, ns=2, nsrc=nsrc, nrec=nrec) if w else \
+        acoustic_case(seed=43, n0=28, n1=52, nb=6, nt=20, ns=2, nsrc=nsrc, nrec=nrec)
+    assert c["shape"] == (40, 64)
+    # the sources of a shot in cells of their own: two that share a cell are added in an order the families need not share
+    assert all(len(set(s)) == nsrc for s in c["sc"].reshape(2, nsrc).tolist())
+    dev = torch.device("cuda:0")
+    prof = ("ab0", "ab1") if w else ("q0", "q1")
+    geo = [torch.tensor(c[k]) for k in prof + ("sc", "sw", "rc", "rw")]
+    dr = torch.tensor(c["r"] * 0.05 * np.random.default_rng(8).standard_normal(c["r"].shape), dtype=torch.float32, device=dev)
+    outs = []
+    for flag in ("1", "0"):
+        monkeypatch.setenv("MIFWI_AC_CLUSTER", flag)
+        monkeypatch.setenv("MIFWI_AC_NW", str(nw) if flag == "1" else "0")
+        if flag == "1":                                      # cannot pass by running the per-step family
+            pl = AcousticPlan(40, 64, 20, 2, nsrc, nrec, 1, c["c0"], c["c1"], 0, 0, 0, w)
+            slabs = pl.cluster_slabs(False)
+            pl.close()
+            assert slabs >= 2
+        r = torch.tensor(c["r"], dtype=torch.float32, device=dev)
+        f = torch.tensor(c["f"], dtype=torch.float32, device=dev)
+        plain = acoustic.propagate(r, f, *geo, c["c0"], c["c1"], cpml_width=w)           # no snapshots
+        r.requires_grad_(True); f.requires_grad_(True)
+        rec = acoustic.propagate(r, f, *geo, c["c0"], c["c1"], cpml_width=w)
+        rec.backward(torch.sign(rec.detach()) + 0.5)
+        out = [plain, rec.detach().clone(), r.grad.clone(), f.grad.clone()]
+        if not w:
+            out.append(acoustic.born(r.detach(), f.detach(), dr, *geo, c["c0"], c["c1"])[1])
+        outs.append(out)
+    a, b = outs
+    print(kind, "max |trace|", float(a[0].abs().max()), "single-launch vs per-step: max |diff| without snapshots",
+          float((a[0] - b[0]).abs().max()), "with", float((a[1] - b[1]).abs().max()), "without vs with",
+          float((a[0] - a[1]).abs().max()), "grad_r", rel_l2(a[2].cpu().numpy(), b[2].cpu().numpy()),
+          "grad_f", rel_l2(a[3].cpu().numpy(), b[3].cpu().numpy()))
+    assert float(a[0].abs().max()) > 0 and torch.equal(a[0], b[0]) and torch.equal(a[1], b[1]) and torch.equal(a[0], a[1])
+    assert float(b[2].abs().max()) > 0 and rel_l2(a[2].cpu().numpy(), b[2].cpu().numpy()) <= TOL_GRAD
+    assert float(b[3].abs().max()) > 0 and rel_l2(a[3].cpu().numpy(), b[3].cpu().numpy()) <= TOL_GRAD
+    if not w:
+        assert float(a[4].abs().max()) > 0 and torch.equal(a[4], b[4])
+
+
+@pytest.mark.parametrize("w", [0, 6])
+@pytest.mark.parametrize("n1,lx", [(52, 16), (116, 32), (244, 64)])
+def test_per_step_rows_per_thread_and_tile_widths_agree(monkeypatch, n1, lx, w):
+    """Every ac_step instantiation the per-step launch can pick: rows per thread 1 / 4 / 8 (MIFWI_AC_RZ) against the default
+    2, on 37-row grids of 64, 128 and 256 columns, which get tiles of 16, 32 and 64 lanes per row (widest tile with at most
+    20 % padding) and cut the rows into whole and ragged tiles (256 / lx rows x rz per tile).  Forward without and with
+    snapshots, backward.  A C-PML plan (w > 0) marches two rows whatever the knob says: the same kernel, so the same bits.
+    The per-cell arithmetic does not depend on the tile, so traces are the same bits as with rz = 2 and as the default
+    family's; gradients agree to summation order (2e-5, as everywhere in this file)."""
+    from physicsbasedfwi2_amd import acoustic
+    c = _cpml_case(seed=47, n0=25, n1=n1, w=w, nt=80, ns=2, nrec=9) if w else \
+        acoustic_case(seed=47, n0=25, n1=n1, nb=6, nt=80, ns=2, nrec=9)
+    assert c["shape"] == (37, n1 + 12)
+    # sources in mid-grid and the receiver line three columns beside them, whatever the width: 80 steps then carry the
+    # wave to the receivers and the adjoint wave back to the sources (the case's own geometry is drawn over the whole width)
+    N1 = n1 + 12
+    for s in range(2):
+        c["sc"][s, 0, 0] = 18 * N1 + N1 // 2 + 7 * s
+        c["rc"][s, :, 0] = (c["rc"][s, :, 0] // N1) * N1 + N1 // 2 + 7 * s - 3
+    ng = (n1 + 12) // 4
+    assert lx == next((t for t in (64, 32) if -(-ng // t) * t * 10 <= ng * 12), 16)      # the plan's rule for this width
+    dev = torch.device("cuda:0")
+    geo = [torch.tensor(c[k]) for k in (("ab0", "ab1") if w else ("q0", "q1")) + ("sc", "sw", "rc", "rw")]
+
+    def run():
+        r = torch.tensor(c["r"], dtype=torch.float32, device=dev)
+        f = torch.tensor(c["f"], dtype=torch.float32, device=dev)
+        plain = acoustic.propagate(r, f, *geo, c["c0"], c["c1"], cpml_width=w)           # no snapshots
+        r.requires_grad_(True); f.requires_grad_(True)
+        rec = acoustic.propagate(r, f, *geo, c["c0"], c["c1"], cpml_width=w)
+        rec.backward(torch.sign(rec.detach()) + 0.5)
+        return plain, rec.detach().clone(), r.grad.clone(), f.grad.clone()
+
+    default_family = run()
+    monkeypatch.setenv("MIFWI_AC_CLUSTER", "0")
+    ref = run()
+    assert float(ref[0].abs().max()) > 0 and float(ref[2].abs().max()) > 0 and float(ref[3].abs().max()) > 0
+    assert torch.equal(ref[0], ref[1]) and torch.equal(ref[0], default_family[0])
+    for rz in ("1", "4", "8"):
+        monkeypatch.setenv("MIFWI_AC_RZ", rz)
+        got = run()
+        eg = [rel_l2(got[k].cpu().numpy(), ref[k].cpu().numpy()) for k in (2, 3)]
+        print("lx %d w %d rz %s: max |trace diff| %g %g, grad_r %.2e grad_f %.2e"
+              % (lx, w, rz, float((got[0] - ref[0]).abs().max()), float((got[1] - ref[1]).abs().max()), eg[0], eg[1]))
+        assert torch.equal(got[0], ref[0]) and torch.equal(got[1], ref[1])
+        assert max(eg) <= TOL_GRAD
+        if w:
+            assert torch.equal(got[2], ref[2]) and torch.equal(got[3], ref[3])
+
+
 def test_geometry_cache_follows_tensor_identity_and_version():
     """propagate() keeps the device-resident geometry (and the validation of its cells: a host round trip) of tap tensors it
     has seen - while the very same device tensors are passed again, unmodified.  An in-place change makes a new one (and is

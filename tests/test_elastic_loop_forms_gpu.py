@@ -49,7 +49,7 @@ def _case(cid):
     nz, nx, nw, kw = CASES[cid]
     kw = dict(dict(fw=6, ns=2, nrec=12), **kw)
     case = elastic_case(seed=311 + nz + nx, nz=nz, nx=nx, **kw)
-    b = nz // nw + (1 if nz % nw else 0)                   # first row of the second slab (ec_slab_rows)
+    b = nz // nw + (1 if nz % nw else 0)                   # first row of the second slab (slab_rows)
     sz = np.array([[b], [b - 1]])                          # a boundary row of either slab
     rx = np.linspace(1, nx - 2, kw["nrec"]).astype(int)    # first and last group of the row included
     sx = np.array([[rx[kw["nrec"] // 3] + 2], [nx - 6]])    # two and four cells from a receiver
