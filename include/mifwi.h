@@ -396,6 +396,42 @@ int mifwi_misfit_filtered(int device, int32_t kind, const float *pred, const flo
                           float *work, void *stream);
 
 /* ======================================================================================
+ * TRACE SELECTION inside the misfit kernels: trace kill, trace weights and time windows
+ *
+ * Replaces what DENISE does with TRKILL (a table of dead channels) and TIMEWIN (a window around picked times with a Gaussian
+ * taper, GAMMA) when the data are a field survey (AutoRealData, models/networks.py:10321-10540): samples leave the objective,
+ * not the arrays.  This library's documented choice (DENISE's binary is not available to pin against): the diagonal operator
+ *     w[t, tr] = a[tr] g(t; t_on[tr], t_off[tr], gamma),   d = max(t_on - t, t - t_off, 0),   g = d == 0 ? 1 : exp(-gamma d^2)
+ * with t the sample index, evaluated in double from the float inputs.
+ *   trace_w  device [ntrace] or NULL (= 1): a >= 0 and finite; 0 kills the trace
+ *   t_on, t_off  device [ntrace], both or neither (NULL = no window, g = 1): in samples, may lie outside [0, nt - 1] and
+ *            may be reversed (t_on > t_off: no sample is inside)
+ *   gamma    >= 0 per sample^2; +inf is a boxcar
+ * W is applied after the stage filter F (the identity when nsec == 0) and before the norm:
+ *   L2                  r = float(W F(pred - obs));  loss = 1/2 sum r^2;  adj_out = float(F^T W r)
+ *   GLOBAL_CORRELATION  s = float(W F pred), o = float(W F obs);  loss = - sum_traces <s, o> / (|s| |o|);
+ *                       adj_out = float(F^T W dloss/ds)  (a trace with |s| = 0 or |o| = 0 contributes nothing, adj_out 0)
+ * W selects, it does not multiply: where w == 0 exactly the sample's value is not used.  A KILLED trace (a == 0) may hold
+ * anything in pred and obs, NaN and Inf included: its loss contribution and its adj_out column are exactly 0.  Inside a
+ * live trace there is no such guarantee (a NaN stays in the state of the recursive filter).
+ *   mifwi_misfit_selected  sos (HOST) and nsec as for mifwi_misfit_filtered, or sos == NULL and nsec == 0: no stage.
+ *     pred, obs, loss_out, adj_out (NULL = loss only, the same bits) as for mifwi_misfit; no atomics, fixed summation order.
+ *     work: mifwi_misfit_selected_work_elems(kind, nt, ntrace, nsec) floats, 8-byte aligned.
+ *     trace_w, t_on and t_off all NULL: the call IS mifwi_misfit_filtered / mifwi_misfit (the same kernels, the same bits).
+ *   mifwi_trace_window     y = W x; x, y [nt][ntrace]; y == x allowed
+ * MIFWI_EINVAL: exactly one of t_on / t_off NULL, gamma negative or NaN, sos NULL with nsec != 0 or the reverse, kind
+ * L1_TRACE_NORM, and everything mifwi_misfit_filtered rejects.  The values of trace_w are the caller's to check (they are
+ * on the device; misfit.TraceSelection validates them once on the host).
+ * ==================================================================================== */
+int64_t mifwi_misfit_selected_work_elems(int32_t kind, int64_t nt, int64_t ntrace, int32_t nsec);
+int mifwi_misfit_selected(int device, int32_t kind, const float *pred, const float *obs, int64_t nt, int64_t ntrace,
+                          const double *sos /* host, NULL iff nsec == 0 */, int32_t nsec,
+                          const float *trace_w, const float *t_on, const float *t_off, double gamma,
+                          float *loss_out, float *adj_out, float *work, void *stream);
+int mifwi_trace_window(int device, const float *x, float *y, int64_t nt, int64_t ntrace,
+                       const float *trace_w, const float *t_on, const float *t_off, double gamma, void *stream);
+
+/* ======================================================================================
  * GRADIENT CONDITIONING on the device (what sits between d.get_fwi_gradients(...) and fake_Vp.backward(grad))
  *
  * Replaces the numpy / scipy post-processing of the model gradients in the elastic prop() methods:

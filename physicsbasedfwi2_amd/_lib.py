@@ -95,6 +95,10 @@ SIGNATURES = {
     "mifwi_misfit_filtered_work_elems": (ctypes.c_int64, [ctypes.c_int32, ctypes.c_int64, ctypes.c_int64]),
     "mifwi_misfit_filtered": (ctypes.c_int, [ctypes.c_int, ctypes.c_int32] + [_P] * 2 + [ctypes.c_int64] * 2 +
                               [_P, ctypes.c_int32] + [_P] * 4),
+    "mifwi_misfit_selected_work_elems": (ctypes.c_int64, [ctypes.c_int32, ctypes.c_int64, ctypes.c_int64, ctypes.c_int32]),
+    "mifwi_misfit_selected": (ctypes.c_int, [ctypes.c_int, ctypes.c_int32] + [_P] * 2 + [ctypes.c_int64] * 2 +
+                              [_P, ctypes.c_int32] + [_P] * 3 + [ctypes.c_double] + [_P] * 4),
+    "mifwi_trace_window": (ctypes.c_int, [ctypes.c_int] + [_P] * 2 + [ctypes.c_int64] * 2 + [_P] * 3 + [ctypes.c_double, _P]),
     "mifwi_gradient_condition_work_elems": (ctypes.c_int64, [ctypes.c_int32]),
     "mifwi_gradient_condition": (ctypes.c_int, [ctypes.c_int] + [_P] * 3 + [ctypes.c_int32] * 3 + [_P, ctypes.c_float] +
                                  [ctypes.c_int32] * 2 + [_P] * 3),

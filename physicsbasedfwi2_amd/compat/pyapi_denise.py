@@ -240,7 +240,7 @@ _SERVED = frozenset((
     "root", "verbose", "device", "save_folder", "PHYSICS", "TIME", "DT", "FD_ORDER", "FW", "DAMPING", "FPML", "npower",
     "k_max_PML", "FREE_SURF", "QUELLART", "QUELLTYP", "QUELLTYPB", "FC_SPIKE_1", "FC_SPIKE_2", "ORDER_SPIKE", "SEISMO",
     "ITERMAX", "DATA_DIR", "SWS_TAPER_GRAD_HOR", "EXP_TAPER_GRAD_HOR", "GRADT1", "GRADT2", "GRADT3", "GRADT4", "INVMAT1",
-    "EPRECOND", "EPSILON_WE", "fwi_stages", "loss", "DT_used"))
+    "EPRECOND", "EPSILON_WE", "TRKILL", "fwi_stages", "loss", "DT_used"))
 # DENISE parameters that cannot change what ONE gradient evaluation (ITERMAX = 1) returns: the MPI decomposition, names of
 # files this shim keeps in memory, logging, model bounds and line-search / optimiser settings that only act on model
 # updates, grid sizes that come from the Model object.  Accepted; one warning per name says so.
@@ -251,10 +251,12 @@ _INERT = frozenset((
     "SIGNAL_FILE", "GRAD_METHOD", "PCG_BETA", "NLBFGS", "EPS_SCALE", "STEPMAX", "SCALEFAC", "TESTSHOT_START", "TESTSHOT_END",
     "TESTSHOT_INCR", "PRO", "MIN_ITER", "SNAP", "SNAP_FORMAT", "SNAP_FILE", "TSNAP1", "TSNAP2", "TSNAPINC", "IDX", "IDY"))
 # parameters that DO change the result and are not built: only their neutral value is accepted
-_NEUTRAL = {"TIMEWIN": 0, "TRKILL": 0, "NORMALIZE": 0, "INV_STF": 0, "SPATFILTER": 0, "MODEL_FILTER": 0, "SWS_TAPER_GRAD_VERT": 0,
+_NEUTRAL = {"TIMEWIN": 0, "NORMALIZE": 0, "INV_STF": 0, "SPATFILTER": 0, "MODEL_FILTER": 0, "SWS_TAPER_GRAD_VERT": 0,
             "SWS_TAPER_GRAD_SOURCES": 0, "SWS_TAPER_CIRCULAR_PER_SHOT": 0, "SWS_TAPER_FILE": 0, "NDT": 1, "MAXRELERROR": 0,
             "RTMOD": 0, "GRAVITY": 0, "INVMAT": 0, "RUN_MULTIPLE_SHOTS": 1, "READREC": 0, "READMOD": 0,
             "TW_IND": 0, "GAMMA": 0, "BOUNDARY": 0}
+# what serves the purpose of a refused parameter instead
+_INSTEAD = {"TIMEWIN": "time windows are passed as arrays: d.set_time_windows(picks, before, after, gamma=...)"}
 _warned = set()
 
 
@@ -277,7 +279,8 @@ class Denise:
         if name in _NEUTRAL:
             if value != _NEUTRAL[name]:
                 raise MifwiError("%s=%r is not implemented: this parameter changes the gradient and only its neutral "
-                                 "value %r is served" % (name, value, _NEUTRAL[name]))
+                                 "value %r is served%s" % (name, value, _NEUTRAL[name],
+                                                           "; " + _INSTEAD[name] if name in _INSTEAD else ""))
             return object.__setattr__(self, name, value)
         raise AttributeError("pyapi_denise shim: unknown parameter %r (served: %s)" % (name, ", ".join(sorted(
             n for n in _SERVED if n.isupper() or n in ("npower", "k_max_PML", "fwi_stages", "save_folder")))))
@@ -326,6 +329,10 @@ class Denise:
         # water level, DENISE.inp's 0.005, one value for all three planes
         self.EPRECOND = 0
         self.EPSILON_WE = 0.005
+        # TRKILL: 1 takes the traces of the table given to set_trace_kill() out of the objective (DENISE's TRKILL_FILE)
+        self.TRKILL = 0
+        self._trace_kill = None
+        self._time_windows = None
         self.fwi_stages = []
         self._observed = None
         self._gradients = None
@@ -358,6 +365,57 @@ class Denise:
         self._observed = (torch.as_tensor(np.asarray(vx) if not torch.is_tensor(vx) else vx).float(),
                           torch.as_tensor(np.asarray(vy) if not torch.is_tensor(vy) else vy).float())
         self._observed_p = None if p is None else torch.as_tensor(np.asarray(p) if not torch.is_tensor(p) else p).float()
+
+    # -- which samples enter the objective (misfit.TraceSelection) -------------------------------------
+    def set_trace_kill(self, table):
+        """DENISE's TRKILL_FILE as an array [nrec, nshot], 1 = the trace is dead; acted on when ``TRKILL = 1``.  A killed
+        trace may hold anything in the observed data, NaN included.  ``None`` forgets the table."""
+        if table is None:
+            self._trace_kill = None
+            return
+        t = np.asarray(table.detach().cpu().numpy() if torch.is_tensor(table) else table)
+        if t.ndim != 2:
+            raise MifwiError("the trace-kill table is [nrec, nshot] (TRKILL_FILE: one row per receiver), got shape %s"
+                             % (t.shape,))
+        self._trace_kill = np.ascontiguousarray(t.T != 0)                  # -> [nshot, nrec]
+
+    def set_time_windows(self, picks, before=0.0, after=0.0, gamma=float("inf")):
+        """Time windows around picked arrivals: ``picks`` [nshot, nrec] in seconds, the window runs from ``before`` s ahead
+        of the pick to ``after`` s behind it (scalars or [nshot, nrec]), outside it the traces are tapered with
+        exp(-gamma (distance in s)**2) (``inf``: cut).  Applied by grad() after the stage filter to modelled and observed
+        traces of every component; independent of the TIMEWIN attribute, which stays at 0.  ``picks=None`` removes them."""
+        if picks is None:
+            self._time_windows = None
+            return
+        p = np.asarray(picks.detach().cpu().numpy() if torch.is_tensor(picks) else picks, dtype=np.float64)
+        if p.ndim != 2:
+            raise MifwiError("picks are [nshot, nrec] seconds, got shape %s" % (p.shape,))
+        if not float(gamma) >= 0:
+            raise MifwiError("gamma=%r: the taper needs gamma >= 0" % (gamma,))
+        self._time_windows = (p, np.asarray(before, dtype=np.float64), np.asarray(after, dtype=np.float64), float(gamma))
+
+    def _selection(self, shape, dt):
+        """The TraceSelection of this run for traces [nshot, nrec] = ``shape``, or None when nothing is selected."""
+        kill = None
+        if int(self.TRKILL) not in (0, 1):
+            raise MifwiError("TRKILL=%s not implemented (0: off, 1: the table of set_trace_kill)" % self.TRKILL)
+        if int(self.TRKILL) == 1:
+            if self._trace_kill is None:
+                raise MifwiError("TRKILL=1 needs the table of dead traces: d.set_trace_kill(table [nrec, nshot])")
+            kill = self._trace_kill
+        if kill is None and self._time_windows is None:
+            return None
+        for name, a in (("trace-kill table", kill), ("picks", None if self._time_windows is None else self._time_windows[0])):
+            if a is not None and a.shape != tuple(shape):
+                raise MifwiError("the %s is for %s (nshot, nrec), the run has %s" % (name, a.shape, tuple(shape)))
+        weight = None if kill is None else np.where(kill, 0.0, 1.0)
+        try:
+            if self._time_windows is None:
+                return misfit.TraceSelection(weight=weight)
+            picks, before, after, gamma = self._time_windows
+            return misfit.TraceSelection.from_picks(picks, before, after, dt, gamma_per_s2=gamma, weight=weight)
+        except ValueError as exc:
+            raise MifwiError("trace selection: %s" % exc)
 
     def load_observed_su(self, nshots):
         """DENISE layout: DATA_DIR + '_x.su.shot<k>' / '_y.su.shot<k>' (networks.py:7690-7692)."""
@@ -524,7 +582,15 @@ class Denise:
         if lnorm not in (2, 5):
             raise MifwiError("lnorm=%s not implemented (2: L2, 5: global correlation)" % lnorm)
         kernel = misfit.l2_half if lnorm == 2 else misfit.global_correlation
-        objective = (lambda v, o: kernel(v, o, sos=sos)) if sos is not None else kernel
+        # TRKILL and the time windows: one selection W for every component, after the stage filter and before the norm, in
+        # the same launch (csrc/mifwi_misfit_select.h); with the frequency-domain stage W is its own kernel in between
+        sel = self._selection(vx.shape[1:], dt)
+        if sel is None:
+            objective = (lambda v, o: kernel(v, o, sos=sos)) if sos is not None else kernel
+        elif mode == "fft":
+            objective = lambda v, o: kernel(misfit.trace_window(v, sel), misfit.trace_window(o, sel))
+        else:
+            objective = lambda v, o: kernel(v, o, sos=sos, select=sel)
         loss = 0.0
         if self.QUELLTYPB in (1, 2):
             loss = loss + objective(fl(vy), fl(oy))

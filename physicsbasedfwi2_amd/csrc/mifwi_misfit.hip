@@ -182,6 +182,7 @@ int l2_blocks(long long n) { return (int)std::min<long long>(2048, (n / 4 + 255)
 }  // namespace
 
 #include "mifwi_misfit_filter.h"
+#include "mifwi_misfit_select.h"
 
 extern "C" {
 
@@ -291,6 +292,80 @@ int mifwi_misfit_filtered(int device, int32_t kind, const float *pred, const flo
         mifwi_filter::launch_gc(nsec, (unsigned)nblk, st, c, pred, obs, (int)nt, (long long)ntrace, adj_out, fobs, partial);
         hipLaunchKernelGGL(misfit_finish, dim3(1), dim3(256), 0, st, partial, (int)nblk, 1.0, loss_out);
     }
+    MIFWI_HIP_TRY(hipGetLastError());
+    return MIFWI_OK;
+}
+
+int64_t mifwi_misfit_selected_work_elems(int32_t kind, int64_t nt, int64_t ntrace, int32_t nsec)
+{
+    if (nt < 1 || ntrace < 1) return 0;
+    if (nsec > 0) return mifwi_misfit_filtered_work_elems(kind, nt, ntrace);
+    // without a selection the call is mifwi_misfit, whose L2 sums over another grid
+    return std::max<int64_t>(mifwi_misfit_work_elems(kind, nt, ntrace), mifwi::round_up64(2 * mifwi_filter::blocks(ntrace) + 2, 64));
+}
+
+int mifwi_misfit_selected(int device, int32_t kind, const float *pred, const float *obs, int64_t nt, int64_t ntrace,
+                          const double *sos, int32_t nsec, const float *trace_w, const float *t_on, const float *t_off,
+                          double gamma, float *loss_out, float *adj_out, float *work, void *stream)
+{
+    if (kind == MIFWI_MISFIT_L1_TRACE_NORM)
+        return mifwi::fail(MIFWI_EINVAL, "the trace-normalised L1 misfit has no trace selection (the acoustic protocol has none)");
+    if ((sos != nullptr) != (nsec != 0))
+        return mifwi::fail(MIFWI_EINVAL, "sos and nsec=%d disagree: sos is NULL exactly when nsec is 0 (no stage)", nsec);
+    int rc = mifwi_select::check(t_on, t_off, gamma);
+    if (rc) return rc;
+    if (!trace_w && !t_on)         // nothing selected: the very kernels of the calls without a selection
+        return sos ? mifwi_misfit_filtered(device, kind, pred, obs, nt, ntrace, sos, nsec, loss_out, adj_out, work, stream)
+                   : mifwi_misfit(device, kind, pred, obs, nullptr, nt, ntrace, loss_out, adj_out, work, stream);
+    if (!pred || !obs || !loss_out || !work) return mifwi::fail(MIFWI_EINVAL, "null argument");
+    if (kind != MIFWI_MISFIT_L2 && kind != MIFWI_MISFIT_GLOBAL_CORRELATION)
+        return mifwi::fail(MIFWI_EINVAL, "unknown misfit kind %d", kind);
+    if ((reinterpret_cast<uintptr_t>(work) & 7) != 0) return mifwi::fail(MIFWI_EINVAL, "work must be 8-byte aligned");
+    mifwi_filter::Sos c;
+    if (sos) {
+        rc = mifwi_filter::check(nt, ntrace, sos, nsec, &c);
+        if (rc) return rc;
+    } else {
+        if (nt < 1 || ntrace < 1 || nt > 0x7fffffff)
+            return mifwi::fail(MIFWI_EINVAL, "bad sizes nt=%lld ntrace=%lld", (long long)nt, (long long)ntrace);
+        if (mifwi_filter::blocks(ntrace) > 0x7fffffff) return mifwi::fail(MIFWI_EINVAL, "too many traces");
+        memset(&c, 0, sizeof(c));
+    }
+    rc = mifwi::check_device(device);
+    if (rc) return rc;
+    MIFWI_HIP_TRY(hipSetDevice(device));
+    hipStream_t st = (hipStream_t)stream;
+    const long long nblk = mifwi_filter::blocks(ntrace);
+    const mifwi_select::Sel sel = {trace_w, t_on, t_off, gamma};
+    double *partial = reinterpret_cast<double *>(work);
+    if (kind == MIFWI_MISFIT_L2) {
+        mifwi_select::launch_l2(nsec, (unsigned)nblk, st, c, sel, pred, obs, (int)nt, (long long)ntrace, adj_out, partial);
+        hipLaunchKernelGGL(misfit_finish, dim3(1), dim3(256), 0, st, partial, (int)nblk, 0.5, loss_out);
+    } else {
+        float *fobs = work + mifwi::round_up64(2 * nblk + 2, 64);          // read with a stage only
+        mifwi_select::launch_gc(nsec, (unsigned)nblk, st, c, sel, pred, obs, (int)nt, (long long)ntrace, adj_out, fobs, partial);
+        hipLaunchKernelGGL(misfit_finish, dim3(1), dim3(256), 0, st, partial, (int)nblk, 1.0, loss_out);
+    }
+    MIFWI_HIP_TRY(hipGetLastError());
+    return MIFWI_OK;
+}
+
+int mifwi_trace_window(int device, const float *x, float *y, int64_t nt, int64_t ntrace, const float *trace_w,
+                       const float *t_on, const float *t_off, double gamma, void *stream)
+{
+    if (!x || !y) return mifwi::fail(MIFWI_EINVAL, "null argument");
+    if (nt < 1 || ntrace < 1 || nt > 0x7fffffff)
+        return mifwi::fail(MIFWI_EINVAL, "bad sizes nt=%lld ntrace=%lld", (long long)nt, (long long)ntrace);
+    if (mifwi_filter::blocks(ntrace) > 0x7fffffff) return mifwi::fail(MIFWI_EINVAL, "too many traces");
+    int rc = mifwi_select::check(t_on, t_off, gamma);
+    if (rc) return rc;
+    rc = mifwi::check_device(device);
+    if (rc) return rc;
+    MIFWI_HIP_TRY(hipSetDevice(device));
+    const mifwi_select::Sel sel = {trace_w, t_on, t_off, gamma};
+    hipLaunchKernelGGL(mifwi_select::trace_window, dim3((unsigned)mifwi_filter::blocks(ntrace)),
+                       dim3(mifwi_select::kLanes * mifwi_select::kSl), 0, (hipStream_t)stream, sel, x, y, (int)nt,
+                       (long long)ntrace);
     MIFWI_HIP_TRY(hipGetLastError());
     return MIFWI_OK;
 }
