@@ -300,6 +300,87 @@ int mifwi_acoustic_plan_cluster_slabs(const mifwi_acoustic_plan *plan, int32_t a
 int mifwi_elastic_plan_cluster_slabs(const mifwi_elastic_plan *plan, int32_t adjoint);
 
 /* ======================================================================================
+ * 2-D variable-density ACOUSTIC (fluid) velocity-pressure propagator (forward + exact discrete adjoint)
+ *
+ * Serves the DENISE runs with PHYSICS = 2 behind pyapi_denise (models/networks.py:10445-10453: an acoustic medium
+ * driven by a point force) with the fields the physics has: the elastic scheme above with Vs = 0, where
+ * sxx = szz = p and sxz = 0.  Same grid, staggering, Dp / Dm, C-PML recursion and pz / px tables as the elastic
+ * propagator; its seismograms are the elastic ones on mat = [K, K, 0, bx, bz] bit for bit.
+ *   state per shot: vx, vz, p and four memory variables (x strips: d1 @half, e1 @int; z strips: d4 @half, e2 @int)
+ *   mat [3][nz][gp] = K dt/h, dt/(h rho_x), dt/(h rho_z), K = rho Vp^2 (columns >= nx must be 0; under a free
+ *                     surface row 0 of K must be 0)
+ * Forward step n ( ' : through the C-PML; S0..S2: the snapshot planes):
+ *   free surface: p(-1,.) = -p(1,.)
+ *   V:  d1 = Dp_x p, d4 = Dp_z p;  vx = fmaf(bx, d1', vx), vz = fmaf(bz, d4', vz);  S1 = d1', S2 = d4'
+ *   source_type 1 / 2: vx / vz [cell] += w f[n]
+ *   P:  e1 = Dm_x vx, e2 = Dm_z vz;  p = fmaf(K, e1', fmaf(K, e2', p));  S0 = e1' + e2'
+ *   source_type 0: p[cell] += w f[n];  free surface: p(0,.) = 0
+ *   receivers: rec_vx, rec_vz = sum fmaf(w, v, .), rec_p = sum fmaf(w, p + p, .)  (the elastic sxx + szz; DENISE's
+ *   pressure is -rec_p)
+ * Adjoint step n = nt-1 .. 0, the exact transpose:
+ *   vx_bar += w g_vx, vz_bar += w g_vz, p_bar += 2 w g_p;  free surface: p_bar(0,.) = 0
+ *   source_type 0: grad_f[n] = sum w p_bar
+ *   P^T: acc_K += S0 p_bar;  E1, E2 = pmlT(K p_bar) with the x / z tables at integer nodes;
+ *        vx_bar -= Dp_x E1, vz_bar -= Dp_z E2
+ *   source_type 1 / 2: grad_f[n] = sum w vx_bar / vz_bar
+ *   V^T: acc_bx += S1 vx_bar, acc_bz += S2 vz_bar;  D1, D4 = pmlT(bx vx_bar), pmlT(bz vz_bar) with the x / z tables at
+ *        half nodes;  p_bar -= Dm_x D1 + Dm_z D4;  free surface: p_bar(1,.) += C2 D4(0,.)
+ * One launch per half step in both directions; there is no single-launch form.
+ * ==================================================================================== */
+typedef struct {
+    int32_t nz, nx;          /* grid, z = depth is the slow axis                              */
+    int32_t nt, nshot, nsrc, nrec, ntap;
+    int32_t pml_width;       /* C-PML nodes per side (0 = none)                               */
+    int32_t free_surface;    /* 1: pressure-free surface on row 0 (needs nz >= 3)             */
+    int32_t shots_per_group; /* adjoint: shots sharing one gradient accumulator; 0 = auto     */
+    int32_t source_type;     /* 0: explosive (p), 1 / 2: point force on vx / vz               */
+    int32_t fd_order;        /* 4 (0 means 4) or 2                                            */
+} mifwi_fluid_desc;
+
+typedef struct {
+    int32_t gp, pitch, ngroups, shots_per_group;
+    int64_t coef_elems;           /* nz*gp: one material / gradient plane                     */
+    int64_t state_elems;          /* forward state (3 fields + memory variables) at the start
+                                     of `work`: what a time checkpoint copies                 */
+    int64_t work_forward_elems;
+    int64_t work_backward_elems;
+    int64_t snap_step_elems;      /* floats one time step of the snapshot buffer takes (all shots): three f32 planes
+                                     per shot, blocked by columns of 16 four-cell groups      */
+} mifwi_fluid_layout;
+
+typedef struct mifwi_fluid_plan mifwi_fluid_plan;
+
+int mifwi_fluid_plan_create(mifwi_fluid_plan **plan, int device, const mifwi_fluid_desc *desc);
+int mifwi_fluid_plan_destroy(mifwi_fluid_plan *plan);
+int mifwi_fluid_plan_layout(const mifwi_fluid_plan *plan, mifwi_fluid_layout *out);
+/* shots per forward pass, shot groups per adjoint pass over the time range (Infinity Cache residency) */
+int mifwi_fluid_plan_pass_sizes(const mifwi_fluid_plan *plan, int32_t *forward_shots, int32_t *adjoint_groups);
+/* always 0: the fluid plan runs one launch per half step */
+int mifwi_fluid_plan_cluster_slabs(const mifwi_fluid_plan *plan, int32_t adjoint);
+
+/* Steps n = n_begin .. n_end-1; arguments as mifwi_elastic_forward.
+ *   rec_vx, rec_vz [nt][nshot][nrec] or both NULL;  rec_p [nt][nshot][nrec] or NULL
+ *   snap NULL or [n_end-n_begin][layout.snap_step_elems]
+ *   work: layout.work_forward_elems floats, the state (layout.state_elems) at its head.  The calls take no buffer sizes:
+ *         that `work` (here and in mifwi_fluid_backward: layout.work_backward_elems floats), `snap` and the outputs are
+ *         large enough is the caller's to ensure and is NOT checked.                            */
+int mifwi_fluid_forward(mifwi_fluid_plan *plan, const float *mat, const float *pz, const float *px, const float *f,
+                        const int32_t *src_cell, const float *src_w, const int32_t *rec_cell, const float *rec_w,
+                        float *rec_vx, float *rec_vz, float *rec_p, float *snap, float *work, int32_t n_begin,
+                        int32_t n_end, int32_t flags, void *stream);
+
+/* Adjoint steps n = n_hi down to n_lo (full run: nt-1 .. 0, ZERO_STATE|FINALIZE); ranges, snap_first and flags as in
+ * mifwi_elastic_backward.
+ *   g_vx, g_vz, g_p [nt][nshot][nrec] = dJ/d rec, each NULL = zero
+ *   grad_mat [3][nz][gp] (on FINALIZE): dJ/d mat summed over the plan's shots, shot groups added in order
+ *   grad_f NULL or [nt][nshot][nsrc]                                                            */
+int mifwi_fluid_backward(mifwi_fluid_plan *plan, const float *mat, const float *pz, const float *px,
+                         const int32_t *src_cell, const float *src_w, const int32_t *rec_cell, const float *rec_w,
+                         const float *g_vx, const float *g_vz, const float *g_p, const float *snap, int32_t snap_first,
+                         float *grad_mat, float *grad_f, float *work, int32_t n_hi, int32_t n_lo, int32_t flags,
+                         void *stream);
+
+/* ======================================================================================
  * Diagonal PSEUDO-HESSIAN of the elastic gradient (Shin's preconditioner)
  *
  * Serves: DENISE's EPRECOND = 1 / EPSILON_WE, reachable through pyapi_denise as every DENISE parameter is.  The

@@ -52,6 +52,21 @@ class ElasticLayout(ctypes.Structure):
                 ("snapshot_format", ctypes.c_int32), ("kernel_flags", ctypes.c_int32)]
 
 
+class FluidDesc(ctypes.Structure):
+    _fields_ = [("nz", ctypes.c_int32), ("nx", ctypes.c_int32), ("nt", ctypes.c_int32),
+                ("nshot", ctypes.c_int32), ("nsrc", ctypes.c_int32), ("nrec", ctypes.c_int32),
+                ("ntap", ctypes.c_int32), ("pml_width", ctypes.c_int32),
+                ("free_surface", ctypes.c_int32), ("shots_per_group", ctypes.c_int32),
+                ("source_type", ctypes.c_int32), ("fd_order", ctypes.c_int32)]
+
+
+class FluidLayout(ctypes.Structure):
+    _fields_ = [("gp", ctypes.c_int32), ("pitch", ctypes.c_int32), ("ngroups", ctypes.c_int32),
+                ("shots_per_group", ctypes.c_int32), ("coef_elems", ctypes.c_int64),
+                ("state_elems", ctypes.c_int64), ("work_forward_elems", ctypes.c_int64),
+                ("work_backward_elems", ctypes.c_int64), ("snap_step_elems", ctypes.c_int64)]
+
+
 EL_KERNEL_FWD_SINGLE_LAUNCH, EL_KERNEL_ADJ_SINGLE_LAUNCH, EL_KERNEL_FWD_FUSED_STEP, EL_KERNEL_ADJ_FUSED_STEP = 1, 2, 4, 8
 EL_KERNEL_FWD_LANE_HALO, EL_KERNEL_ADJ_LANE_HALO = 16, 32
 SNAPSHOT_F32, SNAPSHOT_BF16 = 0, 1
@@ -88,6 +103,13 @@ SIGNATURES = {
     "mifwi_acoustic_born": (ctypes.c_int, [_P] * 8 + [ctypes.c_int32] + [_P] * 2 + [ctypes.c_int32] * 3 + [_P]),
     "mifwi_acoustic_plan_cluster_slabs": (ctypes.c_int, [_P, ctypes.c_int32]),
     "mifwi_elastic_plan_cluster_slabs": (ctypes.c_int, [_P, ctypes.c_int32]),
+    "mifwi_fluid_plan_create": (ctypes.c_int, [ctypes.POINTER(_P), ctypes.c_int, ctypes.POINTER(FluidDesc)]),
+    "mifwi_fluid_plan_destroy": (ctypes.c_int, [_P]),
+    "mifwi_fluid_plan_layout": (ctypes.c_int, [_P, ctypes.POINTER(FluidLayout)]),
+    "mifwi_fluid_plan_pass_sizes": (ctypes.c_int, [_P, _P, _P]),
+    "mifwi_fluid_plan_cluster_slabs": (ctypes.c_int, [_P, ctypes.c_int32]),
+    "mifwi_fluid_forward": (ctypes.c_int, [_P] * 14 + [ctypes.c_int32] * 3 + [_P]),
+    "mifwi_fluid_backward": (ctypes.c_int, [_P] * 12 + [ctypes.c_int32] + [_P] * 3 + [ctypes.c_int32] * 3 + [_P]),
     "mifwi_misfit_work_elems": (ctypes.c_int64, [ctypes.c_int32, ctypes.c_int64, ctypes.c_int64]),
     "mifwi_misfit": (ctypes.c_int, [ctypes.c_int, ctypes.c_int32] + [_P] * 3 + [ctypes.c_int64] * 2 +
                      [_P] * 4),
