@@ -170,3 +170,128 @@ def sum_taps(a):
     """[nt, ns, 4 n] of a flattened run -> [nt, ns, n]."""
     a = np.asarray(a, dtype=np.float64)
     return a.reshape(a.shape[0], a.shape[1], -1, 4).sum(axis=-1)
+
+
+# ---- the fluid (variable-density acoustic) propagator against the elastic oracle on mat5 = [K, K, 0, bx, bz] ------------
+FLUID_TOL_GRAD = 2e-5
+FLUID_KINDS = {0: "explosive", 1: "fx", 2: "fz"}
+FLUID_TRACES = ("rec_vx", "rec_vz", "rec_p")
+
+
+def fluid_planes(c, fs):
+    """mat5 = [K, K, 0, bx, bz] of the case's Vp and rho (Vs dropped) and the fluid's [K, bx, bz]."""
+    m5 = H.elastic_materials(c["vp"], np.zeros_like(c["vp"]), c["rho"], c["dt"], c["h"]).astype(np.float32)
+    assert np.array_equal(m5[0], m5[1]) and not m5[2].any()
+    if fs:
+        m5[0, 0] = 0.0
+        m5[1, 0] = 0.0
+    c["mat5"], c["mat3"] = m5, np.ascontiguousarray(m5[[0, 3, 4]])
+    return c
+
+
+def fluid_sources_off_the_surface(c):
+    """Under a free surface the two models differ on row 0 by construction: active source taps of row 0 go one row down."""
+    nx = c["vp"].shape[1]
+    sc = np.asarray(c["sc"])
+    c["sc"] = np.where((sc >= 0) & (sc // nx == 0), sc + nx, sc).astype(np.int32)
+    assert ((c["sc"] < 0) | (c["sc"] // nx >= 1)).all()
+    return c
+
+
+def fluid_oracle(c, st, order, g=None, pressure=True):
+    """The f32 oracle's traces, the adjoint inputs (``g`` None: drawn with seed 12 at the size of each trace; or "ones";
+    without ``pressure`` receivers only g_vx and g_vz), its gradients - all read-only, to be shared and never modified -
+    and ``own``, the distance of its gL + gM from the f64 oracle's (row 0 left out under a free surface)."""
+    import oracle
+    o, o64 = oracle.load("f32"), oracle.load("f64")
+    geo = (c["sc"], c["sw"], c["rc"], c["rw"])
+    ovx, ovz, S, orp = o.elastic_forward(c["mat5"], c["pz"], c["px"], c["f"], *geo, save=True, free_surface=c["fs"],
+                                         source_type=st, pressure=True, fd_order=order)
+    if g is None:
+        rng = np.random.default_rng(12)
+        g = [(rng.standard_normal(a.shape) * np.abs(a).max()).astype(np.float32) for a in (ovx, ovz, orp)]
+    elif isinstance(g, str):
+        assert g == "ones"
+        g = [np.ones_like(a) for a in (ovx, ovz, orp)]
+    g = list(g) if pressure else [g[0], g[1], None]
+    gm, gf = o.elastic_backward(c["mat5"], c["pz"], c["px"], *geo, g[0], g[1], S, free_surface=c["fs"], source_type=st,
+                                g_p=g[2], fd_order=order)
+    S64 = o64.elastic_forward(c["mat5"], c["pz"], c["px"], c["f"], *geo, save=True, free_surface=c["fs"], source_type=st,
+                              fd_order=order)[2]
+    gm64, _ = o64.elastic_backward(c["mat5"], c["pz"], c["px"], *geo, g[0], g[1], S64, free_surface=c["fs"],
+                                   source_type=st, g_p=g[2], fd_order=order, want_grad_f=False)
+    r0 = 1 if c["fs"] else 0
+    own = rel_l2((gm[0].astype(np.float64) + gm[1])[r0:], (gm64[0] + gm64[1])[r0:])
+    g = tuple(g[:3 if pressure else 2])
+    for a in (ovx, ovz, orp, gm, gf) + g:
+        a.setflags(write=False)
+    return (ovx, ovz, orp), g, gm, gf, own
+
+
+def fluid_precondition(c, ref, zero=()):
+    """What a case must hold before the library is compared with ``ref = fluid_oracle(c, ...)``, on the CPU: the checker's
+    own gL + gM within a quarter of the bound of the f64 oracle's (tests/test_fluid_gpu.py), and nothing that is compared
+    all zero - except the names in ``zero`` (of rec_vx, rec_vz, rec_p, gK, gbx, gbz, grad_f), which must be.  Returns the
+    oracle's traces and gradients by name."""
+    otr, g, gm_o, gf_o, own = ref
+    assert own <= FLUID_TOL_GRAD / 4, "the checker's own gL + gM is %.1e from the f64 oracle: not a case for this bound" % own
+    r0 = 1 if c["fs"] else 0
+    want = dict(zip(FLUID_TRACES, otr[:len(g)]))
+    want.update(gK=(gm_o[0].astype(np.float64) + gm_o[1].astype(np.float64))[r0:], gbx=gm_o[3], gbz=gm_o[4], grad_f=gf_o)
+    for name, o in want.items():
+        assert (not o.any()) == (name in zero), "%s: the oracle's is %szero" % (name, "" if not o.any() else "not ")
+    return want
+
+
+def fluid_run(c, st, order, gs=0, budget=None, record_pressure=True, mat_grad=True, f_grad=True, dev="cuda:0"):
+    """fluid.propagate on the case: (mat, f, outputs)."""
+    import torch
+    from physicsbasedfwi2_amd import fluid
+    mat = torch.tensor(c["mat3"], dtype=torch.float32, device=dev, requires_grad=mat_grad)
+    f = torch.tensor(c["f"], dtype=torch.float32, device=dev, requires_grad=f_grad)
+    kw = {} if budget is None else {"snapshot_budget": budget}
+    out = fluid.propagate(mat, f, torch.tensor(c["pz"]), torch.tensor(c["px"]), torch.tensor(c["sc"]),
+                          torch.tensor(c["sw"]), torch.tensor(c["rc"]), torch.tensor(c["rw"]), c["fw"],
+                          free_surface=bool(c["fs"]), source_type=FLUID_KINDS[st], record_pressure=record_pressure,
+                          fd_order=order, shots_per_group=gs, **kw)
+    return mat, f, out
+
+
+def fluid_backward(out, g, dev="cuda:0"):
+    import torch
+    torch.autograd.backward(list(out), [torch.tensor(a, device=dev) for a in g[:len(out)]])
+
+
+def fluid_bits(mat, f, out):
+    """Everything a run returns, on the host: the traces, grad_mat, grad_f."""
+    return [a.detach().cpu().numpy() for a in out] + [mat.grad.cpu().numpy(), f.grad.cpu().numpy()]
+
+
+def fluid_check(c, ref, st, order, gs=0, tol=FLUID_TOL_GRAD, zero=(), budget=None, pressure=True):
+    """The library on case ``c`` against ``ref = fluid_oracle(c, st, order, ...)``: the precondition on the checker, the
+    three traces (two without ``pressure`` receivers) bit for bit, grad_mat[0] against gL + gM (row 0 left out under a
+    free surface, where the library's must be 0), grad_mat[1], grad_mat[2] and grad_f to rel-L2 <= ``tol``.  The names in
+    ``zero`` are zero by construction (fluid_precondition) and must be exactly zero in the library.  Returns the measured
+    gradient errors and what the run returned (fluid_bits)."""
+    g = ref[1]
+    want = fluid_precondition(c, ref, zero)
+    r0 = 1 if c["fs"] else 0
+    mat, f, out = fluid_run(c, st, order, gs, budget, record_pressure=pressure)
+    assert len(out) == len(g) == (3 if pressure else 2)
+    for name, h in zip(FLUID_TRACES, out):
+        h, o = h.detach().cpu().numpy(), want.pop(name)
+        print("%s max |hip - oracle| %.3e of %.3e" % (name, np.abs(h - o).max(), np.abs(o).max()))
+        assert np.array_equal(h, o), name
+    fluid_backward(out, g)
+    gm_h = mat.grad.cpu().numpy()
+    got = dict(gK=gm_h[0][r0:], gbx=gm_h[1], gbz=gm_h[2], grad_f=f.grad.cpu().numpy())
+    errs = {k: rel_l2(got[k], want[k]) for k in want}
+    print("gradient rel-L2", {k: "%.2e" % v for k, v in errs.items()})
+    if c["fs"]:
+        assert not gm_h[0][0].any(), "row 0 of the K gradient under a free surface"
+    for k, v in errs.items():
+        if k in zero:
+            assert not got[k].any(), k + " must be exactly zero"
+        else:
+            assert v <= tol, (k, v)
+    return errs, fluid_bits(mat, f, out)

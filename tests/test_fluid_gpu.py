@@ -18,28 +18,16 @@ import numpy as np
 import pytest
 import torch
 
-from cases import elastic_case, elastic_case_taps4, rel_l2
+from cases import (FLUID_KINDS as KINDS, FLUID_TOL_GRAD as TOL_GRAD, elastic_case, elastic_case_taps4, fluid_backward,
+                   fluid_check, fluid_oracle, fluid_planes as _fluid_planes, fluid_run, rel_l2)
 from oracle import helpers as H
 
 pytestmark = pytest.mark.gpu
 TOL_TRACE = 1e-6
-TOL_GRAD = 2e-5
 DEV = "cuda:0"
-KINDS = {0: "explosive", 1: "fx", 2: "fz"}
 # nz x nx -> lanes per row of the forward tiles by the plan's rule (mifwi::pick_lx on 18, 34, 30 and 60 four-cell groups per
 # row): the three widths the family instantiates; nx % 4 = 2, 1, 0; two or three adjoint tile rows, two to four tile columns
 SHAPES = {(37, 70): 16, (37, 133): 16, (44, 120): 32, (23, 240): 64}
-
-
-def _fluid_planes(c, fs):
-    """mat5 = [K, K, 0, bx, bz] of the case's Vp and rho (Vs dropped) and the fluid's [K, bx, bz]."""
-    m5 = H.elastic_materials(c["vp"], np.zeros_like(c["vp"]), c["rho"], c["dt"], c["h"]).astype(np.float32)
-    assert np.array_equal(m5[0], m5[1]) and not m5[2].any()
-    if fs:
-        m5[0, 0] = 0.0
-        m5[1, 0] = 0.0
-    c["mat5"], c["mat3"] = m5, np.ascontiguousarray(m5[[0, 3, 4]])
-    return c
 
 
 @functools.lru_cache(maxsize=None)
@@ -64,24 +52,7 @@ def _case(nz, nx, fs, nt=150, seed=7):
 def _oracle_run(key, st, order):
     """The oracle's traces, the adjoint inputs, its gradients (shared by the tests of one case, never modified) and the
     distance of its gL + gM from the f64 oracle's."""
-    import oracle
-    o, o64 = oracle.load("f32"), oracle.load("f64")
-    c = _CASES[key]()
-    ovx, ovz, S, orp = o.elastic_forward(c["mat5"], c["pz"], c["px"], c["f"], c["sc"], c["sw"], c["rc"], c["rw"], save=True,
-                                         free_surface=c["fs"], source_type=st, pressure=True, fd_order=order)
-    rng = np.random.default_rng(12)
-    g = [(rng.standard_normal(a.shape) * np.abs(a).max()).astype(np.float32) for a in (ovx, ovz, orp)]
-    gm, gf = o.elastic_backward(c["mat5"], c["pz"], c["px"], c["sc"], c["sw"], c["rc"], c["rw"], g[0], g[1], S,
-                                free_surface=c["fs"], source_type=st, g_p=g[2], fd_order=order)
-    S64 = o64.elastic_forward(c["mat5"], c["pz"], c["px"], c["f"], c["sc"], c["sw"], c["rc"], c["rw"], save=True,
-                              free_surface=c["fs"], source_type=st, fd_order=order)[2]
-    gm64, _ = o64.elastic_backward(c["mat5"], c["pz"], c["px"], c["sc"], c["sw"], c["rc"], c["rw"], g[0], g[1], S64,
-                                   free_surface=c["fs"], source_type=st, g_p=g[2], fd_order=order, want_grad_f=False)
-    r0 = 1 if c["fs"] else 0
-    own = rel_l2((gm[0].astype(np.float64) + gm[1])[r0:], (gm64[0] + gm64[1])[r0:])
-    for a in (ovx, ovz, orp, gm, gf) + tuple(g):
-        a.setflags(write=False)
-    return (ovx, ovz, orp), g, gm, gf, own
+    return fluid_oracle(_CASES[key](), st, order)
 
 
 _CASES = {}
@@ -108,43 +79,15 @@ def _taps4(fs):
 
 
 def _run_hip(c, st, order, gs=0, budget=None):
-    from physicsbasedfwi2_amd import fluid
-    mat = torch.tensor(c["mat3"], dtype=torch.float32, device=DEV, requires_grad=True)
-    f = torch.tensor(c["f"], dtype=torch.float32, device=DEV, requires_grad=True)
-    kw = {} if budget is None else {"snapshot_budget": budget}
-    out = fluid.propagate(mat, f, torch.tensor(c["pz"]), torch.tensor(c["px"]), torch.tensor(c["sc"]),
-                          torch.tensor(c["sw"]), torch.tensor(c["rc"]), torch.tensor(c["rw"]), c["fw"],
-                          free_surface=bool(c["fs"]), source_type=KINDS[st], record_pressure=True, fd_order=order,
-                          shots_per_group=gs, **kw)
-    return mat, f, out
+    return fluid_run(c, st, order, gs, budget)
 
 
 def _backward(out, g):
-    torch.autograd.backward(list(out), [torch.tensor(a, device=DEV) for a in g])
+    fluid_backward(out, g)
 
 
 def _check_parity(key, st, order, gs):
-    c = _CASES[key]()
-    otr, g, gm_o, gf_o, own = _oracle_run(key, st, order)
-    assert own <= TOL_GRAD / 4, "the checker's own gL + gM is %.1e from the f64 oracle: not a case for this bound" % own
-    mat, f, out = _run_hip(c, st, order, gs)
-    for name, h, o in zip(("rec_vx", "rec_vz", "rec_p"), out, otr):
-        h = h.detach().cpu().numpy()
-        assert np.abs(o).max() > 0, name + ": the oracle's traces are zero"
-        print("%s max |hip - oracle| %.3e of %.3e" % (name, np.abs(h - o).max(), np.abs(o).max()))
-        assert np.array_equal(h, o), name
-    _backward(out, g)
-    gm_h = mat.grad.cpu().numpy()
-    gK_o = gm_o[0].astype(np.float64) + gm_o[1].astype(np.float64)
-    r0 = 1 if c["fs"] else 0
-    errs = dict(gK=rel_l2(gm_h[0][r0:], gK_o[r0:]), gbx=rel_l2(gm_h[1], gm_o[3]), gbz=rel_l2(gm_h[2], gm_o[4]),
-                grad_f=rel_l2(f.grad.cpu().numpy(), gf_o))
-    print("gradient rel-L2", {k: "%.2e" % v for k, v in errs.items()})
-    assert np.abs(gK_o).max() > 0 and np.abs(gm_o[3]).max() > 0 and np.abs(gm_o[4]).max() > 0 and np.abs(gf_o).max() > 0
-    if c["fs"]:
-        assert not gm_h[0][0].any(), "row 0 of the K gradient under a free surface"
-    for k, v in errs.items():
-        assert v <= TOL_GRAD, (k, v)
+    fluid_check(_CASES[key](), _oracle_run(key, st, order), st, order, gs)
 
 
 COMBOS = [(order, fs, st) for order in (2, 4) for fs in (0, 1) for st in (0, 1, 2)]

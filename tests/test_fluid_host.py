@@ -114,3 +114,9 @@ def test_shim_refuses_what_the_fluid_kernels_do_not_serve(monkeypatch):
         d.grad(model, src, rec)
     with pytest.raises(api.MifwiError, match="EPRECOND"):
         d.forward(model, src, rec)
+
+
+def test_fuzz_draws_of_the_fluid_family_cover_what_they_are_meant_to():
+    """The committed draws of test_fuzz_gpu.test_random_fluid_configuration: tile widths, nx % 4, source type x surface."""
+    import test_fuzz_gpu
+    test_fuzz_gpu.test_fluid_draws_cover_the_tile_widths_and_column_remainders()

@@ -113,6 +113,84 @@ def test_random_acoustic_configuration(oracle32, monkeypatch, k, cfg, opt):
     assert rel_l2(f.grad.cpu().numpy(), gf_o) <= 5e-5, (cfg, opt)
 
 
+# A generator of its own for the fluid draws.  The seed was chosen on the CPU: the first from 2031 on whose 16 draws cover
+# what test_fluid_draws_cover_the_tile_widths_and_column_remainders asks for and all keep the f32 oracle's gL + gM within
+# 5e-6 of the f64 oracle's (the largest is 3.3e-6) with no compared quantity all zero.
+FLUID_SEED = 2037
+
+
+def _pick_lx(ng):
+    """The plan's rule for the forward tile width (mifwi::pick_lx in csrc/mifwi_host.h), restated: 64 lanes per row, then
+    32, where padding a row of ng four-cell groups to a multiple of that costs at most 20 %; otherwise 16."""
+    for cand in (64, 32):
+        if -(-ng // cand) * cand * 10 <= ng * 12:
+            return cand
+    return 16
+
+
+def _fluid_configs(seed=FLUID_SEED):
+    rng = np.random.default_rng(seed)
+    out = []
+    for k in range(16):
+        fw = int(rng.choice([0, 3, 6, 9]))
+        cfg = dict(nz=int(rng.integers(max(24, 2 * fw + 4), 75)), nx=int(rng.integers(40, 260)), fw=fw,
+                   ns=int(rng.integers(1, 6)), nsrc=int(rng.integers(1, 3)), nrec=int(rng.integers(1, 20)),
+                   nt=int(rng.integers(60, 120)), free_surface=bool(rng.integers(0, 2)))
+        # segments 0: the default snapshot budget (resident snapshots); 3 or 4: a budget that holds that share of the steps
+        opt = dict(source_type=int(rng.integers(0, 3)), order=int(rng.choice([2, 4])), pressure=bool(rng.integers(0, 2)),
+                   gs=int(rng.integers(0, 4)), pass_shots=str(int(rng.integers(1, 4))),
+                   pass_groups=str(int(rng.integers(1, 3))), segments=int(rng.choice([0, 0, 3, 4])))
+        out.append((k, cfg, opt))
+    return out
+
+
+def _fluid_case(k, cfg):
+    from cases import fluid_planes, fluid_sources_off_the_surface
+    c = elastic_case(seed=400 + k, water=0, **cfg)
+    if cfg["free_surface"]:
+        fluid_sources_off_the_surface(c)
+    return fluid_planes(c, c["fs"])
+
+
+def test_fluid_draws_cover_the_tile_widths_and_column_remainders():
+    """Needs no GPU.  Over the 16 draws: every forward tile width at least twice, every nx % 4, every source type with and
+    without a free surface."""
+    draws = _fluid_configs()
+    widths = [_pick_lx(-(-cfg["nx"] // 4)) for _, cfg, _ in draws]
+    assert all(widths.count(lx) >= 2 for lx in (16, 32, 64)), widths
+    assert {cfg["nx"] % 4 for _, cfg, _ in draws} == {0, 1, 2, 3}
+    assert {(opt["source_type"], cfg["free_surface"]) for _, cfg, opt in draws} == {(st, fs) for st in range(3)
+                                                                                    for fs in (False, True)}
+
+
+@pytest.mark.parametrize("k,cfg,opt", _fluid_configs())
+def test_random_fluid_configuration(monkeypatch, k, cfg, opt):
+    """Random grids, layer widths, shot and point counts, surface, source type, FD order, pressure receivers, group size,
+    pass sizes and checkpoint segments of the fluid propagator against the f32 oracle of the elastic scheme on
+    mat5 = [K, K, 0, bx, bz]: the reference and the bounds of tests/test_fluid_gpu.py (cases.fluid_check)."""
+    from cases import fluid_check, fluid_oracle, fluid_precondition
+    from physicsbasedfwi2_amd import fluid
+    from physicsbasedfwi2_amd._driver import checkpoint_schedule, segment_length
+    c = _fluid_case(k, cfg)
+    st, order = opt["source_type"], opt["order"]
+    ref = fluid_oracle(c, st, order, pressure=opt["pressure"])
+    fluid_precondition(c, ref)
+    monkeypatch.setenv("MIFWI_FL_PASS_SHOTS", opt["pass_shots"])
+    monkeypatch.setenv("MIFWI_FL_PASS_GROUPS", opt["pass_groups"])
+    pl = fluid.FluidPlan(cfg["nz"], cfg["nx"], cfg["nt"], cfg["ns"], cfg["nsrc"], cfg["nrec"], 1, cfg["fw"], 0, opt["gs"],
+                         c["fs"], st, order)
+    step_bytes = 4 * pl.layout.snap_step_elems
+    assert pl.pass_sizes()[0] == min(int(opt["pass_shots"]), cfg["ns"])
+    pl.close()
+    budget = None
+    if opt["segments"]:
+        seg = -(-cfg["nt"] // opt["segments"])
+        budget = 2 * seg * step_bytes
+        assert segment_length(budget, torch.device(DEV), step_bytes, cfg["nt"]) == seg
+        assert len(checkpoint_schedule(cfg["nt"], seg, "elastic")[0]) >= 2
+    fluid_check(c, ref, st, order, gs=opt["gs"], budget=budget, pressure=opt["pressure"])
+
+
 def _cpml_configs():
     rng = np.random.default_rng(2029)
     out = []

@@ -369,6 +369,26 @@ def _stream_calls():
         calls.append(("elastic %s" % env, env, elastic_run,
                       [t(ec["mat"]), t(ec["f"]), torch.tensor(ec["sc"], device=DEV), t(ec["sw"]),
                        torch.tensor(ec["rc"], device=DEV), t(ec["rw"])] + [t(rng.standard_normal((70, 2, 9))) for _ in range(2)]))
+
+    # the fluid family: the source's bounding box, the per-tile receiver lists, the pressure receivers and their adjoint, the
+    # point-force sampling and the finalize are launches of their own beside the four of a step
+    from cases import fluid_planes
+    from physicsbasedfwi2_amd import fluid
+    fc = fluid_planes(elastic_case(seed=6, nz=37, nx=53, fw=6, nt=60, ns=2, nrec=9, water=0), 0)
+
+    def fluid_run(kind):
+        def run(mat, f, sc, sw, rc, rw, gx, gz, gp):
+            mat, f = mat.requires_grad_(True), f.requires_grad_(True)
+            out = fluid.propagate(mat, f, torch.tensor(fc["pz"]), torch.tensor(fc["px"]), sc, sw, rc, rw, fc["fw"],
+                                  source_type=kind, record_pressure=True)
+            torch.autograd.backward(list(out), [gx, gz, gp])
+            return tuple(a.detach() for a in out) + (mat.grad, f.grad)
+        return run
+
+    for kind in ("explosive", "fx"):
+        calls.append(("fluid " + kind, {}, fluid_run(kind),
+                      [t(fc["mat3"]), t(fc["f"]), torch.tensor(fc["sc"], device=DEV), t(fc["sw"]),
+                       torch.tensor(fc["rc"], device=DEV), t(fc["rw"])] + [t(rng.standard_normal((60, 2, 9))) for _ in range(3)]))
     return calls
 
 
