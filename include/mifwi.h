@@ -29,7 +29,7 @@ extern "C" {
 #endif
 
 #define MIFWI_VERSION_MAJOR 0
-#define MIFWI_VERSION_MINOR 7   /* 3: elastic desc gained snapshot_format, fd_order; layout snap_step_elems, snapshot_format; 4: mifwi_fallback_count; 5: mifwi_agent_handoff_count, mifwi_slow_handoff_count; acoustic desc gained cpml_width, layout state_elems; 6: mifwi_elastic_materials(_vjp), mifwi_acoustic_coefficients(_vjp); 7: mifwi_elastic_gradient_parametrization; elastic snapshot planes column-blocked in plans without a single-launch kernel; later additions that leave every existing call as it was keep 7: mifwi_elastic_snapshot_moments, mifwi_elastic_pseudo_hessian, mifwi_gradient_precondition, mifwi_elastic_born, mifwi_acoustic_snapshot_moments, mifwi_acoustic_pseudo_hessian */
+#define MIFWI_VERSION_MINOR 7   /* 3: elastic desc gained snapshot_format, fd_order; layout snap_step_elems, snapshot_format; 4: mifwi_fallback_count; 5: mifwi_agent_handoff_count, mifwi_slow_handoff_count; acoustic desc gained cpml_width, layout state_elems; 6: mifwi_elastic_materials(_vjp), mifwi_acoustic_coefficients(_vjp); 7: mifwi_elastic_gradient_parametrization; elastic snapshot planes column-blocked in plans without a single-launch kernel; later additions that leave every existing call as it was keep 7: mifwi_elastic_snapshot_moments, mifwi_elastic_pseudo_hessian, mifwi_gradient_precondition, mifwi_elastic_born, mifwi_acoustic_snapshot_moments, mifwi_acoustic_pseudo_hessian, mifwi_fluid_born, mifwi_fluid_snapshot_moments, mifwi_fluid_pseudo_hessian */
 
 enum {
     MIFWI_OK = 0,
@@ -380,6 +380,41 @@ int mifwi_fluid_backward(mifwi_fluid_plan *plan, const float *mat, const float *
                          float *grad_mat, float *grad_f, float *work, int32_t n_hi, int32_t n_lo, int32_t flags,
                          void *stream);
 
+/* Born (linearised) modelling with the fluid kernels: drec = J (dmat, df), the first-order change of the three
+ * seismograms, steps n = n_begin .. n_end-1 - the JVP partner of mifwi_fluid_backward's (grad_mat, grad_f).  The perturbed
+ * state (dvx, dvz, dp) and its four memory variables obey the forward recursion above (same mat, pz / px, free surface
+ * with dp(-1,.) = -dp(1,.) and dp(0,.) = 0, fd_order); the three snapshot planes S0..S2 the background run saved at
+ * step n are its virtual sources.  Perturbed step n, the chain of each update:
+ *   V:  dvx = fmaf(dmat[1], S1, fmaf(bx, d1', dvx)),  dvz = fmaf(dmat[2], S2, fmaf(bz, d4', dvz))   (d1, d4 of dp)
+ *   source_type 1 / 2: dvx / dvz [cell] += w df[n]
+ *   P:  dp = fmaf(dmat[0], S0, fmaf(K, e1', fmaf(K, e2', dp)))                                        (e1, e2 of dvx, dvz)
+ *   source_type 0: dp[cell] += w df[n];  free surface: dp(0,.) = 0
+ *   dmat [3][nz][gp]: perturbation of `mat`, same layout (columns >= nx must be 0)
+ *   df   NULL or [nt][nshot][nsrc]: perturbation of f, injected exactly where f is for all three source types (for a
+ *        force source the caller differentiates its own amplitude scaling)
+ *   snap: the planes as mifwi_fluid_forward of the same plan wrote them; step n at
+ *         snap + (n - snap_first) * layout.snap_step_elems.  They are read with 16-byte loads, none is written.
+ *   drec_vx, drec_vz [nt][nshot][nrec] or both NULL; drec_p NULL or [nt][nshot][nrec] = sum w (dp + dp): sampled as the
+ *         forward samples rec_vx, rec_vz and rec_p
+ *   work: layout.work_forward_elems floats; the perturbed state lives at its head (MIFWI_ZERO_STATE as in the forward)
+ * The same tiles, launch order and Infinity Cache passes as the forward (a compile-time variant of its two kernels).
+ * MIFWI_EINVAL: null dmat / snap / work, a bad step range, snap_first < 0 or > n_begin. */
+int mifwi_fluid_born(mifwi_fluid_plan *plan, const float *mat, const float *dmat, const float *pz, const float *px,
+                     const float *df, const int32_t *src_cell, const float *src_w, const int32_t *rec_cell,
+                     const float *rec_w, const float *snap, int32_t snap_first, float *drec_vx, float *drec_vz,
+                     float *drec_p, float *work, int32_t n_begin, int32_t n_end, int32_t flags, void *stream);
+
+/* Second moments of the fluid snapshot planes, the ingredient of mifwi_fluid_pseudo_hessian:
+ *   moments [3][nz][gp]:  M0 = sum S0^2,  M1 = sum S1^2,  M2 = sum S2^2   (each term fmaf(S, S, M))
+ * per cell over the plan's shots and the steps n in [n_begin, n_end) with n % stride == 0, each weighted by stride.
+ * Arguments, ranges, flags, alignment and refusals as mifwi_elastic_snapshot_moments; work:
+ * mifwi_fluid_snapshot_moments_work_elems(plan) floats.  One thread owns one 4-cell group, the pad groups of the last
+ * column block are never read; partial planes of the step range are added in a fixed order: no atomics, two identical
+ * calls give the same bits. */
+int64_t mifwi_fluid_snapshot_moments_work_elems(const mifwi_fluid_plan *plan);
+int mifwi_fluid_snapshot_moments(mifwi_fluid_plan *plan, const float *snap, int32_t snap_first, int32_t n_begin,
+                                 int32_t n_end, int32_t stride, float *moments, float *work, int32_t flags, void *stream);
+
 /* ======================================================================================
  * Diagonal PSEUDO-HESSIAN of the elastic gradient (Shin's preconditioner)
  *
@@ -586,6 +621,19 @@ int mifwi_elastic_gradient_parametrization(int device, int32_t parametrization, 
 int mifwi_elastic_pseudo_hessian(int device, int32_t parametrization, const float *vp, const float *vs,
                                  const float *rho, const float *moments, int32_t nz, int32_t nx, int32_t gp,
                                  float dt_over_h, float *h_a, float *h_b, float *h_rho, void *stream);
+
+/* The pseudo-Hessian planes of the fluid propagator's parameter sets from the moments of mifwi_fluid_snapshot_moments
+ * [3][nz][gp]: mifwi_elastic_pseudo_hessian with Vs = 0, so that a preconditioned update does not depend on which kernels
+ * ran.  There L_p = M_p = K_p and the fluid's S0 is the elastic S0 + S1, so the stress terms collapse:
+ *   H_p = fmaf(2 K_p^2, M0, b_p^2 (M1 + M2)), clamped at 0       (2: the two identical stress equations the fluid merges)
+ *   VELOCITY   Vp: K_p = 2 rho Vp s, b_p = 0      rho: K_p = Vp^2 s,  b_p = -s / rho^2
+ *   IMPEDANCE  Zp: K_p = 2 Vp s,     b_p = 0      rho: K_p = -Vp^2 s, b_p = -s / rho^2
+ *   LAME       K:  K_p = s,          b_p = 0      rho: K_p = 0,       b_p = -s / rho^2
+ * with s = dt/h; a term whose divisor is zero contributes 0; the same collocated approximation.  vp, rho, h_a (Vp / Zp / K),
+ * h_rho [nz][nx] device, no padding.  Every output is finite and >= 0. */
+int mifwi_fluid_pseudo_hessian(int device, int32_t parametrization, const float *vp, const float *rho,
+                               const float *moments, int32_t nz, int32_t nx, int32_t gp, float dt_over_h, float *h_a,
+                               float *h_rho, void *stream);
 
 /* vp [nz][nx] (m/s) -> r [nz + 2 pad][nx + 2 pad] = (vp dt/h)^2 with the model edge-replicated into the absorbing
  * layer: the coefficient of the scalar scheme as the deepwave-shaped call protocol needs it per call

@@ -110,6 +110,11 @@ SIGNATURES = {
     "mifwi_fluid_plan_cluster_slabs": (ctypes.c_int, [_P, ctypes.c_int32]),
     "mifwi_fluid_forward": (ctypes.c_int, [_P] * 14 + [ctypes.c_int32] * 3 + [_P]),
     "mifwi_fluid_backward": (ctypes.c_int, [_P] * 12 + [ctypes.c_int32] + [_P] * 3 + [ctypes.c_int32] * 3 + [_P]),
+    "mifwi_fluid_born": (ctypes.c_int, [_P] * 11 + [ctypes.c_int32] + [_P] * 4 + [ctypes.c_int32] * 3 + [_P]),
+    "mifwi_fluid_snapshot_moments_work_elems": (ctypes.c_int64, [_P]),
+    "mifwi_fluid_snapshot_moments": (ctypes.c_int, [_P] * 2 + [ctypes.c_int32] * 4 + [_P] * 2 + [ctypes.c_int32, _P]),
+    "mifwi_fluid_pseudo_hessian": (ctypes.c_int, [ctypes.c_int, ctypes.c_int32] + [_P] * 3 + [ctypes.c_int32] * 3 +
+                                   [ctypes.c_float] + [_P] * 3),
     "mifwi_misfit_work_elems": (ctypes.c_int64, [ctypes.c_int32, ctypes.c_int64, ctypes.c_int64]),
     "mifwi_misfit": (ctypes.c_int, [ctypes.c_int, ctypes.c_int32] + [_P] * 3 + [ctypes.c_int64] * 2 +
                      [_P] * 4),

@@ -19,6 +19,9 @@
 // Tiles are taken in an XCD-contiguous order, the drivers sweep the time range a few shots (shot groups) at a time when
 // all of them would not stay inside the Infinity Cache.  Snapshots: f32, three planes per shot-step, blocked by columns
 // of 16 groups (whole 128-byte lines per tile row).  There is no single-launch form.
+// Born (mifwi_fluid_born): the same two launches on the perturbed state; instead of writing the step's three snapshot
+// planes they read the background run's and add dmat times them (SAVE = kBorn), the JVP partner of the adjoint's gradients.
+// Snapshot moments (the pseudo-Hessian's ingredient): mifwi_fluid_moments.h, included at the end.
 // Arithmetic = the explicit fmaf chain stated in include/mifwi.h (build with -ffp-contract=off).
 #include "mifwi_cluster_host.h"      // mifwi::env_int
 #include "mifwi_host.h"
@@ -49,10 +52,11 @@ struct FlParams {
     int fsurf;
     long long psix_shot, psiz_shot;   // floats per shot: 2*nz*wx, 2*2W*gp
     const float *mat, *pz, *px;
+    const float *dmat;           // Born step (SAVE kBorn): perturbation of the three material planes, [3][nz][gp] like mat
     float *fields;
     float *psix, *psiz;          // forward: updated in place; adjoint: read side
     float *psix_out, *psiz_out;  // adjoint: write side (ping-pong)
-    float *S;                    // snapshot slice of this step: [nshot][3] planes of splane floats
+    float *S;                    // snapshot slice of this step: [nshot][3] planes of splane floats (Born: read)
     unsigned splane;             // floats per snapshot / accumulator plane: nz * 64 * ceil(ng / 16)
     float *acc;                  // [ngroups][3] planes
     // injection (V: vx | vz += a; P: p += a; P^T: vx += a0, vz += a1)
@@ -210,10 +214,14 @@ __device__ __forceinline__ PxTab px_tab(const FlParams &p, int g, int half)
     return PxTab{ld4(t), ld4(t + p.gp), ld4(t + 2 * p.gp)};
 }
 
+// SAVE 0: no snapshots, 1: write the three planes, 2 (kBorn): the Born step - the state is the perturbed one, the planes of
+// the background run are read and dmat times them is added
+constexpr int kBorn = 2;
+
 // ================================================================================================
 // forward V launch:  vx += bx (Dp_x p)',  vz += bz (Dp_z p)',  then the point force of the tile
 // ================================================================================================
-template <int LX, bool SAVE>
+template <int LX, int SAVE>
 __global__ __launch_bounds__(kThreads) void fl_step_v(const FlParams p)
 {
     const FdK K = p.fd;
@@ -256,6 +264,12 @@ __global__ __launch_bounds__(kThreads) void fl_step_v(const FlParams p)
     const float2 Lp = ld2(pp + o - 2), Rp = ld2(pp + o + 4);
     float4 vxv = ld4(vx + o), vzv = ld4(vz + o);
     const float4 bxs = ld4(p.mat + M_BX * ncell + cc), bzs = ld4(p.mat + M_BZ * ncell + cc);
+    float4 B1 = zero4, B2 = zero4, dbx = zero4, dbz = zero4;
+    if (SAVE == kBorn) {
+        const float *Sp = p.S + 3LL * s * p.splane + snap_cell(p, j, g);
+        B1 = mifwi::ldnt4(Sp + (long long)p.splane); B2 = mifwi::ldnt4(Sp + 2 * (long long)p.splane);
+        dbx = ld4(p.dmat + M_BX * ncell + cc); dbz = ld4(p.dmat + M_BZ * ncell + cc);
+    }
     if (p.fsurf && j == 0) b0 = make_float4(-b2.x, -b2.y, -b2.z, -b2.w);      // p(-1) = -p(1)
     const float xx[8] = {Lp.x, Lp.y, b1.x, b1.y, b1.z, b1.w, Rp.x, Rp.y};
     float d1[4], d4[4];
@@ -281,6 +295,10 @@ __global__ __launch_bounds__(kThreads) void fl_step_v(const FlParams p)
     for (int c = 0; c < 4; ++c) {
         nvx[c] = fmaf(comp(bxs, c), d1[c], comp(vxv, c));
         nvz[c] = fmaf(comp(bzs, c), d4[c], comp(vzv, c));
+        if (SAVE == kBorn) {
+            nvx[c] = fmaf(comp(dbx, c), comp(B1, c), nvx[c]);
+            nvz[c] = fmaf(comp(dbz, c), comp(B2, c), nvz[c]);
+        }
         if (has_inj) {
             const float a = inj[lz * TX + 4 * lx + c];
             if (p.inj_field == F_VX) nvx[c] += a; else nvz[c] += a;
@@ -288,7 +306,7 @@ __global__ __launch_bounds__(kThreads) void fl_step_v(const FlParams p)
     }
     st4(vx + o, mk4(nvx));
     st4(vz + o, mk4(nvz));
-    if (SAVE) {
+    if (SAVE == 1) {
         float *Sp = p.S + 3LL * s * p.splane + snap_cell(p, j, g);
         mifwi::stnt4(Sp + (long long)p.splane, mk4(d1));
         mifwi::stnt4(Sp + 2 * (long long)p.splane, mk4(d4));
@@ -298,7 +316,7 @@ __global__ __launch_bounds__(kThreads) void fl_step_v(const FlParams p)
 // ================================================================================================
 // forward P launch:  p += K (Dm_x vx)' + K (Dm_z vz)',  the explosive source of the tile;  extra workgroups sample vx, vz
 // ================================================================================================
-template <int LX, bool SAVE>
+template <int LX, int SAVE>
 __global__ __launch_bounds__(kThreads) void fl_step_p(const FlParams p)
 {
     const FdK K = p.fd;
@@ -343,6 +361,11 @@ __global__ __launch_bounds__(kThreads) void fl_step_p(const FlParams p)
     const float2 Lvx = ld2(vx + o - 2), Rvx = ld2(vx + o + 4);
     const float4 pv = ld4(pp + o);
     const float4 Ks = ld4(p.mat + cc);
+    float4 B0 = zero4, dK = zero4;
+    if (SAVE == kBorn) {
+        B0 = mifwi::ldnt4(p.S + 3LL * s * p.splane + snap_cell(p, j, g));
+        dK = ld4(p.dmat + cc);
+    }
     const float xv[8] = {Lvx.x, Lvx.y, cvx.x, cvx.y, cvx.z, cvx.w, Rvx.x, Rvx.y};
     float e1[4], e2[4];
 #pragma unroll
@@ -367,11 +390,12 @@ __global__ __launch_bounds__(kThreads) void fl_step_p(const FlParams p)
     for (int c = 0; c < 4; ++c) {
         s0v[c] = e1[c] + e2[c];
         np[c] = fmaf(comp(Ks, c), e1[c], fmaf(comp(Ks, c), e2[c], comp(pv, c)));
+        if (SAVE == kBorn) np[c] = fmaf(comp(dK, c), comp(B0, c), np[c]);
         if (has_inj) np[c] += inj[lz * TX + 4 * lx + c];
         if (p.fsurf && j == 0) np[c] = 0.f;
     }
     st4(pp + o, mk4(np));
-    if (SAVE) mifwi::stnt4(p.S + 3LL * s * p.splane + snap_cell(p, j, g), mk4(s0v));
+    if (SAVE == 1) mifwi::stnt4(p.S + 3LL * s * p.splane + snap_cell(p, j, g), mk4(s0v));
 }
 
 // ================================================================================================
@@ -777,13 +801,14 @@ FlParams fl_base(const mifwi_fluid_plan *pl, const float *mat, const float *pz, 
     return p;
 }
 
-// the two launches of a forward step, fl_step_v / fl_step_p<LX, SAVE>: lanes per row 64 | 32 | 16; snapshots written or not
+// the two launches of a forward step, fl_step_v / fl_step_p<LX, SAVE>: lanes per row 64 | 32 | 16; save kBorn (the
+// background's snapshots read) | 1 (snapshots written) | 0
 using FlKernel = void (*)(FlParams);
 struct FlStepKernels { FlKernel v, p; };
-FlStepKernels fl_step_variant(int lx, bool save)
+FlStepKernels fl_step_variant(int lx, int save)
 {
     return mifwi::with_int<64, 32, 16>(lx, [&](auto LX) {
-    return mifwi::with_bool(save, [&](auto SAVE) {
+    return mifwi::with_int<kBorn, 1, 0>(save, [&](auto SAVE) {
         return FlStepKernels{fl_step_v<decltype(LX)::value, decltype(SAVE)::value>,
                              fl_step_p<decltype(LX)::value, decltype(SAVE)::value>};
     }); });
@@ -803,6 +828,47 @@ FlWork work_map(const mifwi_fluid_plan *pl, bool backward)
     m.bbox = m.tile = m.state;
     m.total = m.state + (backward ? pl->tile_elems : mifwi::round_up64(4LL * pl->d.nshot, 64));
     return m;
+}
+
+// The time loop of the forward (save 0 | 1: `snap` is written when save == 1) and of the Born pass (save kBorn: `snap` is
+// the background run's, read; p.dmat set; p.fields / psix / psiz the perturbed state).  Step n of the snapshot buffer sits
+// at snap + (n - snap_first) * snap_step.  f NULL: nothing is injected.  rec_vx / rec_vz (together) and rec_p NULL: not
+// sampled.  Shots are independent: taken a few at a time, their state and the materials stay inside the Infinity Cache.
+void fl_forward_steps(const mifwi_fluid_plan *pl, FlParams p, int save, const float *f, const int32_t *src_cell,
+                      const float *src_w, const int *bbox, const int32_t *rec_cell, const float *rec_w, float *rec_vx,
+                      float *rec_vz, float *rec_p, float *snap, int snap_first, int n_begin, int n_end, hipStream_t st)
+{
+    const mifwi_fluid_desc &d = pl->d;
+    const bool inject = f != nullptr, want_v = rec_vx != nullptr, want_p = rec_p != nullptr;
+    const FlStepKernels step = fl_step_variant(pl->lx, save);
+    p.ntap_inj = d.ntap; p.inj_cell = src_cell; p.inj_w = src_w; p.inj_bbox = bbox;
+    p.inj_field = d.source_type == 1 ? F_VX : F_VZ;
+    p.nsmp = d.nrec; p.ntap_smp = d.ntap; p.smp_cell = rec_cell; p.smp_w = rec_w;
+    const long long snap_step = 3 * pl->splane * d.nshot;
+    const int lz = kThreads / pl->lx;
+    const int tiles_x = mifwi::ceil_div(pl->ng, pl->lx), tiles_z = mifwi::ceil_div(d.nz, lz);
+    const int extra = want_v ? mifwi::ceil_div(mifwi::ceil_div(d.nrec, kThreads), tiles_x) : 0;
+    p.tiles_z = tiles_z;
+    for (int s0 = 0; s0 < d.nshot; s0 += pl->pass_shots) {
+        const int cs = std::min(pl->pass_shots, d.nshot - s0);
+        p.s0 = s0;
+        for (int n = n_begin; n < n_end; ++n) {
+            p.S = save ? snap + (long long)(n - snap_first) * snap_step : nullptr;
+            p.inj_amp0 = inject ? f + (long long)n * d.nshot * d.nsrc : nullptr;
+            FlParams pv = p, pp = p;
+            pv.ninj = (inject && d.source_type != 0) ? d.nsrc : 0;
+            pp.ninj = (inject && d.source_type == 0) ? d.nsrc : 0;
+            hipLaunchKernelGGL(step.v, dim3(tiles_x, tiles_z, cs), dim3(kThreads), 0, st, pv);
+            pp.smp_out0 = want_v ? rec_vx + (long long)n * d.nshot * d.nrec : nullptr;
+            pp.smp_out1 = want_v ? rec_vz + (long long)n * d.nshot * d.nrec : nullptr;
+            hipLaunchKernelGGL(step.p, dim3(tiles_x, tiles_z + extra, cs), dim3(kThreads), 0, st, pp);
+            if (want_p) {
+                FlParams pq = p;
+                pq.gs = cs; pq.smp_out0 = rec_p + (long long)n * d.nshot * d.nrec;
+                hipLaunchKernelGGL(fl_sample_pressure, dim3(mifwi::ceil_div(cs * d.nrec, 64)), dim3(64), 0, st, pq);
+            }
+        }
+    }
 }
 
 }  // namespace
@@ -936,39 +1002,47 @@ int mifwi_fluid_forward(mifwi_fluid_plan *pl, const float *mat, const float *pz,
     int *bbox = reinterpret_cast<int *>(work + m.bbox);
     const bool inject = d.nsrc > 0;
     if (inject) launch_points_bbox(src_cell, d.nshot, d.nsrc * d.ntap, d.nx, bbox, st);
-    const bool want_v = rec_vx != nullptr && d.nrec > 0, want_p = rec_p != nullptr && d.nrec > 0;
-    const FlStepKernels step = fl_step_variant(pl->lx, snap != nullptr);
     FlParams p = fl_base(pl, mat, pz, px);
     p.fields = work + m.fields; p.psix = work + m.psi; p.psiz = p.psix + pl->psix_elems;
-    p.ntap_inj = d.ntap; p.inj_cell = src_cell; p.inj_w = src_w; p.inj_bbox = bbox;
-    p.inj_field = d.source_type == 1 ? F_VX : F_VZ;
-    p.nsmp = d.nrec; p.ntap_smp = d.ntap; p.smp_cell = rec_cell; p.smp_w = rec_w;
-    const long long snap_step = 3 * pl->splane * d.nshot;
-    const int lz = kThreads / pl->lx;
-    const int tiles_x = mifwi::ceil_div(pl->ng, pl->lx), tiles_z = mifwi::ceil_div(d.nz, lz);
-    const int extra = want_v ? mifwi::ceil_div(mifwi::ceil_div(d.nrec, kThreads), tiles_x) : 0;
-    p.tiles_z = tiles_z;
-    // shots are independent: taken a few at a time, their state and the materials stay inside the Infinity Cache
-    for (int s0 = 0; s0 < d.nshot; s0 += pl->pass_shots) {
-        const int cs = std::min(pl->pass_shots, d.nshot - s0);
-        p.s0 = s0;
-        for (int n = n_begin; n < n_end; ++n) {
-            p.S = snap ? snap + (long long)(n - n_begin) * snap_step : nullptr;
-            p.inj_amp0 = inject ? f + (long long)n * d.nshot * d.nsrc : nullptr;
-            FlParams pv = p, pp = p;
-            pv.ninj = (inject && d.source_type != 0) ? d.nsrc : 0;
-            pp.ninj = (inject && d.source_type == 0) ? d.nsrc : 0;
-            hipLaunchKernelGGL(step.v, dim3(tiles_x, tiles_z, cs), dim3(kThreads), 0, st, pv);
-            pp.smp_out0 = want_v ? rec_vx + (long long)n * d.nshot * d.nrec : nullptr;
-            pp.smp_out1 = want_v ? rec_vz + (long long)n * d.nshot * d.nrec : nullptr;
-            hipLaunchKernelGGL(step.p, dim3(tiles_x, tiles_z + extra, cs), dim3(kThreads), 0, st, pp);
-            if (want_p) {
-                FlParams pq = p;
-                pq.gs = cs; pq.smp_out0 = rec_p + (long long)n * d.nshot * d.nrec;
-                hipLaunchKernelGGL(fl_sample_pressure, dim3(mifwi::ceil_div(cs * d.nrec, 64)), dim3(64), 0, st, pq);
-            }
-        }
-    }
+    const bool want_v = rec_vx != nullptr && d.nrec > 0, want_p = rec_p != nullptr && d.nrec > 0;
+    fl_forward_steps(pl, p, snap ? 1 : 0, inject ? f : nullptr, src_cell, src_w, bbox, rec_cell, rec_w,
+                     want_v ? rec_vx : nullptr, want_v ? rec_vz : nullptr, want_p ? rec_p : nullptr, snap, n_begin, n_begin,
+                     n_end, st);
+    MIFWI_HIP_TRY(hipGetLastError());
+    return MIFWI_OK;
+}
+
+int mifwi_fluid_born(mifwi_fluid_plan *pl, const float *mat, const float *dmat, const float *pz, const float *px,
+                     const float *df, const int32_t *src_cell, const float *src_w, const int32_t *rec_cell,
+                     const float *rec_w, const float *snap, int32_t snap_first, float *drec_vx, float *drec_vz,
+                     float *drec_p, float *work, int32_t n_begin, int32_t n_end, int32_t flags, void *stream)
+{
+    if (!pl || !mat || !pz || !px) return mifwi::fail(MIFWI_EINVAL, "null argument");
+    if (!dmat || !snap || !work) return mifwi::fail(MIFWI_EINVAL, "born: dmat, snap and work must not be null");
+    const mifwi_fluid_desc &d = pl->d;
+    int rc = mifwi::check_steps(n_begin, n_end, d.nt);
+    if (!rc) rc = mifwi::check_snapshots(snap_first, n_begin);
+    if (rc) return rc;
+    if (snap_first < 0) return mifwi::fail(MIFWI_EINVAL, "born: snap_first %d < 0", snap_first);
+    if (df && d.nsrc > 0 && (!src_cell || !src_w))
+        return mifwi::fail(MIFWI_EINVAL, "df given but src_cell/src_w is null");
+    if ((drec_vx == nullptr) != (drec_vz == nullptr))
+        return mifwi::fail(MIFWI_EINVAL, "drec_vx and drec_vz go together");
+    if ((drec_vx || drec_p) && (!rec_cell || !rec_w))
+        return mifwi::fail(MIFWI_EINVAL, "receiver output needs rec_cell and rec_w");
+    const FlWork m = work_map(pl, false);                 // the perturbed state: the forward's map of `work`
+    hipStream_t st;
+    if ((rc = mifwi::open_call(pl->device, stream, work, m, flags, &st))) return rc;
+    int *bbox = reinterpret_cast<int *>(work + m.bbox);
+    const bool inject = df != nullptr && d.nsrc > 0;
+    if (inject) launch_points_bbox(src_cell, d.nshot, d.nsrc * d.ntap, d.nx, bbox, st);
+    FlParams p = fl_base(pl, mat, pz, px);
+    p.dmat = dmat;
+    p.fields = work + m.fields; p.psix = work + m.psi; p.psiz = p.psix + pl->psix_elems;
+    const bool want_v = drec_vx != nullptr && d.nrec > 0, want_p = drec_p != nullptr && d.nrec > 0;
+    fl_forward_steps(pl, p, kBorn, inject ? df : nullptr, src_cell, src_w, bbox, rec_cell, rec_w,
+                     want_v ? drec_vx : nullptr, want_v ? drec_vz : nullptr, want_p ? drec_p : nullptr,
+                     const_cast<float *>(snap), snap_first, n_begin, n_end, st);
     MIFWI_HIP_TRY(hipGetLastError());
     return MIFWI_OK;
 }
@@ -1056,3 +1130,5 @@ int mifwi_fluid_backward(mifwi_fluid_plan *pl, const float *mat, const float *pz
 }
 
 }  // extern "C"
+
+#include "mifwi_fluid_moments.h"

@@ -189,6 +189,36 @@ __global__ __launch_bounds__(kMT) void pseudo_hessian(const float *vp, const flo
     }
 }
 
+// The fluid propagator's counterpart (three moments, mifwi_fluid_moments.h): pseudo_hessian above with Vs = 0, where
+// L_p = M_p = K_p and the fluid's S0 is the elastic S0 + S1, so (L_p^2 + M_p^2)(M0 + M1) + 4 L_p M_p M5 collapses to
+// 2 K_p^2 M0 - the factor 2 is the two identical stress equations the fluid merges.  H_p = 2 K_p^2 M0 + b_p^2 (M1 + M2).
+__device__ __forceinline__ float fl_hess_of(float K, float b, float m0, float m12)
+{
+    return fmaxf(fmaf(2.0f * K * K, m0, b * b * m12), 0.f);
+}
+template <int MODE>
+__global__ __launch_bounds__(kMT) void fluid_pseudo_hessian(const float *vp, const float *rho, const float *mom, int nz, int nx,
+                                                            int gp, float s, float *ha, float *hrho)
+{
+    const long long k = (long long)blockIdx.x * kMT + threadIdx.x, n = (long long)nz * nx;
+    if (k >= n) return;
+    const int i = (int)(k / nx), j = (int)(k - (long long)i * nx);
+    const long long c = (long long)i * gp + j, pl = (long long)nz * gp;
+    const float m0 = mom[c], m12 = mom[pl + c] + mom[2 * pl + c];
+    const float p = vp[k], r = rho[k];
+    const float brho = r == 0.f ? 0.f : -s / (r * r);          // a term whose divisor is zero contributes 0
+    if (MODE == MIFWI_PARAM_VELOCITY) {
+        ha[k] = fl_hess_of(2.0f * r * p * s, 0.f, m0, m12);
+        hrho[k] = fl_hess_of(p * p * s, brho, m0, m12);
+    } else if (MODE == MIFWI_PARAM_IMPEDANCE) {
+        ha[k] = fl_hess_of(2.0f * p * s, 0.f, m0, m12);
+        hrho[k] = fl_hess_of(-(p * p) * s, brho, m0, m12);
+    } else {
+        ha[k] = fl_hess_of(s, 0.f, m0, m12);
+        hrho[k] = fl_hess_of(0.f, brho, m0, m12);
+    }
+}
+
 // ---- scalar scheme: vp [nz][nx] -> r [nz + 2 pad][nx + 2 pad] = (vp dt / h)^2, the model replicated into the absorbing
 // layer (what the deepwave-shaped shim computes per call: compat/deepwave/scalar.py) ------------------------------------
 __global__ __launch_bounds__(kMT) void coef_fwd(const float *vp, float *r, int nz, int nx, int pad, float c)
@@ -342,6 +372,27 @@ int mifwi_elastic_pseudo_hessian(int device, int32_t parametrization, const floa
         hipLaunchKernelGGL(pseudo_hessian<MIFWI_PARAM_IMPEDANCE>, grid, block, 0, st, vp, vs, rho, moments, nz, nx, gp, dt_over_h, h_a, h_b, h_rho);
     else
         hipLaunchKernelGGL(pseudo_hessian<MIFWI_PARAM_LAME>, grid, block, 0, st, vp, vs, rho, moments, nz, nx, gp, dt_over_h, h_a, h_b, h_rho);
+    MIFWI_HIP_TRY(hipGetLastError());
+    return MIFWI_OK;
+}
+
+int mifwi_fluid_pseudo_hessian(int device, int32_t parametrization, const float *vp, const float *rho, const float *moments,
+                               int32_t nz, int32_t nx, int32_t gp, float dt_over_h, float *h_a, float *h_rho, void *stream)
+{
+    if (!vp || !rho || !moments || !h_a || !h_rho || nz < 1 || nx < 1 || gp < nx)
+        return mifwi::fail(MIFWI_EINVAL, "mifwi_fluid_pseudo_hessian: bad argument");
+    if (parametrization < MIFWI_PARAM_VELOCITY || parametrization > MIFWI_PARAM_LAME)
+        return mifwi::fail(MIFWI_EINVAL, "parametrization %d: 1 = Vp/rho, 2 = Zp/rho, 3 = K/rho", parametrization);
+    MIFWI_HIP_TRY(hipSetDevice(device));
+    hipStream_t st = (hipStream_t)stream;
+    const long long n = (long long)nz * nx;
+    const dim3 grid((unsigned)((n + kMT - 1) / kMT)), block(kMT);
+    if (parametrization == MIFWI_PARAM_VELOCITY)
+        hipLaunchKernelGGL(fluid_pseudo_hessian<MIFWI_PARAM_VELOCITY>, grid, block, 0, st, vp, rho, moments, nz, nx, gp, dt_over_h, h_a, h_rho);
+    else if (parametrization == MIFWI_PARAM_IMPEDANCE)
+        hipLaunchKernelGGL(fluid_pseudo_hessian<MIFWI_PARAM_IMPEDANCE>, grid, block, 0, st, vp, rho, moments, nz, nx, gp, dt_over_h, h_a, h_rho);
+    else
+        hipLaunchKernelGGL(fluid_pseudo_hessian<MIFWI_PARAM_LAME>, grid, block, 0, st, vp, rho, moments, nz, nx, gp, dt_over_h, h_a, h_rho);
     MIFWI_HIP_TRY(hipGetLastError());
     return MIFWI_OK;
 }
