@@ -548,6 +548,41 @@ int mifwi_trace_window(int device, const float *x, float *y, int64_t nt, int64_t
                        const float *trace_w, const float *t_on, const float *t_off, double gamma, void *stream);
 
 /* ======================================================================================
+ * MATCHING FILTER: source-wavelet estimation in front of the objective (DENISE's INV_STF)
+ *
+ * Replaces what DENISE does with INV_STF = 1 (libstfinv): per shot, the filter that best maps the modelled seismograms onto
+ * the recorded ones, carried through the objective.  This library's documented choice (neither binary is available to pin
+ * against; libstfinv works in the frequency domain): the time-domain equivalent, a finite-lag Wiener filter with a water
+ * level.  The library delivers the two device-side pieces; the Toeplitz solve in between is host code in float64
+ * (misfit.solve_matching_filter).
+ * Traces are [nt][nshot][nrec], time slowest.  lag_before >= 0 acausal and lag_after >= 0 causal lags,
+ * nlag = lag_before + lag_after + 1 <= MIFWI_STF_MAX_LAGS; a filter is [nshot][nlag], index i holds lag k = i - lag_before.
+ * Lags may exceed nt: a term whose time index falls outside [0, nt) is absent, never wrapped.
+ *   mifwi_stf_correlate    per shot, in double (a product of two floats is exact there), x = pred, d = obs:
+ *       auto_out[s][j]  = sum_r w^2 sum_t x[t] x[t+j],   j = 0 .. nlag-1
+ *       cross_out[s][i] = sum_r w^2 sum_t d[t] x[t-k],   k = i - lag_before
+ *     trace_w device [nshot][nrec] or NULL (= 1): weights >= 0 that multiply the traces, so the sums carry w^2; a trace with
+ *     w == 0 is not read (it may hold NaN or Inf and changes no bit).  auto_out, cross_out device [nshot][nlag] double.
+ *     No atomics: time ascending inside a receiver's sum, the receivers of a 64-wide tile in index order, the tiles in index
+ *     order; a workgroup never mixes shots, so two identical calls give identical bits and a shot computed alone gives
+ *     the bits it has in the whole call.  work: mifwi_stf_correlate_work_elems(...) floats, 8-byte aligned.
+ *   mifwi_trace_convolve   y[t,s,r] = sum_i filt[s][i] x[t-k, s, r]   (transpose != 0: sum_i filt[s][i] x[t+k, s, r], its
+ *     exact transpose), t in [0, nt); filt device [nshot][nlag] float; float accumulation with one fma per lag in ascending
+ *     i, so |y - exact| <= (nlag + 1) 2^-24 sum_i |filt_i| |x_{t-k}|.  y == x is NOT allowed (every output reads nlag rows).
+ * MIFWI_EINVAL: a null required argument, nt, nshot or nrec < 1, a negative lag, nlag > MIFWI_STF_MAX_LAGS, work not 8-byte
+ * aligned, y == x, nt or nrec beyond 2^31 - 1, more than 65535 shots or 65535 * 64 receivers per shot (launch-grid axes).
+ * ==================================================================================== */
+enum { MIFWI_STF_MAX_LAGS = 1024 };
+
+int64_t mifwi_stf_correlate_work_elems(int64_t nt, int64_t nshot, int64_t nrec, int32_t lag_before, int32_t lag_after);
+int mifwi_stf_correlate(int device, const float *pred, const float *obs, const float *trace_w /* NULL or [nshot][nrec] */,
+                        int64_t nt, int64_t nshot, int64_t nrec, int32_t lag_before, int32_t lag_after,
+                        double *auto_out /* [nshot][nlag] */, double *cross_out /* [nshot][nlag] */, float *work, void *stream);
+int mifwi_trace_convolve(int device, const float *x, float *y, const float *filt /* device, [nshot][nlag] */,
+                         int64_t nt, int64_t nshot, int64_t nrec, int32_t lag_before, int32_t lag_after,
+                         int32_t transpose, void *stream);
+
+/* ======================================================================================
  * GRADIENT CONDITIONING on the device (what sits between d.get_fwi_gradients(...) and fake_Vp.backward(grad))
  *
  * Replaces the numpy / scipy post-processing of the model gradients in the elastic prop() methods:

@@ -30,7 +30,7 @@ import numpy as np
 import torch
 
 from .. import elastic, fluid, misfit, profiles
-from .._lib import MifwiError
+from .._lib import STF_MAX_LAGS, MifwiError
 
 
 class Model:
@@ -231,6 +231,19 @@ def _nice_dt(limit):
     return best
 
 
+def _convolve_host(h, lag_before, wav):
+    """``h`` [nshot, nlag] (index i = lag i - lag_before) convolved with the wavelets ``wav`` [nt, nshot] in float64, cut to
+    the record: [nshot, nt]."""
+    nt = wav.shape[0]
+    out = np.zeros((h.shape[0], nt))
+    for i in range(h.shape[1]):
+        k = i - lag_before
+        lo, hi = max(0, k), min(nt, nt + k)
+        if lo < hi:
+            out[:, lo:hi] += h[:, i:i + 1] * wav[lo - k:hi - k].T
+    return out
+
+
 # ---- what an assignment `d.NAME = value` means here -----------------------------------------------------------------
 # pyapi_denise is an attribute bag written into DENISE's parameter file; the reference configures a run by assignment only
 # (networks.py:7603-7731, 9686-9833, 10419-10505, 10899-11090).  A silent bag would accept a parameter this library does
@@ -240,7 +253,8 @@ _SERVED = frozenset((
     "root", "verbose", "device", "save_folder", "PHYSICS", "TIME", "DT", "FD_ORDER", "FW", "DAMPING", "FPML", "npower",
     "k_max_PML", "FREE_SURF", "QUELLART", "QUELLTYP", "QUELLTYPB", "FC_SPIKE_1", "FC_SPIKE_2", "ORDER_SPIKE", "SEISMO",
     "ITERMAX", "DATA_DIR", "SWS_TAPER_GRAD_HOR", "EXP_TAPER_GRAD_HOR", "GRADT1", "GRADT2", "GRADT3", "GRADT4", "INVMAT1",
-    "EPRECOND", "EPSILON_WE", "TRKILL", "fwi_stages", "loss", "DT_used", "acoustic_kernels"))
+    "EPRECOND", "EPSILON_WE", "TRKILL", "INV_STF", "fwi_stages", "loss", "DT_used", "acoustic_kernels", "stf_filters",
+    "stf_wavelets"))
 # DENISE parameters that cannot change what ONE gradient evaluation (ITERMAX = 1) returns: the MPI decomposition, names of
 # files this shim keeps in memory, logging, model bounds and line-search / optimiser settings that only act on model
 # updates, grid sizes that come from the Model object.  Accepted; one warning per name says so.
@@ -251,7 +265,7 @@ _INERT = frozenset((
     "SIGNAL_FILE", "GRAD_METHOD", "PCG_BETA", "NLBFGS", "EPS_SCALE", "STEPMAX", "SCALEFAC", "TESTSHOT_START", "TESTSHOT_END",
     "TESTSHOT_INCR", "PRO", "MIN_ITER", "SNAP", "SNAP_FORMAT", "SNAP_FILE", "TSNAP1", "TSNAP2", "TSNAPINC", "IDX", "IDY"))
 # parameters that DO change the result and are not built: only their neutral value is accepted
-_NEUTRAL = {"TIMEWIN": 0, "NORMALIZE": 0, "INV_STF": 0, "SPATFILTER": 0, "MODEL_FILTER": 0, "SWS_TAPER_GRAD_VERT": 0,
+_NEUTRAL = {"TIMEWIN": 0, "NORMALIZE": 0, "SPATFILTER": 0, "MODEL_FILTER": 0, "SWS_TAPER_GRAD_VERT": 0,
             "SWS_TAPER_GRAD_SOURCES": 0, "SWS_TAPER_CIRCULAR_PER_SHOT": 0, "SWS_TAPER_FILE": 0, "NDT": 1, "MAXRELERROR": 0,
             "RTMOD": 0, "GRAVITY": 0, "INVMAT": 0, "RUN_MULTIPLE_SHOTS": 1, "READREC": 0, "READMOD": 0,
             "TW_IND": 0, "GAMMA": 0, "BOUNDARY": 0}
@@ -270,6 +284,8 @@ class Denise:
         if name == "acoustic_kernels" and value not in ("elastic", "fluid"):
             raise MifwiError("acoustic_kernels=%r: \"elastic\" (the P-SV kernels with Vs = 0) or \"fluid\" (the "
                              "three-field kernels of physicsbasedfwi2_amd.fluid)" % (value,))
+        if name == "INV_STF" and value not in (0, 1):
+            raise MifwiError("INV_STF=%r not implemented (0: off, 1: the per-shot matching filter of set_stf)" % (value,))
         if name.startswith("_") or name in _SERVED:
             return object.__setattr__(self, name, value)
         if name in _INERT:
@@ -339,6 +355,14 @@ class Denise:
         self.TRKILL = 0
         self._trace_kill = None
         self._time_windows = None
+        # INV_STF: 1 estimates, per shot, the filter that maps the modelled onto the observed seismograms and carries it
+        # through the objective (set_stf() gives its lags and water level; misfit.estimate_matching_filter).  After grad():
+        # stf_filters [nshot, nlag] and stf_wavelets [nshot, nt], the corrected wavelets for Sources(..., wavelets=)
+        self.INV_STF = 0
+        self._stf = None
+        self._wavelets = None
+        self.stf_filters = None
+        self.stf_wavelets = None
         self.fwi_stages = []
         self._observed = None
         self._gradients = None
@@ -399,6 +423,51 @@ class Denise:
         if not float(gamma) >= 0:
             raise MifwiError("gamma=%r: the taper needs gamma >= 0" % (gamma,))
         self._time_windows = (p, np.asarray(before, dtype=np.float64), np.asarray(after, dtype=np.float64), float(gamma))
+
+    # -- source-wavelet estimation (misfit.estimate_matching_filter) -----------------------------------
+    def set_stf(self, before=0.0, after=0.0, water_level=1e-2, per_shot=True, weight=None):
+        """The matching filter of ``INV_STF = 1``: it reaches ``before`` s ahead (acausal lags) and ``after`` s behind
+        (causal lags) in steps of DT; ``water_level`` > 0 is added to the diagonal of the normal equations as a fraction of
+        the zero-lag autocorrelation (1e-2 is this library's default); ``per_shot=False`` estimates one filter for all shots.
+        ``weight``: an optional [nshot, nrec] table of weights >= 0 for the estimate alone (DENISE's TRKILL_STF: 0 takes a
+        trace out of the estimate, not out of the objective); the trace-kill table of TRKILL = 1 applies to both."""
+        if not (float(before) >= 0 and float(after) >= 0):
+            raise MifwiError("set_stf: before=%r and after=%r are lengths in seconds, >= 0" % (before, after))
+        if not float(water_level) > 0:
+            raise MifwiError("set_stf: water_level=%r must be > 0" % (water_level,))
+        if weight is not None:
+            weight = np.asarray(weight.detach().cpu().numpy() if torch.is_tensor(weight) else weight, dtype=np.float64)
+            if weight.ndim != 2 or not np.isfinite(weight).all() or not (weight >= 0).all():
+                raise MifwiError("set_stf: weight is a finite [nshot, nrec] table of weights >= 0")
+        self._stf = (float(before), float(after), float(water_level), bool(per_shot), weight)
+
+    def _stf_filter(self, pairs, sos, dt, shape, dev):
+        """The filter of this run as a float32 device tensor [nshot, nlag] and its acausal lag count: correlations of the
+        (stage-filtered) ``pairs`` (modelled, observed) summed over the components, one solve.  Keeps ``stf_filters``."""
+        before, after, water, per_shot, weight = self._stf
+        lb, la = int(round(before / dt)), int(round(after / dt))
+        if lb + la + 1 > STF_MAX_LAGS:
+            raise MifwiError("set_stf: %g s + %g s at DT=%g s are %d lags; the kernels take %d"
+                             % (before, after, dt, lb + la + 1, STF_MAX_LAGS))
+        w = None
+        if int(self.TRKILL) == 1 and self._trace_kill is not None:
+            w = np.where(self._trace_kill, 0.0, 1.0)
+        if weight is not None:
+            w = weight if w is None else w * weight
+        if w is not None and w.shape != tuple(shape):
+            raise MifwiError("the trace weights of the matching filter are for %s (nshot, nrec), the run has %s"
+                             % (w.shape, tuple(shape)))
+        sel = None if w is None else misfit.TraceSelection(weight=w)
+        a = c = 0.0
+        with torch.no_grad():
+            for v, o in pairs:
+                if sos is not None:
+                    v, o = misfit.trace_filter(v, sos), misfit.trace_filter(o, sos)
+                ai, ci = misfit.stf_correlations(v, o, lb, la, sel)
+                a, c = a + ai, c + ci
+        h = misfit.solve_matching_filter(a, c, water, per_shot, lb)
+        self.stf_filters = h.numpy()
+        return h.to(device=dev, dtype=torch.float32), lb
 
     def _selection(self, shape, dt):
         """The TraceSelection of this run for traces [nshot, nrec] = ``shape``, or None when nothing is selected."""
@@ -503,6 +572,7 @@ class Denise:
         # explosive source: moment-rate density added to sxx and szz; a point force keeps the bare wavelet
         # here and gets dt/(h^2 rho) at the source node from elastic.force_amplitude (differentiable)
         scale = dt / (h * h) if self.QUELLTYP == 1 else 1.0
+        self._wavelets = np.asarray(wav, dtype=np.float64)      # [nt, nshot], Sources.amp applied (for stf_wavelets)
         f = torch.tensor(wav * scale, dtype=torch.float32).view(nt, ns, 1)
         fw = int(self.FW)
         fsurf = bool(int(self.FREE_SURF))
@@ -582,6 +652,9 @@ class Denise:
                              "receiver-side term of 3 is not built)" % self.EPRECOND)
         if not float(self.EPSILON_WE) > 0:
             raise MifwiError("EPSILON_WE=%s: the water level of the preconditioner must be > 0" % self.EPSILON_WE)
+        if int(self.INV_STF) == 1 and self._stf is None:
+            raise MifwiError("INV_STF=1 needs the reach of the matching filter: d.set_stf(before=..., after=... [s], "
+                             "water_level=1e-2)")
         dev, h, dt, nt, g, f, pz, px, fw, fsurf = self._setup(model, src, rec)
         prm, mat = self._materials(model, dev, dt, h, True, fsurf)
         self._pseudo_hessian = elastic.PseudoHessian() if int(self.EPRECOND) == 1 else None
@@ -617,15 +690,25 @@ class Denise:
             objective = lambda v, o: kernel(misfit.trace_window(v, sel), misfit.trace_window(o, sel))
         else:
             objective = lambda v, o: kernel(v, o, sos=sos, select=sel)
-        loss = 0.0
+        comps = []
         if self.QUELLTYPB in (1, 2):
-            loss = loss + objective(fl(vy), fl(oy))
+            comps.append((vy, oy))
         if self.QUELLTYPB in (1, 3):
-            loss = loss + objective(fl(vx), fl(ox))
+            comps.append((vx, ox))
         if self.QUELLTYPB == 4:
             if self._observed_p is None:
                 raise MifwiError("QUELLTYPB=4: pass the observed pressure with set_observed(vx, vy, p=...)")
-            loss = loss + objective(fl(p), fl(self._observed_p.to(dev).permute(1, 0, 2)))
+            comps.append((p, self._observed_p.to(dev).permute(1, 0, 2)))
+        if int(self.INV_STF) == 1:
+            # the propagator is linear and time-invariant in the source: a filter on the modelled traces is a filter on the
+            # wavelet, and it commutes with the stage filter.  One filter per shot from the stage-filtered traces of every
+            # component in the objective, held fixed in the gradient (as DENISE holds the wavelet), in front of `objective`
+            filt, lb = self._stf_filter([(fl(v.detach()), fl(o)) for v, o in comps], sos, dt, vx.shape[1:], dev)
+            comps = [(misfit.trace_convolve(v, filt, lb), o) for v, o in comps]
+            self.stf_wavelets = _convolve_host(self.stf_filters, lb, self._wavelets)
+        loss = 0.0
+        for v, o in comps:
+            loss = loss + objective(fl(v), fl(o))
         loss.backward()
         self.loss = float(loss.detach())
         with open("loss_curve_grad.out", "w") as fh:

@@ -22,6 +22,14 @@ Drop-in for the torch expressions the reference evaluates between the propagator
 
 All return a 0-d tensor that back-propagates into ``pred`` (one kernel pass produces the loss and
 dloss/dpred).  No CPU fallback: CPU tensors raise.
+
+* ``estimate_matching_filter(pred, obs, lag_before, lag_after)`` and ``trace_convolve(x, h, lag_before)`` -- source-wavelet
+  estimation (DENISE's INV_STF) in front of any of the objectives above: per shot, the finite-lag Wiener filter ``h`` with a
+  water level that best maps the modelled traces onto the observed ones (``stf_correlations`` on the device,
+  ``solve_matching_filter`` on the host in float64), and the convolution of traces ``[nt, nshot, nrec]`` with it, whose
+  backward is its exact transpose (csrc/mifwi_stf.hip).  ``l2_half(trace_convolve(pred, h, lag_before), obs, ...)`` is the
+  objective with the wavelet corrected; its gradient is exact with ``h`` held fixed.  This is this library's time-domain
+  choice (libstfinv works in the frequency domain); the default water level 1e-2 is ours.
 """
 import ctypes
 
@@ -318,3 +326,121 @@ def trace_window(x, select):
     """y = W x, W the diagonal of ``select`` (:class:`TraceSelection`), time on axis 0.  Differentiable: W is its own
     transpose, so the backward is the same call."""
     return _TraceWindowFn.apply(x, select)
+
+
+# ---- matching filter: source-wavelet estimation in front of the objective (csrc/mifwi_stf.hip) -------------------------
+def _lags(lag_before, lag_after):
+    lb, la = int(lag_before), int(lag_after)
+    if lb < 0 or la < 0 or lb + la + 1 > _lib.STF_MAX_LAGS:
+        raise ValueError("lags before=%d after=%d: both >= 0 and before + after + 1 <= %d" % (lb, la, _lib.STF_MAX_LAGS))
+    return lb, la
+
+
+def stf_correlations(pred, obs, lag_before, lag_after, select=None):
+    """The correlations behind the matching filter of traces ``[nt, nshot, nrec]``, per shot, summed in double:
+
+        a[s, j] = sum_r w**2 sum_t pred[t] pred[t + j]           j = 0 .. nlag - 1,  nlag = lag_before + lag_after + 1
+        c[s, i] = sum_r w**2 sum_t obs[t] pred[t - (i - lag_before)]
+
+    (terms outside the record are absent).  ``select``: a :class:`TraceSelection` with a ``weight`` only - w multiplies the
+    traces, a trace with w == 0 is not read; window the traces with :func:`trace_window` first if windows are wanted.
+    Returns float64 device tensors ``[nshot, nlag]``.  Fixed summation order: identical calls give identical bits."""
+    if not pred.is_cuda:
+        raise _lib.MifwiError("stf_correlations needs CUDA/HIP tensors (libmifwi has no CPU fallback)")
+    if pred.dim() != 3 or obs.shape != pred.shape:
+        raise ValueError("pred and obs must share one [nt, nshot, nrec] shape")
+    lb, la = _lags(lag_before, lag_after)
+    w = None
+    if select is not None:
+        if select.t_on is not None:
+            raise ValueError("stf_correlations takes trace weights only: apply the time windows to both sides with "
+                             "trace_window(x, select) first and pass a selection that holds the weight alone")
+        w = select._on(pred.device, pred.shape[1:])[0]
+    lib = _lib.load()
+    p = pred.detach().contiguous().float()
+    o = obs.detach().contiguous().float()
+    nt, ns, nr = p.shape
+    a = torch.empty((ns, lb + la + 1), device=p.device, dtype=torch.float64)
+    c = torch.empty_like(a)
+    if p.numel() == 0:
+        raise ValueError("empty traces")
+    work = torch.empty(lib.mifwi_stf_correlate_work_elems(nt, ns, nr, lb, la), device=p.device, dtype=torch.float32)
+    _lib.check(lib.mifwi_stf_correlate(p.device.index or 0, _lib.ptr(p), _lib.ptr(o), _lib.ptr(w), nt, ns, nr, lb, la,
+                                       _lib.ptr(a), _lib.ptr(c), _lib.ptr(work),
+                                       torch.cuda.current_stream(p.device).cuda_stream))
+    return a, c
+
+
+def solve_matching_filter(a, c, water_level=1e-2, per_shot=True, lag_before=0):
+    """The filter of the correlations ``a``, ``c`` ``[nshot, nlag]`` (:func:`stf_correlations`; CPU or device tensors):
+    per shot ``T h = c`` with ``T[i, j] = a[|i - j|] + water_level * a[0] * (i == j)``, solved in float64 on the host.
+    ``water_level`` > 0 (1e-2 is this library's default).  A shot without energy (``a[0] == 0``) gets the unit spike at lag
+    0, which sits at index ``lag_before``.  ``per_shot=False``: the correlations are summed over the shots first and every
+    shot gets the one filter.  Returns float64 CPU ``[nshot, nlag]``.
+
+    The autocorrelation (Toeplitz) method: ``h`` is the exact least-squares filter only when the modelled traces have died
+    out ``lag_after`` samples before the record ends and start ``lag_before`` samples after it begins."""
+    if not float(water_level) > 0:
+        raise ValueError("water_level=%r: the water level must be > 0" % (water_level,))
+    a = torch.as_tensor(a).detach().to("cpu", torch.float64)
+    c = torch.as_tensor(c).detach().to("cpu", torch.float64)
+    if a.dim() != 2 or a.shape != c.shape:
+        raise ValueError("a and c must share one [nshot, nlag] shape")
+    ns, nlag = a.shape
+    if not 0 <= int(lag_before) < nlag:
+        raise ValueError("lag_before=%r is not a lag of a filter with %d taps" % (lag_before, nlag))
+    if not per_shot:
+        a, c = a.sum(0, keepdim=True), c.sum(0, keepdim=True)
+    idx = (torch.arange(nlag)[:, None] - torch.arange(nlag)[None, :]).abs()
+    h = torch.zeros_like(c)
+    for s in range(a.shape[0]):
+        if a[s, 0] == 0:
+            h[s, int(lag_before)] = 1.0
+            continue
+        t = a[s][idx] + float(water_level) * a[s, 0] * torch.eye(nlag, dtype=torch.float64)
+        h[s] = torch.linalg.solve(t, c[s])
+    return h if per_shot else h.expand(ns, nlag).contiguous()
+
+
+class _TraceConvolveFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, h, lag_before, transpose):
+        if not x.is_cuda:
+            raise _lib.MifwiError("trace_convolve needs CUDA/HIP tensors (libmifwi has no CPU fallback)")
+        if x.dim() != 3 or h.dim() != 2 or h.shape[0] != x.shape[1]:
+            raise ValueError("x must be [nt, nshot, nrec] and h [nshot, nlag]")
+        lb, la = _lags(lag_before, h.shape[1] - 1 - int(lag_before))
+        lib = _lib.load()
+        xc = x.detach().contiguous().float()
+        y = torch.empty_like(xc)
+        nt, ns, nr = xc.shape
+        if xc.numel():
+            _lib.check(lib.mifwi_trace_convolve(xc.device.index or 0, _lib.ptr(xc), _lib.ptr(y), _lib.ptr(h), nt, ns, nr, lb, la,
+                                                int(transpose), torch.cuda.current_stream(xc.device).cuda_stream))
+        ctx.h, ctx.lag_before, ctx.transpose = h, lb, transpose
+        return y
+
+    @staticmethod
+    def backward(ctx, g):
+        return _TraceConvolveFn.apply(g, ctx.h, ctx.lag_before, not ctx.transpose), None, None, None
+
+
+def trace_convolve(x, h, lag_before, transpose=False):
+    """y[t, s, r] = sum_i h[s, i] x[t - (i - lag_before), s, r] for traces ``[nt, nshot, nrec]`` and per-shot taps
+    ``h [nshot, nlag]`` (terms outside the record are absent); ``transpose=True``: the same sum with x[t + (i - lag_before)].
+    Differentiable in ``x``: the backward of one is the other.  ``h`` is held fixed (no gradient)."""
+    h = torch.as_tensor(h).detach().to(device=x.device, dtype=torch.float32).contiguous()
+    return _TraceConvolveFn.apply(x, h, int(lag_before), bool(transpose))
+
+
+def estimate_matching_filter(pred, obs, lag_before, lag_after, water_level=1e-2, sos=None, select=None, per_shot=True):
+    """The matching filter of ``pred`` onto ``obs`` (:func:`stf_correlations`, :func:`solve_matching_filter`) as a float32
+    device tensor ``[nshot, nlag]`` for :func:`trace_convolve`.  With ``sos`` it is estimated from the stage-filtered traces
+    of both sides - the filter commutes with the stage, so it belongs in front of ``l2_half(..., sos=sos)`` unchanged.
+    Nothing here is differentiated."""
+    with torch.no_grad():
+        if sos is not None:
+            pred, obs = trace_filter(pred, sos), trace_filter(obs, sos)
+        a, c = stf_correlations(pred, obs, lag_before, lag_after, select)
+    h = solve_matching_filter(a, c, water_level, per_shot, lag_before)
+    return h.to(device=pred.device, dtype=torch.float32)
