@@ -5,12 +5,14 @@ models/networks.py:5464/5491 and ``FWILoss`` does at seisgan/fwi/layers.py:158-1
 
 All arithmetic happens in libmifwi.so (HIP); there is no CPU path here.
 """
+import os
+
 import torch
 
 from . import _lib
 from ._lib import MifwiError
 from ._driver import (_GEOMETRIES, _Geometry, _MomentsHolder, _Plan, _require_cuda, _stream,  # noqa: F401 (re-exported)
-                      pad_columns, ptrs, run_backward, run_forward, segment_length)
+                      Physics, Propagate, linearised, pad_columns)
 
 # snapshots kept resident between forward and backward; above this the time axis is cut
 # into checkpointed segments that are re-propagated during the adjoint (exact, ~1 extra forward)
@@ -36,17 +38,12 @@ class PseudoHessian(_MomentsHolder):
     (``mifwi_acoustic_snapshot_moments``), no extra propagation; ``stride = 4`` reads a quarter of it."""
 
     def _hessian(self, what, parametrization, model, pad, scale):
-        if self.moments is None:
-            raise MifwiError("PseudoHessian.%s: no moments yet - run a backward pass through "
-                             "propagate(..., pseudo_hessian=holder) first" % what)
-        mom = self.moments.contiguous()
+        mom = self._held(what)
         n0, n1 = mom.shape
         pad = int(pad)
         nz, nx = n0 - 2 * pad, n1 - 2 * pad
-        mdl = torch.as_tensor(model).detach().to(device=mom.device, dtype=torch.float32).contiguous()
-        if pad < 0 or tuple(mdl.shape) != (nz, nx):
-            raise MifwiError("PseudoHessian.%s: the model must be [%d, %d] (moments [%d, %d], pad %d), got %s"
-                             % (what, nz, nx, n0, n1, pad, tuple(mdl.shape)))
+        mdl, = self._model_planes(what, mom, (model,), (nz, nx),
+                                  "(moments [%d, %d], pad %d), got %%(got)s" % (n0, n1, pad), pad >= 0)
         out = torch.empty((nz, nx), device=mom.device, dtype=torch.float32)
         with torch.cuda.device(mom.device):
             _lib.check(_lib.load().mifwi_acoustic_pseudo_hessian(
@@ -87,111 +84,46 @@ def _acoustic_inputs(r, q0, q1, cpml_width, gp):
 
 
 def _forward_call(plan, coef, f_d, geo, rec):
-    """``forward(snap_ptr, work_ptr, b, e, flags)`` as the drivers take it; ``rec`` None: a re-run that samples nothing."""
+    """``forward(snap_ptr, work_ptr, b, e, flags)`` as the drivers take it; ``rec`` = [traces], or None: a re-run that
+    samples nothing."""
     lib = _lib.load()
-    args = (plan.handle, *coef, _lib.ptr(f_d), *geo, _lib.ptr(rec))
+    args = (plan.handle, *coef, _lib.ptr(f_d), *geo, _lib.ptr(rec[0] if rec else None))
     return lambda snap, work, b, e, flags: _lib.check(
         lib.mifwi_acoustic_forward(*args, snap, work, b, e, flags, _stream()))
 
 
 def _adjoint_call(plan, coef, geo, g, grad_r, grad_f, work):
-    """``adjoint(snap_ptr, snap_first, hi, lo, flags)`` as the backward driver takes it."""
+    """``adjoint(snap_ptr, snap_first, hi, lo, flags)`` as the backward driver takes it; g = [adjoint source]."""
     lib = _lib.load()
     return lambda snap, first, hi, lo, flags: _lib.check(lib.mifwi_acoustic_backward(
-        plan.handle, *coef, *geo, _lib.ptr(g), snap, first, _lib.ptr(grad_r), _lib.ptr(grad_f), _lib.ptr(work), hi, lo,
+        plan.handle, *coef, *geo, _lib.ptr(g[0]), snap, first, _lib.ptr(grad_r), _lib.ptr(grad_f), _lib.ptr(work), hi, lo,
         flags, _stream()))
 
 
-class _AcousticFn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, r, f, q0, q1, geom, c0, c1, shots_per_group, snapshot_budget, edge_rows, cpml_width=0,
-                pseudo_hessian=None):
-        _require_cuda(r, "r")
-        dev = r.device
-        n0, n1 = r.shape
-        nt, ns, nsrc = f.shape
-        if geom.src_cell.shape[:2] != (ns, nsrc):
-            raise MifwiError("f is [nt,%d,%d] but src_cell is %s" % (ns, nsrc,
-                                                                      tuple(geom.src_cell.shape)))
-        nrec, ntap = geom.rec_cell.shape[1], geom.rec_cell.shape[2]
-        geom.check_cells(n0 * n1, "%dx%d" % (n0, n1))
-        with torch.cuda.device(dev):
-            plan = AcousticPlan(n0, n1, nt, ns, nsrc, nrec, ntap, c0, c1, dev.index,
-                                shots_per_group, edge_rows, cpml_width)
-            lay = plan.layout
-            r_p, q0_d, q1_p = _acoustic_inputs(r, q0, q1, cpml_width, lay.gp)
-            f_d = f.detach().to(dtype=torch.float32).contiguous()
-            rec = torch.empty((nt, ns, nrec), device=dev, dtype=torch.float32)
-            work = torch.empty(lay.work_forward_elems, device=dev, dtype=torch.float32)
-            need_grad = r.requires_grad or f.requires_grad
-            if pseudo_hessian is not None and not need_grad:
-                raise MifwiError("pseudo_hessian: the moments are taken from the snapshots of a backward pass, and "
-                                 "neither r nor f requires a gradient in this run")
-            seg, snap = nt, None
-            if need_grad:
-                seg = segment_length(snapshot_budget, dev, 4 * ns * lay.coef_elems, nt)
-                if seg == nt:
-                    snap = torch.empty((nt, ns, n0, lay.gp), device=dev, dtype=torch.float32)
-            geo = ptrs(geom.src_cell, geom.src_w, geom.rec_cell, geom.rec_w)
-            ckpt = run_forward(_forward_call(plan, ptrs(r_p, q0_d, q1_p), f_d, geo, rec), nt, seg, work,
-                               lay.state_elems, snap)
-            if need_grad:
-                ctx.plan = plan
-                ctx.geom = geom
-                ctx.seg = seg
-                ctx.ckpt = ckpt
-                ctx.snap = snap
-                ctx.dims = (n0, n1, nt, ns, nsrc, nrec)
-                ctx.need_f = f.requires_grad
-                ctx.hess = pseudo_hessian
-                ctx.save_for_backward(r_p, q0_d, q1_p, f_d)
-            else:
-                plan.close()
-        return rec
+def _born_call(plan, coef, dr_p, df_d, geo, snap, drec, work, nt):
+    _lib.check(_lib.load().mifwi_acoustic_born(plan.handle, *coef, _lib.ptr(dr_p), geo[2], geo[3], _lib.ptr(snap), 0,
+                                               _lib.ptr(drec[0]), _lib.ptr(work), 0, nt, _lib.ZERO_STATE, _stream()))
 
-    @staticmethod
-    def backward(ctx, grad_rec):
-        lib = _lib.load()
-        if ctx.plan is None:
-            raise MifwiError("backward through the acoustic propagator was called twice: the forward snapshots "
-                             "(or checkpoints) are freed by the first call - run the forward again")
-        r_p, q0_d, q1_p, f_d = ctx.saved_tensors
-        plan, geom = ctx.plan, ctx.geom
-        lay = plan.layout
-        n0, n1, nt, ns, nsrc, nrec = ctx.dims
-        dev = r_p.device
-        with torch.cuda.device(dev):
-            g = grad_rec.to(dtype=torch.float32).contiguous()
-            grad_r = torch.empty((n0, lay.gp), device=dev, dtype=torch.float32)
-            grad_f = (torch.zeros((nt, ns, nsrc), device=dev, dtype=torch.float32)
-                      if ctx.need_f else None)
-            work = torch.empty(lay.work_backward_elems, device=dev, dtype=torch.float32)
-            hess = ctx.hess
-            moments = None
-            if hess is not None:
-                mom = torch.zeros((n0, lay.gp), device=dev, dtype=torch.float32)
-                mwork = torch.empty(lib.mifwi_acoustic_snapshot_moments_work_elems(plan.handle), device=dev,
-                                    dtype=torch.float32)
 
-                def moments(snap, first, b, e):
-                    # one more read of a snapshot range this pass has in hand, each range once (absolute step numbers, so
-                    # segments select the steps the resident buffer would); G^{nt-1} never reaches a recorded sample
-                    _lib.check(lib.mifwi_acoustic_snapshot_moments(
-                        plan.handle, snap, first, b, e, hess.stride, _lib.ptr(mom), _lib.ptr(mwork), 0, _stream()))
-            coef = ptrs(r_p, q0_d, q1_p)
-            geo = ptrs(geom.src_cell, geom.src_w, geom.rec_cell, geom.rec_w)
-            if nt < 2:                           # no adjoint step, so no visit: nothing writes the gradient
-                grad_r.zero_()
-            run_backward("acoustic", nt, ctx.seg, ctx.snap, _adjoint_call(plan, coef, geo, g, grad_r, grad_f, work), moments,
-                         _forward_call(plan, coef, f_d, geo, None), ctx.ckpt, lay, (ns, n0, lay.gp))
-            if hess is not None:
-                hess._add(mom[:, :n1])
-                ctx.hess = None
-            plan.close()
-            ctx.plan = None
-            ctx.snap = None
-            ctx.ckpt = None
-        return (grad_r[:, :n1].contiguous(), grad_f) + (None,) * 10
+class _Acoustic(Physics):
+    """The scalar scheme as :class:`_driver.Propagate` and :func:`_driver.linearised` see it.  opts: c0, c1,
+    shots_per_group, edge_rows, cpml_width."""
+    name = rule = "acoustic"
+    model = "r"
+    zero_moments = True         # G^{nt-1} never reaches a recorded sample: no range ends the run, a run of one step has none
+    not_served = "products across time checkpoints are not served"
+    weight_returns = "a tensor of the shape of its argument"
+    Plan = AcousticPlan
+    forward_call, adjoint_call, born_call = (staticmethod(fn) for fn in (_forward_call, _adjoint_call, _born_call))
+    inputs = staticmethod(lambda r, q0, q1, gp, o: _acoustic_inputs(r, q0, q1, o["cpml_width"], gp))
+    snap_step = staticmethod(lambda lay, ns: (ns, lay.coef_elems // lay.gp, lay.gp))
+    traces = staticmethod(lambda o: 1)
+    weigh = staticmethod(lambda weight, drec: (weight(drec[0]),))
+
+
+def _options(c0, c1, shots_per_group, edge_rows, cpml_width):
+    return dict(c0=float(c0), c1=float(c1), shots_per_group=int(shots_per_group), edge_rows=int(edge_rows),
+                cpml_width=int(cpml_width))
 
 
 def propagate(r, f, q0, q1, src_cell, src_w, rec_cell, rec_w, c0=1.0, c1=1.0,
@@ -228,16 +160,15 @@ def propagate(r, f, q0, q1, src_cell, src_w, rec_cell, rec_w, c0=1.0, c1=1.0,
         flat = _Geometry(geom.src_cell.reshape(ns, nsrc * ntap, 1), geom.src_w.reshape(ns, nsrc * ntap, 1),
                          geom.rec_cell.reshape(ns, nrec * ntap, 1), geom.rec_w.reshape(ns, nrec * ntap, 1),
                          r.device)
-        rec = _AcousticFn.apply(r, f.repeat_interleave(ntap, dim=2), q0, q1, flat, float(c0), float(c1),
-                                int(shots_per_group), int(snapshot_budget), int(edge_rows), 0, pseudo_hessian)
+        rec, = Propagate.apply(r, f.repeat_interleave(ntap, dim=2), _Acoustic, q0, q1, flat, int(snapshot_budget),
+                               pseudo_hessian, _options(c0, c1, shots_per_group, edge_rows, 0))
         return rec.reshape(rec.shape[0], ns, nrec, ntap).sum(dim=3)
-    return _AcousticFn.apply(r, f, q0, q1, geom, float(c0), float(c1), int(shots_per_group),
-                             int(snapshot_budget), int(edge_rows), int(cpml_width), pseudo_hessian)
+    return Propagate.apply(r, f, _Acoustic, q0, q1, geom, int(snapshot_budget), pseudo_hessian,
+                           _options(c0, c1, shots_per_group, edge_rows, cpml_width))[0]
 
 
 def _flatten_taps_pays(r, f, geom, c0, c1, edge_rows):
     """True when the flattened (single-tap) problem runs on the single-launch kernels' fast paths."""
-    import os
     if os.environ.get("MIFWI_AC_FLATTEN_TAPS", "1") == "0":
         return False
     ns, nsrc, ntap = geom.src_cell.shape
@@ -255,70 +186,14 @@ def _flatten_taps_pays(r, f, geom, c0, c1, edge_rows):
 
 def _linearised(name, r, dr, f, q0, q1, src_cell, src_w, rec_cell, rec_w, c0, c1, cpml_width, snapshot_budget, adjoint,
                 weight):
-    """born / gauss_newton_product: per shot chunk one plan, one background forward with resident snapshots, the Born
-    pass over that buffer and - ``adjoint`` - the adjoint pass over it too.  Returns (rec, drec, hv); rec is None with
+    """born / gauss_newton_product through :func:`_driver.linearised`.  Returns (rec, drec, hv); rec is None with
     ``adjoint``, hv without."""
     _require_cuda(r, "r")
-    dev = r.device
-    lib = _lib.load()
-    geom = _Geometry.get(src_cell, src_w, rec_cell, rec_w, dev)
-    n0, n1 = r.shape
-    nt, ns, nsrc = f.shape
-    if geom.src_cell.shape[:2] != (ns, nsrc):
-        raise MifwiError("f is [nt,%d,%d] but src_cell is %s" % (ns, nsrc, tuple(geom.src_cell.shape)))
-    nrec, ntap = geom.rec_cell.shape[1], geom.rec_cell.shape[2]
-    if tuple(dr.shape) != (n0, n1):
+    if tuple(dr.shape) != tuple(r.shape):
         raise MifwiError("dr must have the shape of r")
-    geom.check_cells(n0 * n1, "%dx%d" % (n0, n1))
-    with torch.cuda.device(dev), torch.no_grad():
-        gp = 4 * ((n1 + 3) // 4)
-        budget = min(int(snapshot_budget), int(0.8 * _lib.free_device_bytes(dev)))
-        chunk = min(ns, budget // (4 * nt * n0 * gp))
-        if chunk < 1:
-            raise MifwiError("%s keeps the forward snapshots of all %d steps resident, and not even one shot's fit the "
-                             "snapshot budget; products across time checkpoints are not served" % (name, nt))
-        r_p, q0_d, q1_p = _acoustic_inputs(r, q0, q1, cpml_width, gp)
-        dr_p = pad_columns(dr.to(dev), gp)
-        f_d = f.detach().to(device=dev, dtype=torch.float32).contiguous()
-        rec = None if adjoint else torch.empty((nt, ns, nrec), device=dev, dtype=torch.float32)
-        drec = torch.empty((nt, ns, nrec), device=dev, dtype=torch.float32)
-        hv = torch.zeros((n0, n1), device=dev, dtype=torch.float32) if adjoint else None
-        coef = ptrs(r_p, q0_d, q1_p)
-        # Born modelling of all shots at once writes its outputs in place; a product's traces stay the chunk's own tensor,
-        # which is what the caller's weight() gets
-        in_place = chunk == ns and not adjoint
-        for a in range(0, ns, chunk):
-            c = min(chunk, ns - a)
-            sl = slice(a, a + c)
-            plan = AcousticPlan(n0, n1, nt, c, nsrc, nrec, ntap, float(c0), float(c1), dev.index, 0, 0, int(cpml_width))
-            try:
-                lay = plan.layout
-                taps = [t[sl].contiguous() for t in (geom.src_cell, geom.src_w, geom.rec_cell, geom.rec_w)]
-                geo = ptrs(*taps)
-                fc = f_d[:, sl].contiguous()
-                rec_c, drc = (rec, drec) if in_place else (
-                    torch.empty((nt, c, nrec), device=dev, dtype=torch.float32) for _ in range(2))
-                work = torch.empty(max(lay.work_forward_elems, lay.work_backward_elems if adjoint else 0), device=dev,
-                                   dtype=torch.float32)
-                snap = torch.empty((nt, c, n0, gp), device=dev, dtype=torch.float32)
-                run_forward(_forward_call(plan, coef, fc, geo, rec_c), nt, nt, work, lay.state_elems, snap)
-                _lib.check(lib.mifwi_acoustic_born(plan.handle, *coef, _lib.ptr(dr_p), geo[2], geo[3], _lib.ptr(snap), 0,
-                                                   _lib.ptr(drc), _lib.ptr(work), 0, nt, _lib.ZERO_STATE, _stream()))
-                if not in_place:
-                    drec[:, sl] = drc
-                    if rec is not None:
-                        rec[:, sl] = rec_c
-                if adjoint and nt >= 2:
-                    g = drc if weight is None else weight(drc)
-                    g = g.detach().to(device=dev, dtype=torch.float32).contiguous()
-                    if g.shape != drc.shape:
-                        raise MifwiError("weight must return a tensor of the shape of its argument")
-                    grad = torch.empty((n0, gp), device=dev, dtype=torch.float32)
-                    run_backward("acoustic", nt, nt, snap, _adjoint_call(plan, coef, geo, g, grad, None, work))
-                    hv += grad[:, :n1]
-            finally:
-                plan.close()
-    return rec, drec, hv
+    rec, drec, hv = linearised(_Acoustic, name, r, dr, f, None, q0, q1, (src_cell, src_w, rec_cell, rec_w), snapshot_budget,
+                               adjoint, weight, _options(c0, c1, 0, 0, cpml_width))
+    return rec and rec[0], drec[0], hv
 
 
 def born(r, f, dr, q0, q1, src_cell, src_w, rec_cell, rec_w, c0=1.0, c1=1.0,

@@ -26,15 +26,11 @@ struct AcMomParams {
     float *part;            // [gridDim.y][n0][gp]
 };
 
-// enough threads to keep the snapshot stream busy (256 CUs x 16 waves), at most 64 partial planes
-constexpr long long kAcMomThreads = 256LL * 16 * 64;
-constexpr int kAcMomMaxSplit = 64;
 constexpr int kAcMomUnroll = 4;
 
-inline int ac_mom_max_split(const mifwi_acoustic_plan *pl)
+inline MomShape ac_mom_shape(const mifwi_acoustic_plan *pl)
 {
-    const long long t = pl->coef_elems / 4;
-    return (int)std::min<long long>(kAcMomMaxSplit, std::max<long long>(1, (kAcMomThreads + t - 1) / t));
+    return {1, pl->coef_elems / 4, pl->coef_elems, pl->d.n1};
 }
 
 __device__ __forceinline__ void ac_mom_add(float4 &m, const float4 &v)
@@ -69,41 +65,20 @@ extern "C" {
 
 int64_t mifwi_acoustic_snapshot_moments_work_elems(const mifwi_acoustic_plan *pl)
 {
-    return pl ? pl->coef_elems * ac_mom_max_split(pl) : 0;
+    return moments_work_elems(pl, ac_mom_shape);
 }
 
 int mifwi_acoustic_snapshot_moments(mifwi_acoustic_plan *pl, const float *snap, int32_t snap_first, int32_t n_begin,
                                     int32_t n_end, int32_t stride, float *moments, float *work, int32_t flags, void *stream)
 {
-    if (!pl || !snap || !moments || !work) return mifwi::fail(MIFWI_EINVAL, "null argument");
-    const mifwi_acoustic_desc &d = pl->d;
-    int rc = moments_check(d.nt, snap, moments, work, snap_first, n_begin, n_end, stride);
-    if (rc) return rc;
-    hipStream_t st;
-    if ((rc = mifwi::select_device(pl->device, stream, &st))) return rc;
-    // selected steps: the multiples of stride inside the range (absolute n, so a run cut into ranges anywhere selects
-    // the same steps as the whole run)
-    const long long first = ((long long)n_begin + stride - 1) / stride * stride;
-    const int nsel = first < n_end ? (int)((n_end - 1 - first) / stride) + 1 : 0;
-    const long long snap_step = pl->coef_elems * d.nshot;
-    int nsplit = 0;
-    if (nsel > 0) {
-        AcMomParams m;
-        m.per = mifwi::ceil_div(nsel, std::min(nsel, ac_mom_max_split(pl)));
-        nsplit = mifwi::ceil_div(nsel, m.per);
-        m.snap = snap + (first - snap_first) * snap_step;
-        m.step = (long long)stride * snap_step;
+    return snapshot_moments<AcMomParams>(pl, ac_mom_shape, snap, snap_first, n_begin, n_end, stride, moments, work, flags,
+                                         stream, [pl](AcMomParams &m, int nsplit, hipStream_t st) {
         m.shot = pl->coef_elems;
-        m.nshot = d.nshot;
+        m.nshot = pl->d.nshot;
         m.ngr = (int)(pl->coef_elems / 4);
-        m.nsel = nsel;
-        m.part = work;
         const dim3 grid((unsigned)mifwi::ceil_div(m.ngr, kThreads), nsplit), block(kThreads);
         hipLaunchKernelGGL(ac_snapshot_moments, grid, block, 0, st, m);
-    }
-    launch_moments_sum(work, nsplit, pl->coef_elems, pl->gp, d.n1, (float)stride, (flags & MIFWI_ZERO_STATE) ? 0 : 1, moments, st);
-    MIFWI_HIP_TRY(hipGetLastError());
-    return MIFWI_OK;
+    });
 }
 
 }  // extern "C"

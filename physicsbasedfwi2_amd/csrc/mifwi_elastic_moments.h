@@ -27,21 +27,13 @@ struct MomParams {
     float *part;            // [gridDim.y][6][nz][gp], row-major whatever the snapshot layout
 };
 
-// enough threads to keep the snapshot stream busy (256 CUs x 16 waves), at most 64 partial planes
-constexpr long long kMomThreads = 256LL * 16 * 64;
-constexpr int kMomMaxSplit = 64;
-
 // threads of one partial plane: the 4-cell groups in the order they lie in a snapshot plane (blocked planes carry the
 // pad groups of their last column block)
 inline long long mom_threads(const mifwi_elastic_plan *pl)
 {
     return pl->sblk ? 16LL * mifwi::ceil_div(pl->ng, 16) * pl->d.nz : (long long)pl->d.nz * pl->ng;
 }
-inline int mom_max_split(const mifwi_elastic_plan *pl)
-{
-    const long long t = mom_threads(pl);
-    return (int)std::min<long long>(kMomMaxSplit, std::max<long long>(1, (kMomThreads + t - 1) / t));
-}
+inline MomShape mom_shape(const mifwi_elastic_plan *pl) { return {6, mom_threads(pl), pl->snap_shot, pl->d.nx}; }
 
 template <bool BF16>
 __global__ __launch_bounds__(kThreads) void el_snapshot_moments(const ElParams p, const MomParams m)
@@ -92,41 +84,19 @@ extern "C" {
 
 int64_t mifwi_elastic_snapshot_moments_work_elems(const mifwi_elastic_plan *pl)
 {
-    return pl ? 6LL * pl->coef_elems * mom_max_split(pl) : 0;
+    return moments_work_elems(pl, mom_shape);
 }
 
 int mifwi_elastic_snapshot_moments(mifwi_elastic_plan *pl, const float *snap, int32_t snap_first, int32_t n_begin,
                                    int32_t n_end, int32_t stride, float *moments, float *work, int32_t flags, void *stream)
 {
-    if (!pl || !snap || !moments || !work) return mifwi::fail(MIFWI_EINVAL, "null argument");
-    const mifwi_elastic_desc &d = pl->d;
-    int rc = moments_check(d.nt, snap, moments, work, snap_first, n_begin, n_end, stride);
-    if (rc) return rc;
-    hipStream_t st;
-    if ((rc = mifwi::select_device(pl->device, stream, &st))) return rc;
-    // selected steps: the multiples of stride inside the range (absolute n, so a run cut into ranges anywhere selects
-    // the same steps as the whole run)
-    const long long first = ((long long)n_begin + stride - 1) / stride * stride;
-    const int nsel = first < n_end ? (int)((n_end - 1 - first) / stride) + 1 : 0;
-    const long long snap_step = pl->snap_shot * d.nshot;
-    int nsplit = 0;
-    if (nsel > 0) {
-        MomParams m;
-        m.per = mifwi::ceil_div(nsel, std::min(nsel, mom_max_split(pl)));
-        nsplit = mifwi::ceil_div(nsel, m.per);
-        m.snap = snap + (first - snap_first) * snap_step;
-        m.step = (long long)stride * snap_step;
-        m.nsel = nsel;
-        m.part = work;
+    return snapshot_moments<MomParams>(pl, mom_shape, snap, snap_first, n_begin, n_end, stride, moments, work, flags, stream,
+                                       [pl](const MomParams &m, int nsplit, hipStream_t st) {
         const ElParams p = el_base(pl, nullptr, nullptr, nullptr);
         const dim3 grid((unsigned)((mom_threads(pl) + kThreads - 1) / kThreads), nsplit), block(kThreads);
         if (pl->snap_bf16) hipLaunchKernelGGL(el_snapshot_moments<true>, grid, block, 0, st, p, m);
         else hipLaunchKernelGGL(el_snapshot_moments<false>, grid, block, 0, st, p, m);
-    }
-    const long long n6 = 6LL * pl->coef_elems;
-    launch_moments_sum(work, nsplit, n6, pl->gp, d.nx, (float)stride, (flags & MIFWI_ZERO_STATE) ? 0 : 1, moments, st);
-    MIFWI_HIP_TRY(hipGetLastError());
-    return MIFWI_OK;
+    });
 }
 
 }  // extern "C"

@@ -26,17 +26,9 @@ struct FlMomParams {
     float *part;            // [gridDim.y][3][nz][gp], row-major
 };
 
-// enough threads to keep the snapshot stream busy (256 CUs x 16 waves), at most 64 partial planes
-constexpr long long kFlMomThreads = 256LL * 16 * 64;
-constexpr int kFlMomMaxSplit = 64;
-
 // threads of one partial plane: the 4-cell groups of a snapshot plane, pad groups of the last column block included
 inline long long fl_mom_threads(const mifwi_fluid_plan *pl) { return pl->splane / 4; }
-inline int fl_mom_max_split(const mifwi_fluid_plan *pl)
-{
-    const long long t = fl_mom_threads(pl);
-    return (int)std::min<long long>(kFlMomMaxSplit, std::max<long long>(1, (kFlMomThreads + t - 1) / t));
-}
+inline MomShape fl_mom_shape(const mifwi_fluid_plan *pl) { return {3, fl_mom_threads(pl), 3 * pl->splane, pl->d.nx}; }
 
 __global__ __launch_bounds__(kThreads) void fl_snapshot_moments(const FlParams p, const FlMomParams m)
 {
@@ -73,40 +65,18 @@ extern "C" {
 
 int64_t mifwi_fluid_snapshot_moments_work_elems(const mifwi_fluid_plan *pl)
 {
-    return pl ? 3LL * pl->coef_elems * fl_mom_max_split(pl) : 0;
+    return moments_work_elems(pl, fl_mom_shape);
 }
 
 int mifwi_fluid_snapshot_moments(mifwi_fluid_plan *pl, const float *snap, int32_t snap_first, int32_t n_begin,
                                  int32_t n_end, int32_t stride, float *moments, float *work, int32_t flags, void *stream)
 {
-    if (!pl || !snap || !moments || !work) return mifwi::fail(MIFWI_EINVAL, "null argument");
-    const mifwi_fluid_desc &d = pl->d;
-    int rc = moments_check(d.nt, snap, moments, work, snap_first, n_begin, n_end, stride);
-    if (rc) return rc;
-    hipStream_t st;
-    if ((rc = mifwi::select_device(pl->device, stream, &st))) return rc;
-    // selected steps: the multiples of stride inside the range (absolute n, so a run cut into ranges anywhere selects
-    // the same steps as the whole run)
-    const long long first = ((long long)n_begin + stride - 1) / stride * stride;
-    const int nsel = first < n_end ? (int)((n_end - 1 - first) / stride) + 1 : 0;
-    const long long snap_step = 3 * pl->splane * d.nshot;
-    int nsplit = 0;
-    if (nsel > 0) {
-        FlMomParams m;
-        m.per = mifwi::ceil_div(nsel, std::min(nsel, fl_mom_max_split(pl)));
-        nsplit = mifwi::ceil_div(nsel, m.per);
-        m.snap = snap + (first - snap_first) * snap_step;
-        m.step = (long long)stride * snap_step;
-        m.nsel = nsel;
-        m.part = work;
+    return snapshot_moments<FlMomParams>(pl, fl_mom_shape, snap, snap_first, n_begin, n_end, stride, moments, work, flags,
+                                         stream, [pl](const FlMomParams &m, int nsplit, hipStream_t st) {
         const FlParams p = fl_base(pl, nullptr, nullptr, nullptr);
         const dim3 grid((unsigned)((fl_mom_threads(pl) + kThreads - 1) / kThreads), nsplit), block(kThreads);
         hipLaunchKernelGGL(fl_snapshot_moments, grid, block, 0, st, p, m);
-    }
-    const long long n3 = 3LL * pl->coef_elems;
-    launch_moments_sum(work, nsplit, n3, pl->gp, d.nx, (float)stride, (flags & MIFWI_ZERO_STATE) ? 0 : 1, moments, st);
-    MIFWI_HIP_TRY(hipGetLastError());
-    return MIFWI_OK;
+    });
 }
 
 }  // extern "C"

@@ -1,23 +1,9 @@
-// What the two snapshot-moments passes share (mifwi_elastic_moments.h, mifwi_acoustic_moments.h): the argument checks of
-// their entry points, and their second launch - the partial planes the first launch left in `work` are added in index
-// order, a fixed order, no atomics.
+// What the three snapshot-moments passes share (mifwi_acoustic_moments.h, mifwi_elastic_moments.h, mifwi_fluid_moments.h):
+// the host body of their entry points - argument checks, selection of the steps, split into partial planes - and their
+// second launch: the partial planes the first launch left in `work` are added in index order, a fixed order, no atomics.
 #pragma once
 
 namespace {
-
-// the argument checks both snapshot-moments entry points open with (behind their null checks)
-inline int moments_check(int nt, const void *snap, const void *moments, const void *work, int snap_first, int n_begin,
-                         int n_end, int stride)
-{
-    if (stride < 1) return mifwi::fail(MIFWI_EINVAL, "stride %d: must be >= 1", stride);
-    if (n_begin < 0 || n_end > nt || n_begin >= n_end)
-        return mifwi::fail(MIFWI_EINVAL, "bad step range [%d,%d) for nt=%d", n_begin, n_end, nt);
-    if (snap_first < 0 || snap_first > n_begin)
-        return mifwi::fail(MIFWI_EINVAL, "snap_first %d lies behind the range [%d,%d)", snap_first, n_begin, n_end);
-    if (((uintptr_t)snap | (uintptr_t)moments | (uintptr_t)work) & 15)
-        return mifwi::fail(MIFWI_EINVAL, "snap, moments and work must be 16-byte aligned");
-    return MIFWI_OK;
-}
 
 constexpr int kMomSumThreads = 256;
 
@@ -47,6 +33,69 @@ inline void launch_moments_sum(const float *part, int nsplit, long long n, int g
 {
     hipLaunchKernelGGL(moments_sum, dim3((unsigned)((n / 4 + kMomSumThreads - 1) / kMomSumThreads)), dim3(kMomSumThreads), 0, st,
                        part, nsplit, n, gp, nx, w, add, out);
+}
+
+// enough threads to keep the snapshot stream busy (256 CUs x 16 waves), at most 64 partial planes
+constexpr long long kMomThreads = 256LL * 16 * 64;
+constexpr int kMomMaxSplit = 64;
+
+// what a pass tells the shared host code about its plan: moment planes, threads of one partial plane (its 4-cell groups
+// in the order they lie in a snapshot plane), floats of one shot in a snapshot step, visible columns of a row
+struct MomShape {
+    int planes;
+    long long threads, snap_shot;
+    int ncol;
+};
+
+inline int moments_max_split(const MomShape &s)
+{
+    return (int)std::min<long long>(kMomMaxSplit, std::max<long long>(1, (kMomThreads + s.threads - 1) / s.threads));
+}
+
+template <class Plan, class Shape>
+int64_t moments_work_elems(const Plan *pl, Shape shape)
+{
+    return pl ? shape(pl).planes * pl->coef_elems * moments_max_split(shape(pl)) : 0;
+}
+
+// The body of mifwi_<physics>_snapshot_moments.  `shape(pl)` -> MomShape; `launch(m, nsplit, st)` launches the pass's own
+// kernel over `nsplit` partial planes with Params m, whose snap, step, nsel, per and part are filled in here.
+template <class Params, class Plan, class Shape, class Launch>
+int snapshot_moments(const Plan *pl, Shape shape, const float *snap, int snap_first, int n_begin, int n_end, int stride,
+                     float *moments, float *work, int flags, void *stream, Launch launch)
+{
+    if (!pl || !snap || !moments || !work) return mifwi::fail(MIFWI_EINVAL, "null argument");
+    const int nt = pl->d.nt;
+    if (stride < 1) return mifwi::fail(MIFWI_EINVAL, "stride %d: must be >= 1", stride);
+    if (n_begin < 0 || n_end > nt || n_begin >= n_end)
+        return mifwi::fail(MIFWI_EINVAL, "bad step range [%d,%d) for nt=%d", n_begin, n_end, nt);
+    if (snap_first < 0 || snap_first > n_begin)
+        return mifwi::fail(MIFWI_EINVAL, "snap_first %d lies behind the range [%d,%d)", snap_first, n_begin, n_end);
+    if (((uintptr_t)snap | (uintptr_t)moments | (uintptr_t)work) & 15)
+        return mifwi::fail(MIFWI_EINVAL, "snap, moments and work must be 16-byte aligned");
+    hipStream_t st;
+    if (int rc = mifwi::select_device(pl->device, stream, &st)) return rc;
+    const MomShape s = shape(pl);
+    // selected steps: the multiples of stride inside the range (absolute n, so a run cut into ranges anywhere selects
+    // the same steps as the whole run)
+    const long long first = ((long long)n_begin + stride - 1) / stride * stride;
+    const int nsel = first < n_end ? (int)((n_end - 1 - first) / stride) + 1 : 0;
+    const long long snap_step = s.snap_shot * pl->d.nshot;
+    int nsplit = 0;
+    if (nsel > 0) {
+        Params m;
+        m.per = mifwi::ceil_div(nsel, std::min(nsel, moments_max_split(s)));
+        nsplit = mifwi::ceil_div(nsel, m.per);
+        m.snap = snap + (first - snap_first) * snap_step;
+        m.step = (long long)stride * snap_step;
+        m.nsel = nsel;
+        m.part = work;
+        launch(m, nsplit, st);
+    }
+    launch_moments_sum(work, nsplit, s.planes * pl->coef_elems, pl->gp, s.ncol, (float)stride,
+                       (flags & MIFWI_ZERO_STATE) ? 0 : 1, moments, st);
+    MIFWI_HIP_TRY(hipGetLastError());
+    return MIFWI_OK;
 }
 
 }  // namespace

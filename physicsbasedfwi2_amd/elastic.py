@@ -13,8 +13,7 @@ import torch
 
 from . import _lib
 from ._lib import MifwiError
-from ._driver import (_Geometry, _MomentsHolder, _Plan, _require_cuda, _stream, pad_columns, ptrs, run_backward,
-                      run_forward, segment_length)
+from ._driver import _Geometry, _MomentsHolder, _Plan, _require_cuda, _stream, Physics, Propagate, linearised, pad_columns
 
 # bytes of snapshot planes + time checkpoints a call may hold (288 GB of HBM per GPU; the rest is left to the caller's
 # network and data); MIFWI_EL_SNAPSHOT_BUDGET_GB overrides it (measurements of the checkpointed path on short runs)
@@ -22,13 +21,21 @@ DEFAULT_SNAPSHOT_BUDGET = int(float(os.environ.get("MIFWI_EL_SNAPSHOT_BUDGET_GB"
 
 
 SNAPSHOT_FORMATS = {"f32": _lib.SNAPSHOT_F32, "bf16": _lib.SNAPSHOT_BF16}
+SOURCE_TYPES = {"explosive": 0, "fx": 1, "fz": 2, 0: 0, 1: 1, 2: 2}
+
+
+def source_type_code(source_type):
+    """"explosive" / "fx" / "fz" (or 0 / 1 / 2) -> the plans' source_type."""
+    try:
+        return SOURCE_TYPES[source_type]
+    except KeyError:
+        raise MifwiError("source_type must be one of %s" % sorted(k for k in SOURCE_TYPES if isinstance(k, str)))
 
 
 def snapshot_mode():
     """Default storage of the five forward snapshot planes between the forward and the adjoint pass:
     "f32" (exact discrete adjoint) unless MIFWI_EL_SNAP=bf16 asks for the compressed planes (see
     :func:`propagate`, ``snapshot_format``)."""
-    import os
     v = os.environ.get("MIFWI_EL_SNAP", "f32").lower()
     if v not in SNAPSHOT_FORMATS:
         raise MifwiError("MIFWI_EL_SNAP must be f32 or bf16 (got %r)" % v)
@@ -180,14 +187,9 @@ class PseudoHessian(_MomentsHolder):
         partials of the collocated materials (include/mifwi.h has the table).  A collocated approximation: the
         staggered averages, the harmonic mu_xz and the effective row 0 under a free surface are ignored.  Finite and
         >= 0 everywhere (a term whose divisor is zero contributes 0)."""
-        if self.moments is None:
-            raise MifwiError("PseudoHessian.hessian: no moments yet - run a backward pass through "
-                             "propagate(..., pseudo_hessian=holder) first")
-        mom = self.moments.contiguous()
+        mom = self._held("hessian")
         _, nz, nx = mom.shape
-        prm = [torch.as_tensor(t).detach().to(device=mom.device, dtype=torch.float32).contiguous() for t in (vp, vs, rho)]
-        if any(tuple(t.shape) != (nz, nx) for t in prm):
-            raise MifwiError("PseudoHessian.hessian: the model must be [%d, %d] like the moments" % (nz, nx))
+        prm = self._model_planes("hessian", mom, (vp, vs, rho), (nz, nx))
         out = torch.empty((3, nz, nx), device=mom.device, dtype=torch.float32)
         with torch.cuda.device(mom.device):
             _lib.check(_lib.load().mifwi_elastic_pseudo_hessian(
@@ -244,11 +246,6 @@ class _SnapshotArena:
         return self.buf[:need].view(nt, elems)
 
 
-def _padded_planes(t, gp):
-    """[5, nz, nx] -> float32 [5, nz, gp] on the same device, pad columns 0 (the layout of ``mat`` in include/mifwi.h)."""
-    return pad_columns(t, gp)
-
-
 def _padded_inputs(mat, pz, px, gp):
     """The material planes and C-PML tables as the C calls take them: on mat's device, rows padded to gp columns
     (materials and a, b 0, 1/kappa - rows 2 and 5 of the table - 1 there)."""
@@ -258,136 +255,104 @@ def _padded_inputs(mat, pz, px, gp):
     return pad_columns(mat, gp), pz.to(device=dev, dtype=torch.float32).contiguous(), px_p
 
 
-def _forward_call(plan, coef, f_d, geo, rvx, rvz):
-    """``forward(snap_ptr, work_ptr, b, e, flags)`` as the drivers take it; rvx, rvz None: a re-run that samples nothing."""
+def _forward_call(plan, coef, f_d, geo, rec):
+    """``forward(snap_ptr, work_ptr, b, e, flags)`` as the drivers take it; rec = [rec_vx, rec_vz, ...] (pressure traces
+    are bound to the plan), or None: a re-run that samples nothing."""
     lib = _lib.load()
+    rvx, rvz = rec[:2] if rec else (None, None)
     args = (plan.handle, *coef, _lib.ptr(f_d), *geo, _lib.ptr(rvx), _lib.ptr(rvz))
     return lambda snap, work, b, e, flags: _lib.check(
         lib.mifwi_elastic_forward(*args, snap, work, b, e, flags, _stream()))
 
 
-def _adjoint_call(plan, coef, geo, gx, gz, grad_mat, grad_f, work):
-    """``adjoint(snap_ptr, snap_first, hi, lo, flags)`` as the backward driver takes it."""
+def _adjoint_call(plan, coef, geo, g, grad_mat, grad_f, work):
+    """``adjoint(snap_ptr, snap_first, hi, lo, flags)`` as the backward driver takes it; g = [g_vx, g_vz]."""
     lib = _lib.load()
     return lambda snap, first, hi, lo, flags: _lib.check(lib.mifwi_elastic_backward(
-        plan.handle, *coef, *geo, _lib.ptr(gx), _lib.ptr(gz), snap, first, _lib.ptr(grad_mat), _lib.ptr(grad_f),
+        plan.handle, *coef, *geo, _lib.ptr(g[0]), _lib.ptr(g[1]), snap, first, _lib.ptr(grad_mat), _lib.ptr(grad_f),
         _lib.ptr(work), hi, lo, flags, _stream()))
 
 
-class _ElasticFn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, mat, f, pz, px, geom, pml_width, shots_per_group, snapshot_budget, free_surface,
-                source_type=0, record_pressure=0, snapshot_format=None, fd_order=4, pseudo_hessian=None):
-        _require_cuda(mat, "mat")
-        dev = mat.device
-        lib = _lib.load()
-        _, nz, nx = mat.shape
-        nt, ns, nsrc = f.shape
-        if geom.src_cell.shape[:2] != (ns, nsrc):
-            raise MifwiError("f is [nt,%d,%d] but src_cell is %s" % (ns, nsrc,
-                                                                      tuple(geom.src_cell.shape)))
-        nrec, ntap = geom.rec_cell.shape[1], geom.rec_cell.shape[2]
-        geom.check_cells(nz * nx, "%dx%d" % (nz, nx))
-        with torch.cuda.device(dev):
-            plan = ElasticPlan(nz, nx, nt, ns, nsrc, nrec, ntap, pml_width, dev.index,
-                               shots_per_group, free_surface, source_type, record_pressure, snapshot_format,
-                               fd_order)
-            lay = plan.layout
-            gp = lay.gp
-            mat_p, pz_d, px_p = _padded_inputs(mat, pz, px, gp)
-            f_d = f.detach().to(dtype=torch.float32).contiguous()
-            rvx = torch.empty((nt, ns, nrec), device=dev, dtype=torch.float32)
-            rvz = torch.empty((nt, ns, nrec), device=dev, dtype=torch.float32)
-            # pressure receivers: sum w (sxx + szz), bound to the plan (mifwi_elastic_plan_bind_pressure)
-            rp = torch.empty((nt, ns, nrec) if record_pressure else (0,), device=dev, dtype=torch.float32)
-            if record_pressure:
-                _lib.check(lib.mifwi_elastic_plan_bind_pressure(plan.handle, _lib.ptr(rp), None))
-            work = torch.empty(lay.work_forward_elems, device=dev, dtype=torch.float32)
-            need_grad = mat.requires_grad or f.requires_grad
-            if pseudo_hessian is not None and not need_grad:
-                raise MifwiError("pseudo_hessian: the moments are taken from the snapshots of a backward pass, and "
-                                 "neither mat nor f requires a gradient in this run")
-            seg, snap = nt, None
-            arena = _SnapshotArena.current
-            lease = None
-            if need_grad and arena is not None:
-                snap = arena.take(nt, lay.snap_step_elems, dev)       # memory already held: no budget question
-                if snap is not None:
-                    lease = arena.lease()
-            if need_grad and snap is None:
-                seg = segment_length(snapshot_budget, dev, 4 * lay.snap_step_elems, nt)
-                if seg == nt:
-                    snap = torch.empty((nt, lay.snap_step_elems), device=dev, dtype=torch.float32)
-                    if arena is not None and arena.buf is None:
-                        arena.buf = snap.view(-1)
-                        lease = arena.lease()
-            geo = ptrs(geom.src_cell, geom.src_w, geom.rec_cell, geom.rec_w)
-            ckpt = run_forward(_forward_call(plan, ptrs(mat_p, pz_d, px_p), f_d, geo, rvx, rvz), nt, seg, work,
-                               lay.state_elems, snap)
-            if need_grad:
-                ctx.plan, ctx.geom, ctx.seg, ctx.ckpt, ctx.snap = plan, geom, seg, ckpt, snap
-                ctx.lease = lease
-                ctx.dims = (nz, nx, nt, ns, nsrc, nrec)
-                ctx.need_f = f.requires_grad
-                ctx.record_pressure = record_pressure
-                ctx.hess = pseudo_hessian
-                ctx.save_for_backward(mat_p, pz_d, px_p, f_d)
-            else:
-                plan.close()
-        return rvx, rvz, rp
+def _born_call(plan, coef, dmat_p, df_d, geo, snap, drec, work, nt):
+    _lib.check(_lib.load().mifwi_elastic_born(plan.handle, coef[0], _lib.ptr(dmat_p), *coef[1:], _lib.ptr(df_d), *geo,
+                                              _lib.ptr(snap), 0, _lib.ptr(drec[0]), _lib.ptr(drec[1]), _lib.ptr(work), 0, nt,
+                                              _lib.ZERO_STATE, _stream()))
+
+
+class _Elastic(Physics):
+    """The P-SV scheme as :class:`_driver.Propagate` and :func:`_driver.linearised` see it.  opts: pml_width,
+    shots_per_group, free_surface, source_type, record_pressure, snapshot_format, fd_order - the plan's."""
+    name = rule = "elastic"
+    model = "mat"
+    grad_planes, moment_planes = (5,), (6,)
+    not_served = "Born modelling across time checkpoints is not served"
+    weight_returns = "(g_vx, g_vz) of the shape of its arguments"
+    forward_call, adjoint_call, born_call = (staticmethod(fn) for fn in (_forward_call, _adjoint_call, _born_call))
+    Plan = ElasticPlan
+    inputs = staticmethod(lambda mat, pz, px, gp, o: _padded_inputs(mat, pz, px, gp))
+    traces = staticmethod(lambda o: 3 if o["record_pressure"] else 2)
+
+    @classmethod
+    def outputs(cls, plan, shape, dev, o):
+        rec = super().outputs(plan, shape, dev, o)
+        if o["record_pressure"]:      # pressure receivers: sum w (sxx + szz), bound to the plan
+            _lib.check(_lib.load().mifwi_elastic_plan_bind_pressure(plan.handle, _lib.ptr(rec[2]), None))
+        return rec
 
     @staticmethod
-    def backward(ctx, g_vx, g_vz, g_p=None):
-        lib = _lib.load()
-        if ctx.plan is None:
-            raise MifwiError("backward through the elastic propagator was called twice: the forward snapshots "
-                             "(or checkpoints) are freed by the first call - run the forward again")
-        mat_p, pz_d, px_p, f_d = ctx.saved_tensors
-        plan, geom = ctx.plan, ctx.geom
-        lay = plan.layout
-        nz, nx, nt, ns, nsrc, nrec = ctx.dims
-        dev = mat_p.device
-        with torch.cuda.device(dev):
-            gx = (torch.zeros((nt, ns, nrec), device=dev) if g_vx is None
-                  else g_vx.to(dtype=torch.float32).contiguous())
-            gz = (torch.zeros((nt, ns, nrec), device=dev) if g_vz is None
-                  else g_vz.to(dtype=torch.float32).contiguous())
-            if ctx.record_pressure:
-                gp_ = (None if g_p is None or g_p.numel() == 0 else g_p.to(dtype=torch.float32).contiguous())
-                # the forward re-runs of a checkpointed backward must not sample again: rec_p unbound
-                _lib.check(lib.mifwi_elastic_plan_bind_pressure(plan.handle, None, _lib.ptr(gp_)))
-            grad_mat = torch.empty((5, nz, lay.gp), device=dev, dtype=torch.float32)
-            grad_f = (torch.zeros((nt, ns, nsrc), device=dev, dtype=torch.float32)
-                      if ctx.need_f else None)
-            work = torch.empty(lay.work_backward_elems, device=dev, dtype=torch.float32)
-            hess = ctx.hess
-            moments = None
-            if hess is not None:
-                mom = torch.empty((6, nz, lay.gp), device=dev, dtype=torch.float32)
-                mwork = torch.empty(lib.mifwi_elastic_snapshot_moments_work_elems(plan.handle), device=dev,
-                                    dtype=torch.float32)
+    def adjoint_sources(plan, g, shape, dev, o):
+        gx, gz = (torch.zeros(shape, device=dev) if t is None else t.to(dtype=torch.float32).contiguous() for t in g[:2])
+        g_p = None
+        if o["record_pressure"]:
+            g_p = None if g[2] is None or g[2].numel() == 0 else g[2].to(dtype=torch.float32).contiguous()
+            # the forward re-runs of a checkpointed backward must not sample again: rec_p unbound
+            _lib.check(_lib.load().mifwi_elastic_plan_bind_pressure(plan.handle, None, _lib.ptr(g_p)))
+        return [gx, gz, g_p]                # g_p is bound to the plan: the caller keeps it alive with the other two
 
-                def moments(snap, first, b, e):
-                    # one more read of a snapshot range this pass has in hand, each range once (absolute step numbers, so
-                    # segments select the steps the resident buffer would); the range that ends the run comes first
-                    _lib.check(lib.mifwi_elastic_snapshot_moments(
-                        plan.handle, snap, first, b, e, hess.stride, _lib.ptr(mom), _lib.ptr(mwork),
-                        _lib.ZERO_STATE if e == nt else 0, _stream()))
-            coef = ptrs(mat_p, pz_d, px_p)
-            geo = ptrs(geom.src_cell, geom.src_w, geom.rec_cell, geom.rec_w)
-            run_backward("elastic", nt, ctx.seg, ctx.snap, _adjoint_call(plan, coef, geo, gx, gz, grad_mat, grad_f, work),
-                         moments, _forward_call(plan, coef, f_d, geo, None, None), ctx.ckpt, lay, (lay.snap_step_elems,))
-            if hess is not None:
-                hess._add(mom[:, :, :nx])
-                ctx.hess = None
+    @staticmethod
+    def snapshots(snapshot_budget, dev, nt, step):
+        """The tensor of the current :class:`_SnapshotArena` when it is free and large enough (memory already held: no
+        budget question); else as every propagator, and the first resident buffer inside an arena becomes the arena's."""
+        arena = _SnapshotArena.current
+        snap = arena.take(nt, step[0], dev) if arena is not None else None
+        if snap is not None:
+            return nt, snap, arena.lease()
+        seg, snap, _ = Physics.snapshots(snapshot_budget, dev, nt, step)
+        if snap is None or arena is None or arena.buf is not None:
+            return seg, snap, None
+        arena.buf = snap.view(-1)
+        return seg, snap, arena.lease()
+
+    @staticmethod
+    def backward_done(lease):
+        if lease is not None:               # the arena's tensor may serve the next forward
+            lease.released = True
+
+    @staticmethod
+    def shot_chunk(make_plan, dims, budget):
+        n0, n1, nt, ns = dims[:4]
+        return resident_shot_chunk(ns, nt, n0, n1, budget, "f32")
+
+    @staticmethod
+    def chunk_plan(name, make_plan, c, nt, budget):
+        for c in range(c, 0, -1):           # the plan's own plane size decides (column-blocked planes are padded)
+            plan = make_plan(c)
+            if 4 * nt * plan.layout.snap_step_elems <= budget:
+                if plan.layout.snapshot_format != _lib.SNAPSHOT_F32:
+                    plan.close()
+                    raise MifwiError("%s reads f32 snapshot planes: this plan keeps them as bf16" % name)
+                return plan
             plan.close()
-            ctx.plan = None
-            ctx.snap = None
-            ctx.ckpt = None
-            if ctx.lease is not None:               # the arena's tensor may serve the next forward
-                ctx.lease.released = True
-                ctx.lease = None
-        return (grad_mat[:, :, :nx].contiguous(), grad_f) + (None,) * 12
+        return None
+
+
+def _options(pml_width, shots_per_group, free_surface, source_type, record_pressure, snapshot_format, fd_order):
+    st = source_type_code(source_type)
+    if snapshot_format is not None and snapshot_format not in SNAPSHOT_FORMATS:
+        raise MifwiError("snapshot_format must be one of %s" % sorted(SNAPSHOT_FORMATS))
+    return dict(pml_width=int(pml_width), shots_per_group=int(shots_per_group), free_surface=1 if free_surface else 0,
+                source_type=st, record_pressure=1 if record_pressure else 0, snapshot_format=snapshot_format,
+                fd_order=int(fd_order))
 
 
 def propagate(mat, f, pz, px, src_cell, src_w, rec_cell, rec_w, pml_width,
@@ -423,18 +388,10 @@ def propagate(mat, f, pz, px, src_cell, src_w, rec_cell, rec_w, pml_width,
     _require_cuda(mat, "mat")
     geom = _Geometry.get(src_cell, src_w, rec_cell, rec_w, mat.device)
     f = f.to(device=mat.device)
-    try:
-        st = SOURCE_TYPES[source_type]
-    except KeyError:
-        raise MifwiError("source_type must be one of %s" % sorted(k for k in SOURCE_TYPES if isinstance(k, str)))
-    if snapshot_format is not None and snapshot_format not in SNAPSHOT_FORMATS:
-        raise MifwiError("snapshot_format must be one of %s" % sorted(SNAPSHOT_FORMATS))
+    opts = _options(pml_width, shots_per_group, free_surface, source_type, record_pressure, snapshot_format, fd_order)
     if pseudo_hessian is not None and not isinstance(pseudo_hessian, PseudoHessian):
         raise MifwiError("pseudo_hessian must be an elastic.PseudoHessian holder or None")
-    rvx, rvz, rp = _ElasticFn.apply(mat, f, pz, px, geom, int(pml_width), int(shots_per_group),
-                                    int(snapshot_budget), 1 if free_surface else 0, st,
-                                    1 if record_pressure else 0, snapshot_format, int(fd_order), pseudo_hessian)
-    return (rvx, rvz, rp) if record_pressure else (rvx, rvz)
+    return Propagate.apply(mat, f, _Elastic, pz, px, geom, int(snapshot_budget), pseudo_hessian, opts)
 
 
 def materials_jvp(vp, vs, rho, dvp, dvs, drho, dt, h, free_surface=False):
@@ -452,19 +409,11 @@ def materials_jvp(vp, vs, rho, dvp, dvs, drho, dt, h, free_surface=False):
 
 def _linearised(name, mat, dmat, f, pz, px, src_cell, src_w, rec_cell, rec_w, pml_width, df, free_surface, fd_order,
                 snapshot_budget, source_type, record_pressure, snapshot_format, adjoint, weight):
-    """born / gauss_newton_product: per shot chunk one plan, one background forward with resident f32 snapshots, the
-    Born pass over that buffer and - ``adjoint`` - the adjoint pass over it too."""
+    """born / gauss_newton_product through :func:`_driver.linearised`, over resident f32 snapshots.  Returns (background
+    traces, perturbed traces, hv): lists of 2 tensors."""
     _require_cuda(mat, "mat")
-    dev = mat.device
-    lib = _lib.load()
-    geom = _Geometry.get(src_cell, src_w, rec_cell, rec_w, dev)
-    try:
-        st = SOURCE_TYPES[source_type]
-    except KeyError:
-        raise MifwiError("source_type must be one of %s" % sorted(k for k in SOURCE_TYPES if isinstance(k, str)))
-    if snapshot_format is not None and snapshot_format not in SNAPSHOT_FORMATS:
-        raise MifwiError("snapshot_format must be one of %s" % sorted(SNAPSHOT_FORMATS))
-    if st != 0 or record_pressure:
+    opts = _options(pml_width, 0, free_surface, source_type, record_pressure, snapshot_format, fd_order)
+    if opts["source_type"] != 0 or record_pressure:
         raise MifwiError("%s serves explosive sources and velocity receivers only (force sources need df from the "
                          "density at the source node, pressure receivers a sampling pass of their own)" % name)
     if mat.dim() != 3 or mat.shape[0] != 5:
@@ -472,68 +421,8 @@ def _linearised(name, mat, dmat, f, pz, px, src_cell, src_w, rec_cell, rec_w, pm
     if tuple(dmat.shape) != tuple(mat.shape):
         raise MifwiError("dmat must have the shape of mat, %s (got %s)" % (tuple(mat.shape), tuple(dmat.shape)))
     _require_cuda(dmat, "dmat")
-    _, nz, nx = mat.shape
-    nt, ns, nsrc = f.shape
-    if geom.src_cell.shape[:2] != (ns, nsrc):
-        raise MifwiError("f is [nt,%d,%d] but src_cell is %s" % (ns, nsrc, tuple(geom.src_cell.shape)))
-    if df is not None and tuple(df.shape) != tuple(f.shape):
-        raise MifwiError("df must have the shape of f, %s (got %s)" % (tuple(f.shape), tuple(df.shape)))
-    nrec, ntap = geom.rec_cell.shape[1], geom.rec_cell.shape[2]
-    geom.check_cells(nz * nx, "%dx%d" % (nz, nx))
-    with torch.cuda.device(dev), torch.no_grad():
-        f_d = f.detach().to(device=dev, dtype=torch.float32).contiguous()
-        df_d = None if df is None else df.detach().to(device=dev, dtype=torch.float32).contiguous()
-        out = [torch.empty((nt, ns, nrec), device=dev, dtype=torch.float32) for _ in range(4)]
-        hv = torch.zeros((5, nz, nx), device=dev, dtype=torch.float32) if adjoint else None
-        budget = min(int(snapshot_budget), int(0.8 * _lib.free_device_bytes(dev)))
-        chunk = resident_shot_chunk(ns, nt, nz, nx, budget, "f32")
-        a = 0
-        while a < ns:
-            plan = None
-            for c in range(min(chunk, ns - a), 0, -1):     # the plan's own plane size decides (column-blocked planes are padded)
-                plan = ElasticPlan(nz, nx, nt, c, nsrc, nrec, ntap, int(pml_width), dev.index, 0,
-                                   1 if free_surface else 0, 0, 0, snapshot_format, int(fd_order))
-                if 4 * nt * plan.layout.snap_step_elems <= budget:
-                    break
-                plan.close()
-                plan = None
-            if plan is None:
-                raise MifwiError("%s keeps the forward snapshots of all %d steps resident, and not even one shot's fit "
-                                 "the snapshot budget; Born modelling across time checkpoints is not served" % (name, nt))
-            try:
-                lay = plan.layout
-                if lay.snapshot_format != _lib.SNAPSHOT_F32:
-                    raise MifwiError("%s reads f32 snapshot planes: this plan keeps them as bf16" % name)
-                sl = slice(a, a + c)
-                mat_p, pz_d, px_p = _padded_inputs(mat, pz, px, lay.gp)
-                dmat_p = pad_columns(dmat.to(dev), lay.gp)
-                taps = [t[sl].contiguous() for t in (geom.src_cell, geom.src_w, geom.rec_cell, geom.rec_w)]
-                geo = ptrs(*taps)
-                fc = f_d[:, sl].contiguous()
-                dfc = None if df_d is None else df_d[:, sl].contiguous()
-                rec = [torch.empty((nt, c, nrec), device=dev, dtype=torch.float32) for _ in range(4)]
-                work = torch.empty(max(lay.work_forward_elems, lay.work_backward_elems if adjoint else 0), device=dev,
-                                   dtype=torch.float32)
-                snap = torch.empty((nt, lay.snap_step_elems), device=dev, dtype=torch.float32)
-                coef = ptrs(mat_p, pz_d, px_p)
-                run_forward(_forward_call(plan, coef, fc, geo, rec[0], rec[1]), nt, nt, work, lay.state_elems, snap)
-                _lib.check(lib.mifwi_elastic_born(plan.handle, coef[0], _lib.ptr(dmat_p), *coef[1:], _lib.ptr(dfc), *geo,
-                                                  _lib.ptr(snap), 0, _lib.ptr(rec[2]), _lib.ptr(rec[3]), _lib.ptr(work), 0, nt,
-                                                  _lib.ZERO_STATE, _stream()))
-                for o, r in zip(out, rec):
-                    o[:, sl] = r
-                if adjoint:
-                    g = (rec[2], rec[3]) if weight is None else weight(rec[2], rec[3])
-                    g = [t.detach().to(device=dev, dtype=torch.float32).contiguous() for t in g]
-                    if len(g) != 2 or any(t.shape != rec[2].shape for t in g):
-                        raise MifwiError("weight must return (g_vx, g_vz) of the shape of its arguments")
-                    grad = torch.empty((5, nz, lay.gp), device=dev, dtype=torch.float32)
-                    run_backward("elastic", nt, nt, snap, _adjoint_call(plan, coef, geo, g[0], g[1], grad, None, work))
-                    hv += grad[:, :, :nx]
-            finally:
-                plan.close()
-            a += c
-    return out, hv
+    return linearised(_Elastic, name, mat, dmat, f, df, pz, px, (src_cell, src_w, rec_cell, rec_w), snapshot_budget,
+                      adjoint, weight, opts)
 
 
 def born(mat, dmat, f, pz, px, src_cell, src_w, rec_cell, rec_w, pml_width, df=None, free_surface=False, fd_order=4,
@@ -550,9 +439,9 @@ def born(mat, dmat, f, pz, px, src_cell, src_w, rec_cell, rec_w, pml_width, df=N
     not even one shot fits, ``MifwiError`` - Born across time checkpoints is not served, nor are bf16 snapshot planes,
     force sources and pressure receivers (``source_type``, ``record_pressure``, ``snapshot_format`` are accepted so
     that a caller's propagate() arguments can be passed along, and refused)."""
-    out, _ = _linearised("born", mat, dmat, f, pz, px, src_cell, src_w, rec_cell, rec_w, pml_width, df, free_surface,
-                         fd_order, snapshot_budget, source_type, record_pressure, snapshot_format, False, None)
-    return tuple(out)
+    rec, drec, _ = _linearised("born", mat, dmat, f, pz, px, src_cell, src_w, rec_cell, rec_w, pml_width, df, free_surface,
+                               fd_order, snapshot_budget, source_type, record_pressure, snapshot_format, False, None)
+    return tuple(rec) + tuple(drec)
 
 
 def gauss_newton_product(mat, dmat, f, pz, px, src_cell, src_w, rec_cell, rec_w, pml_width, df=None, free_surface=False,
@@ -566,13 +455,10 @@ def gauss_newton_product(mat, dmat, f, pz, px, src_cell, src_w, rec_cell, rec_w,
     or the second derivative of another misfit.  Shots are taken a few at a time like :func:`born` when their
     snapshots do not fit the budget; ``hv`` sums over the chunks and ``weight`` is then called once per chunk with that
     chunk's [nt, shots, nrec] traces, so it must act shot by shot.  Other arguments and refusals as :func:`born`."""
-    out, hv = _linearised("gauss_newton_product", mat, dmat, f, pz, px, src_cell, src_w, rec_cell, rec_w, pml_width, df,
-                          free_surface, fd_order, snapshot_budget, source_type, record_pressure, snapshot_format, True,
-                          weight)
-    return hv, out[2], out[3]
-
-
-SOURCE_TYPES = {"explosive": 0, "fx": 1, "fz": 2, 0: 0, 1: 1, 2: 2}
+    _, drec, hv = _linearised("gauss_newton_product", mat, dmat, f, pz, px, src_cell, src_w, rec_cell, rec_w, pml_width,
+                              df, free_surface, fd_order, snapshot_budget, source_type, record_pressure, snapshot_format,
+                              True, weight)
+    return (hv,) + tuple(drec)
 
 
 def resident_shot_chunk(nshot, nt, nz, nx, snapshot_budget=DEFAULT_SNAPSHOT_BUDGET, snapshot_format=None, device=None):

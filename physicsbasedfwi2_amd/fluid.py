@@ -12,8 +12,7 @@ import torch
 
 from . import _lib, elastic
 from ._lib import MifwiError
-from ._driver import (_Geometry, _MomentsHolder, _Plan, _require_cuda, _stream, pad_columns, ptrs, run_backward,
-                      run_forward, segment_length)
+from ._driver import _Geometry, _MomentsHolder, _Plan, _require_cuda, _stream, Physics, Propagate, linearised, ptrs
 from .elastic import DEFAULT_SNAPSHOT_BUDGET, PARAM_IMPEDANCE, PARAM_LAME, PARAM_VELOCITY, SOURCE_TYPES  # noqa: F401
 
 
@@ -52,14 +51,9 @@ class PseudoHessian(_MomentsHolder):
         """[2, nz, nx]: the pseudo-Hessian planes of (Vp, rho), (Zp, rho) or (K, rho) from the moments held and the
         model the run used: ``H_p = 2 K_p^2 M0 + b_p^2 (M1 + M2)`` (include/mifwi.h has the table) - planes 0 and 2 of
         ``elastic.PseudoHessian.hessian(vp, 0, rho, ...)`` of the elastic route's run.  Finite and >= 0 everywhere."""
-        if self.moments is None:
-            raise MifwiError("PseudoHessian.hessian: no moments yet - run a backward pass through "
-                             "propagate(..., pseudo_hessian=holder) first")
-        mom = self.moments.contiguous()
+        mom = self._held("hessian")
         _, nz, nx = mom.shape
-        prm = [torch.as_tensor(t).detach().to(device=mom.device, dtype=torch.float32).contiguous() for t in (vp, rho)]
-        if any(tuple(t.shape) != (nz, nx) for t in prm):
-            raise MifwiError("PseudoHessian.hessian: the model must be [%d, %d] like the moments" % (nz, nx))
+        prm = self._model_planes("hessian", mom, (vp, rho), (nz, nx))
         out = torch.empty((2, nz, nx), device=mom.device, dtype=torch.float32)
         with torch.cuda.device(mom.device):
             _lib.check(_lib.load().mifwi_fluid_pseudo_hessian(
@@ -68,104 +62,57 @@ class PseudoHessian(_MomentsHolder):
         return out
 
 
-def _forward_call(plan, coef, f_d, geo, rvx, rvz, rp):
-    """``forward(snap_ptr, work_ptr, b, e, flags)`` as the drivers take it; no outputs: a re-run that samples nothing."""
+def _three(tensors):
+    """Device pointers of (vx, vz[, p]) traces, NULL for a missing one."""
+    return ptrs(*(list(tensors or ()) + [None] * 3)[:3])
+
+
+def _forward_call(plan, coef, f_d, geo, rec):
+    """``forward(snap_ptr, work_ptr, b, e, flags)`` as the drivers take it; rec = [rec_vx, rec_vz[, rec_p]], or None: a
+    re-run that samples nothing."""
     lib = _lib.load()
-    args = (plan.handle, *coef, _lib.ptr(f_d), *geo, _lib.ptr(rvx), _lib.ptr(rvz), _lib.ptr(rp))
+    args = (plan.handle, *coef, _lib.ptr(f_d), *geo, *_three(rec))
     return lambda snap, work, b, e, flags: _lib.check(lib.mifwi_fluid_forward(*args, snap, work, b, e, flags, _stream()))
 
 
 def _adjoint_call(plan, coef, geo, g, grad_mat, grad_f, work):
-    """``adjoint(snap_ptr, snap_first, hi, lo, flags)`` as the backward driver takes it; g = (g_vx, g_vz, g_p), each a
+    """``adjoint(snap_ptr, snap_first, hi, lo, flags)`` as the backward driver takes it; g = [g_vx, g_vz[, g_p]], each a
     tensor or None."""
     lib = _lib.load()
     return lambda snap, first, hi, lo, flags: _lib.check(lib.mifwi_fluid_backward(
-        plan.handle, *coef, *geo, *ptrs(*g), snap, first, _lib.ptr(grad_mat), _lib.ptr(grad_f), _lib.ptr(work), hi, lo,
+        plan.handle, *coef, *geo, *_three(g), snap, first, _lib.ptr(grad_mat), _lib.ptr(grad_f), _lib.ptr(work), hi, lo,
         flags, _stream()))
 
 
-class _FluidFn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, mat, f, pz, px, geom, pml_width, shots_per_group, snapshot_budget, free_surface, source_type,
-                record_pressure, fd_order, pseudo_hessian=None):
-        dev = mat.device
-        _, nz, nx = mat.shape
-        nt, ns, nsrc = f.shape
-        if geom.src_cell.shape[:2] != (ns, nsrc):
-            raise MifwiError("f is [nt,%d,%d] but src_cell is %s" % (ns, nsrc, tuple(geom.src_cell.shape)))
-        nrec, ntap = geom.rec_cell.shape[1], geom.rec_cell.shape[2]
-        geom.check_cells(nz * nx, "%dx%d" % (nz, nx))
-        with torch.cuda.device(dev):
-            plan = FluidPlan(nz, nx, nt, ns, nsrc, nrec, ntap, pml_width, dev.index, shots_per_group, free_surface,
-                             source_type, fd_order)
-            lay = plan.layout
-            mat_p, pz_d, px_p = elastic._padded_inputs(mat, pz, px, lay.gp)
-            f_d = f.detach().to(dtype=torch.float32).contiguous()
-            rvx = torch.empty((nt, ns, nrec), device=dev, dtype=torch.float32)
-            rvz = torch.empty((nt, ns, nrec), device=dev, dtype=torch.float32)
-            rp = torch.empty((nt, ns, nrec), device=dev, dtype=torch.float32) if record_pressure else None
-            work = torch.empty(lay.work_forward_elems, device=dev, dtype=torch.float32)
-            need_grad = mat.requires_grad or f.requires_grad
-            if pseudo_hessian is not None and not need_grad:
-                raise MifwiError("pseudo_hessian: the moments are taken from the snapshots of a backward pass, and "
-                                 "neither mat nor f requires a gradient in this run")
-            seg, snap = nt, None
-            if need_grad:
-                seg = segment_length(snapshot_budget, dev, 4 * lay.snap_step_elems, nt)
-                if seg == nt:
-                    snap = torch.empty((nt, lay.snap_step_elems), device=dev, dtype=torch.float32)
-            geo = ptrs(geom.src_cell, geom.src_w, geom.rec_cell, geom.rec_w)
-            ckpt = run_forward(_forward_call(plan, ptrs(mat_p, pz_d, px_p), f_d, geo, rvx, rvz, rp), nt, seg, work,
-                               lay.state_elems, snap)
-            if need_grad:
-                ctx.plan, ctx.geom, ctx.seg, ctx.ckpt, ctx.snap = plan, geom, seg, ckpt, snap
-                ctx.dims = (nz, nx, nt, ns, nsrc, nrec)
-                ctx.need_f = f.requires_grad
-                ctx.hess = pseudo_hessian
-                ctx.save_for_backward(mat_p, pz_d, px_p, f_d)
-            else:
-                plan.close()
-        return rvx, rvz, (rp if record_pressure else torch.empty(0, device=dev))
+def _born_call(plan, coef, dmat_p, df_d, geo, snap, drec, work, nt):
+    _lib.check(_lib.load().mifwi_fluid_born(plan.handle, coef[0], _lib.ptr(dmat_p), *coef[1:], _lib.ptr(df_d), *geo,
+                                            _lib.ptr(snap), 0, *_three(drec), _lib.ptr(work), 0, nt, _lib.ZERO_STATE,
+                                            _stream()))
+
+
+class _Fluid(Physics):
+    """The three-field scheme as :class:`_driver.Propagate` and :func:`_driver.linearised` see it.  opts: pml_width,
+    shots_per_group, free_surface, source_type, fd_order (the plan's) and record_pressure."""
+    name = "fluid"
+    rule = "elastic"
+    model = "mat"
+    grad_planes = moment_planes = (3,)
+    not_served = "Born modelling across time checkpoints is not served"
+    weight_returns = "%(n)d tensors of the shape of its arguments"
+    forward_call, adjoint_call, born_call = (staticmethod(fn) for fn in (_forward_call, _adjoint_call, _born_call))
+    inputs = staticmethod(lambda mat, pz, px, gp, o: elastic._padded_inputs(mat, pz, px, gp))
+    traces = staticmethod(lambda o: 3 if o["record_pressure"] else 2)
 
     @staticmethod
-    def backward(ctx, g_vx, g_vz, g_p=None):
-        lib = _lib.load()
-        if ctx.plan is None:
-            raise MifwiError("backward through the fluid propagator was called twice: the forward snapshots "
-                             "(or checkpoints) are freed by the first call - run the forward again")
-        mat_p, pz_d, px_p, f_d = ctx.saved_tensors
-        plan, geom = ctx.plan, ctx.geom
-        lay = plan.layout
-        nz, nx, nt, ns, nsrc, nrec = ctx.dims
-        dev = mat_p.device
-        with torch.cuda.device(dev):
-            g = [None if t is None or t.numel() == 0 else t.to(dtype=torch.float32).contiguous() for t in (g_vx, g_vz, g_p)]
-            grad_mat = torch.empty((3, nz, lay.gp), device=dev, dtype=torch.float32)
-            grad_f = torch.zeros((nt, ns, nsrc), device=dev, dtype=torch.float32) if ctx.need_f else None
-            work = torch.empty(lay.work_backward_elems, device=dev, dtype=torch.float32)
-            coef = ptrs(mat_p, pz_d, px_p)
-            geo = ptrs(geom.src_cell, geom.src_w, geom.rec_cell, geom.rec_w)
-            hess = ctx.hess
-            moments = None
-            if hess is not None:
-                mom = torch.empty((3, nz, lay.gp), device=dev, dtype=torch.float32)
-                mwork = torch.empty(lib.mifwi_fluid_snapshot_moments_work_elems(plan.handle), device=dev,
-                                    dtype=torch.float32)
+    def plan(dims, device_index, o):
+        return FluidPlan(*dims, o["pml_width"], device_index, o["shots_per_group"], o["free_surface"], o["source_type"],
+                         o["fd_order"])
 
-                def moments(snap, first, b, e):
-                    # one more read of a snapshot range this pass has in hand, each range once (absolute step numbers, so
-                    # segments select the steps the resident buffer would); the range that ends the run comes first
-                    _lib.check(lib.mifwi_fluid_snapshot_moments(
-                        plan.handle, snap, first, b, e, hess.stride, _lib.ptr(mom), _lib.ptr(mwork),
-                        _lib.ZERO_STATE if e == nt else 0, _stream()))
-            run_backward("elastic", nt, ctx.seg, ctx.snap, _adjoint_call(plan, coef, geo, g, grad_mat, grad_f, work), moments,
-                         _forward_call(plan, coef, f_d, geo, None, None, None), ctx.ckpt, lay, (lay.snap_step_elems,))
-            if hess is not None:
-                hess._add(mom[:, :, :nx])
-                ctx.hess = None
-            plan.close()
-            ctx.plan = ctx.snap = ctx.ckpt = None
-        return (grad_mat[:, :, :nx].contiguous(), grad_f) + (None,) * 11
+
+def _options(pml_width, shots_per_group, free_surface, source_type, fd_order, record_pressure):
+    return dict(pml_width=int(pml_width), shots_per_group=int(shots_per_group), free_surface=1 if free_surface else 0,
+                source_type=elastic.source_type_code(source_type), fd_order=int(fd_order),
+                record_pressure=bool(record_pressure))
 
 
 def propagate(mat, f, pz, px, src_cell, src_w, rec_cell, rec_w, pml_width, free_surface=False, source_type="explosive",
@@ -192,15 +139,10 @@ def propagate(mat, f, pz, px, src_cell, src_w, rec_cell, rec_w, pml_width, free_
         raise MifwiError("mat must be [3, nz, nx] (fluid.materials)")
     geom = _Geometry.get(src_cell, src_w, rec_cell, rec_w, mat.device)
     f = f.to(device=mat.device)
-    try:
-        st = SOURCE_TYPES[source_type]
-    except KeyError:
-        raise MifwiError("source_type must be one of %s" % sorted(k for k in SOURCE_TYPES if isinstance(k, str)))
+    opts = _options(pml_width, shots_per_group, free_surface, source_type, fd_order, record_pressure)
     if pseudo_hessian is not None and not isinstance(pseudo_hessian, PseudoHessian):
         raise MifwiError("pseudo_hessian must be a fluid.PseudoHessian holder or None")
-    rvx, rvz, rp = _FluidFn.apply(mat, f, pz, px, geom, int(pml_width), int(shots_per_group), int(snapshot_budget),
-                                  1 if free_surface else 0, st, bool(record_pressure), int(fd_order), pseudo_hessian)
-    return (rvx, rvz, rp) if record_pressure else (rvx, rvz)
+    return Propagate.apply(mat, f, _Fluid, pz, px, geom, int(snapshot_budget), pseudo_hessian, opts)
 
 
 def force_amplitude(wavelet, mat, src_cell, src_w, h, source_type):
@@ -230,85 +172,17 @@ def materials_jvp(vp, rho, dvp, drho, dt, h, free_surface=False):
 
 def _linearised(name, mat, dmat, f, pz, px, src_cell, src_w, rec_cell, rec_w, pml_width, df, free_surface, source_type,
                 record_pressure, fd_order, snapshot_budget, adjoint, weight):
-    """born / gauss_newton_product, on the pattern of ``elastic._linearised``: per shot chunk one plan, one background
-    forward with resident snapshots, the Born pass over that buffer and - ``adjoint`` - the adjoint pass over it too.
-    Returns (background traces, perturbed traces, hv): two lists of 2 or 3 tensors."""
+    """born / gauss_newton_product through :func:`_driver.linearised`.  Returns (background traces, perturbed traces,
+    hv): lists of 2 or 3 tensors."""
     _require_cuda(mat, "mat")
-    dev = mat.device
-    lib = _lib.load()
-    geom = _Geometry.get(src_cell, src_w, rec_cell, rec_w, dev)
-    try:
-        st = SOURCE_TYPES[source_type]
-    except KeyError:
-        raise MifwiError("source_type must be one of %s" % sorted(k for k in SOURCE_TYPES if isinstance(k, str)))
+    opts = _options(pml_width, 0, free_surface, source_type, fd_order, record_pressure)
     if mat.dim() != 3 or mat.shape[0] != 3:
         raise MifwiError("mat must be [3, nz, nx] (fluid.materials)")
     if tuple(dmat.shape) != tuple(mat.shape):
         raise MifwiError("dmat must have the shape of mat, %s (got %s)" % (tuple(mat.shape), tuple(dmat.shape)))
     _require_cuda(dmat, "dmat")
-    _, nz, nx = mat.shape
-    nt, ns, nsrc = f.shape
-    if geom.src_cell.shape[:2] != (ns, nsrc):
-        raise MifwiError("f is [nt,%d,%d] but src_cell is %s" % (ns, nsrc, tuple(geom.src_cell.shape)))
-    if df is not None and tuple(df.shape) != tuple(f.shape):
-        raise MifwiError("df must have the shape of f, %s (got %s)" % (tuple(f.shape), tuple(df.shape)))
-    nrec, ntap = geom.rec_cell.shape[1], geom.rec_cell.shape[2]
-    geom.check_cells(nz * nx, "%dx%d" % (nz, nx))
-    ntr = 3 if record_pressure else 2
-    fs = 1 if free_surface else 0
-
-    def make_plan(c):
-        return FluidPlan(nz, nx, nt, c, nsrc, nrec, ntap, int(pml_width), dev.index, 0, fs, st, int(fd_order))
-    with torch.cuda.device(dev), torch.no_grad():
-        f_d = f.detach().to(device=dev, dtype=torch.float32).contiguous()
-        df_d = None if df is None else df.detach().to(device=dev, dtype=torch.float32).contiguous()
-        rec = [torch.empty((nt, ns, nrec), device=dev, dtype=torch.float32) for _ in range(ntr)]
-        drec = [torch.empty((nt, ns, nrec), device=dev, dtype=torch.float32) for _ in range(ntr)]
-        hv = torch.zeros((3, nz, nx), device=dev, dtype=torch.float32) if adjoint else None
-        budget = min(int(snapshot_budget), int(0.8 * _lib.free_device_bytes(dev)))
-        one = make_plan(1)
-        chunk = min(ns, budget // (4 * nt * one.layout.snap_step_elems))     # the planes of a step are per shot
-        one.close()
-        if chunk < 1:
-            raise MifwiError("%s keeps the forward snapshots of all %d steps resident, and not even one shot's fit "
-                             "the snapshot budget; Born modelling across time checkpoints is not served" % (name, nt))
-        for a in range(0, ns, chunk):
-            c = min(chunk, ns - a)
-            plan = make_plan(c)
-            try:
-                lay = plan.layout
-                sl = slice(a, a + c)
-                mat_p, pz_d, px_p = elastic._padded_inputs(mat, pz, px, lay.gp)
-                dmat_p = pad_columns(dmat.to(dev), lay.gp)
-                taps = [t[sl].contiguous() for t in (geom.src_cell, geom.src_w, geom.rec_cell, geom.rec_w)]
-                geo = ptrs(*taps)
-                fc = f_d[:, sl].contiguous()
-                dfc = None if df_d is None else df_d[:, sl].contiguous()
-                r, dr = ([torch.empty((nt, c, nrec), device=dev, dtype=torch.float32) for _ in range(ntr)] + [None] * (3 - ntr)
-                         for _ in range(2))
-                work = torch.empty(max(lay.work_forward_elems, lay.work_backward_elems if adjoint else 0), device=dev,
-                                   dtype=torch.float32)
-                snap = torch.empty((nt, lay.snap_step_elems), device=dev, dtype=torch.float32)
-                coef = ptrs(mat_p, pz_d, px_p)
-                run_forward(_forward_call(plan, coef, fc, geo, *r), nt, nt, work, lay.state_elems, snap)
-                _lib.check(lib.mifwi_fluid_born(plan.handle, coef[0], _lib.ptr(dmat_p), *coef[1:], _lib.ptr(dfc), *geo,
-                                                _lib.ptr(snap), 0, *ptrs(*dr), _lib.ptr(work), 0, nt, _lib.ZERO_STATE,
-                                                _stream()))
-                for k in range(ntr):
-                    rec[k][:, sl] = r[k]
-                    drec[k][:, sl] = dr[k]
-                if adjoint:
-                    g = tuple(dr[:ntr]) if weight is None else weight(*dr[:ntr])
-                    g = [t.detach().to(device=dev, dtype=torch.float32).contiguous() for t in g]
-                    if len(g) != ntr or any(t.shape != dr[0].shape for t in g):
-                        raise MifwiError("weight must return %d tensors of the shape of its arguments" % ntr)
-                    grad = torch.empty((3, nz, lay.gp), device=dev, dtype=torch.float32)
-                    run_backward("elastic", nt, nt, snap,
-                                 _adjoint_call(plan, coef, geo, g + [None] * (3 - ntr), grad, None, work))
-                    hv += grad[:, :, :nx]
-            finally:
-                plan.close()
-    return rec, drec, hv
+    return linearised(_Fluid, name, mat, dmat, f, df, pz, px, (src_cell, src_w, rec_cell, rec_w), snapshot_budget, adjoint,
+                      weight, opts)
 
 
 def born(mat, dmat, f, pz, px, src_cell, src_w, rec_cell, rec_w, pml_width, df=None, free_surface=False,

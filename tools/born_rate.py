@@ -22,6 +22,7 @@ import torch  # noqa: E402
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from physicsbasedfwi2_amd import _lib, elastic, profiles  # noqa: E402
+from physicsbasedfwi2_amd._driver import pad_columns  # noqa: E402
 
 CASES = [(350, 1700, 6), (100, 300, 32)]
 STEPS, WARMUP, REPS = 200, 20, 5
@@ -43,7 +44,7 @@ def run_case(nz, nx, ns, dev):
     lay = plan.layout
     assert lay.kernel_flags == 0 and lay.snapshot_format == _lib.SNAPSHOT_F32, "not the two-launch f32 plan"
     mat_p, pz_d, px_p = elastic._padded_inputs(mat, pz, px, lay.gp)
-    dmat_p = elastic._padded_planes(dmat, lay.gp)
+    dmat_p = pad_columns(dmat, lay.gp)
     f = (profiles.ricker(12.0, STEPS, dt, 0.1)[:, None, None] * torch.ones(1, ns, 1)).to(dev).contiguous()
     sx = torch.linspace(20, nx - 21, ns).long()
     src_cell = (12 * nx + sx).to(torch.int32).reshape(ns, 1, 1).to(dev)

@@ -109,11 +109,11 @@ def main():
     rvx, rvz = (torch.empty((NT, NS, NREC), device=dev) for _ in range(2))
     work = torch.empty(max(lay.work_forward_elems, lay.work_backward_elems), device=dev)
     snap = torch.empty((NT, lay.snap_step_elems), device=dev)
-    run_forward(fluid._forward_call(plan, coef, f.contiguous(), g, rvx, rvz, None), NT, NT, work, lay.state_elems, snap)
+    run_forward(fluid._forward_call(plan, coef, f.contiguous(), g, [rvx, rvz]), NT, NT, work, lay.state_elems, snap)
     grad = torch.empty((3, NZ, lay.gp), device=dev)
     mom = torch.empty((3, NZ, lay.gp), device=dev)
     mwork = torch.empty(lib.mifwi_fluid_snapshot_moments_work_elems(plan.handle), device=dev)
-    adjoint = fluid._adjoint_call(plan, coef, g, (rvx, rvz, None), grad, None, work)
+    adjoint = fluid._adjoint_call(plan, coef, g, [rvx, rvz], grad, None, work)
 
     def moments(stride):
         _lib.check(lib.mifwi_fluid_snapshot_moments(plan.handle, _lib.ptr(snap), 0, 0, NT, stride, _lib.ptr(mom),
