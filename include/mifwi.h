@@ -300,6 +300,79 @@ int mifwi_acoustic_plan_cluster_slabs(const mifwi_acoustic_plan *plan, int32_t a
 int mifwi_elastic_plan_cluster_slabs(const mifwi_elastic_plan *plan, int32_t adjoint);
 
 /* ======================================================================================
+ * 2-D P-SV ELASTIC propagator in a medium with VERTICAL TRANSVERSE ISOTROPY (VTI; forward + exact discrete adjoint)
+ *
+ * Serves pyapi_denise runs with PHYSICS = 3 (this library's number for the P-SV VTI medium; no DENISE table of PHYSICS
+ * values is at hand to pin against): Thomsen media, where far-offset kinematics need epsilon and delta.  The elastic
+ * scheme above - same grid, staggering, Dp / Dm, C-PML recursion, pz / px tables, free surface, sources, receivers and
+ * five snapshot planes - with four stiffnesses instead of lambda, lambda + 2 mu and mu: c11, c13 and c33 on the sxx / szz
+ * node, c44 on the sxz node.
+ *   mat [6][nz][gp] = c13, c11, c44_xz, dt/(h rho_x), dt/(h rho_z), c33, the stiffnesses times dt/h.  Planes 0..4 stand
+ *                     where the elastic lambda, lambda + 2 mu, mu_xz, bx, bz stand; c33 is appended.  Columns >= nx must
+ *                     be 0; under a free surface row 0 must hold c13 = 0 and c11 - c13^2 / c33 (szz = 0 there).
+ * Forward step n ( ' : through the C-PML; S0..S4 the snapshot planes, as in the elastic scheme):
+ *   V:  unchanged (the elastic V launch):  vx = fmaf(bx, d1' + d2', vx), vz = fmaf(bz, d3' + d4', vz);  S3, S4
+ *   source_type 1 / 2: vx / vz [cell] += w f[n]
+ *   S:  e1 = Dm_x vx, e2 = Dm_z vz, e3 = Dp_z vx, e4 = Dp_x vz;  S0 = e1', S1 = e2', S2 = e3' + e4'
+ *       sxx = fmaf(c11, e1', fmaf(c13, e2', sxx));  szz = fmaf(c13, e1', fmaf(c33, e2', szz));  sxz = fmaf(c44, S2, sxz)
+ *   source_type 0: sxx, szz [cell] += w f[n];  free surface: szz(0,.) = 0
+ * With c33 == c11 every operation is the elastic one: the seismograms of mifwi_elastic_forward bit for bit.
+ * Adjoint step n = nt-1 .. 0, the exact transpose (V^T is the elastic launch):
+ *   S^T: E1 = pmlT(fmaf(c11, sxx_bar, c13 szz_bar)), E2 = pmlT(fmaf(c13, sxx_bar, c33 szz_bar)), E3 = E4 = pmlT(c44 sxz_bar)
+ *        g_c11 += S0 sxx_bar;  g_c33 += S1 szz_bar;  g_c13 = fmaf(S1, sxx_bar, fmaf(S0, szz_bar, g_c13));  g_c44 += S2 sxz_bar
+ *        g_bx += S3 vx_bar, g_bz += S4 vz_bar (the new v_bar)
+ * Born step: after S  dsxx += dmat[1] S0 + dmat[0] S1,  dszz += dmat[0] S0 + dmat[5] S1,  dsxz += dmat[2] S2; V as elastic.
+ * One launch per half step in both directions: there is no single-launch and no fused V+S form, no bf16 snapshot
+ * planes and no pressure receivers.  Snapshots are f32 [nshot][5][nz][gp] planes, blocked by columns of 16 four-cell
+ * groups; grad_mat and dmat are [6][nz][gp] like mat.
+ * ==================================================================================== */
+typedef struct {
+    int32_t nz, nx;          /* grid, z = depth is the slow axis                              */
+    int32_t nt, nshot, nsrc, nrec, ntap;
+    int32_t pml_width;       /* C-PML nodes per side (0 = none)                               */
+    int32_t free_surface;    /* 1: stress-free surface on row 0 (needs nz >= 4)               */
+    int32_t shots_per_group; /* adjoint: shots sharing one gradient accumulator; 0 = auto     */
+    int32_t source_type;     /* 0: explosive (sxx, szz), 1 / 2: point force on vx / vz        */
+    int32_t fd_order;        /* 4 (0 means 4) or 2                                            */
+} mifwi_vti_desc;
+
+typedef struct {
+    int32_t gp, pitch, ngroups, shots_per_group;
+    int64_t coef_elems;           /* nz*gp: one material / gradient plane                     */
+    int64_t state_elems;          /* forward state (5 fields + memory variables) at the start
+                                     of `work`: what a time checkpoint copies                 */
+    int64_t work_forward_elems;
+    int64_t work_backward_elems;
+    int64_t snap_step_elems;      /* floats one time step of the snapshot buffer takes (all shots) */
+} mifwi_vti_layout;
+
+typedef struct mifwi_vti_plan mifwi_vti_plan;
+
+/* MIFWI_EINVAL as mifwi_elastic_plan_create: nulls, bad sizes, ntap other than 1 or 4, a grid too small for the layer */
+int mifwi_vti_plan_create(mifwi_vti_plan **plan, int device, const mifwi_vti_desc *desc);
+int mifwi_vti_plan_destroy(mifwi_vti_plan *plan);
+int mifwi_vti_plan_layout(const mifwi_vti_plan *plan, mifwi_vti_layout *out);
+/* shots per forward pass, shot groups per adjoint pass over the time range (Infinity Cache residency, six planes) */
+int mifwi_vti_plan_pass_sizes(const mifwi_vti_plan *plan, int32_t *forward_shots, int32_t *adjoint_groups);
+/* always 0: the VTI plan runs one launch per half step */
+int mifwi_vti_plan_cluster_slabs(const mifwi_vti_plan *plan, int32_t adjoint);
+
+/* Arguments, step ranges, flags and refusals as mifwi_elastic_forward / _backward / _born; mat, grad_mat, dmat
+ * [6][nz][gp].  Born is served for source_type 0 only. */
+int mifwi_vti_forward(mifwi_vti_plan *plan, const float *mat, const float *pz, const float *px, const float *f,
+                      const int32_t *src_cell, const float *src_w, const int32_t *rec_cell, const float *rec_w,
+                      float *rec_vx, float *rec_vz, float *snap, float *work, int32_t n_begin, int32_t n_end,
+                      int32_t flags, void *stream);
+int mifwi_vti_backward(mifwi_vti_plan *plan, const float *mat, const float *pz, const float *px, const int32_t *src_cell,
+                       const float *src_w, const int32_t *rec_cell, const float *rec_w, const float *g_vx, const float *g_vz,
+                       const float *snap, int32_t snap_first, float *grad_mat, float *grad_f, float *work, int32_t n_hi,
+                       int32_t n_lo, int32_t flags, void *stream);
+int mifwi_vti_born(mifwi_vti_plan *plan, const float *mat, const float *dmat, const float *pz, const float *px,
+                   const float *df, const int32_t *src_cell, const float *src_w, const int32_t *rec_cell, const float *rec_w,
+                   const float *snap, int32_t snap_first, float *drec_vx, float *drec_vz, float *work, int32_t n_begin,
+                   int32_t n_end, int32_t flags, void *stream);
+
+/* ======================================================================================
  * 2-D variable-density ACOUSTIC (fluid) velocity-pressure propagator (forward + exact discrete adjoint)
  *
  * Serves the DENISE runs with PHYSICS = 2 behind pyapi_denise (models/networks.py:10445-10453: an acoustic medium

@@ -67,6 +67,14 @@ class FluidLayout(ctypes.Structure):
                 ("work_backward_elems", ctypes.c_int64), ("snap_step_elems", ctypes.c_int64)]
 
 
+class VtiDesc(ctypes.Structure):
+    _fields_ = list(FluidDesc._fields_)          # the elastic descriptor without record_pressure and snapshot_format
+
+
+class VtiLayout(ctypes.Structure):
+    _fields_ = list(FluidLayout._fields_)
+
+
 EL_KERNEL_FWD_SINGLE_LAUNCH, EL_KERNEL_ADJ_SINGLE_LAUNCH, EL_KERNEL_FWD_FUSED_STEP, EL_KERNEL_ADJ_FUSED_STEP = 1, 2, 4, 8
 EL_KERNEL_FWD_LANE_HALO, EL_KERNEL_ADJ_LANE_HALO = 16, 32
 SNAPSHOT_F32, SNAPSHOT_BF16 = 0, 1
@@ -115,6 +123,14 @@ SIGNATURES = {
     "mifwi_fluid_snapshot_moments": (ctypes.c_int, [_P] * 2 + [ctypes.c_int32] * 4 + [_P] * 2 + [ctypes.c_int32, _P]),
     "mifwi_fluid_pseudo_hessian": (ctypes.c_int, [ctypes.c_int, ctypes.c_int32] + [_P] * 3 + [ctypes.c_int32] * 3 +
                                    [ctypes.c_float] + [_P] * 3),
+    "mifwi_vti_plan_create": (ctypes.c_int, [ctypes.POINTER(_P), ctypes.c_int, ctypes.POINTER(VtiDesc)]),
+    "mifwi_vti_plan_destroy": (ctypes.c_int, [_P]),
+    "mifwi_vti_plan_layout": (ctypes.c_int, [_P, ctypes.POINTER(VtiLayout)]),
+    "mifwi_vti_plan_pass_sizes": (ctypes.c_int, [_P, _P, _P]),
+    "mifwi_vti_plan_cluster_slabs": (ctypes.c_int, [_P, ctypes.c_int32]),
+    "mifwi_vti_forward": (ctypes.c_int, [_P] * 13 + [ctypes.c_int32] * 3 + [_P]),
+    "mifwi_vti_backward": (ctypes.c_int, [_P] * 11 + [ctypes.c_int32] + [_P] * 3 + [ctypes.c_int32] * 3 + [_P]),
+    "mifwi_vti_born": (ctypes.c_int, [_P] * 11 + [ctypes.c_int32] + [_P] * 3 + [ctypes.c_int32] * 3 + [_P]),
     "mifwi_misfit_work_elems": (ctypes.c_int64, [ctypes.c_int32, ctypes.c_int64, ctypes.c_int64]),
     "mifwi_misfit": (ctypes.c_int, [ctypes.c_int, ctypes.c_int32] + [_P] * 3 + [ctypes.c_int64] * 2 +
                      [_P] * 4),

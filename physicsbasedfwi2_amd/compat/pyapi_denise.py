@@ -29,7 +29,7 @@ import struct
 import numpy as np
 import torch
 
-from .. import elastic, fluid, misfit, profiles
+from .. import elastic, fluid, misfit, profiles, vti
 from .._lib import STF_MAX_LAGS, MifwiError
 
 
@@ -255,6 +255,7 @@ _SERVED = frozenset((
     "ITERMAX", "DATA_DIR", "SWS_TAPER_GRAD_HOR", "EXP_TAPER_GRAD_HOR", "GRADT1", "GRADT2", "GRADT3", "GRADT4", "INVMAT1",
     "EPRECOND", "EPSILON_WE", "TRKILL", "INV_STF", "fwi_stages", "loss", "DT_used", "acoustic_kernels", "stf_filters",
     "stf_wavelets"))
+# (PHYSICS = 3, the P-SV VTI medium, takes Thomsen's epsilon and delta through d.set_thomsen(): arrays, not attributes)
 # DENISE parameters that cannot change what ONE gradient evaluation (ITERMAX = 1) returns: the MPI decomposition, names of
 # files this shim keeps in memory, logging, model bounds and line-search / optimiser settings that only act on model
 # updates, grid sizes that come from the Model object.  Accepted; one warning per name says so.
@@ -371,6 +372,8 @@ class Denise:
         self._shots = None
         self._shots_p = None
         self._observed_p = None
+        self._thomsen = None               # (epsilon, delta) of set_thomsen, for PHYSICS = 3
+        self._gradients_thomsen = None
         self.loss = None
 
     # -- protocol no-ops ------------------------------------------------------------------------
@@ -395,6 +398,20 @@ class Denise:
         self._observed = (torch.as_tensor(np.asarray(vx) if not torch.is_tensor(vx) else vx).float(),
                           torch.as_tensor(np.asarray(vy) if not torch.is_tensor(vy) else vy).float())
         self._observed_p = None if p is None else torch.as_tensor(np.asarray(p) if not torch.is_tensor(p) else p).float()
+
+    # -- anisotropy (PHYSICS = 3) -------------------------------------------------------------------
+    def set_thomsen(self, epsilon, delta):
+        """Thomsen's epsilon and delta of a ``PHYSICS = 3`` (P-SV VTI) run: [ny, nx] arrays in the caller's flipud
+        convention, like the planes of :class:`Model`, whose vp and vs are then the vertical velocities.  ``None, None``
+        forgets them."""
+        if epsilon is None and delta is None:
+            self._thomsen = None
+            return
+        e, dl = (np.asarray(a.detach().cpu().numpy() if torch.is_tensor(a) else a, dtype=np.float32) for a in (epsilon, delta))
+        if e.ndim != 2 or e.shape != dl.shape:
+            raise MifwiError("set_thomsen: epsilon and delta are [ny, nx] arrays of one shape (got %s and %s)"
+                             % (e.shape, dl.shape))
+        self._thomsen = (e, dl)
 
     # -- which samples enter the objective (misfit.TraceSelection) -------------------------------------
     def set_trace_kill(self, table):
@@ -514,14 +531,36 @@ class Denise:
                              "plan; use acoustic_kernels=\"elastic\"" % self.EPRECOND)
         return True
 
+    def _vti(self, model=None):
+        """True when this run is a ``PHYSICS = 3`` (P-SV VTI) run; what the VTI propagator does not serve is refused before
+        any device work."""
+        if self.PHYSICS != 3:
+            return False
+        if self._thomsen is None:
+            raise MifwiError("PHYSICS=3 (P-SV VTI) needs Thomsen's parameters: d.set_thomsen(epsilon, delta)")
+        if model is not None and self._thomsen[0].shape != model.vp.shape:
+            raise MifwiError("set_thomsen: epsilon and delta are %s, the model is %s"
+                             % (self._thomsen[0].shape, model.vp.shape))
+        if int(self.INVMAT1) != 1:
+            raise MifwiError("PHYSICS=3: INVMAT1=%s is not served (1: Vp0, Vs0, rho, epsilon, delta)" % self.INVMAT1)
+        if int(self.EPRECOND) != 0:
+            raise MifwiError("PHYSICS=3: the pseudo-Hessian (EPRECOND=%s) is not built for VTI media" % self.EPRECOND)
+        if self.SEISMO != 1 or self.QUELLTYPB == 4:
+            raise MifwiError("PHYSICS=3: pressure seismograms (SEISMO=%s, QUELLTYPB=%s) are not served; SEISMO = 1 and "
+                             "QUELLTYPB 1, 2 or 3" % (self.SEISMO, self.QUELLTYPB))
+        return True
+
     def _setup(self, model, src, rec):
         self._fluid()
-        if self.PHYSICS not in (1, 2):
-            raise MifwiError("PHYSICS=%s not implemented (1 = P-SV elastic, 2 = acoustic)" % self.PHYSICS)
+        if self.PHYSICS not in (1, 2, 3):
+            raise MifwiError("PHYSICS=%s not implemented (1 = P-SV elastic, 2 = acoustic, 3 = P-SV VTI)" % self.PHYSICS)
         dev = torch.device(self.device) if self.device is not None else \
             torch.device("cuda", torch.cuda.current_device())
         h = model.dx
         vmax = float(model.vp.max())
+        if self._vti(model):
+            # the fastest qP phase velocity of a Thomsen medium is bounded by vp0 sqrt(1 + 2 max(epsilon, delta, 0))
+            vmax = vti.max_velocity(model.vp, *self._thomsen)
         # FD_ORDER (left commented at networks.py:10447): 2 or 4 are built (Taylor weights, MAXRELERROR = 0)
         if int(self.FD_ORDER) not in (2, 4):
             raise MifwiError("FD_ORDER=%s not implemented: the staggered-grid stencils are built for order 2 "
@@ -585,9 +624,11 @@ class Denise:
     def _materials(self, model, dev, dt, h, requires_grad, fsurf=False):
         # undo the caller's flipud: internally row 0 is the surface
         # PHYSICS = 2 (acoustic): the same velocity-stress solver in a fluid, Vs = 0 everywhere
-        vs = model.vs if self.PHYSICS == 1 else np.zeros_like(model.vs)
-        prm = [torch.tensor(np.flipud(a).copy(), device=dev, requires_grad=requires_grad)
-               for a in (model.vp, vs, model.rho)]
+        vs = model.vs if self.PHYSICS in (1, 3) else np.zeros_like(model.vs)
+        planes = (model.vp, vs, model.rho) + (self._thomsen if self._vti(model) else ())
+        prm = [torch.tensor(np.flipud(a).copy(), device=dev, requires_grad=requires_grad) for a in planes]
+        if self._vti():
+            return prm, vti.materials(*prm, dt, h, free_surface=fsurf)
         if self._fluid():
             return prm, fluid.materials(prm[0], prm[2], dt, h, free_surface=fsurf)
         return prm, elastic.staggered_materials(prm[0], prm[1], prm[2], dt, h, free_surface=fsurf)
@@ -601,7 +642,11 @@ class Denise:
                                   source_type=kind, record_pressure=self.SEISMO in (2, 4), fd_order=int(self.FD_ORDER))
             return (out[0], out[1], -out[2]) if len(out) == 3 else (out[0], out[1], None)
         if kind != "explosive":
-            f = elastic.force_amplitude(f, mat, g["sc"], g["sw"], h, kind)
+            f = elastic.force_amplitude(f, mat, g["sc"], g["sw"], h, kind)      # planes 3 and 4: the VTI planes' too
+        if self._vti():
+            out = vti.propagate(mat, f, pz, px, g["sc"], g["sw"], g["rc"], g["rw"], fw, free_surface=fsurf,
+                                source_type=kind, fd_order=int(self.FD_ORDER))
+            return out[0], out[1], None
         out = elastic.propagate(mat, f, pz, px, g["sc"], g["sw"], g["rc"], g["rw"], fw,
                                 free_surface=fsurf, source_type=kind, record_pressure=self.SEISMO in (2, 4),
                                 fd_order=int(self.FD_ORDER), pseudo_hessian=pseudo_hessian)
@@ -645,6 +690,7 @@ class Denise:
         if int(self.ITERMAX) != 1:
             raise MifwiError("ITERMAX=%s: grad() is one gradient evaluation (the reference sets ITERMAX = 1 and lets its "
                              "own optimiser update the model)" % self.ITERMAX)
+        self._vti(model)
         if int(self.INVMAT1) not in (1, 2, 3):
             raise MifwiError("INVMAT1=%s not implemented (1: Vp, Vs, rho; 2: Zp, Zs, rho; 3: lambda, mu, rho)" % self.INVMAT1)
         if int(self.EPRECOND) not in (0, 1):
@@ -729,6 +775,9 @@ class Denise:
             w = torch.tensor(gradient_taper(model.ny, h, self.GRADT1, self.GRADT2, self.GRADT3, self.GRADT4,
                                             self.EXP_TAPER_GRAD_HOR), device=dev)[:, None]
             grads = [g * w for g in grads]
+        # PHYSICS = 3: five gradients, (Vp0, Vs0, rho, epsilon, delta); the first three go where they always go
+        self._gradients_thomsen = tuple(np.flipud(g.cpu().numpy()).copy() for g in grads[3:]) if len(grads) == 5 else None
+        grads = grads[:3]
         self._gradients_dev = torch.stack(grads)           # [vp, vs, rho] (INVMAT1 = 2: Zp, Zs, rho; 3: lambda, mu, rho), row 0 = surface
         gvp, gvs, grho = (np.flipud(g.cpu().numpy()).copy() for g in grads)
         self._gradients = {"rho": grho, "vp": gvp, "vs": gvs}
@@ -746,6 +795,14 @@ class Denise:
         sel = [n for n in names if all(k in n for k in keys)]
         out = [self._gradients[n.rsplit("_", 1)[1].split(".")[0]] for n in sel]
         return (out, sel) if return_filenames else out
+
+
+    def get_thomsen_gradients(self):
+        """(epsilon, delta) gradients of the last ``PHYSICS = 3`` grad(), [ny, nx] arrays in the caller's flipud
+        convention, the depth taper of SWS_TAPER_GRAD_HOR applied as to the other three."""
+        if self._gradients_thomsen is None:
+            raise MifwiError("run grad() with PHYSICS = 3 first")
+        return self._gradients_thomsen
 
 
 def conditioned_gradients(d, vp, vs, rho, mute_rows=25, rho_factor=0.1, sigma=0.0):

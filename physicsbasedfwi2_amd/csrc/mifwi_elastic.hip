@@ -25,6 +25,8 @@
 // 256 MiB Infinity Cache (plan->pass_shots / pass_groups).  Grids whose shot fits the LDS of a few CUs run
 // the whole time loop in one launch instead (mifwi_elastic_cluster.h); point forces (source_type 1 / 2) and
 // the opt-in fused V+S launch (el_step_fused) live on the per-step path only.
+// VTI (mifwi_vti_*): the same scheme with c11, c13, c33, c44 for lambda + 2 mu, lambda, mu - one more material plane (M_C33), a
+// compile-time variant of el_step_s, el_adj_s / stage_E and el_finalize on the per-step path; with c33 == c11 the same bits.
 // Arithmetic = the explicit fmaf chain of oracle/elastic.c (build with -ffp-contract=off).
 #include "mifwi_cluster_host.h"
 #include "mifwi_host.h"
@@ -49,6 +51,8 @@ inline FdK fd_weights(int order)
 
 enum { F_VX = 0, F_VZ = 1, F_SXX = 2, F_SZZ = 3, F_SXZ = 4 };
 enum { M_L = 0, M_M = 1, M_MU = 2, M_BX = 3, M_BZ = 4 };
+// VTI variant (mifwi_vti_*): the same planes with c13 at M_L, c11 at M_M, c44_xz at M_MU, and c33 appended as a sixth plane
+enum { M_C33 = 5 };
 enum { PA = 0, PB = 1, PK = 2, PAH = 3, PBH = 4, PKH = 5 };
 // psi index: x strips hold (0: d1 sxx_x @half, 1: d3 sxz_x @int, 2: e1 vx_x @int, 3: e4 vz_x @half)
 //            z strips hold (0: d2 sxz_z @int, 1: d4 szz_z @half, 2: e2 vz_z @int, 3: e3 vx_z @half)
@@ -468,7 +472,9 @@ __global__ __launch_bounds__(kThreads, MIFWI_EL_MINWAVES) void el_step_v(const E
 // ================================================================================================
 // forward S launch: stresses from the new velocities + source injection + receiver sampling
 // ================================================================================================
-template <int LX, int RZ, int SAVE>
+// VTI: sxx = fmaf(c11, e1, fmaf(c13, e2, sxx)), szz = fmaf(c13, e1, fmaf(c33, e2, szz)) with c33 read from plane M_C33 (of
+// mat and, Born step, of dmat); c33 == c11 gives the isotropic bits.
+template <int LX, int RZ, int SAVE, bool VTI = false>
 __global__ __launch_bounds__(kThreads, MIFWI_EL_MINWAVES) void el_step_s(const ElParams p)
 {
     const FdK K = p.K;
@@ -525,6 +531,8 @@ __global__ __launch_bounds__(kThreads, MIFWI_EL_MINWAVES) void el_step_s(const E
                     const float4 Ls = ld4(p.mat + M_L * ncell + cc), Ms = ld4(p.mat + M_M * ncell + cc);
                     const float4 mus = ld4(p.mat + M_MU * ncell + cc);
                     const float4 zero4 = make_float4(0.f, 0.f, 0.f, 0.f);
+                    float4 Cs = Ms, dC = zero4;                  // the szz-on-ezz modulus and its perturbation: c33 under VTI
+                    if (VTI) Cs = ld4(p.mat + M_C33 * ncell + cc);
                     float4 B0 = zero4, B1 = zero4, B2 = zero4, dL = zero4, dM = zero4, dmu = zero4;
                     if (SAVE == kBorn) {
                         const float *Sp = p.S + (long long)s * p.snap_shot + snap_cell(p, j, g);
@@ -532,6 +540,7 @@ __global__ __launch_bounds__(kThreads, MIFWI_EL_MINWAVES) void el_step_s(const E
                         B2 = mifwi::ldnt4(Sp + 2 * (long long)p.splane);
                         dL = ld4(p.dmat + M_L * ncell + cc); dM = ld4(p.dmat + M_M * ncell + cc);
                         dmu = ld4(p.dmat + M_MU * ncell + cc);
+                        dC = VTI ? ld4(p.dmat + M_C33 * ncell + cc) : dM;
                     }
                     const float xv[8] = {Lvx.x, Lvx.y, b1.x, b1.y, b1.z, b1.w, Rvx.x, Rvx.y};
                     const float zv[8] = {Lvz.x, Lvz.y, a2.x, a2.y, a2.z, a2.w, Rvz.x, Rvz.y};
@@ -577,11 +586,11 @@ __global__ __launch_bounds__(kThreads, MIFWI_EL_MINWAVES) void el_step_s(const E
                     for (int c = 0; c < 4; ++c) {
                         s3v[c] = e3[c] + e4[c];
                         nxx[c] = fmaf(comp(Ms, c), e1[c], fmaf(comp(Ls, c), e2[c], comp(vxx, c)));
-                        nzz[c] = fmaf(comp(Ls, c), e1[c], fmaf(comp(Ms, c), e2[c], comp(vzz, c)));
+                        nzz[c] = fmaf(comp(Ls, c), e1[c], fmaf(comp(Cs, c), e2[c], comp(vzz, c)));
                         nxz[c] = fmaf(comp(mus, c), s3v[c], comp(vxz, c));
                         if (SAVE == kBorn) {
                             nxx[c] = fmaf(comp(dM, c), comp(B0, c), fmaf(comp(dL, c), comp(B1, c), nxx[c]));
-                            nzz[c] = fmaf(comp(dL, c), comp(B0, c), fmaf(comp(dM, c), comp(B1, c), nzz[c]));
+                            nzz[c] = fmaf(comp(dL, c), comp(B0, c), fmaf(comp(dC, c), comp(B1, c), nzz[c]));
                             nxz[c] = fmaf(comp(dmu, c), comp(B2, c), nxz[c]);
                         }
                         if (has_inj) {
@@ -648,16 +657,20 @@ __device__ __forceinline__ void halo_item(int h, int &sr, int &sg)
 }
 
 struct AdjIn { float4 a, b, c, m0, m1, m2; };
+struct AdjInVti : AdjIn { float4 m3; };     // + c33 (m0 = c13, m1 = c11, m2 = c44_xz)
 
 // E1..E4 of one group: C^T sigma_bar through the transposed C-PML (memory variables written by the owner)
-__device__ __forceinline__ void stage_E(const ElParams &p, int s, int j, int g, const AdjIn &in, bool mine,
+__device__ __forceinline__ const float4 &adj_c33(const AdjIn &in) { return in.m1; }
+__device__ __forceinline__ const float4 &adj_c33(const AdjInVti &in) { return in.m3; }
+template <class In>
+__device__ __forceinline__ void stage_E(const ElParams &p, int s, int j, int g, const In &in, bool mine,
                                         float4 &E1, float4 &E2, float4 &E3, float4 &E4)
 {
     float e1[4], e2[4], e3[4], e4[4];
 #pragma unroll
     for (int c = 0; c < 4; ++c) {
         e1[c] = fmaf(comp(in.m1, c), comp(in.a, c), comp(in.m0, c) * comp(in.b, c));
-        e2[c] = fmaf(comp(in.m0, c), comp(in.a, c), comp(in.m1, c) * comp(in.b, c));
+        e2[c] = fmaf(comp(in.m0, c), comp(in.a, c), comp(adj_c33(in), c) * comp(in.b, c));
         e3[c] = comp(in.m2, c) * comp(in.c, c);
         e4[c] = e3[c];
     }
@@ -746,9 +759,12 @@ __global__ void el_build_tile_taps(const int *cell, int ntaps, int nx, int tx, i
 // Register budget pinned at three waves per SIMD (<= 168 VGPRs; 146 in use since the plane loads address as uniform
 // base + 32-bit lane offset and the C-PML branches derive their addresses from opaque indices - 207 before): three
 // workgroups per CU, 768 workgroup slots.  1000x3000 adjoint pair 885 -> 853-864 us per step.
-template <bool BF16>
+// VTI: six accumulators per group - acc[M_M] (c11) takes S1 sxx_bar alone, acc[M_C33] takes S2 szz_bar, acc[M_L] (c13) is
+// the isotropic lambda sum; E2 uses c33 (stage_E).  158 VGPRs, no scratch: the bound of three waves per SIMD holds.
+template <bool BF16, bool VTI = false>
 __global__ __launch_bounds__(kThreads, 3) void el_adj_s(const ElParams p)
 {
+    constexpr int NACC = VTI ? 6 : 5;
     const FdK K = p.K;
     int bx, by, bz;
     xcd_tile(p, bx, by, bz);
@@ -775,19 +791,22 @@ __global__ __launch_bounds__(kThreads, 3) void el_adj_s(const ElParams p)
     const unsigned hcc = (unsigned)hj * p.gp + 4 * hgg;
     const unsigned ho = (unsigned)(hj + 2) * p.pitch + 4 + 4 * hgg;
     const float4 zero4 = make_float4(0.f, 0.f, 0.f, 0.f);
-    float4 acc[5];
-    AdjIn own, halo;
+    float4 acc[NACC];
+    typename std::conditional<VTI, AdjInVti, AdjIn>::type own, halo;
     own.m0 = own.m1 = own.m2 = halo.m0 = halo.m1 = halo.m2 = zero4;
+    if constexpr (VTI) own.m3 = halo.m3 = zero4;
     if (own_ok) {
 #pragma unroll
-        for (int k = 0; k < 5; ++k)          // accumulator planes share the snapshot planes' layout (snap_cell)
-            acc[k] = ld4(el_at(p.acc + ((long long)(p.s0 / p.gs + bz) * 5 + k) * p.splane, osc));
+        for (int k = 0; k < NACC; ++k)       // accumulator planes share the snapshot planes' layout (snap_cell)
+            acc[k] = ld4(el_at(p.acc + ((long long)(p.s0 / p.gs + bz) * NACC + k) * p.splane, osc));
         own.m0 = ld4(el_at(p.mat + M_L * ncell, occ)); own.m1 = ld4(el_at(p.mat + M_M * ncell, occ));
         own.m2 = ld4(el_at(p.mat + M_MU * ncell, occ));
+        if constexpr (VTI) own.m3 = ld4(el_at(p.mat + M_C33 * ncell, occ));
     }
     if (halo_ok) {
         halo.m0 = ld4(el_at(p.mat + M_L * ncell, hcc)); halo.m1 = ld4(el_at(p.mat + M_M * ncell, hcc));
         halo.m2 = ld4(el_at(p.mat + M_MU * ncell, hcc));
+        if constexpr (VTI) halo.m3 = ld4(el_at(p.mat + M_C33 * ncell, hcc));
     }
     for (int si = 0; si < p.gs; ++si) {
         const int s = p.s0 + bz * p.gs + si;
@@ -885,8 +904,15 @@ __global__ __launch_bounds__(kThreads, 3) void el_adj_s(const ElParams p)
                 bf_widen(packed, S1, S2, S3, S4, S5);
             }
 #define ACC3(dst, a, b, c_, d) dst = fmaf(a, b, fmaf(c_, d, dst))
+            if constexpr (VTI) {
+                acc[M_M].x = fmaf(S1.x, bxx.x, acc[M_M].x); acc[M_M].y = fmaf(S1.y, bxx.y, acc[M_M].y);
+                acc[M_M].z = fmaf(S1.z, bxx.z, acc[M_M].z); acc[M_M].w = fmaf(S1.w, bxx.w, acc[M_M].w);
+                acc[NACC - 1].x = fmaf(S2.x, bzz.x, acc[NACC - 1].x); acc[NACC - 1].y = fmaf(S2.y, bzz.y, acc[NACC - 1].y);
+                acc[NACC - 1].z = fmaf(S2.z, bzz.z, acc[NACC - 1].z); acc[NACC - 1].w = fmaf(S2.w, bzz.w, acc[NACC - 1].w);
+            } else {
             ACC3(acc[M_M].x, S1.x, bxx.x, S2.x, bzz.x); ACC3(acc[M_M].y, S1.y, bxx.y, S2.y, bzz.y);
             ACC3(acc[M_M].z, S1.z, bxx.z, S2.z, bzz.z); ACC3(acc[M_M].w, S1.w, bxx.w, S2.w, bzz.w);
+            }
             ACC3(acc[M_L].x, S2.x, bxx.x, S1.x, bzz.x); ACC3(acc[M_L].y, S2.y, bxx.y, S1.y, bzz.y);
             ACC3(acc[M_L].z, S2.z, bxx.z, S1.z, bzz.z); ACC3(acc[M_L].w, S2.w, bxx.w, S1.w, bzz.w);
 #undef ACC3
@@ -901,8 +927,8 @@ __global__ __launch_bounds__(kThreads, 3) void el_adj_s(const ElParams p)
     }
     if (own_ok) {
 #pragma unroll
-        for (int k = 0; k < 5; ++k)
-            st4(el_at(p.acc + ((long long)(p.s0 / p.gs + bz) * 5 + k) * p.splane, osc), acc[k]);
+        for (int k = 0; k < NACC; ++k)
+            st4(el_at(p.acc + ((long long)(p.s0 / p.gs + bz) * NACC + k) * p.splane, osc), acc[k]);
     }
 }
 
@@ -1132,17 +1158,27 @@ __global__ void el_inject_pressure(const ElParams p)
 
 // grad[k][cell] = sum over shot groups of acc[group][k][cell]; grad is row-major [5][nz][gp] (the C-ABI's layout), the
 // accumulator planes are `aplane` floats apart and column-blocked when sblk (snap_cell)
-__global__ void el_finalize(const float *acc, int ngroups, int nz, int gp, long long aplane, int sblk, float *grad)
+template <int NP>
+__device__ __forceinline__ void el_finalize_body(const float *acc, int ngroups, int nz, int gp, long long aplane, int sblk, float *grad)
 {
     const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x, ncell = (long long)nz * gp;
-    if (idx >= 5 * ncell) return;
+    if (idx >= NP * ncell) return;
     const int k = (int)(idx / ncell);
     const long long c = idx - (long long)k * ncell;
     const int j = (int)(c / gp), i = (int)(c - (long long)j * gp), g = i >> 2;
     const long long off = sblk ? ((long long)(g >> 4) * nz + j) * 64 + 4 * (g & 15) + (i & 3) : c;
     float a = 0.f;
-    for (int gidx = 0; gidx < ngroups; ++gidx) a += acc[((long long)gidx * 5 + k) * aplane + off];
+    for (int gidx = 0; gidx < ngroups; ++gidx) a += acc[((long long)gidx * NP + k) * aplane + off];
     grad[idx] = a;
+}
+__global__ void el_finalize(const float *acc, int ngroups, int nz, int gp, long long aplane, int sblk, float *grad)
+{
+    el_finalize_body<5>(acc, ngroups, nz, gp, aplane, sblk, grad);
+}
+// VTI: grad [6][nz][gp] from six accumulator planes per group
+__global__ void el_finalize_vti(const float *acc, int ngroups, int nz, int gp, long long aplane, int sblk, float *grad)
+{
+    el_finalize_body<6>(acc, ngroups, nz, gp, aplane, sblk, grad);
 }
 
 #include "mifwi_elastic_cluster.h"
@@ -1177,7 +1213,11 @@ struct mifwi_elastic_plan {
     int cl_adj, adj_NW, adj_shots, adj_lds, adj_ng, adj_zrows;
     long long xbuf_elems, list_elems, xcc_elems;
     long long tile_elems;                  // per-tile receiver lists of el_adj_s (ints, in floats)
+    int vti;               // mifwi_vti_*: the six-plane kernels (el_step_s / el_adj_s with VTI = true, el_finalize_vti), per-step family only
+    int nmat;              // material / gradient / accumulator planes: 5, or 6 under vti
 };
+// a VTI plan is an elastic plan with the flag set (el_plan_create); the C ABI keeps the two handle types apart
+struct mifwi_vti_plan;
 
 namespace {
 
@@ -1213,6 +1253,15 @@ ElStepKernels el_step_variant(int lx, int save)
     return with_int<kBorn, 2, 1, 0>(save, [&](auto SAVE) {
         return ElStepKernels{el_step_v<decltype(LX)::value, 1, decltype(SAVE)::value>,
                              el_step_s<decltype(LX)::value, 1, decltype(SAVE)::value>};
+    }); });
+}
+// VTI plans: the same V launch, el_step_s<LX, 1, SAVE, true>; save kBorn | 1 | 0 (f32 planes only)
+ElStepKernels el_step_variant_vti(int lx, int save)
+{
+    return with_int<64, 32, 16>(lx, [&](auto LX) {
+    return with_int<kBorn, 1, 0>(save, [&](auto SAVE) {
+        return ElStepKernels{el_step_v<decltype(LX)::value, 1, decltype(SAVE)::value>,
+                             el_step_s<decltype(LX)::value, 1, decltype(SAVE)::value, true>};
     }); });
 }
 // el_fwd_fused<SAVE>: save 2 | 1 | 0 (no Born form: that pass runs the two launches)
@@ -1334,7 +1383,7 @@ void el_cluster_setup(mifwi_elastic_plan *pl)
         const long long ntiles = (long long)mifwi::ceil_div(pl->ng, AGO) * mifwi::ceil_div(pl->d.nz, ATZ);
         pl->tile_elems = std::max<long long>(1024, mifwi::round_up64(pl->d.nshot * (2 * ntiles + 1 + (long long)pl->d.nrec * pl->d.ntap), 64));
     }
-    if (pl->d.ntap != 1 || pl->d.source_type != 0 || pl->d.record_pressure) return;   // per-step kernels only
+    if (pl->vti || pl->d.ntap != 1 || pl->d.source_type != 0 || pl->d.record_pressure) return;   // per-step kernels only
     const bool want_fwd = env_int("MIFWI_EL_CLUSTER", 1) != 0;
     int ncu = 0;
     if (hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, pl->device) != hipSuccess) return;
@@ -1408,7 +1457,7 @@ ElWork work_map(const mifwi_elastic_plan *pl, bool backward)
     ElWork m;
     m.fields = 0; m.psi = pl->fields_elems; m.psiB = m.psi + pl->psi_elems;
     m.acc = backward ? m.psiB + pl->psi_elems : m.psiB;
-    m.state = m.acc + (backward ? 5LL * pl->ngroups * pl->splane : 0);      // accumulator planes: the snapshot planes' layout and size
+    m.state = m.acc + (backward ? (long long)pl->nmat * pl->ngroups * pl->splane : 0);      // accumulator planes: the snapshot planes' layout and size
     m.bbox = m.state; m.xbuf = m.bbox + mifwi::round_up64(4LL * pl->d.nshot, 64);
     m.lists = m.xbuf + (single ? pl->xbuf_elems : 0);
     m.backup = m.lists + (single && backward ? pl->list_elems : 0);
@@ -1463,7 +1512,7 @@ void el_two_launch_steps(const mifwi_elastic_plan *pl, ElParams p, int save, con
     const mifwi_elastic_desc &d = pl->d;
     const long long snap_step = pl->snap_shot * d.nshot;
     const bool want_rec = rec_vx != nullptr;
-    const ElStepKernels step = el_step_variant(pl->lx, save);
+    const ElStepKernels step = pl->vti ? el_step_variant_vti(pl->lx, save) : el_step_variant(pl->lx, save);
     ElParams ps = p;
     const bool force = d.source_type != 0;      // point force: injected into vx / vz by a launch of its own
     ps.ninj = (force || !f) ? 0 : d.nsrc; ps.ntap_inj = d.ntap; ps.inj_cell = src_cell; ps.inj_w = src_w;
@@ -1498,11 +1547,7 @@ void el_two_launch_steps(const mifwi_elastic_plan *pl, ElParams p, int save, con
     }
 }
 
-}  // namespace
-
-extern "C" {
-
-int mifwi_elastic_plan_create(mifwi_elastic_plan **plan, int device, const mifwi_elastic_desc *d)
+int el_plan_create(mifwi_elastic_plan **plan, int device, const mifwi_elastic_desc *d, int vti)
 {
     if (!plan || !d) return mifwi::fail(MIFWI_EINVAL, "null plan/desc");
     if (d->nz < 1 || d->nx < 1 || d->nt < 1 || d->nshot < 1 || d->nsrc < 0 || d->nrec < 0)
@@ -1530,6 +1575,7 @@ int mifwi_elastic_plan_create(mifwi_elastic_plan **plan, int device, const mifwi
     pl->d = *d;
     if (pl->d.fd_order == 0) pl->d.fd_order = 4;
     pl->device = device;
+    pl->vti = vti; pl->nmat = vti ? 6 : 5;
     pl->rec_p = nullptr; pl->g_p = nullptr;
     pl->ng = mifwi::ceil_div(d->nx, 4);
     pl->gp = 4 * pl->ng;
@@ -1588,7 +1634,7 @@ int mifwi_elastic_plan_create(mifwi_elastic_plan **plan, int device, const mifwi
         // 1000x3000: forward 3 shots (240 MB) 0.61 ms, 4 shots (300 MB) 0.82 ms = the all-shots time
         constexpr double kResident = 250e6;
         const double cells = (double)pl->coef_elems;
-        const double mats = 4.0 * 5.0 * cells;
+        const double mats = 4.0 * pl->nmat * cells;
         const double psi1 = 4.0 * (double)(pl->psix_elems + pl->psiz_elems) / d->nshot;
         const double fstate = 4.0 * (double)pl->shot_stride + psi1;
         // forward a little below the adjoint's bound: 1000x3000 runs 0.61 ms with 3 shots (240 MB) and 0.62 ms with 2
@@ -1598,7 +1644,7 @@ int mifwi_elastic_plan_create(mifwi_elastic_plan **plan, int device, const mifwi
         // adjoint: groups of gs shots share one accumulator set; when the groups do not all fit, smaller groups
         // (more accumulator traffic, 40/gs B per cell-step) can still pay: 1000x3000, gs 2, one group per pass
         // 0.87 ms against 0.98 ms for gs 4 over all shots
-        const double astate = 4.0 * (double)pl->shot_stride + 2.0 * psi1, accg = 4.0 * 5.0 * cells;
+        const double astate = 4.0 * (double)pl->shot_stride + 2.0 * psi1, accg = 4.0 * pl->nmat * cells;
         if (!pl->cl_adj && d->shots_per_group <= 0 && env_int("MIFWI_EL_GS", 0) <= 0 &&
             pl->ngroups * (pl->gs * astate + accg) + mats > kResident) {
             int g = pl->gs;
@@ -1617,7 +1663,7 @@ int mifwi_elastic_plan_create(mifwi_elastic_plan **plan, int device, const mifwi
     // 1000x3000 x 16 shots: 622 -> 558 us per step, 516 with bf16 planes; 350x1700 x 32: 232 -> 232, 214 -> 209) and
     // on any launch of a million cells or more (350x1700 x 4 shots, the chunks of a shot-chunked gradient pass:
     // 286 -> 260 us per step of all 32 shots)
-    pl->fused = !pl->cluster && d->source_type == 0 && !d->record_pressure &&
+    pl->fused = !pl->vti && !pl->cluster && d->source_type == 0 && !d->record_pressure &&
                 env_int("MIFWI_EL_FUSED", (pl->pass_shots < d->nshot || (double)d->nz * d->nx * d->nshot >= 1e6) ? 1 : 0) != 0;
     {
         const double cells = (double)pl->coef_elems, mats = 4.0 * 5.0 * cells;
@@ -1632,6 +1678,15 @@ int mifwi_elastic_plan_create(mifwi_elastic_plan **plan, int device, const mifwi
     }
     *plan = pl;
     return MIFWI_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int mifwi_elastic_plan_create(mifwi_elastic_plan **plan, int device, const mifwi_elastic_desc *d)
+{
+    return el_plan_create(plan, device, d, 0);
 }
 
 int mifwi_elastic_plan_cluster_slabs(const mifwi_elastic_plan *plan, int32_t adjoint)
@@ -1922,7 +1977,8 @@ int mifwi_elastic_backward(mifwi_elastic_plan *pl, const float *mat, const float
             hipLaunchKernelGGL(el_inject_pressure, dim3(mifwi::ceil_div(cs * d.nrec * d.ntap, 64)), dim3(64), 0,
                                st, pq);
         }
-        if (pl->snap_bf16) hipLaunchKernelGGL(el_adj_s<true>, dim3(tx, tz + ex, cg), dim3(kThreads), 0, st, ps);
+        if (pl->vti) hipLaunchKernelGGL((el_adj_s<false, true>), dim3(tx, tz + ex, cg), dim3(kThreads), 0, st, ps);
+        else if (pl->snap_bf16) hipLaunchKernelGGL(el_adj_s<true>, dim3(tx, tz + ex, cg), dim3(kThreads), 0, st, ps);
         else hipLaunchKernelGGL(el_adj_s<false>, dim3(tx, tz + ex, cg), dim3(kThreads), 0, st, ps);
         if (want_f && force) {
             ElParams pq = ps;
@@ -1933,12 +1989,86 @@ int mifwi_elastic_backward(mifwi_elastic_plan *pl, const float *mat, const float
         hipLaunchKernelGGL(el_adj_v, dim3(tx, tz, cs), dim3(kThreads), 0, st, p);
     }
     if (flags & MIFWI_FINALIZE) {
-        const long long n5 = 5LL * pl->coef_elems;
-        hipLaunchKernelGGL(el_finalize, dim3((unsigned)((n5 + 255) / 256)), dim3(256), 0, st, acc,
+        const long long n5 = (long long)pl->nmat * pl->coef_elems;
+        hipLaunchKernelGGL(pl->vti ? el_finalize_vti : el_finalize, dim3((unsigned)((n5 + 255) / 256)), dim3(256), 0, st, acc,
                            pl->ngroups, d.nz, pl->gp, pl->splane, pl->cl_adj ? 0 : pl->sblk, grad_mat);
     }
     MIFWI_HIP_TRY(hipGetLastError());
     return MIFWI_OK;
+}
+
+// ---- VTI: the elastic plan with six planes, one launch per half step (include/mifwi.h) ---------------------------------
+static mifwi_elastic_plan *vti_plan(mifwi_vti_plan *p) { return reinterpret_cast<mifwi_elastic_plan *>(p); }
+static const mifwi_elastic_plan *vti_plan(const mifwi_vti_plan *p) { return reinterpret_cast<const mifwi_elastic_plan *>(p); }
+// (a handle of mifwi_elastic_plan_create passed by mistake would run the six-plane kernels on five planes)
+static int vti_check(const mifwi_vti_plan *p)
+{
+    return (p && !vti_plan(p)->vti) ? mifwi::fail(MIFWI_EINVAL, "the plan was not created by mifwi_vti_plan_create") : MIFWI_OK;
+}
+
+int mifwi_vti_plan_create(mifwi_vti_plan **plan, int device, const mifwi_vti_desc *d)
+{
+    if (!plan || !d) return mifwi::fail(MIFWI_EINVAL, "null plan/desc");
+    mifwi_elastic_desc e;
+    e.nz = d->nz; e.nx = d->nx; e.nt = d->nt; e.nshot = d->nshot; e.nsrc = d->nsrc; e.nrec = d->nrec; e.ntap = d->ntap;
+    e.pml_width = d->pml_width; e.free_surface = d->free_surface; e.shots_per_group = d->shots_per_group;
+    e.source_type = d->source_type; e.record_pressure = 0; e.snapshot_format = MIFWI_SNAPSHOT_F32; e.fd_order = d->fd_order;
+    return el_plan_create(reinterpret_cast<mifwi_elastic_plan **>(plan), device, &e, 1);
+}
+
+int mifwi_vti_plan_destroy(mifwi_vti_plan *plan)
+{
+    delete vti_plan(plan);
+    return MIFWI_OK;
+}
+
+int mifwi_vti_plan_layout(const mifwi_vti_plan *plan, mifwi_vti_layout *out)
+{
+    if (!plan || !out) return mifwi::fail(MIFWI_EINVAL, "null plan/layout");
+    mifwi_elastic_layout e;
+    const int rc = mifwi_elastic_plan_layout(vti_plan(plan), &e);
+    if (rc) return rc;
+    out->gp = e.gp; out->pitch = e.pitch; out->ngroups = e.ngroups; out->shots_per_group = e.shots_per_group;
+    out->coef_elems = e.coef_elems; out->state_elems = e.state_elems; out->work_forward_elems = e.work_forward_elems;
+    out->work_backward_elems = e.work_backward_elems; out->snap_step_elems = e.snap_step_elems;
+    return MIFWI_OK;
+}
+
+int mifwi_vti_plan_pass_sizes(const mifwi_vti_plan *plan, int32_t *forward_shots, int32_t *adjoint_groups)
+{
+    return mifwi_elastic_plan_pass_sizes(vti_plan(plan), forward_shots, adjoint_groups);
+}
+
+int mifwi_vti_plan_cluster_slabs(const mifwi_vti_plan *, int32_t) { return 0; }
+
+int mifwi_vti_forward(mifwi_vti_plan *plan, const float *mat, const float *pz, const float *px, const float *f,
+                      const int32_t *src_cell, const float *src_w, const int32_t *rec_cell, const float *rec_w,
+                      float *rec_vx, float *rec_vz, float *snap, float *work, int32_t n_begin, int32_t n_end,
+                      int32_t flags, void *stream)
+{
+    if (const int rc = vti_check(plan)) return rc;
+    return mifwi_elastic_forward(vti_plan(plan), mat, pz, px, f, src_cell, src_w, rec_cell, rec_w, rec_vx, rec_vz, snap, work,
+                                 n_begin, n_end, flags, stream);
+}
+
+int mifwi_vti_backward(mifwi_vti_plan *plan, const float *mat, const float *pz, const float *px, const int32_t *src_cell,
+                       const float *src_w, const int32_t *rec_cell, const float *rec_w, const float *g_vx, const float *g_vz,
+                       const float *snap, int32_t snap_first, float *grad_mat, float *grad_f, float *work, int32_t n_hi,
+                       int32_t n_lo, int32_t flags, void *stream)
+{
+    if (const int rc = vti_check(plan)) return rc;
+    return mifwi_elastic_backward(vti_plan(plan), mat, pz, px, src_cell, src_w, rec_cell, rec_w, g_vx, g_vz, snap, snap_first,
+                                  grad_mat, grad_f, work, n_hi, n_lo, flags, stream);
+}
+
+int mifwi_vti_born(mifwi_vti_plan *plan, const float *mat, const float *dmat, const float *pz, const float *px,
+                   const float *df, const int32_t *src_cell, const float *src_w, const int32_t *rec_cell, const float *rec_w,
+                   const float *snap, int32_t snap_first, float *drec_vx, float *drec_vz, float *work, int32_t n_begin,
+                   int32_t n_end, int32_t flags, void *stream)
+{
+    if (const int rc = vti_check(plan)) return rc;
+    return mifwi_elastic_born(vti_plan(plan), mat, dmat, pz, px, df, src_cell, src_w, rec_cell, rec_w, snap, snap_first,
+                              drec_vx, drec_vz, work, n_begin, n_end, flags, stream);
 }
 
 }  // extern "C"
