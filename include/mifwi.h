@@ -373,6 +373,84 @@ int mifwi_vti_born(mifwi_vti_plan *plan, const float *mat, const float *dmat, co
                    int32_t n_end, int32_t flags, void *stream);
 
 /* ======================================================================================
+ * 2-D P-SV VISCOELASTIC propagator: one relaxation mechanism of a generalised standard linear solid (forward + exact
+ * discrete adjoint)
+ *
+ * Serves pyapi_denise runs with PHYSICS = 1 and L = 1 (FL1, Qp / Qs models).  The elastic scheme above - same grid,
+ * staggering, Dp / Dm, C-PML recursion, pz / px tables, free surface, sources, receivers and five snapshot planes - with
+ * three memory variables per shot, rxx and rzz on the sxx node and rxz on the sxz node, which hold dt times DENISE's r.
+ *   mat [8][nz][gp] = lam_u, lam2mu_u, mu_u_xz, dt/(h rho_x), dt/(h rho_z), R2, R1, rmu_xz: the UNRELAXED moduli where the
+ *                     elastic ones stand, then R2 = pi_r tau_p - 2 mu_r tau_s, R1 = pi_r tau_p on the sxx node and
+ *                     mu_r tau_s on the sxz node, all moduli times dt/h.  Columns >= nx must be 0; under a free surface
+ *                     row 0 holds the effective form (lam_u = 0, R2 = 0; physicsbasedfwi2_amd.visco.materials).
+ *   relax_a = (2 - eta) / (2 + eta), relax_b = 2 eta / (2 + eta) with eta = dt / tau_sigma = 2 pi FL dt, computed in double.
+ * Forward step n ( ' : through the C-PML; S0..S4 the snapshot planes, as in the elastic scheme):
+ *   V:  unchanged (the elastic V launch); S3, S4.   source_type 1 / 2: vx / vz [cell] += w f[n]
+ *   S:  S0 = e1', S1 = e2', S2 = e3' + e4' as elastic;  qxx = R1 S0 + R2 S1, qzz = R2 S0 + R1 S1, qxz = rmu_xz S2
+ *       sxx = fmaf(lam2mu_u, S0, fmaf(lam_u, S1, sxx)) + ((1 + a)/2 rxx - b/2 qxx)     (szz, sxz alike)
+ *       r*  = a r* - b q*
+ *   source_type 0: sxx, szz [cell] += w f[n];  free surface: szz(0,.) = 0
+ * With planes 5..7 zero the memory variables stay 0 and every stress is the elastic fmaf chain's: the seismograms of
+ * mifwi_elastic_forward (per-step kernels) bit for bit.
+ * Adjoint step n = nt-1 .. 0, the exact transpose (r_bar: the adjoint memory variables, in the three extra fields):
+ *   S^T: w* = -b (r*_bar + s*_bar / 2);  E1 = pmlT(lam2mu_u sxx_bar + lam_u szz_bar + R1 wxx + R2 wzz), E2 alike,
+ *        E3 = E4 = pmlT(mu_u_xz sxz_bar + rmu_xz wxz);  v_bar -= stencils(E)
+ *        gradients of planes 0..4 as elastic;  g_R1 += S0 wxx + S1 wzz;  g_R2 += S1 wxx + S0 wzz;  g_rmu += S2 wxz
+ *   V^T: r*_bar = a r*_bar + (1 + a)/2 s*_bar with the s_bar that S^T saw, then s_bar -= stencils(D) as elastic
+ *        (S^T reads r_bar of neighbouring cells for its halo, so the launch that advances it is V^T)
+ * Born step: q* += dmat[5..7] times S0..S2 in the same pattern, the stresses += dmat[0..2] terms as elastic.
+ * One launch per half step in both directions: no single-launch and no fused V+S form, no bf16 snapshot planes, no
+ * pressure receivers.  The state of a shot is eight fields: time checkpoints (state_elems) carry the memory variables.
+ * grad_mat and dmat are [8][nz][gp] like mat.
+ * ==================================================================================== */
+typedef struct {
+    int32_t nz, nx;          /* grid, z = depth is the slow axis                              */
+    int32_t nt, nshot, nsrc, nrec, ntap;
+    int32_t pml_width;       /* C-PML nodes per side (0 = none)                               */
+    int32_t free_surface;    /* 1: stress-free surface on row 0 (needs nz >= 4)               */
+    int32_t shots_per_group; /* adjoint: shots sharing one gradient accumulator; 0 = auto     */
+    int32_t source_type;     /* 0: explosive (sxx, szz), 1 / 2: point force on vx / vz        */
+    int32_t fd_order;        /* 4 (0 means 4) or 2                                            */
+    float relax_a, relax_b;  /* the two relaxation scalars, each inside (0, 1)                */
+} mifwi_visco_desc;
+
+typedef struct {
+    int32_t gp, pitch, ngroups, shots_per_group;
+    int64_t coef_elems;           /* nz*gp: one material / gradient plane                     */
+    int64_t state_elems;          /* forward state (8 fields + C-PML memory variables) at the start
+                                     of `work`: what a time checkpoint copies                 */
+    int64_t work_forward_elems;
+    int64_t work_backward_elems;
+    int64_t snap_step_elems;      /* floats one time step of the snapshot buffer takes (all shots) */
+} mifwi_visco_layout;
+
+typedef struct mifwi_visco_plan mifwi_visco_plan;
+
+/* MIFWI_EINVAL as mifwi_elastic_plan_create, and for relax_a or relax_b outside (0, 1) */
+int mifwi_visco_plan_create(mifwi_visco_plan **plan, int device, const mifwi_visco_desc *desc);
+int mifwi_visco_plan_destroy(mifwi_visco_plan *plan);
+int mifwi_visco_plan_layout(const mifwi_visco_plan *plan, mifwi_visco_layout *out);
+/* shots per forward pass, shot groups per adjoint pass over the time range (Infinity Cache residency, eight planes) */
+int mifwi_visco_plan_pass_sizes(const mifwi_visco_plan *plan, int32_t *forward_shots, int32_t *adjoint_groups);
+/* always 0: the viscoelastic plan runs one launch per half step */
+int mifwi_visco_plan_cluster_slabs(const mifwi_visco_plan *plan, int32_t adjoint);
+
+/* Arguments, step ranges, flags and refusals as mifwi_elastic_forward / _backward / _born; mat, grad_mat, dmat
+ * [8][nz][gp].  Born is served for source_type 0 only. */
+int mifwi_visco_forward(mifwi_visco_plan *plan, const float *mat, const float *pz, const float *px, const float *f,
+                        const int32_t *src_cell, const float *src_w, const int32_t *rec_cell, const float *rec_w,
+                        float *rec_vx, float *rec_vz, float *snap, float *work, int32_t n_begin, int32_t n_end,
+                        int32_t flags, void *stream);
+int mifwi_visco_backward(mifwi_visco_plan *plan, const float *mat, const float *pz, const float *px, const int32_t *src_cell,
+                         const float *src_w, const int32_t *rec_cell, const float *rec_w, const float *g_vx, const float *g_vz,
+                         const float *snap, int32_t snap_first, float *grad_mat, float *grad_f, float *work, int32_t n_hi,
+                         int32_t n_lo, int32_t flags, void *stream);
+int mifwi_visco_born(mifwi_visco_plan *plan, const float *mat, const float *dmat, const float *pz, const float *px,
+                     const float *df, const int32_t *src_cell, const float *src_w, const int32_t *rec_cell, const float *rec_w,
+                     const float *snap, int32_t snap_first, float *drec_vx, float *drec_vz, float *work, int32_t n_begin,
+                     int32_t n_end, int32_t flags, void *stream);
+
+/* ======================================================================================
  * 2-D variable-density ACOUSTIC (fluid) velocity-pressure propagator (forward + exact discrete adjoint)
  *
  * Serves the DENISE runs with PHYSICS = 2 behind pyapi_denise (models/networks.py:10445-10453: an acoustic medium

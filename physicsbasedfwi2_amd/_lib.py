@@ -75,6 +75,14 @@ class VtiLayout(ctypes.Structure):
     _fields_ = list(FluidLayout._fields_)
 
 
+class ViscoDesc(ctypes.Structure):
+    _fields_ = list(VtiDesc._fields_) + [("relax_a", ctypes.c_float), ("relax_b", ctypes.c_float)]
+
+
+class ViscoLayout(ctypes.Structure):
+    _fields_ = list(FluidLayout._fields_)
+
+
 EL_KERNEL_FWD_SINGLE_LAUNCH, EL_KERNEL_ADJ_SINGLE_LAUNCH, EL_KERNEL_FWD_FUSED_STEP, EL_KERNEL_ADJ_FUSED_STEP = 1, 2, 4, 8
 EL_KERNEL_FWD_LANE_HALO, EL_KERNEL_ADJ_LANE_HALO = 16, 32
 SNAPSHOT_F32, SNAPSHOT_BF16 = 0, 1
@@ -131,6 +139,14 @@ SIGNATURES = {
     "mifwi_vti_forward": (ctypes.c_int, [_P] * 13 + [ctypes.c_int32] * 3 + [_P]),
     "mifwi_vti_backward": (ctypes.c_int, [_P] * 11 + [ctypes.c_int32] + [_P] * 3 + [ctypes.c_int32] * 3 + [_P]),
     "mifwi_vti_born": (ctypes.c_int, [_P] * 11 + [ctypes.c_int32] + [_P] * 3 + [ctypes.c_int32] * 3 + [_P]),
+    "mifwi_visco_plan_create": (ctypes.c_int, [ctypes.POINTER(_P), ctypes.c_int, ctypes.POINTER(ViscoDesc)]),
+    "mifwi_visco_plan_destroy": (ctypes.c_int, [_P]),
+    "mifwi_visco_plan_layout": (ctypes.c_int, [_P, ctypes.POINTER(ViscoLayout)]),
+    "mifwi_visco_plan_pass_sizes": (ctypes.c_int, [_P, _P, _P]),
+    "mifwi_visco_plan_cluster_slabs": (ctypes.c_int, [_P, ctypes.c_int32]),
+    "mifwi_visco_forward": (ctypes.c_int, [_P] * 13 + [ctypes.c_int32] * 3 + [_P]),
+    "mifwi_visco_backward": (ctypes.c_int, [_P] * 11 + [ctypes.c_int32] + [_P] * 3 + [ctypes.c_int32] * 3 + [_P]),
+    "mifwi_visco_born": (ctypes.c_int, [_P] * 11 + [ctypes.c_int32] + [_P] * 3 + [ctypes.c_int32] * 3 + [_P]),
     "mifwi_misfit_work_elems": (ctypes.c_int64, [ctypes.c_int32, ctypes.c_int64, ctypes.c_int64]),
     "mifwi_misfit": (ctypes.c_int, [ctypes.c_int, ctypes.c_int32] + [_P] * 3 + [ctypes.c_int64] * 2 +
                      [_P] * 4),

@@ -29,7 +29,7 @@ import struct
 import numpy as np
 import torch
 
-from .. import elastic, fluid, misfit, profiles, vti
+from .. import elastic, fluid, misfit, profiles, visco, vti
 from .._lib import STF_MAX_LAGS, MifwiError
 
 
@@ -254,7 +254,8 @@ _SERVED = frozenset((
     "k_max_PML", "FREE_SURF", "QUELLART", "QUELLTYP", "QUELLTYPB", "FC_SPIKE_1", "FC_SPIKE_2", "ORDER_SPIKE", "SEISMO",
     "ITERMAX", "DATA_DIR", "SWS_TAPER_GRAD_HOR", "EXP_TAPER_GRAD_HOR", "GRADT1", "GRADT2", "GRADT3", "GRADT4", "INVMAT1",
     "EPRECOND", "EPSILON_WE", "TRKILL", "INV_STF", "fwi_stages", "loss", "DT_used", "acoustic_kernels", "stf_filters",
-    "stf_wavelets"))
+    "stf_wavelets", "L", "FL1", "F_REF"))
+# (L = 1, attenuation with one relaxation mechanism, takes the Qp and Qs models through d.set_attenuation(): arrays)
 # (PHYSICS = 3, the P-SV VTI medium, takes Thomsen's epsilon and delta through d.set_thomsen(): arrays, not attributes)
 # DENISE parameters that cannot change what ONE gradient evaluation (ITERMAX = 1) returns: the MPI decomposition, names of
 # files this shim keeps in memory, logging, model bounds and line-search / optimiser settings that only act on model
@@ -287,6 +288,9 @@ class Denise:
                              "three-field kernels of physicsbasedfwi2_amd.fluid)" % (value,))
         if name == "INV_STF" and value not in (0, 1):
             raise MifwiError("INV_STF=%r not implemented (0: off, 1: the per-shot matching filter of set_stf)" % (value,))
+        if name == "L" and value not in (0, 1):
+            raise MifwiError("L=%r not implemented (0: elastic, 1: one relaxation mechanism at FL1; the generalised "
+                             "standard linear solid with more mechanisms is not built)" % (value,))
         if name.startswith("_") or name in _SERVED:
             return object.__setattr__(self, name, value)
         if name in _INERT:
@@ -374,6 +378,15 @@ class Denise:
         self._observed_p = None
         self._thomsen = None               # (epsilon, delta) of set_thomsen, for PHYSICS = 3
         self._gradients_thomsen = None
+        # L: relaxation mechanisms of the P-SV medium - 0 elastic, 1 one standard linear solid with relaxation frequency FL1
+        # [Hz] and the Qp / Qs models of set_attenuation().  F_REF [Hz]: the frequency at which Model.vp and Model.vs are
+        # the phase velocities (DENISE's convention); None: the centre frequency of the first source
+        self.L = 0
+        self.FL1 = 5.0
+        self.F_REF = None
+        self._attenuation = None           # (qp, qs) of set_attenuation, for L = 1
+        self._gradients_q = None
+        self._f_ref = None                 # the reference frequency of the last _setup with L = 1
         self.loss = None
 
     # -- protocol no-ops ------------------------------------------------------------------------
@@ -412,6 +425,20 @@ class Denise:
             raise MifwiError("set_thomsen: epsilon and delta are [ny, nx] arrays of one shape (got %s and %s)"
                              % (e.shape, dl.shape))
         self._thomsen = (e, dl)
+
+    # -- attenuation (L = 1) ------------------------------------------------------------------------
+    def set_attenuation(self, qp, qs):
+        """The quality factors of an ``L = 1`` (viscoelastic P-SV) run: [ny, nx] arrays in the caller's flipud convention,
+        like the planes of :class:`Model`; ``inf`` means lossless.  ``None, None`` forgets them."""
+        if qp is None and qs is None:
+            self._attenuation = None
+            return
+        if qp is None or qs is None:
+            raise MifwiError("set_attenuation: give both qp and qs (or None, None)")
+        a, b = (np.asarray(t.detach().cpu().numpy() if torch.is_tensor(t) else t, dtype=np.float32) for t in (qp, qs))
+        if a.ndim != 2 or a.shape != b.shape:
+            raise MifwiError("set_attenuation: qp and qs are [ny, nx] arrays of one shape (got %s and %s)" % (a.shape, b.shape))
+        self._attenuation = (a, b)
 
     # -- which samples enter the objective (misfit.TraceSelection) -------------------------------------
     def set_trace_kill(self, table):
@@ -550,10 +577,31 @@ class Denise:
                              "QUELLTYPB 1, 2 or 3" % (self.SEISMO, self.QUELLTYPB))
         return True
 
+    def _visco(self, model=None):
+        """True when this run is an ``L = 1`` (viscoelastic P-SV) run; what the viscoelastic propagator does not serve is
+        refused before any device work."""
+        if int(self.L) == 0:
+            return False
+        if self.PHYSICS != 1:
+            raise MifwiError("L=1 (attenuation) serves PHYSICS = 1 only (PHYSICS=%s): Q with the acoustic or the VTI medium "
+                             "is not built" % self.PHYSICS)
+        if int(self.EPRECOND) != 0:
+            raise MifwiError("L=1: the pseudo-Hessian (EPRECOND=%s) is not built for viscoelastic media" % self.EPRECOND)
+        if self.SEISMO != 1 or self.QUELLTYPB == 4:
+            raise MifwiError("L=1: pressure seismograms (SEISMO=%s, QUELLTYPB=%s) are not served; SEISMO = 1 and "
+                             "QUELLTYPB 1, 2 or 3" % (self.SEISMO, self.QUELLTYPB))
+        if self._attenuation is None:
+            raise MifwiError("L=1 needs the Qp and Qs models: d.set_attenuation(qp, qs)")
+        if model is not None and self._attenuation[0].shape != model.vp.shape:
+            raise MifwiError("set_attenuation: qp and qs are %s, the model is %s"
+                             % (self._attenuation[0].shape, model.vp.shape))
+        return True
+
     def _setup(self, model, src, rec):
         self._fluid()
         if self.PHYSICS not in (1, 2, 3):
             raise MifwiError("PHYSICS=%s not implemented (1 = P-SV elastic, 2 = acoustic, 3 = P-SV VTI)" % self.PHYSICS)
+        self._visco(model)             # (refusals come before the device is looked up)
         dev = torch.device(self.device) if self.device is not None else \
             torch.device("cuda", torch.cuda.current_device())
         h = model.dx
@@ -561,6 +609,10 @@ class Denise:
         if self._vti(model):
             # the fastest qP phase velocity of a Thomsen medium is bounded by vp0 sqrt(1 + 2 max(epsilon, delta, 0))
             vmax = vti.max_velocity(model.vp, *self._thomsen)
+        if self._visco(model):
+            # Model.vp is the phase velocity at F_REF; the fastest the medium carries is the unrelaxed one
+            self._f_ref = float(self.F_REF) if self.F_REF is not None else float(np.atleast_1d(src.f)[0])
+            vmax = visco.max_velocity(model.vp, self._attenuation[0], self._f_ref, float(self.FL1))
         # FD_ORDER (left commented at networks.py:10447): 2 or 4 are built (Taylor weights, MAXRELERROR = 0)
         if int(self.FD_ORDER) not in (2, 4):
             raise MifwiError("FD_ORDER=%s not implemented: the staggered-grid stencils are built for order 2 "
@@ -626,14 +678,17 @@ class Denise:
         # PHYSICS = 2 (acoustic): the same velocity-stress solver in a fluid, Vs = 0 everywhere
         vs = model.vs if self.PHYSICS in (1, 3) else np.zeros_like(model.vs)
         planes = (model.vp, vs, model.rho) + (self._thomsen if self._vti(model) else ())
+        planes = planes + (self._attenuation if self._visco(model) else ())
         prm = [torch.tensor(np.flipud(a).copy(), device=dev, requires_grad=requires_grad) for a in planes]
+        if self._visco():
+            return prm, visco.materials(*prm, self._f_ref, float(self.FL1), dt, h, free_surface=fsurf)
         if self._vti():
             return prm, vti.materials(*prm, dt, h, free_surface=fsurf)
         if self._fluid():
             return prm, fluid.materials(prm[0], prm[2], dt, h, free_surface=fsurf)
         return prm, elastic.staggered_materials(prm[0], prm[1], prm[2], dt, h, free_surface=fsurf)
 
-    def _propagate(self, mat, f, pz, px, g, fw, fsurf, h, pseudo_hessian=None):
+    def _propagate(self, mat, f, pz, px, g, fw, fsurf, h, pseudo_hessian=None, dt=None):
         kind = {1: "explosive", 2: "fx", 3: "fz"}[self.QUELLTYP]
         if self._fluid():
             if kind != "explosive":
@@ -643,6 +698,10 @@ class Denise:
             return (out[0], out[1], -out[2]) if len(out) == 3 else (out[0], out[1], None)
         if kind != "explosive":
             f = elastic.force_amplitude(f, mat, g["sc"], g["sw"], h, kind)      # planes 3 and 4: the VTI planes' too
+        if self._visco():
+            out = visco.propagate(mat, f, pz, px, g["sc"], g["sw"], g["rc"], g["rw"], fw, float(self.FL1), dt,
+                                  free_surface=fsurf, source_type=kind, fd_order=int(self.FD_ORDER))
+            return out[0], out[1], None
         if self._vti():
             out = vti.propagate(mat, f, pz, px, g["sc"], g["sw"], g["rc"], g["rw"], fw, free_surface=fsurf,
                                 source_type=kind, fd_order=int(self.FD_ORDER))
@@ -658,7 +717,7 @@ class Denise:
         dev, h, dt, nt, g, f, pz, px, fw, fsurf = self._setup(model, src, rec)
         with torch.no_grad():
             _, mat = self._materials(model, dev, dt, h, False, fsurf)
-            vx, vy, p = self._propagate(mat, f.to(dev), pz, px, g, fw, fsurf, h)
+            vx, vy, p = self._propagate(mat, f.to(dev), pz, px, g, fw, fsurf, h, dt=dt)
         self._shots = (vx.permute(1, 2, 0).cpu().numpy(), vy.permute(1, 2, 0).cpu().numpy())
         self._shots_p = None if p is None else p.permute(1, 2, 0).cpu().numpy()
         self.DT_used = dt
@@ -691,6 +750,7 @@ class Denise:
             raise MifwiError("ITERMAX=%s: grad() is one gradient evaluation (the reference sets ITERMAX = 1 and lets its "
                              "own optimiser update the model)" % self.ITERMAX)
         self._vti(model)
+        self._visco(model)
         if int(self.INVMAT1) not in (1, 2, 3):
             raise MifwiError("INVMAT1=%s not implemented (1: Vp, Vs, rho; 2: Zp, Zs, rho; 3: lambda, mu, rho)" % self.INVMAT1)
         if int(self.EPRECOND) not in (0, 1):
@@ -704,7 +764,7 @@ class Denise:
         dev, h, dt, nt, g, f, pz, px, fw, fsurf = self._setup(model, src, rec)
         prm, mat = self._materials(model, dev, dt, h, True, fsurf)
         self._pseudo_hessian = elastic.PseudoHessian() if int(self.EPRECOND) == 1 else None
-        vx, vy, p = self._propagate(mat, f.to(dev), pz, px, g, fw, fsurf, h, self._pseudo_hessian)
+        vx, vy, p = self._propagate(mat, f.to(dev), pz, px, g, fw, fsurf, h, self._pseudo_hessian, dt=dt)
         ox, oy = (o.to(dev).permute(1, 0, 2) for o in self._observed)     # -> [nt, ns, nrec]
         if ox.shape != vx.shape:
             raise MifwiError("observed data %s do not match modelled %s (nt, nshot, nrec)"
@@ -765,7 +825,9 @@ class Denise:
         if int(self.INVMAT1) != 1:
             # the same objective differentiated with respect to (Zp, Zs, rho) or (lambda, mu, rho): exact chain rule of
             # the change of variables, one launch (csrc/mifwi_materials.hip: mifwi_elastic_gradient_parametrization)
-            grads = list(elastic.gradient_parametrization([q.detach() for q in prm], grads, int(self.INVMAT1)))
+            # (L = 1: Vp and Vs are the phase velocities at F_REF, so lambda, mu, Zp, Zs are the moduli and impedances there;
+            # Qp and Qs are held fixed and keep their own gradients)
+            grads = list(elastic.gradient_parametrization([q.detach() for q in prm[:3]], grads[:3], int(self.INVMAT1))) + grads[3:]
         if self._pseudo_hessian is not None:
             # after the change of variables, with the Hessian of the same parametrisation; before the depth taper
             from .. import conditioning
@@ -776,7 +838,10 @@ class Denise:
                                             self.EXP_TAPER_GRAD_HOR), device=dev)[:, None]
             grads = [g * w for g in grads]
         # PHYSICS = 3: five gradients, (Vp0, Vs0, rho, epsilon, delta); the first three go where they always go
-        self._gradients_thomsen = tuple(np.flipud(g.cpu().numpy()).copy() for g in grads[3:]) if len(grads) == 5 else None
+        # L = 1: five as well, (Vp, Vs, rho, Qp, Qs)
+        extra = tuple(np.flipud(g.cpu().numpy()).copy() for g in grads[3:]) if len(grads) == 5 else None
+        self._gradients_thomsen = None if self._visco() else extra
+        self._gradients_q = extra if self._visco() else None
         grads = grads[:3]
         self._gradients_dev = torch.stack(grads)           # [vp, vs, rho] (INVMAT1 = 2: Zp, Zs, rho; 3: lambda, mu, rho), row 0 = surface
         gvp, gvs, grho = (np.flipud(g.cpu().numpy()).copy() for g in grads)
@@ -803,6 +868,14 @@ class Denise:
         if self._gradients_thomsen is None:
             raise MifwiError("run grad() with PHYSICS = 3 first")
         return self._gradients_thomsen
+
+
+    def get_attenuation_gradients(self):
+        """(Qp, Qs) gradients of the last ``L = 1`` grad(), [ny, nx] arrays in the caller's flipud convention, the depth
+        taper of SWS_TAPER_GRAD_HOR applied as to the other three."""
+        if self._gradients_q is None:
+            raise MifwiError("run grad() with L = 1 first")
+        return self._gradients_q
 
 
 def conditioned_gradients(d, vp, vs, rho, mute_rows=25, rho_factor=0.1, sigma=0.0):

@@ -27,6 +27,9 @@
 // the opt-in fused V+S launch (el_step_fused) live on the per-step path only.
 // VTI (mifwi_vti_*): the same scheme with c11, c13, c33, c44 for lambda + 2 mu, lambda, mu - one more material plane (M_C33), a
 // compile-time variant of el_step_s, el_adj_s / stage_E and el_finalize on the per-step path; with c33 == c11 the same bits.
+// Viscoelastic (mifwi_visco_*): one relaxation mechanism - three memory variables behind the five fields of a shot, three more
+// material planes; a compile-time VISCO variant of el_step_s, el_adj_s / stage_E, el_adj_v (which advances the adjoint memory
+// variables) and el_finalize on the per-step path; with the three planes zero the same bits.
 // Arithmetic = the explicit fmaf chain of oracle/elastic.c (build with -ffp-contract=off).
 #include "mifwi_cluster_host.h"
 #include "mifwi_host.h"
@@ -53,6 +56,10 @@ enum { F_VX = 0, F_VZ = 1, F_SXX = 2, F_SZZ = 3, F_SXZ = 4 };
 enum { M_L = 0, M_M = 1, M_MU = 2, M_BX = 3, M_BZ = 4 };
 // VTI variant (mifwi_vti_*): the same planes with c13 at M_L, c11 at M_M, c44_xz at M_MU, and c33 appended as a sixth plane
 enum { M_C33 = 5 };
+// viscoelastic variant (mifwi_visco_*, one relaxation mechanism): three memory variables behind the five fields, and three planes
+// behind the five unrelaxed ones: R2 = pi_r tau_p - 2 mu_r tau_s, R1 = pi_r tau_p, mu_r tau_s at the sxz node (all times dt/h)
+enum { F_RXX = 5, F_RZZ = 6, F_RXZ = 7 };
+enum { M_RL = 5, M_RM = 6, M_RMU = 7 };
 enum { PA = 0, PB = 1, PK = 2, PAH = 3, PBH = 4, PKH = 5 };
 // psi index: x strips hold (0: d1 sxx_x @half, 1: d3 sxz_x @int, 2: e1 vx_x @int, 3: e4 vz_x @half)
 //            z strips hold (0: d2 sxz_z @int, 1: d4 szz_z @half, 2: e2 vz_z @int, 3: e3 vx_z @half)
@@ -60,7 +67,7 @@ enum { PA = 0, PB = 1, PK = 2, PAH = 3, PBH = 4, PKH = 5 };
 struct ElParams {
     int nz, nx, ng, gp, pitch;
     unsigned field_stride;       // (nz+4)*pitch
-    long long shot_stride;       // 5*field_stride
+    long long shot_stride;       // 5*field_stride; 8*field_stride on a viscoelastic plan (F_RXX..F_RXZ)
     int nshot, gs;
     int s0;                      // first shot of this pass over the time range (blockIdx.z counts from it)
     int W, wl, xr0, wx;          // C-PML strip geometry; W = 0 disables the layer
@@ -75,7 +82,7 @@ struct ElParams {
     long long snap_shot;         // floats per shot of one snapshot step (5 * splane for f32)
     unsigned splane;             // floats per snapshot plane: nz*gp, or nz * 64 * ceil(ng / 16) in the column-blocked layout
     int sblk;                    // 1: snapshot planes stored as [column block of 16 groups][row][64 floats] (snap_cell)
-    float *acc;                  // [ngroups][5][nz][gp]
+    float *acc;                  // [ngroups][5][nz][gp] (6 planes per group on a VTI plan, 8 on a viscoelastic one)
     // injection (S launch: sxx,szz += a ; S^T launch: vx += ax, vz += az)
     int ninj, ntap_inj;
     const int *inj_cell;
@@ -92,6 +99,7 @@ struct ElParams {
     int xcd;                     // XCD-aware tile order (xcd_tile): 1 contiguous runs per shot, 2 whole shots, 3 tile-major over the shots
     FdK K;                       // stencil weights
     const float *dmat;           // Born step (SAVE 3): perturbation of the five material planes, [5][nz][gp] like mat
+    float rel_a, rel_b;          // viscoelastic plans: r <- a r - b q per step, a = (2 - eta) / (2 + eta), b = 2 eta / (2 + eta)
 };
 
 __device__ __forceinline__ float comp(const float4 &v, int c)
@@ -474,7 +482,9 @@ __global__ __launch_bounds__(kThreads, MIFWI_EL_MINWAVES) void el_step_v(const E
 // ================================================================================================
 // VTI: sxx = fmaf(c11, e1, fmaf(c13, e2, sxx)), szz = fmaf(c13, e1, fmaf(c33, e2, szz)) with c33 read from plane M_C33 (of
 // mat and, Born step, of dmat); c33 == c11 gives the isotropic bits.
-template <int LX, int RZ, int SAVE, bool VTI = false>
+// VISCO: q = R e (+ dR S, Born step) from planes M_RL, M_RM, M_RMU; the stress gets (1 + a)/2 r - b/2 q AFTER the fmaf chain and
+// r <- a r - b q.  With the three planes zero r stays 0 and the chain's result is stored: the isotropic bits.
+template <int LX, int RZ, int SAVE, bool VTI = false, bool VISCO = false>
 __global__ __launch_bounds__(kThreads, MIFWI_EL_MINWAVES) void el_step_s(const ElParams p)
 {
     const FdK K = p.K;
@@ -542,6 +552,17 @@ __global__ __launch_bounds__(kThreads, MIFWI_EL_MINWAVES) void el_step_s(const E
                         dmu = ld4(p.dmat + M_MU * ncell + cc);
                         dC = VTI ? ld4(p.dmat + M_C33 * ncell + cc) : dM;
                     }
+                    float4 R2s = zero4, R1s = zero4, Rmu = zero4, rxx = zero4, rzz = zero4, rxz = zero4;
+                    float4 dR2 = zero4, dR1 = zero4, dRmu = zero4;
+                    if (VISCO) {
+                        R2s = ld4(p.mat + M_RL * ncell + cc); R1s = ld4(p.mat + M_RM * ncell + cc);
+                        Rmu = ld4(p.mat + M_RMU * ncell + cc);
+                        rxx = ld4(fl + F_RXX * fs + o); rzz = ld4(fl + F_RZZ * fs + o); rxz = ld4(fl + F_RXZ * fs + o);
+                        if (SAVE == kBorn) {
+                            dR2 = ld4(p.dmat + M_RL * ncell + cc); dR1 = ld4(p.dmat + M_RM * ncell + cc);
+                            dRmu = ld4(p.dmat + M_RMU * ncell + cc);
+                        }
+                    }
                     const float xv[8] = {Lvx.x, Lvx.y, b1.x, b1.y, b1.z, b1.w, Rvx.x, Rvx.y};
                     const float zv[8] = {Lvz.x, Lvz.y, a2.x, a2.y, a2.z, a2.w, Rvz.x, Rvz.y};
                     float e1[4], e2[4], e3[4], e4[4];
@@ -581,7 +602,7 @@ __global__ __launch_bounds__(kThreads, MIFWI_EL_MINWAVES) void el_step_s(const E
                         st4(q6, make_float4(t6[0], t6[1], t6[2], t6[3]));
                         st4(q7, make_float4(t7[0], t7[1], t7[2], t7[3]));
                     }
-                    float nxx[4], nzz[4], nxz[4], s3v[4];
+                    float nxx[4], nzz[4], nxz[4], s3v[4], mxx[4], mzz[4], mxz[4];
 #pragma unroll
                     for (int c = 0; c < 4; ++c) {
                         s3v[c] = e3[c] + e4[c];
@@ -593,6 +614,23 @@ __global__ __launch_bounds__(kThreads, MIFWI_EL_MINWAVES) void el_step_s(const E
                             nzz[c] = fmaf(comp(dL, c), comp(B0, c), fmaf(comp(dC, c), comp(B1, c), nzz[c]));
                             nxz[c] = fmaf(comp(dmu, c), comp(B2, c), nxz[c]);
                         }
+                        if (VISCO) {
+                            const float ha = 0.5f * (1.f + p.rel_a), hb = 0.5f * p.rel_b;
+                            float qxx = fmaf(comp(R1s, c), e1[c], comp(R2s, c) * e2[c]);
+                            float qzz = fmaf(comp(R2s, c), e1[c], comp(R1s, c) * e2[c]);
+                            float qxz = comp(Rmu, c) * s3v[c];
+                            if (SAVE == kBorn) {
+                                qxx = fmaf(comp(dR1, c), comp(B0, c), fmaf(comp(dR2, c), comp(B1, c), qxx));
+                                qzz = fmaf(comp(dR2, c), comp(B0, c), fmaf(comp(dR1, c), comp(B1, c), qzz));
+                                qxz = fmaf(comp(dRmu, c), comp(B2, c), qxz);
+                            }
+                            nxx[c] += fmaf(ha, comp(rxx, c), -(hb * qxx));
+                            nzz[c] += fmaf(ha, comp(rzz, c), -(hb * qzz));
+                            nxz[c] += fmaf(ha, comp(rxz, c), -(hb * qxz));
+                            mxx[c] = fmaf(p.rel_a, comp(rxx, c), -(p.rel_b * qxx));
+                            mzz[c] = fmaf(p.rel_a, comp(rzz, c), -(p.rel_b * qzz));
+                            mxz[c] = fmaf(p.rel_a, comp(rxz, c), -(p.rel_b * qxz));
+                        }
                         if (has_inj) {
                             const float a = inj[(j - tile_j) * TX + 4 * lx + c];
                             nxx[c] += a;
@@ -603,6 +641,11 @@ __global__ __launch_bounds__(kThreads, MIFWI_EL_MINWAVES) void el_step_s(const E
                     st4(sxx + o, make_float4(nxx[0], nxx[1], nxx[2], nxx[3]));
                     st4(szz + o, make_float4(nzz[0], nzz[1], nzz[2], nzz[3]));
                     st4(sxz + o, make_float4(nxz[0], nxz[1], nxz[2], nxz[3]));
+                    if (VISCO) {
+                        st4(fl + F_RXX * fs + o, make_float4(mxx[0], mxx[1], mxx[2], mxx[3]));
+                        st4(fl + F_RZZ * fs + o, make_float4(mzz[0], mzz[1], mzz[2], mzz[3]));
+                        st4(fl + F_RXZ * fs + o, make_float4(mxz[0], mxz[1], mxz[2], mxz[3]));
+                    }
                     if (SAVE == 1) {
                         float *Sp = p.S + (long long)s * p.snap_shot + snap_cell(p, j, g);
                         mifwi::stnt4(Sp, make_float4(e1[0], e1[1], e1[2], e1[3]));
@@ -662,6 +705,22 @@ struct AdjInVti : AdjIn { float4 m3; };     // + c33 (m0 = c13, m1 = c11, m2 = c
 // E1..E4 of one group: C^T sigma_bar through the transposed C-PML (memory variables written by the owner)
 __device__ __forceinline__ const float4 &adj_c33(const AdjIn &in) { return in.m1; }
 __device__ __forceinline__ const float4 &adj_c33(const AdjInVti &in) { return in.m3; }
+// viscoelastic: + R2, R1, mu_r tau_s (m3, m4, m5) and w = -b (r_bar + sigma_bar / 2), the adjoint of q (adj_w)
+struct AdjInVisco : AdjIn { float4 m3, m4, m5, wa, wb, wc; };
+__device__ __forceinline__ const float4 &adj_c33(const AdjInVisco &in) { return in.m1; }
+__device__ __forceinline__ float4 adj_w(float b, const float4 &rb, const float4 &sb)
+{
+    return make_float4(-b * fmaf(0.5f, sb.x, rb.x), -b * fmaf(0.5f, sb.y, rb.y), -b * fmaf(0.5f, sb.z, rb.z),
+                       -b * fmaf(0.5f, sb.w, rb.w));
+}
+// E += R^T w before the transposed C-PML (nothing for the lossless media)
+__device__ __forceinline__ void adj_relax(const AdjIn &, int, float &, float &, float &) {}
+__device__ __forceinline__ void adj_relax(const AdjInVisco &in, int c, float &e1, float &e2, float &e3)
+{
+    e1 += fmaf(comp(in.m4, c), comp(in.wa, c), comp(in.m3, c) * comp(in.wb, c));
+    e2 += fmaf(comp(in.m3, c), comp(in.wa, c), comp(in.m4, c) * comp(in.wb, c));
+    e3 += comp(in.m5, c) * comp(in.wc, c);
+}
 template <class In>
 __device__ __forceinline__ void stage_E(const ElParams &p, int s, int j, int g, const In &in, bool mine,
                                         float4 &E1, float4 &E2, float4 &E3, float4 &E4)
@@ -672,6 +731,7 @@ __device__ __forceinline__ void stage_E(const ElParams &p, int s, int j, int g, 
         e1[c] = fmaf(comp(in.m1, c), comp(in.a, c), comp(in.m0, c) * comp(in.b, c));
         e2[c] = fmaf(comp(in.m0, c), comp(in.a, c), comp(adj_c33(in), c) * comp(in.b, c));
         e3[c] = comp(in.m2, c) * comp(in.c, c);
+        adj_relax(in, c, e1[c], e2[c], e3[c]);
         e4[c] = e3[c];
     }
     const int xs_off = xstrip(p, g);
@@ -761,10 +821,16 @@ __global__ void el_build_tile_taps(const int *cell, int ntaps, int nx, int tx, i
 // workgroups per CU, 768 workgroup slots.  1000x3000 adjoint pair 885 -> 853-864 us per step.
 // VTI: six accumulators per group - acc[M_M] (c11) takes S1 sxx_bar alone, acc[M_C33] takes S2 szz_bar, acc[M_L] (c13) is
 // the isotropic lambda sum; E2 uses c33 (stage_E).  158 VGPRs, no scratch: the bound of three waves per SIMD holds.
-template <bool BF16, bool VTI = false>
-__global__ __launch_bounds__(kThreads, 3) void el_adj_s(const ElParams p)
+// VISCO: eight accumulators; w = -b (r_bar + sigma_bar / 2) on own and halo cells from the OLD r_bar (read only here: the
+// neighbouring tiles stage it too - el_adj_v_visco advances it), E += R^T w in stage_E, acc[M_RM] += S1 wxx + S2 wzz,
+// acc[M_RL] += S2 wxx + S1 wzz, acc[M_RMU] += S3 wxz.  A register bound of its own, two waves per SIMD: r_bar and three
+// more planes on own and halo cells, w across the barrier and three more accumulators do not fit 168 VGPRs (bound at
+// three waves the compiler reports 168 VGPRs and 132 B of scratch per lane).
+constexpr int kAdjWavesVisco = 2;
+template <bool BF16, bool VTI = false, bool VISCO = false>
+__global__ __launch_bounds__(kThreads, VISCO ? kAdjWavesVisco : 3) void el_adj_s(const ElParams p)
 {
-    constexpr int NACC = VTI ? 6 : 5;
+    constexpr int NACC = VISCO ? 8 : VTI ? 6 : 5;
     const FdK K = p.K;
     int bx, by, bz;
     xcd_tile(p, bx, by, bz);
@@ -792,9 +858,10 @@ __global__ __launch_bounds__(kThreads, 3) void el_adj_s(const ElParams p)
     const unsigned ho = (unsigned)(hj + 2) * p.pitch + 4 + 4 * hgg;
     const float4 zero4 = make_float4(0.f, 0.f, 0.f, 0.f);
     float4 acc[NACC];
-    typename std::conditional<VTI, AdjInVti, AdjIn>::type own, halo;
+    typename std::conditional<VISCO, AdjInVisco, typename std::conditional<VTI, AdjInVti, AdjIn>::type>::type own, halo;
     own.m0 = own.m1 = own.m2 = halo.m0 = halo.m1 = halo.m2 = zero4;
     if constexpr (VTI) own.m3 = halo.m3 = zero4;
+    if constexpr (VISCO) own.m3 = own.m4 = own.m5 = halo.m3 = halo.m4 = halo.m5 = zero4;
     if (own_ok) {
 #pragma unroll
         for (int k = 0; k < NACC; ++k)       // accumulator planes share the snapshot planes' layout (snap_cell)
@@ -802,11 +869,19 @@ __global__ __launch_bounds__(kThreads, 3) void el_adj_s(const ElParams p)
         own.m0 = ld4(el_at(p.mat + M_L * ncell, occ)); own.m1 = ld4(el_at(p.mat + M_M * ncell, occ));
         own.m2 = ld4(el_at(p.mat + M_MU * ncell, occ));
         if constexpr (VTI) own.m3 = ld4(el_at(p.mat + M_C33 * ncell, occ));
+        if constexpr (VISCO) {
+            own.m3 = ld4(el_at(p.mat + M_RL * ncell, occ)); own.m4 = ld4(el_at(p.mat + M_RM * ncell, occ));
+            own.m5 = ld4(el_at(p.mat + M_RMU * ncell, occ));
+        }
     }
     if (halo_ok) {
         halo.m0 = ld4(el_at(p.mat + M_L * ncell, hcc)); halo.m1 = ld4(el_at(p.mat + M_M * ncell, hcc));
         halo.m2 = ld4(el_at(p.mat + M_MU * ncell, hcc));
         if constexpr (VTI) halo.m3 = ld4(el_at(p.mat + M_C33 * ncell, hcc));
+        if constexpr (VISCO) {
+            halo.m3 = ld4(el_at(p.mat + M_RL * ncell, hcc)); halo.m4 = ld4(el_at(p.mat + M_RM * ncell, hcc));
+            halo.m5 = ld4(el_at(p.mat + M_RMU * ncell, hcc));
+        }
     }
     for (int si = 0; si < p.gs; ++si) {
         const int s = p.s0 + bz * p.gs + si;
@@ -824,6 +899,15 @@ __global__ __launch_bounds__(kThreads, 3) void el_adj_s(const ElParams p)
             halo.a = ld4(el_at(fl + F_SXX * fs, ho)); halo.b = ld4(el_at(fl + F_SZZ * fs, ho)); halo.c = ld4(el_at(fl + F_SXZ * fs, ho));
         }
         if (own_ok) { vxb = ld4(el_at(fl + F_VX * fs, oo)); vzb = ld4(el_at(fl + F_VZ * fs, oo)); }
+        if constexpr (VISCO) {            // r_bar for now; w once sigma_bar zz of a free surface is cleared
+            own.wa = own.wb = own.wc = halo.wa = halo.wb = halo.wc = zero4;
+            if (own_ok) {
+                own.wa = ld4(el_at(fl + F_RXX * fs, oo)); own.wb = ld4(el_at(fl + F_RZZ * fs, oo)); own.wc = ld4(el_at(fl + F_RXZ * fs, oo));
+            }
+            if (halo_ok) {
+                halo.wa = ld4(el_at(fl + F_RXX * fs, ho)); halo.wb = ld4(el_at(fl + F_RZZ * fs, ho)); halo.wc = ld4(el_at(fl + F_RXZ * fs, ho));
+            }
+        }
         // ---- adjoint sources of this tile (workgroup-uniform branch; E[0], E[1] are free until the staging) -----
         if (p.tile_start != nullptr) {
             const int ntiles = (int)gridDim.x * p.tiles_z, per = p.ninj * p.ntap_inj;
@@ -852,6 +936,10 @@ __global__ __launch_bounds__(kThreads, 3) void el_adj_s(const ElParams p)
         // ---- stage E1..E4 on the tile + halo -------------------------------------------------
         if (p.fsurf && oj == 0) own.b = zero4;            // adjoint of szz(0,.) is discarded
         if (p.fsurf && hj == 0) halo.b = zero4;
+        if constexpr (VISCO) {
+            own.wa = adj_w(p.rel_b, own.wa, own.a); own.wb = adj_w(p.rel_b, own.wb, own.b); own.wc = adj_w(p.rel_b, own.wc, own.c);
+            halo.wa = adj_w(p.rel_b, halo.wa, halo.a); halo.wb = adj_w(p.rel_b, halo.wb, halo.b); halo.wc = adj_w(p.rel_b, halo.wc, halo.c);
+        }
         {
             float4 E1 = zero4, E2 = zero4, E3 = zero4, E4 = zero4;
             if (own_ok) stage_E(p, s, f_opaque(oj), f_opaque(og), own, true, E1, E2, E3, E4);
@@ -918,6 +1006,17 @@ __global__ __launch_bounds__(kThreads, 3) void el_adj_s(const ElParams p)
 #undef ACC3
             acc[M_MU].x = fmaf(S3.x, bxz.x, acc[M_MU].x); acc[M_MU].y = fmaf(S3.y, bxz.y, acc[M_MU].y);
             acc[M_MU].z = fmaf(S3.z, bxz.z, acc[M_MU].z); acc[M_MU].w = fmaf(S3.w, bxz.w, acc[M_MU].w);
+            if constexpr (VISCO) {
+#define ACC3(dst, a, b, c_, d) dst = fmaf(a, b, fmaf(c_, d, dst))
+                const float4 wxx = own.wa, wzz = own.wb, wxz = own.wc;
+                ACC3(acc[M_RM].x, S1.x, wxx.x, S2.x, wzz.x); ACC3(acc[M_RM].y, S1.y, wxx.y, S2.y, wzz.y);
+                ACC3(acc[M_RM].z, S1.z, wxx.z, S2.z, wzz.z); ACC3(acc[M_RM].w, S1.w, wxx.w, S2.w, wzz.w);
+                ACC3(acc[M_RL].x, S2.x, wxx.x, S1.x, wzz.x); ACC3(acc[M_RL].y, S2.y, wxx.y, S1.y, wzz.y);
+                ACC3(acc[M_RL].z, S2.z, wxx.z, S1.z, wzz.z); ACC3(acc[M_RL].w, S2.w, wxx.w, S1.w, wzz.w);
+#undef ACC3
+                acc[M_RMU].x = fmaf(S3.x, wxz.x, acc[M_RMU].x); acc[M_RMU].y = fmaf(S3.y, wxz.y, acc[M_RMU].y);
+                acc[M_RMU].z = fmaf(S3.z, wxz.z, acc[M_RMU].z); acc[M_RMU].w = fmaf(S3.w, wxz.w, acc[M_RMU].w);
+            }
             acc[M_BX].x = fmaf(S4.x, nvx[0], acc[M_BX].x); acc[M_BX].y = fmaf(S4.y, nvx[1], acc[M_BX].y);
             acc[M_BX].z = fmaf(S4.z, nvx[2], acc[M_BX].z); acc[M_BX].w = fmaf(S4.w, nvx[3], acc[M_BX].w);
             acc[M_BZ].x = fmaf(S5.x, nvz[0], acc[M_BZ].x); acc[M_BZ].y = fmaf(S5.y, nvz[1], acc[M_BZ].y);
@@ -985,7 +1084,10 @@ __device__ __forceinline__ void stage_D(const ElParams &p, int s, int j, int g, 
 }
 
 // V^T:  D = B^T v_bar through the transposed C-PML;  sigma_bar -= stencils(D)
-__global__ __launch_bounds__(kThreads) void el_adj_v(const ElParams p)
+// VISCO: the owner also advances r_bar <- a r_bar + (1 + a)/2 sigma_bar with the sigma_bar this launch loaded, i.e. the one
+// S^T saw (zz of a free-surface row counts as 0, as there).  Cell-local, and nothing else reads r_bar in this launch.
+template <bool VISCO>
+__device__ __forceinline__ void el_adj_v_body(const ElParams &p)
 {
     const FdK K = p.K;
     __shared__ float D[4][ASZ][ASX];
@@ -1066,8 +1168,21 @@ __global__ __launch_bounds__(kThreads) void el_adj_v(const ElParams p)
         st4(fl + F_SXX * fs + oo, make_float4(nxx[0], nxx[1], nxx[2], nxx[3]));
         st4(fl + F_SZZ * fs + oo, make_float4(nzz[0], nzz[1], nzz[2], nzz[3]));
         st4(fl + F_SXZ * fs + oo, make_float4(nxz[0], nxz[1], nxz[2], nxz[3]));
+        if (VISCO) {
+            const float ha = 0.5f * (1.f + p.rel_a);
+            if (p.fsurf && oj == 0) bzz = zero4;
+            const float4 rxx = ld4(fl + F_RXX * fs + oo), rzz = ld4(fl + F_RZZ * fs + oo), rxz = ld4(fl + F_RXZ * fs + oo);
+            st4(fl + F_RXX * fs + oo, make_float4(fmaf(p.rel_a, rxx.x, ha * bxx.x), fmaf(p.rel_a, rxx.y, ha * bxx.y),
+                                                  fmaf(p.rel_a, rxx.z, ha * bxx.z), fmaf(p.rel_a, rxx.w, ha * bxx.w)));
+            st4(fl + F_RZZ * fs + oo, make_float4(fmaf(p.rel_a, rzz.x, ha * bzz.x), fmaf(p.rel_a, rzz.y, ha * bzz.y),
+                                                  fmaf(p.rel_a, rzz.z, ha * bzz.z), fmaf(p.rel_a, rzz.w, ha * bzz.w)));
+            st4(fl + F_RXZ * fs + oo, make_float4(fmaf(p.rel_a, rxz.x, ha * bxz.x), fmaf(p.rel_a, rxz.y, ha * bxz.y),
+                                                  fmaf(p.rel_a, rxz.z, ha * bxz.z), fmaf(p.rel_a, rxz.w, ha * bxz.w)));
+        }
     }
 }
+__global__ __launch_bounds__(kThreads) void el_adj_v(const ElParams p) { el_adj_v_body<false>(p); }
+__global__ __launch_bounds__(kThreads) void el_adj_v_visco(const ElParams p) { el_adj_v_body<true>(p); }
 
 #include "mifwi_elastic_fused.h"
 
@@ -1180,6 +1295,11 @@ __global__ void el_finalize_vti(const float *acc, int ngroups, int nz, int gp, l
 {
     el_finalize_body<6>(acc, ngroups, nz, gp, aplane, sblk, grad);
 }
+// viscoelastic: grad [8][nz][gp] from eight accumulator planes per group
+__global__ void el_finalize_visco(const float *acc, int ngroups, int nz, int gp, long long aplane, int sblk, float *grad)
+{
+    el_finalize_body<8>(acc, ngroups, nz, gp, aplane, sblk, grad);
+}
 
 #include "mifwi_elastic_cluster.h"
 
@@ -1214,7 +1334,10 @@ struct mifwi_elastic_plan {
     long long xbuf_elems, list_elems, xcc_elems;
     long long tile_elems;                  // per-tile receiver lists of el_adj_s (ints, in floats)
     int vti;               // mifwi_vti_*: the six-plane kernels (el_step_s / el_adj_s with VTI = true, el_finalize_vti), per-step family only
-    int nmat;              // material / gradient / accumulator planes: 5, or 6 under vti
+    int nmat;              // material / gradient / accumulator planes: 5, 6 under vti, 8 under visco
+    int visco;             // mifwi_visco_*: eight planes and eight fields per shot (el_step_s / el_adj_s with VISCO = true,
+                           // el_adj_v_visco, el_finalize_visco), per-step family only
+    float rel_a, rel_b;    // its relaxation scalars (ElParams)
 };
 // a VTI plan is an elastic plan with the flag set (el_plan_create); the C ABI keeps the two handle types apart
 struct mifwi_vti_plan;
@@ -1236,6 +1359,7 @@ ElParams el_base(const mifwi_elastic_plan *pl, const float *mat, const float *pz
     p.snap_shot = pl->snap_shot;
     p.splane = (unsigned)pl->splane; p.sblk = pl->sblk;
     p.K = fd_weights(pl->d.fd_order);
+    p.rel_a = pl->rel_a; p.rel_b = pl->rel_b;
     return p;
 }
 
@@ -1262,6 +1386,15 @@ ElStepKernels el_step_variant_vti(int lx, int save)
     return with_int<kBorn, 1, 0>(save, [&](auto SAVE) {
         return ElStepKernels{el_step_v<decltype(LX)::value, 1, decltype(SAVE)::value>,
                              el_step_s<decltype(LX)::value, 1, decltype(SAVE)::value, true>};
+    }); });
+}
+// viscoelastic plans: the same V launch, el_step_s<LX, 1, SAVE, false, true>
+ElStepKernels el_step_variant_visco(int lx, int save)
+{
+    return with_int<64, 32, 16>(lx, [&](auto LX) {
+    return with_int<kBorn, 1, 0>(save, [&](auto SAVE) {
+        return ElStepKernels{el_step_v<decltype(LX)::value, 1, decltype(SAVE)::value>,
+                             el_step_s<decltype(LX)::value, 1, decltype(SAVE)::value, false, true>};
     }); });
 }
 // el_fwd_fused<SAVE>: save 2 | 1 | 0 (no Born form: that pass runs the two launches)
@@ -1383,7 +1516,7 @@ void el_cluster_setup(mifwi_elastic_plan *pl)
         const long long ntiles = (long long)mifwi::ceil_div(pl->ng, AGO) * mifwi::ceil_div(pl->d.nz, ATZ);
         pl->tile_elems = std::max<long long>(1024, mifwi::round_up64(pl->d.nshot * (2 * ntiles + 1 + (long long)pl->d.nrec * pl->d.ntap), 64));
     }
-    if (pl->vti || pl->d.ntap != 1 || pl->d.source_type != 0 || pl->d.record_pressure) return;   // per-step kernels only
+    if (pl->vti || pl->visco || pl->d.ntap != 1 || pl->d.source_type != 0 || pl->d.record_pressure) return;   // per-step kernels only
     const bool want_fwd = env_int("MIFWI_EL_CLUSTER", 1) != 0;
     int ncu = 0;
     if (hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, pl->device) != hipSuccess) return;
@@ -1512,7 +1645,8 @@ void el_two_launch_steps(const mifwi_elastic_plan *pl, ElParams p, int save, con
     const mifwi_elastic_desc &d = pl->d;
     const long long snap_step = pl->snap_shot * d.nshot;
     const bool want_rec = rec_vx != nullptr;
-    const ElStepKernels step = pl->vti ? el_step_variant_vti(pl->lx, save) : el_step_variant(pl->lx, save);
+    const ElStepKernels step = pl->visco ? el_step_variant_visco(pl->lx, save)
+                               : pl->vti ? el_step_variant_vti(pl->lx, save) : el_step_variant(pl->lx, save);
     ElParams ps = p;
     const bool force = d.source_type != 0;      // point force: injected into vx / vz by a launch of its own
     ps.ninj = (force || !f) ? 0 : d.nsrc; ps.ntap_inj = d.ntap; ps.inj_cell = src_cell; ps.inj_w = src_w;
@@ -1547,8 +1681,11 @@ void el_two_launch_steps(const mifwi_elastic_plan *pl, ElParams p, int save, con
     }
 }
 
-int el_plan_create(mifwi_elastic_plan **plan, int device, const mifwi_elastic_desc *d, int vti)
+// medium: 0 isotropic, 1 VTI, 2 viscoelastic (rel_a, rel_b: its relaxation scalars)
+int el_plan_create(mifwi_elastic_plan **plan, int device, const mifwi_elastic_desc *d, int medium, float rel_a = 0.f,
+                   float rel_b = 0.f)
 {
+    const int vti = medium == 1, visco = medium == 2;
     if (!plan || !d) return mifwi::fail(MIFWI_EINVAL, "null plan/desc");
     if (d->nz < 1 || d->nx < 1 || d->nt < 1 || d->nshot < 1 || d->nsrc < 0 || d->nrec < 0)
         return mifwi::fail(MIFWI_EINVAL, "bad sizes nz=%d nx=%d nt=%d nshot=%d", d->nz, d->nx, d->nt,
@@ -1575,13 +1712,14 @@ int el_plan_create(mifwi_elastic_plan **plan, int device, const mifwi_elastic_de
     pl->d = *d;
     if (pl->d.fd_order == 0) pl->d.fd_order = 4;
     pl->device = device;
-    pl->vti = vti; pl->nmat = vti ? 6 : 5;
+    pl->vti = vti; pl->visco = visco; pl->nmat = visco ? 8 : vti ? 6 : 5;
+    pl->rel_a = rel_a; pl->rel_b = rel_b;
     pl->rec_p = nullptr; pl->g_p = nullptr;
     pl->ng = mifwi::ceil_div(d->nx, 4);
     pl->gp = 4 * pl->ng;
     pl->pitch = (int)mifwi::round_up64(4 * (pl->ng + 3), 32);
     pl->field_stride = (long long)(d->nz + 4) * pl->pitch;
-    pl->shot_stride = 5 * pl->field_stride;
+    pl->shot_stride = (visco ? 8 : 5) * pl->field_stride;      // + the three memory variables
     pl->fields_elems = pl->shot_stride * d->nshot;
     pl->coef_elems = (long long)d->nz * pl->gp;
     // strip geometry: W = pml_width + 1 nodes per side (half-node profiles reach one node further)
@@ -1663,7 +1801,7 @@ int el_plan_create(mifwi_elastic_plan **plan, int device, const mifwi_elastic_de
     // 1000x3000 x 16 shots: 622 -> 558 us per step, 516 with bf16 planes; 350x1700 x 32: 232 -> 232, 214 -> 209) and
     // on any launch of a million cells or more (350x1700 x 4 shots, the chunks of a shot-chunked gradient pass:
     // 286 -> 260 us per step of all 32 shots)
-    pl->fused = !pl->vti && !pl->cluster && d->source_type == 0 && !d->record_pressure &&
+    pl->fused = !pl->vti && !pl->visco && !pl->cluster && d->source_type == 0 && !d->record_pressure &&
                 env_int("MIFWI_EL_FUSED", (pl->pass_shots < d->nshot || (double)d->nz * d->nx * d->nshot >= 1e6) ? 1 : 0) != 0;
     {
         const double cells = (double)pl->coef_elems, mats = 4.0 * 5.0 * cells;
@@ -1977,7 +2115,8 @@ int mifwi_elastic_backward(mifwi_elastic_plan *pl, const float *mat, const float
             hipLaunchKernelGGL(el_inject_pressure, dim3(mifwi::ceil_div(cs * d.nrec * d.ntap, 64)), dim3(64), 0,
                                st, pq);
         }
-        if (pl->vti) hipLaunchKernelGGL((el_adj_s<false, true>), dim3(tx, tz + ex, cg), dim3(kThreads), 0, st, ps);
+        if (pl->visco) hipLaunchKernelGGL((el_adj_s<false, false, true>), dim3(tx, tz + ex, cg), dim3(kThreads), 0, st, ps);
+        else if (pl->vti) hipLaunchKernelGGL((el_adj_s<false, true>), dim3(tx, tz + ex, cg), dim3(kThreads), 0, st, ps);
         else if (pl->snap_bf16) hipLaunchKernelGGL(el_adj_s<true>, dim3(tx, tz + ex, cg), dim3(kThreads), 0, st, ps);
         else hipLaunchKernelGGL(el_adj_s<false>, dim3(tx, tz + ex, cg), dim3(kThreads), 0, st, ps);
         if (want_f && force) {
@@ -1986,11 +2125,11 @@ int mifwi_elastic_backward(mifwi_elastic_plan *pl, const float *mat, const float
             hipLaunchKernelGGL(el_sample_force, dim3(mifwi::ceil_div(cs * d.nsrc, 64)), dim3(64), 0, st, pq,
                                d.source_type);
         }
-        hipLaunchKernelGGL(el_adj_v, dim3(tx, tz, cs), dim3(kThreads), 0, st, p);
+        hipLaunchKernelGGL(pl->visco ? el_adj_v_visco : el_adj_v, dim3(tx, tz, cs), dim3(kThreads), 0, st, p);
     }
     if (flags & MIFWI_FINALIZE) {
         const long long n5 = (long long)pl->nmat * pl->coef_elems;
-        hipLaunchKernelGGL(pl->vti ? el_finalize_vti : el_finalize, dim3((unsigned)((n5 + 255) / 256)), dim3(256), 0, st, acc,
+        hipLaunchKernelGGL(pl->visco ? el_finalize_visco : pl->vti ? el_finalize_vti : el_finalize, dim3((unsigned)((n5 + 255) / 256)), dim3(256), 0, st, acc,
                            pl->ngroups, d.nz, pl->gp, pl->splane, pl->cl_adj ? 0 : pl->sblk, grad_mat);
     }
     MIFWI_HIP_TRY(hipGetLastError());
@@ -2068,6 +2207,83 @@ int mifwi_vti_born(mifwi_vti_plan *plan, const float *mat, const float *dmat, co
 {
     if (const int rc = vti_check(plan)) return rc;
     return mifwi_elastic_born(vti_plan(plan), mat, dmat, pz, px, df, src_cell, src_w, rec_cell, rec_w, snap, snap_first,
+                              drec_vx, drec_vz, work, n_begin, n_end, flags, stream);
+}
+
+// ---- viscoelastic: the elastic plan with eight planes and eight fields per shot (include/mifwi.h) ----------------------
+static mifwi_elastic_plan *visco_plan(mifwi_visco_plan *p) { return reinterpret_cast<mifwi_elastic_plan *>(p); }
+static const mifwi_elastic_plan *visco_plan(const mifwi_visco_plan *p) { return reinterpret_cast<const mifwi_elastic_plan *>(p); }
+static int visco_check(const mifwi_visco_plan *p)
+{
+    return (p && !visco_plan(p)->visco) ? mifwi::fail(MIFWI_EINVAL, "the plan was not created by mifwi_visco_plan_create") : MIFWI_OK;
+}
+
+int mifwi_visco_plan_create(mifwi_visco_plan **plan, int device, const mifwi_visco_desc *d)
+{
+    if (!plan || !d) return mifwi::fail(MIFWI_EINVAL, "null plan/desc");
+    // a = (2 - eta) / (2 + eta), b = 2 eta / (2 + eta) with 0 < eta < 2: 0 < a < 1 and b = 1 - a
+    if (!(d->relax_a > 0.f && d->relax_a < 1.f && d->relax_b > 0.f && d->relax_b < 1.f))
+        return mifwi::fail(MIFWI_EINVAL, "relax_a = %g, relax_b = %g: both must lie inside (0, 1)", (double)d->relax_a,
+                           (double)d->relax_b);
+    mifwi_elastic_desc e;
+    e.nz = d->nz; e.nx = d->nx; e.nt = d->nt; e.nshot = d->nshot; e.nsrc = d->nsrc; e.nrec = d->nrec; e.ntap = d->ntap;
+    e.pml_width = d->pml_width; e.free_surface = d->free_surface; e.shots_per_group = d->shots_per_group;
+    e.source_type = d->source_type; e.record_pressure = 0; e.snapshot_format = MIFWI_SNAPSHOT_F32; e.fd_order = d->fd_order;
+    return el_plan_create(reinterpret_cast<mifwi_elastic_plan **>(plan), device, &e, 2, d->relax_a, d->relax_b);
+}
+
+int mifwi_visco_plan_destroy(mifwi_visco_plan *plan)
+{
+    delete visco_plan(plan);
+    return MIFWI_OK;
+}
+
+int mifwi_visco_plan_layout(const mifwi_visco_plan *plan, mifwi_visco_layout *out)
+{
+    if (!plan || !out) return mifwi::fail(MIFWI_EINVAL, "null plan/layout");
+    mifwi_elastic_layout e;
+    const int rc = mifwi_elastic_plan_layout(visco_plan(plan), &e);
+    if (rc) return rc;
+    out->gp = e.gp; out->pitch = e.pitch; out->ngroups = e.ngroups; out->shots_per_group = e.shots_per_group;
+    out->coef_elems = e.coef_elems; out->state_elems = e.state_elems; out->work_forward_elems = e.work_forward_elems;
+    out->work_backward_elems = e.work_backward_elems; out->snap_step_elems = e.snap_step_elems;
+    return MIFWI_OK;
+}
+
+int mifwi_visco_plan_pass_sizes(const mifwi_visco_plan *plan, int32_t *forward_shots, int32_t *adjoint_groups)
+{
+    return mifwi_elastic_plan_pass_sizes(visco_plan(plan), forward_shots, adjoint_groups);
+}
+
+int mifwi_visco_plan_cluster_slabs(const mifwi_visco_plan *, int32_t) { return 0; }
+
+int mifwi_visco_forward(mifwi_visco_plan *plan, const float *mat, const float *pz, const float *px, const float *f,
+                        const int32_t *src_cell, const float *src_w, const int32_t *rec_cell, const float *rec_w,
+                        float *rec_vx, float *rec_vz, float *snap, float *work, int32_t n_begin, int32_t n_end,
+                        int32_t flags, void *stream)
+{
+    if (const int rc = visco_check(plan)) return rc;
+    return mifwi_elastic_forward(visco_plan(plan), mat, pz, px, f, src_cell, src_w, rec_cell, rec_w, rec_vx, rec_vz, snap, work,
+                                 n_begin, n_end, flags, stream);
+}
+
+int mifwi_visco_backward(mifwi_visco_plan *plan, const float *mat, const float *pz, const float *px, const int32_t *src_cell,
+                         const float *src_w, const int32_t *rec_cell, const float *rec_w, const float *g_vx, const float *g_vz,
+                         const float *snap, int32_t snap_first, float *grad_mat, float *grad_f, float *work, int32_t n_hi,
+                         int32_t n_lo, int32_t flags, void *stream)
+{
+    if (const int rc = visco_check(plan)) return rc;
+    return mifwi_elastic_backward(visco_plan(plan), mat, pz, px, src_cell, src_w, rec_cell, rec_w, g_vx, g_vz, snap, snap_first,
+                                  grad_mat, grad_f, work, n_hi, n_lo, flags, stream);
+}
+
+int mifwi_visco_born(mifwi_visco_plan *plan, const float *mat, const float *dmat, const float *pz, const float *px,
+                     const float *df, const int32_t *src_cell, const float *src_w, const int32_t *rec_cell, const float *rec_w,
+                     const float *snap, int32_t snap_first, float *drec_vx, float *drec_vz, float *work, int32_t n_begin,
+                     int32_t n_end, int32_t flags, void *stream)
+{
+    if (const int rc = visco_check(plan)) return rc;
+    return mifwi_elastic_born(visco_plan(plan), mat, dmat, pz, px, df, src_cell, src_w, rec_cell, rec_w, snap, snap_first,
                               drec_vx, drec_vz, work, n_begin, n_end, flags, stream);
 }
 
