@@ -248,7 +248,10 @@ int mifwi_elastic_plan_pass_sizes(const mifwi_elastic_plan *plan, int32_t *forwa
  *         adjoint stress update of step n (the exact transpose of the sampling).                          */
 int mifwi_elastic_plan_bind_pressure(mifwi_elastic_plan *plan, float *rec_p, const float *g_p);
 
-/* Steps n = n_begin .. n_end-1.
+/* mifwi_elastic_forward, _backward and _born refuse a plan of mifwi_vti_plan_create or mifwi_visco_plan_create with
+ * MIFWI_EINVAL ("the plan was not created by mifwi_elastic_plan_create"): its kernels read six or eight planes.
+ *
+ * Steps n = n_begin .. n_end-1.
  *   f [nt][nshot][nsrc] (added to sxx and szz - or to vx / vz, desc.source_type - pre-scaled by the host)
  *   rec_vx, rec_vz [nt][nshot][nrec] or both NULL
  *   snap NULL or [n_end-n_begin][layout.snap_step_elems]: per step and shot the five PML-filtered derivative

@@ -1305,6 +1305,20 @@ __global__ void el_finalize_visco(const float *acc, int ngroups, int nz, int gp,
 
 using mifwi::env_int;
 
+// ---- the medium of a plan ---------------------------------------------------------------------------
+// Every plan of this file is a mifwi_elastic_plan; its medium says which kernels serve it and how many planes they take.
+// Isotropic plans have all kernel families; the other media run one launch per half step: el_step_s / el_adj_s with VTI
+// or VISCO = true, el_adj_v_visco, el_finalize_vti / _visco (el_step_variant, el_adj_variant).  A further medium is a row
+// here, a case in those two selectors and its three entry points.
+enum ElMedium { kIsotropic = 0, kVti = 1, kVisco = 2 };
+struct ElMediumInfo {
+    int nmat;                // material / gradient / accumulator planes
+    int nfield;              // fields per shot: the five of the scheme (+ the three memory variables F_RXX..F_RXZ)
+    const char *created_by;  // the family's plan_create, as messages name it
+};
+constexpr ElMediumInfo kMedia[] = {{5, 5, "mifwi_elastic_plan_create"}, {6, 5, "mifwi_vti_plan_create"},
+                                   {8, 8, "mifwi_visco_plan_create"}};
+
 }  // namespace
 
 // ================================================================================================
@@ -1333,14 +1347,12 @@ struct mifwi_elastic_plan {
     int cl_adj, adj_NW, adj_shots, adj_lds, adj_ng, adj_zrows;
     long long xbuf_elems, list_elems, xcc_elems;
     long long tile_elems;                  // per-tile receiver lists of el_adj_s (ints, in floats)
-    int vti;               // mifwi_vti_*: the six-plane kernels (el_step_s / el_adj_s with VTI = true, el_finalize_vti), per-step family only
-    int nmat;              // material / gradient / accumulator planes: 5, 6 under vti, 8 under visco
-    int visco;             // mifwi_visco_*: eight planes and eight fields per shot (el_step_s / el_adj_s with VISCO = true,
-                           // el_adj_v_visco, el_finalize_visco), per-step family only
-    float rel_a, rel_b;    // its relaxation scalars (ElParams)
+    ElMedium medium;       // kMedia[medium]: its planes, fields and entry points
+    float rel_a, rel_b;    // the relaxation scalars of a viscoelastic plan (ElParams)
 };
-// a VTI plan is an elastic plan with the flag set (el_plan_create); the C ABI keeps the two handle types apart
+// a VTI or viscoelastic plan is an elastic plan of that medium (el_plan_create); the C ABI keeps the handle types apart
 struct mifwi_vti_plan;
+struct mifwi_visco_plan;
 
 namespace {
 
@@ -1367,40 +1379,37 @@ using mifwi::with_bool;
 using mifwi::with_int;
 
 // ---- variant tables (mifwi_host.h) ----------------------------------------------------------------
-// the two launches of a per-step forward step, el_step_v / el_step_s<LX, 1, SAVE>: lanes per row 64 | 32 | 16; save
-// kBorn | 2 (bf16 planes) | 1 (f32 planes) | 0
+// the two launches of a per-step forward step, el_step_v<LX, 1, SAVE> (every medium's) / el_step_s<LX, 1, SAVE, VTI, VISCO>:
+// lanes per row 64 | 32 | 16; save kBorn | 2 (bf16 planes; isotropic only) | 1 (f32 planes) | 0
 using ElKernel = void (*)(ElParams);
 struct ElStepKernels { ElKernel v, s; };
-ElStepKernels el_step_variant(int lx, int save)
+ElStepKernels el_step_variant(ElMedium medium, int lx, int save)
 {
     return with_int<64, 32, 16>(lx, [&](auto LX) {
-    return with_int<kBorn, 2, 1, 0>(save, [&](auto SAVE) {
-        return ElStepKernels{el_step_v<decltype(LX)::value, 1, decltype(SAVE)::value>,
-                             el_step_s<decltype(LX)::value, 1, decltype(SAVE)::value>};
-    }); });
-}
-// VTI plans: the same V launch, el_step_s<LX, 1, SAVE, true>; save kBorn | 1 | 0 (f32 planes only)
-ElStepKernels el_step_variant_vti(int lx, int save)
-{
-    return with_int<64, 32, 16>(lx, [&](auto LX) {
-    return with_int<kBorn, 1, 0>(save, [&](auto SAVE) {
-        return ElStepKernels{el_step_v<decltype(LX)::value, 1, decltype(SAVE)::value>,
-                             el_step_s<decltype(LX)::value, 1, decltype(SAVE)::value, true>};
-    }); });
-}
-// viscoelastic plans: the same V launch, el_step_s<LX, 1, SAVE, false, true>
-ElStepKernels el_step_variant_visco(int lx, int save)
-{
-    return with_int<64, 32, 16>(lx, [&](auto LX) {
-    return with_int<kBorn, 1, 0>(save, [&](auto SAVE) {
-        return ElStepKernels{el_step_v<decltype(LX)::value, 1, decltype(SAVE)::value>,
-                             el_step_s<decltype(LX)::value, 1, decltype(SAVE)::value, false, true>};
+    return with_int<kVisco, kVti, kIsotropic>(medium, [&](auto M) {
+        auto pair = [](auto SAVE) {
+            constexpr int L = decltype(LX)::value, S = decltype(SAVE)::value, Md = decltype(M)::value;
+            return ElStepKernels{el_step_v<L, 1, S>, el_step_s<L, 1, S, Md == kVti, Md == kVisco>};
+        };
+        if constexpr (decltype(M)::value == kIsotropic) return with_int<kBorn, 2, 1, 0>(save, pair);
+        else return with_int<kBorn, 1, 0>(save, pair);
     }); });
 }
 // el_fwd_fused<SAVE>: save 2 | 1 | 0 (no Born form: that pass runs the two launches)
 ElKernel el_fwd_fused_variant(int save)
 {
     return with_int<2, 1, 0>(save, [](auto SAVE) -> ElKernel { return el_fwd_fused<decltype(SAVE)::value>; });
+}
+// the three kernels of the per-step adjoint: S^T (bf16 planes: isotropic plans only), V^T and the sum over the shot groups
+using ElFinalizeKernel = void (*)(const float *, int, int, int, long long, int, float *);
+struct ElAdjKernels { ElKernel s, v; ElFinalizeKernel finalize; };
+ElAdjKernels el_adj_variant(ElMedium medium, bool bf16)
+{
+    switch (medium) {
+    case kVti: return {el_adj_s<false, true>, el_adj_v, el_finalize_vti};
+    case kVisco: return {el_adj_s<false, false, true>, el_adj_v_visco, el_finalize_visco};
+    default: return {bf16 ? el_adj_s<true> : el_adj_s<false>, el_adj_v, el_finalize};
+    }
 }
 // el_cluster_fwd<SAVE, NG, AG, XH>: snapshots; one | two groups per thread; granules published at agent scope; x-halo from
 // the neighbouring lanes.  The agent-scope tier keeps the plain reads (one variant less to build): AG takes XH off.
@@ -1516,7 +1525,7 @@ void el_cluster_setup(mifwi_elastic_plan *pl)
         const long long ntiles = (long long)mifwi::ceil_div(pl->ng, AGO) * mifwi::ceil_div(pl->d.nz, ATZ);
         pl->tile_elems = std::max<long long>(1024, mifwi::round_up64(pl->d.nshot * (2 * ntiles + 1 + (long long)pl->d.nrec * pl->d.ntap), 64));
     }
-    if (pl->vti || pl->visco || pl->d.ntap != 1 || pl->d.source_type != 0 || pl->d.record_pressure) return;   // per-step kernels only
+    if (pl->medium != kIsotropic || pl->d.ntap != 1 || pl->d.source_type != 0 || pl->d.record_pressure) return;   // per-step kernels only
     const bool want_fwd = env_int("MIFWI_EL_CLUSTER", 1) != 0;
     int ncu = 0;
     if (hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, pl->device) != hipSuccess) return;
@@ -1590,7 +1599,7 @@ ElWork work_map(const mifwi_elastic_plan *pl, bool backward)
     ElWork m;
     m.fields = 0; m.psi = pl->fields_elems; m.psiB = m.psi + pl->psi_elems;
     m.acc = backward ? m.psiB + pl->psi_elems : m.psiB;
-    m.state = m.acc + (backward ? (long long)pl->nmat * pl->ngroups * pl->splane : 0);      // accumulator planes: the snapshot planes' layout and size
+    m.state = m.acc + (backward ? (long long)kMedia[pl->medium].nmat * pl->ngroups * pl->splane : 0);      // accumulator planes: the snapshot planes' layout and size
     m.bbox = m.state; m.xbuf = m.bbox + mifwi::round_up64(4LL * pl->d.nshot, 64);
     m.lists = m.xbuf + (single ? pl->xbuf_elems : 0);
     m.backup = m.lists + (single && backward ? pl->list_elems : 0);
@@ -1645,8 +1654,7 @@ void el_two_launch_steps(const mifwi_elastic_plan *pl, ElParams p, int save, con
     const mifwi_elastic_desc &d = pl->d;
     const long long snap_step = pl->snap_shot * d.nshot;
     const bool want_rec = rec_vx != nullptr;
-    const ElStepKernels step = pl->visco ? el_step_variant_visco(pl->lx, save)
-                               : pl->vti ? el_step_variant_vti(pl->lx, save) : el_step_variant(pl->lx, save);
+    const ElStepKernels step = el_step_variant(pl->medium, pl->lx, save);
     ElParams ps = p;
     const bool force = d.source_type != 0;      // point force: injected into vx / vz by a launch of its own
     ps.ninj = (force || !f) ? 0 : d.nsrc; ps.ntap_inj = d.ntap; ps.inj_cell = src_cell; ps.inj_w = src_w;
@@ -1681,11 +1689,10 @@ void el_two_launch_steps(const mifwi_elastic_plan *pl, ElParams p, int save, con
     }
 }
 
-// medium: 0 isotropic, 1 VTI, 2 viscoelastic (rel_a, rel_b: its relaxation scalars)
-int el_plan_create(mifwi_elastic_plan **plan, int device, const mifwi_elastic_desc *d, int medium, float rel_a = 0.f,
+// rel_a, rel_b: the relaxation scalars of a viscoelastic plan
+int el_plan_create(mifwi_elastic_plan **plan, int device, const mifwi_elastic_desc *d, ElMedium medium, float rel_a = 0.f,
                    float rel_b = 0.f)
 {
-    const int vti = medium == 1, visco = medium == 2;
     if (!plan || !d) return mifwi::fail(MIFWI_EINVAL, "null plan/desc");
     if (d->nz < 1 || d->nx < 1 || d->nt < 1 || d->nshot < 1 || d->nsrc < 0 || d->nrec < 0)
         return mifwi::fail(MIFWI_EINVAL, "bad sizes nz=%d nx=%d nt=%d nshot=%d", d->nz, d->nx, d->nt,
@@ -1712,14 +1719,14 @@ int el_plan_create(mifwi_elastic_plan **plan, int device, const mifwi_elastic_de
     pl->d = *d;
     if (pl->d.fd_order == 0) pl->d.fd_order = 4;
     pl->device = device;
-    pl->vti = vti; pl->visco = visco; pl->nmat = visco ? 8 : vti ? 6 : 5;
+    pl->medium = medium;
     pl->rel_a = rel_a; pl->rel_b = rel_b;
     pl->rec_p = nullptr; pl->g_p = nullptr;
     pl->ng = mifwi::ceil_div(d->nx, 4);
     pl->gp = 4 * pl->ng;
     pl->pitch = (int)mifwi::round_up64(4 * (pl->ng + 3), 32);
     pl->field_stride = (long long)(d->nz + 4) * pl->pitch;
-    pl->shot_stride = (visco ? 8 : 5) * pl->field_stride;      // + the three memory variables
+    pl->shot_stride = kMedia[medium].nfield * pl->field_stride;
     pl->fields_elems = pl->shot_stride * d->nshot;
     pl->coef_elems = (long long)d->nz * pl->gp;
     // strip geometry: W = pml_width + 1 nodes per side (half-node profiles reach one node further)
@@ -1772,7 +1779,7 @@ int el_plan_create(mifwi_elastic_plan **plan, int device, const mifwi_elastic_de
         // 1000x3000: forward 3 shots (240 MB) 0.61 ms, 4 shots (300 MB) 0.82 ms = the all-shots time
         constexpr double kResident = 250e6;
         const double cells = (double)pl->coef_elems;
-        const double mats = 4.0 * pl->nmat * cells;
+        const double mats = 4.0 * kMedia[medium].nmat * cells;
         const double psi1 = 4.0 * (double)(pl->psix_elems + pl->psiz_elems) / d->nshot;
         const double fstate = 4.0 * (double)pl->shot_stride + psi1;
         // forward a little below the adjoint's bound: 1000x3000 runs 0.61 ms with 3 shots (240 MB) and 0.62 ms with 2
@@ -1782,7 +1789,7 @@ int el_plan_create(mifwi_elastic_plan **plan, int device, const mifwi_elastic_de
         // adjoint: groups of gs shots share one accumulator set; when the groups do not all fit, smaller groups
         // (more accumulator traffic, 40/gs B per cell-step) can still pay: 1000x3000, gs 2, one group per pass
         // 0.87 ms against 0.98 ms for gs 4 over all shots
-        const double astate = 4.0 * (double)pl->shot_stride + 2.0 * psi1, accg = 4.0 * pl->nmat * cells;
+        const double astate = 4.0 * (double)pl->shot_stride + 2.0 * psi1, accg = mats;
         if (!pl->cl_adj && d->shots_per_group <= 0 && env_int("MIFWI_EL_GS", 0) <= 0 &&
             pl->ngroups * (pl->gs * astate + accg) + mats > kResident) {
             int g = pl->gs;
@@ -1801,7 +1808,7 @@ int el_plan_create(mifwi_elastic_plan **plan, int device, const mifwi_elastic_de
     // 1000x3000 x 16 shots: 622 -> 558 us per step, 516 with bf16 planes; 350x1700 x 32: 232 -> 232, 214 -> 209) and
     // on any launch of a million cells or more (350x1700 x 4 shots, the chunks of a shot-chunked gradient pass:
     // 286 -> 260 us per step of all 32 shots)
-    pl->fused = !pl->vti && !pl->visco && !pl->cluster && d->source_type == 0 && !d->record_pressure &&
+    pl->fused = medium == kIsotropic && !pl->cluster && d->source_type == 0 && !d->record_pressure &&
                 env_int("MIFWI_EL_FUSED", (pl->pass_shots < d->nshot || (double)d->nz * d->nx * d->nshot >= 1e6) ? 1 : 0) != 0;
     {
         const double cells = (double)pl->coef_elems, mats = 4.0 * 5.0 * cells;
@@ -1824,7 +1831,7 @@ extern "C" {
 
 int mifwi_elastic_plan_create(mifwi_elastic_plan **plan, int device, const mifwi_elastic_desc *d)
 {
-    return el_plan_create(plan, device, d, 0);
+    return el_plan_create(plan, device, d, kIsotropic);
 }
 
 int mifwi_elastic_plan_cluster_slabs(const mifwi_elastic_plan *plan, int32_t adjoint)
@@ -1876,11 +1883,14 @@ int mifwi_elastic_plan_layout(const mifwi_elastic_plan *pl, mifwi_elastic_layout
     return MIFWI_OK;
 }
 
-int mifwi_elastic_forward(mifwi_elastic_plan *pl, const float *mat, const float *pz,
-                          const float *px, const float *f, const int32_t *src_cell,
-                          const float *src_w, const int32_t *rec_cell, const float *rec_w,
-                          float *rec_vx, float *rec_vz, float *snap, float *work, int32_t n_begin,
-                          int32_t n_end, int32_t flags, void *stream)
+}  // extern "C"
+
+// ---- the three calls of a plan, whatever its medium: what the entry points of the three families run --------------------
+namespace {
+
+int el_forward(mifwi_elastic_plan *pl, const float *mat, const float *pz, const float *px, const float *f,
+               const int32_t *src_cell, const float *src_w, const int32_t *rec_cell, const float *rec_w, float *rec_vx,
+               float *rec_vz, float *snap, float *work, int32_t n_begin, int32_t n_end, int32_t flags, void *stream)
 {
     if (!pl || !mat || !pz || !px || !work) return mifwi::fail(MIFWI_EINVAL, "null argument");
     const mifwi_elastic_desc &d = pl->d;
@@ -1978,11 +1988,10 @@ int mifwi_elastic_forward(mifwi_elastic_plan *pl, const float *mat, const float 
     return MIFWI_OK;
 }
 
-int mifwi_elastic_born(mifwi_elastic_plan *pl, const float *mat, const float *dmat, const float *pz, const float *px,
-                       const float *df, const int32_t *src_cell, const float *src_w,
-                       const int32_t *rec_cell, const float *rec_w,
-                       const float *snap, int32_t snap_first, float *drec_vx, float *drec_vz,
-                       float *work, int32_t n_begin, int32_t n_end, int32_t flags, void *stream)
+int el_born(mifwi_elastic_plan *pl, const float *mat, const float *dmat, const float *pz, const float *px, const float *df,
+            const int32_t *src_cell, const float *src_w, const int32_t *rec_cell, const float *rec_w, const float *snap,
+            int32_t snap_first, float *drec_vx, float *drec_vz, float *work, int32_t n_begin, int32_t n_end, int32_t flags,
+            void *stream)
 {
     if (!pl || !mat || !pz || !px) return mifwi::fail(MIFWI_EINVAL, "null argument");
     if (!dmat || !snap || !work) return mifwi::fail(MIFWI_EINVAL, "born: dmat, snap and work must not be null");
@@ -2016,12 +2025,10 @@ int mifwi_elastic_born(mifwi_elastic_plan *pl, const float *mat, const float *dm
     return MIFWI_OK;
 }
 
-int mifwi_elastic_backward(mifwi_elastic_plan *pl, const float *mat, const float *pz,
-                           const float *px, const int32_t *src_cell, const float *src_w,
-                           const int32_t *rec_cell, const float *rec_w, const float *g_vx,
-                           const float *g_vz, const float *snap, int32_t snap_first,
-                           float *grad_mat, float *grad_f, float *work, int32_t n_hi, int32_t n_lo,
-                           int32_t flags, void *stream)
+int el_backward(mifwi_elastic_plan *pl, const float *mat, const float *pz, const float *px, const int32_t *src_cell,
+                const float *src_w, const int32_t *rec_cell, const float *rec_w, const float *g_vx, const float *g_vz,
+                const float *snap, int32_t snap_first, float *grad_mat, float *grad_f, float *work, int32_t n_hi, int32_t n_lo,
+                int32_t flags, void *stream)
 {
     if (!pl || !mat || !pz || !px || !work || !snap || !g_vx || !g_vz || !rec_cell || !rec_w)
         return mifwi::fail(MIFWI_EINVAL, "null argument");
@@ -2057,6 +2064,7 @@ int mifwi_elastic_backward(mifwi_elastic_plan *pl, const float *mat, const float
         hipLaunchKernelGGL(el_build_tile_taps, dim3(d.nshot), dim3(256), 0, st, rec_cell, d.nrec * d.ntap, d.nx, tiles_x,
                            ntiles, tile_start, cursor, tile_list);
     };
+    const ElAdjKernels adj = el_adj_variant(pl->medium, pl->snap_bf16);
     bool per_step = true;
     if (pl->cl_adj && n_hi >= n_lo) {
         const mifwi::Handoff h = mifwi::cluster_handoff(pl, work, m);
@@ -2115,57 +2123,59 @@ int mifwi_elastic_backward(mifwi_elastic_plan *pl, const float *mat, const float
             hipLaunchKernelGGL(el_inject_pressure, dim3(mifwi::ceil_div(cs * d.nrec * d.ntap, 64)), dim3(64), 0,
                                st, pq);
         }
-        if (pl->visco) hipLaunchKernelGGL((el_adj_s<false, false, true>), dim3(tx, tz + ex, cg), dim3(kThreads), 0, st, ps);
-        else if (pl->vti) hipLaunchKernelGGL((el_adj_s<false, true>), dim3(tx, tz + ex, cg), dim3(kThreads), 0, st, ps);
-        else if (pl->snap_bf16) hipLaunchKernelGGL(el_adj_s<true>, dim3(tx, tz + ex, cg), dim3(kThreads), 0, st, ps);
-        else hipLaunchKernelGGL(el_adj_s<false>, dim3(tx, tz + ex, cg), dim3(kThreads), 0, st, ps);
+        hipLaunchKernelGGL(adj.s, dim3(tx, tz + ex, cg), dim3(kThreads), 0, st, ps);
         if (want_f && force) {
             ElParams pq = ps;
             pq.gs = cs; pq.smp_out0 = grad_f + (long long)n * d.nshot * d.nsrc;
             hipLaunchKernelGGL(el_sample_force, dim3(mifwi::ceil_div(cs * d.nsrc, 64)), dim3(64), 0, st, pq,
                                d.source_type);
         }
-        hipLaunchKernelGGL(pl->visco ? el_adj_v_visco : el_adj_v, dim3(tx, tz, cs), dim3(kThreads), 0, st, p);
+        hipLaunchKernelGGL(adj.v, dim3(tx, tz, cs), dim3(kThreads), 0, st, p);
     }
     if (flags & MIFWI_FINALIZE) {
-        const long long n5 = (long long)pl->nmat * pl->coef_elems;
-        hipLaunchKernelGGL(pl->visco ? el_finalize_visco : pl->vti ? el_finalize_vti : el_finalize, dim3((unsigned)((n5 + 255) / 256)), dim3(256), 0, st, acc,
+        const long long n5 = (long long)kMedia[pl->medium].nmat * pl->coef_elems;
+        hipLaunchKernelGGL(adj.finalize, dim3((unsigned)((n5 + 255) / 256)), dim3(256), 0, st, acc,
                            pl->ngroups, d.nz, pl->gp, pl->splane, pl->cl_adj ? 0 : pl->sblk, grad_mat);
     }
     MIFWI_HIP_TRY(hipGetLastError());
     return MIFWI_OK;
 }
 
-// ---- VTI: the elastic plan with six planes, one launch per half step (include/mifwi.h) ---------------------------------
-static mifwi_elastic_plan *vti_plan(mifwi_vti_plan *p) { return reinterpret_cast<mifwi_elastic_plan *>(p); }
-static const mifwi_elastic_plan *vti_plan(const mifwi_vti_plan *p) { return reinterpret_cast<const mifwi_elastic_plan *>(p); }
-// (a handle of mifwi_elastic_plan_create passed by mistake would run the six-plane kernels on five planes)
-static int vti_check(const mifwi_vti_plan *p)
+// ---- the entry points of the three families (include/mifwi.h) -----------------------------------------------------------
+// A handle of any family is a mifwi_elastic_plan (el_plan_create); plan_cast gives it back.
+template <class Handle>
+auto plan_cast(Handle *h)
 {
-    return (p && !vti_plan(p)->vti) ? mifwi::fail(MIFWI_EINVAL, "the plan was not created by mifwi_vti_plan_create") : MIFWI_OK;
+    using Plan = std::conditional_t<std::is_const<Handle>::value, const mifwi_elastic_plan, mifwi_elastic_plan>;
+    return reinterpret_cast<Plan *>(h);
 }
 
-int mifwi_vti_plan_create(mifwi_vti_plan **plan, int device, const mifwi_vti_desc *d)
+// Refuses the plan of another medium: its kernels would take kMedia[].nmat planes where the caller allocated this
+// family's.  (A null plan passes: the call itself refuses it.)
+int check_medium(const mifwi_elastic_plan *pl, ElMedium medium)
 {
-    if (!plan || !d) return mifwi::fail(MIFWI_EINVAL, "null plan/desc");
+    return (pl && pl->medium != medium) ? mifwi::fail(MIFWI_EINVAL, "the plan was not created by %s", kMedia[medium].created_by)
+                                        : MIFWI_OK;
+}
+
+// mifwi_vti_desc / mifwi_visco_desc -> the elastic descriptor: velocity receivers, f32 snapshot planes
+template <class Desc>
+mifwi_elastic_desc elastic_desc(const Desc &d)
+{
     mifwi_elastic_desc e;
-    e.nz = d->nz; e.nx = d->nx; e.nt = d->nt; e.nshot = d->nshot; e.nsrc = d->nsrc; e.nrec = d->nrec; e.ntap = d->ntap;
-    e.pml_width = d->pml_width; e.free_surface = d->free_surface; e.shots_per_group = d->shots_per_group;
-    e.source_type = d->source_type; e.record_pressure = 0; e.snapshot_format = MIFWI_SNAPSHOT_F32; e.fd_order = d->fd_order;
-    return el_plan_create(reinterpret_cast<mifwi_elastic_plan **>(plan), device, &e, 1);
+    e.nz = d.nz; e.nx = d.nx; e.nt = d.nt; e.nshot = d.nshot; e.nsrc = d.nsrc; e.nrec = d.nrec; e.ntap = d.ntap;
+    e.pml_width = d.pml_width; e.free_surface = d.free_surface; e.shots_per_group = d.shots_per_group;
+    e.source_type = d.source_type; e.record_pressure = 0; e.snapshot_format = MIFWI_SNAPSHOT_F32; e.fd_order = d.fd_order;
+    return e;
 }
 
-int mifwi_vti_plan_destroy(mifwi_vti_plan *plan)
+// mifwi_vti_layout / mifwi_visco_layout: the nine fields they share with the elastic layout
+template <class Layout>
+int family_layout(const mifwi_elastic_plan *pl, Layout *out)
 {
-    delete vti_plan(plan);
-    return MIFWI_OK;
-}
-
-int mifwi_vti_plan_layout(const mifwi_vti_plan *plan, mifwi_vti_layout *out)
-{
-    if (!plan || !out) return mifwi::fail(MIFWI_EINVAL, "null plan/layout");
+    if (!pl || !out) return mifwi::fail(MIFWI_EINVAL, "null plan/layout");
     mifwi_elastic_layout e;
-    const int rc = mifwi_elastic_plan_layout(vti_plan(plan), &e);
+    const int rc = mifwi_elastic_plan_layout(pl, &e);
     if (rc) return rc;
     out->gp = e.gp; out->pitch = e.pitch; out->ngroups = e.ngroups; out->shots_per_group = e.shots_per_group;
     out->coef_elems = e.coef_elems; out->state_elems = e.state_elems; out->work_forward_elems = e.work_forward_elems;
@@ -2173,9 +2183,56 @@ int mifwi_vti_plan_layout(const mifwi_vti_plan *plan, mifwi_vti_layout *out)
     return MIFWI_OK;
 }
 
+}  // namespace
+
+extern "C" {
+
+// isotropic
+int mifwi_elastic_forward(mifwi_elastic_plan *plan, const float *mat, const float *pz, const float *px, const float *f,
+                          const int32_t *src_cell, const float *src_w, const int32_t *rec_cell, const float *rec_w,
+                          float *rec_vx, float *rec_vz, float *snap, float *work, int32_t n_begin, int32_t n_end,
+                          int32_t flags, void *stream)
+{
+    if (const int rc = check_medium(plan, kIsotropic)) return rc;
+    return el_forward(plan, mat, pz, px, f, src_cell, src_w, rec_cell, rec_w, rec_vx, rec_vz, snap, work, n_begin,
+                      n_end, flags, stream);
+}
+
+int mifwi_elastic_backward(mifwi_elastic_plan *plan, const float *mat, const float *pz, const float *px, const int32_t *src_cell,
+                           const float *src_w, const int32_t *rec_cell, const float *rec_w, const float *g_vx, const float *g_vz,
+                           const float *snap, int32_t snap_first, float *grad_mat, float *grad_f, float *work, int32_t n_hi,
+                           int32_t n_lo, int32_t flags, void *stream)
+{
+    if (const int rc = check_medium(plan, kIsotropic)) return rc;
+    return el_backward(plan, mat, pz, px, src_cell, src_w, rec_cell, rec_w, g_vx, g_vz, snap, snap_first, grad_mat,
+                       grad_f, work, n_hi, n_lo, flags, stream);
+}
+
+int mifwi_elastic_born(mifwi_elastic_plan *plan, const float *mat, const float *dmat, const float *pz, const float *px,
+                       const float *df, const int32_t *src_cell, const float *src_w, const int32_t *rec_cell, const float *rec_w,
+                       const float *snap, int32_t snap_first, float *drec_vx, float *drec_vz, float *work, int32_t n_begin,
+                       int32_t n_end, int32_t flags, void *stream)
+{
+    if (const int rc = check_medium(plan, kIsotropic)) return rc;
+    return el_born(plan, mat, dmat, pz, px, df, src_cell, src_w, rec_cell, rec_w, snap, snap_first, drec_vx, drec_vz,
+                   work, n_begin, n_end, flags, stream);
+}
+
+// VTI: six planes, one launch per half step
+int mifwi_vti_plan_create(mifwi_vti_plan **plan, int device, const mifwi_vti_desc *d)
+{
+    if (!plan || !d) return mifwi::fail(MIFWI_EINVAL, "null plan/desc");
+    const mifwi_elastic_desc e = elastic_desc(*d);
+    return el_plan_create(reinterpret_cast<mifwi_elastic_plan **>(plan), device, &e, kVti);
+}
+
+int mifwi_vti_plan_destroy(mifwi_vti_plan *plan) { return mifwi_elastic_plan_destroy(plan_cast(plan)); }
+
+int mifwi_vti_plan_layout(const mifwi_vti_plan *plan, mifwi_vti_layout *out) { return family_layout(plan_cast(plan), out); }
+
 int mifwi_vti_plan_pass_sizes(const mifwi_vti_plan *plan, int32_t *forward_shots, int32_t *adjoint_groups)
 {
-    return mifwi_elastic_plan_pass_sizes(vti_plan(plan), forward_shots, adjoint_groups);
+    return mifwi_elastic_plan_pass_sizes(plan_cast(plan), forward_shots, adjoint_groups);
 }
 
 int mifwi_vti_plan_cluster_slabs(const mifwi_vti_plan *, int32_t) { return 0; }
@@ -2185,9 +2242,9 @@ int mifwi_vti_forward(mifwi_vti_plan *plan, const float *mat, const float *pz, c
                       float *rec_vx, float *rec_vz, float *snap, float *work, int32_t n_begin, int32_t n_end,
                       int32_t flags, void *stream)
 {
-    if (const int rc = vti_check(plan)) return rc;
-    return mifwi_elastic_forward(vti_plan(plan), mat, pz, px, f, src_cell, src_w, rec_cell, rec_w, rec_vx, rec_vz, snap, work,
-                                 n_begin, n_end, flags, stream);
+    if (const int rc = check_medium(plan_cast(plan), kVti)) return rc;
+    return el_forward(plan_cast(plan), mat, pz, px, f, src_cell, src_w, rec_cell, rec_w, rec_vx, rec_vz, snap, work, n_begin,
+                      n_end, flags, stream);
 }
 
 int mifwi_vti_backward(mifwi_vti_plan *plan, const float *mat, const float *pz, const float *px, const int32_t *src_cell,
@@ -2195,9 +2252,9 @@ int mifwi_vti_backward(mifwi_vti_plan *plan, const float *mat, const float *pz, 
                        const float *snap, int32_t snap_first, float *grad_mat, float *grad_f, float *work, int32_t n_hi,
                        int32_t n_lo, int32_t flags, void *stream)
 {
-    if (const int rc = vti_check(plan)) return rc;
-    return mifwi_elastic_backward(vti_plan(plan), mat, pz, px, src_cell, src_w, rec_cell, rec_w, g_vx, g_vz, snap, snap_first,
-                                  grad_mat, grad_f, work, n_hi, n_lo, flags, stream);
+    if (const int rc = check_medium(plan_cast(plan), kVti)) return rc;
+    return el_backward(plan_cast(plan), mat, pz, px, src_cell, src_w, rec_cell, rec_w, g_vx, g_vz, snap, snap_first, grad_mat,
+                       grad_f, work, n_hi, n_lo, flags, stream);
 }
 
 int mifwi_vti_born(mifwi_vti_plan *plan, const float *mat, const float *dmat, const float *pz, const float *px,
@@ -2205,19 +2262,12 @@ int mifwi_vti_born(mifwi_vti_plan *plan, const float *mat, const float *dmat, co
                    const float *snap, int32_t snap_first, float *drec_vx, float *drec_vz, float *work, int32_t n_begin,
                    int32_t n_end, int32_t flags, void *stream)
 {
-    if (const int rc = vti_check(plan)) return rc;
-    return mifwi_elastic_born(vti_plan(plan), mat, dmat, pz, px, df, src_cell, src_w, rec_cell, rec_w, snap, snap_first,
-                              drec_vx, drec_vz, work, n_begin, n_end, flags, stream);
+    if (const int rc = check_medium(plan_cast(plan), kVti)) return rc;
+    return el_born(plan_cast(plan), mat, dmat, pz, px, df, src_cell, src_w, rec_cell, rec_w, snap, snap_first, drec_vx, drec_vz,
+                   work, n_begin, n_end, flags, stream);
 }
 
-// ---- viscoelastic: the elastic plan with eight planes and eight fields per shot (include/mifwi.h) ----------------------
-static mifwi_elastic_plan *visco_plan(mifwi_visco_plan *p) { return reinterpret_cast<mifwi_elastic_plan *>(p); }
-static const mifwi_elastic_plan *visco_plan(const mifwi_visco_plan *p) { return reinterpret_cast<const mifwi_elastic_plan *>(p); }
-static int visco_check(const mifwi_visco_plan *p)
-{
-    return (p && !visco_plan(p)->visco) ? mifwi::fail(MIFWI_EINVAL, "the plan was not created by mifwi_visco_plan_create") : MIFWI_OK;
-}
-
+// viscoelastic: eight planes and eight fields per shot, one launch per half step
 int mifwi_visco_plan_create(mifwi_visco_plan **plan, int device, const mifwi_visco_desc *d)
 {
     if (!plan || !d) return mifwi::fail(MIFWI_EINVAL, "null plan/desc");
@@ -2225,34 +2275,17 @@ int mifwi_visco_plan_create(mifwi_visco_plan **plan, int device, const mifwi_vis
     if (!(d->relax_a > 0.f && d->relax_a < 1.f && d->relax_b > 0.f && d->relax_b < 1.f))
         return mifwi::fail(MIFWI_EINVAL, "relax_a = %g, relax_b = %g: both must lie inside (0, 1)", (double)d->relax_a,
                            (double)d->relax_b);
-    mifwi_elastic_desc e;
-    e.nz = d->nz; e.nx = d->nx; e.nt = d->nt; e.nshot = d->nshot; e.nsrc = d->nsrc; e.nrec = d->nrec; e.ntap = d->ntap;
-    e.pml_width = d->pml_width; e.free_surface = d->free_surface; e.shots_per_group = d->shots_per_group;
-    e.source_type = d->source_type; e.record_pressure = 0; e.snapshot_format = MIFWI_SNAPSHOT_F32; e.fd_order = d->fd_order;
-    return el_plan_create(reinterpret_cast<mifwi_elastic_plan **>(plan), device, &e, 2, d->relax_a, d->relax_b);
+    const mifwi_elastic_desc e = elastic_desc(*d);
+    return el_plan_create(reinterpret_cast<mifwi_elastic_plan **>(plan), device, &e, kVisco, d->relax_a, d->relax_b);
 }
 
-int mifwi_visco_plan_destroy(mifwi_visco_plan *plan)
-{
-    delete visco_plan(plan);
-    return MIFWI_OK;
-}
+int mifwi_visco_plan_destroy(mifwi_visco_plan *plan) { return mifwi_elastic_plan_destroy(plan_cast(plan)); }
 
-int mifwi_visco_plan_layout(const mifwi_visco_plan *plan, mifwi_visco_layout *out)
-{
-    if (!plan || !out) return mifwi::fail(MIFWI_EINVAL, "null plan/layout");
-    mifwi_elastic_layout e;
-    const int rc = mifwi_elastic_plan_layout(visco_plan(plan), &e);
-    if (rc) return rc;
-    out->gp = e.gp; out->pitch = e.pitch; out->ngroups = e.ngroups; out->shots_per_group = e.shots_per_group;
-    out->coef_elems = e.coef_elems; out->state_elems = e.state_elems; out->work_forward_elems = e.work_forward_elems;
-    out->work_backward_elems = e.work_backward_elems; out->snap_step_elems = e.snap_step_elems;
-    return MIFWI_OK;
-}
+int mifwi_visco_plan_layout(const mifwi_visco_plan *plan, mifwi_visco_layout *out) { return family_layout(plan_cast(plan), out); }
 
 int mifwi_visco_plan_pass_sizes(const mifwi_visco_plan *plan, int32_t *forward_shots, int32_t *adjoint_groups)
 {
-    return mifwi_elastic_plan_pass_sizes(visco_plan(plan), forward_shots, adjoint_groups);
+    return mifwi_elastic_plan_pass_sizes(plan_cast(plan), forward_shots, adjoint_groups);
 }
 
 int mifwi_visco_plan_cluster_slabs(const mifwi_visco_plan *, int32_t) { return 0; }
@@ -2262,9 +2295,9 @@ int mifwi_visco_forward(mifwi_visco_plan *plan, const float *mat, const float *p
                         float *rec_vx, float *rec_vz, float *snap, float *work, int32_t n_begin, int32_t n_end,
                         int32_t flags, void *stream)
 {
-    if (const int rc = visco_check(plan)) return rc;
-    return mifwi_elastic_forward(visco_plan(plan), mat, pz, px, f, src_cell, src_w, rec_cell, rec_w, rec_vx, rec_vz, snap, work,
-                                 n_begin, n_end, flags, stream);
+    if (const int rc = check_medium(plan_cast(plan), kVisco)) return rc;
+    return el_forward(plan_cast(plan), mat, pz, px, f, src_cell, src_w, rec_cell, rec_w, rec_vx, rec_vz, snap, work, n_begin,
+                      n_end, flags, stream);
 }
 
 int mifwi_visco_backward(mifwi_visco_plan *plan, const float *mat, const float *pz, const float *px, const int32_t *src_cell,
@@ -2272,9 +2305,9 @@ int mifwi_visco_backward(mifwi_visco_plan *plan, const float *mat, const float *
                          const float *snap, int32_t snap_first, float *grad_mat, float *grad_f, float *work, int32_t n_hi,
                          int32_t n_lo, int32_t flags, void *stream)
 {
-    if (const int rc = visco_check(plan)) return rc;
-    return mifwi_elastic_backward(visco_plan(plan), mat, pz, px, src_cell, src_w, rec_cell, rec_w, g_vx, g_vz, snap, snap_first,
-                                  grad_mat, grad_f, work, n_hi, n_lo, flags, stream);
+    if (const int rc = check_medium(plan_cast(plan), kVisco)) return rc;
+    return el_backward(plan_cast(plan), mat, pz, px, src_cell, src_w, rec_cell, rec_w, g_vx, g_vz, snap, snap_first, grad_mat,
+                       grad_f, work, n_hi, n_lo, flags, stream);
 }
 
 int mifwi_visco_born(mifwi_visco_plan *plan, const float *mat, const float *dmat, const float *pz, const float *px,
@@ -2282,9 +2315,9 @@ int mifwi_visco_born(mifwi_visco_plan *plan, const float *mat, const float *dmat
                      const float *snap, int32_t snap_first, float *drec_vx, float *drec_vz, float *work, int32_t n_begin,
                      int32_t n_end, int32_t flags, void *stream)
 {
-    if (const int rc = visco_check(plan)) return rc;
-    return mifwi_elastic_born(visco_plan(plan), mat, dmat, pz, px, df, src_cell, src_w, rec_cell, rec_w, snap, snap_first,
-                              drec_vx, drec_vz, work, n_begin, n_end, flags, stream);
+    if (const int rc = check_medium(plan_cast(plan), kVisco)) return rc;
+    return el_born(plan_cast(plan), mat, dmat, pz, px, df, src_cell, src_w, rec_cell, rec_w, snap, snap_first, drec_vx, drec_vz,
+                   work, n_begin, n_end, flags, stream);
 }
 
 }  // extern "C"

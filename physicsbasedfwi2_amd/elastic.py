@@ -11,9 +11,10 @@ import weakref
 
 import torch
 
-from . import _lib
+from . import _lib, _psv
 from ._lib import MifwiError
-from ._driver import _Geometry, _MomentsHolder, _Plan, _require_cuda, _stream, Physics, Propagate, linearised, pad_columns
+from ._driver import _Geometry, _MomentsHolder, _Plan, _require_cuda, _stream, Physics, Propagate
+from ._psv import _padded_inputs  # noqa: F401  (fluid.py and the rate tools take it from here)
 
 # bytes of snapshot planes + time checkpoints a call may hold (288 GB of HBM per GPU; the rest is left to the caller's
 # network and data); MIFWI_EL_SNAPSHOT_BUDGET_GB overrides it (measurements of the checkpointed path on short runs)
@@ -246,50 +247,15 @@ class _SnapshotArena:
         return self.buf[:need].view(nt, elems)
 
 
-def _padded_inputs(mat, pz, px, gp):
-    """The material planes and C-PML tables as the C calls take them: on mat's device, rows padded to gp columns
-    (materials and a, b 0, 1/kappa - rows 2 and 5 of the table - 1 there)."""
-    dev = mat.device
-    px_p = pad_columns(px.to(device=dev, dtype=torch.float32), gp)
-    px_p[2::3, mat.shape[2]:] = 1.0
-    return pad_columns(mat, gp), pz.to(device=dev, dtype=torch.float32).contiguous(), px_p
-
-
-def _forward_call(plan, coef, f_d, geo, rec):
-    """``forward(snap_ptr, work_ptr, b, e, flags)`` as the drivers take it; rec = [rec_vx, rec_vz, ...] (pressure traces
-    are bound to the plan), or None: a re-run that samples nothing."""
-    lib = _lib.load()
-    rvx, rvz = rec[:2] if rec else (None, None)
-    args = (plan.handle, *coef, _lib.ptr(f_d), *geo, _lib.ptr(rvx), _lib.ptr(rvz))
-    return lambda snap, work, b, e, flags: _lib.check(
-        lib.mifwi_elastic_forward(*args, snap, work, b, e, flags, _stream()))
-
-
-def _adjoint_call(plan, coef, geo, g, grad_mat, grad_f, work):
-    """``adjoint(snap_ptr, snap_first, hi, lo, flags)`` as the backward driver takes it; g = [g_vx, g_vz]."""
-    lib = _lib.load()
-    return lambda snap, first, hi, lo, flags: _lib.check(lib.mifwi_elastic_backward(
-        plan.handle, *coef, *geo, _lib.ptr(g[0]), _lib.ptr(g[1]), snap, first, _lib.ptr(grad_mat), _lib.ptr(grad_f),
-        _lib.ptr(work), hi, lo, flags, _stream()))
-
-
-def _born_call(plan, coef, dmat_p, df_d, geo, snap, drec, work, nt):
-    _lib.check(_lib.load().mifwi_elastic_born(plan.handle, coef[0], _lib.ptr(dmat_p), *coef[1:], _lib.ptr(df_d), *geo,
-                                              _lib.ptr(snap), 0, _lib.ptr(drec[0]), _lib.ptr(drec[1]), _lib.ptr(work), 0, nt,
-                                              _lib.ZERO_STATE, _stream()))
-
-
-class _Elastic(Physics):
-    """The P-SV scheme as :class:`_driver.Propagate` and :func:`_driver.linearised` see it.  opts: pml_width,
-    shots_per_group, free_surface, source_type, record_pressure, snapshot_format, fd_order - the plan's."""
-    name = rule = "elastic"
-    model = "mat"
-    grad_planes, moment_planes = (5,), (6,)
-    not_served = "Born modelling across time checkpoints is not served"
-    weight_returns = "(g_vx, g_vz) of the shape of its arguments"
-    forward_call, adjoint_call, born_call = (staticmethod(fn) for fn in (_forward_call, _adjoint_call, _born_call))
+class _Elastic(_psv.Psv, planes=5):
+    """The isotropic scheme: what it has beyond :class:`_psv.Psv` - pressure receivers (bound to the plan), the snapshot
+    arena and the plan's own say in the shot chunks.  opts: pml_width, shots_per_group, free_surface, source_type,
+    record_pressure, snapshot_format, fd_order - the plan's."""
+    name = "elastic"
+    moment_planes = (6,)
+    linearised_serves = ("%s serves explosive sources and velocity receivers only (force sources need df from the "
+                         "density at the source node, pressure receivers a sampling pass of their own)")
     Plan = ElasticPlan
-    inputs = staticmethod(lambda mat, pz, px, gp, o: _padded_inputs(mat, pz, px, gp))
     traces = staticmethod(lambda o: 3 if o["record_pressure"] else 2)
 
     @classmethod
@@ -301,13 +267,13 @@ class _Elastic(Physics):
 
     @staticmethod
     def adjoint_sources(plan, g, shape, dev, o):
-        gx, gz = (torch.zeros(shape, device=dev) if t is None else t.to(dtype=torch.float32).contiguous() for t in g[:2])
         g_p = None
         if o["record_pressure"]:
             g_p = None if g[2] is None or g[2].numel() == 0 else g[2].to(dtype=torch.float32).contiguous()
             # the forward re-runs of a checkpointed backward must not sample again: rec_p unbound
             _lib.check(_lib.load().mifwi_elastic_plan_bind_pressure(plan.handle, None, _lib.ptr(g_p)))
-        return [gx, gz, g_p]                # g_p is bound to the plan: the caller keeps it alive with the other two
+        # g_p is bound to the plan: the caller keeps it alive with the other two
+        return _psv.Psv.adjoint_sources(plan, g, shape, dev, o) + [g_p]
 
     @staticmethod
     def snapshots(snapshot_budget, dev, nt, step):
@@ -413,16 +379,8 @@ def _linearised(name, mat, dmat, f, pz, px, src_cell, src_w, rec_cell, rec_w, pm
     traces, perturbed traces, hv): lists of 2 tensors."""
     _require_cuda(mat, "mat")
     opts = _options(pml_width, 0, free_surface, source_type, record_pressure, snapshot_format, fd_order)
-    if opts["source_type"] != 0 or record_pressure:
-        raise MifwiError("%s serves explosive sources and velocity receivers only (force sources need df from the "
-                         "density at the source node, pressure receivers a sampling pass of their own)" % name)
-    if mat.dim() != 3 or mat.shape[0] != 5:
-        raise MifwiError("mat must be [5, nz, nx]")
-    if tuple(dmat.shape) != tuple(mat.shape):
-        raise MifwiError("dmat must have the shape of mat, %s (got %s)" % (tuple(mat.shape), tuple(dmat.shape)))
-    _require_cuda(dmat, "dmat")
-    return linearised(_Elastic, name, mat, dmat, f, df, pz, px, (src_cell, src_w, rec_cell, rec_w), snapshot_budget,
-                      adjoint, weight, opts)
+    return _psv.linearised(_Elastic, name, mat, dmat, f, df, pz, px, (src_cell, src_w, rec_cell, rec_w), snapshot_budget,
+                           adjoint, weight, opts)
 
 
 def born(mat, dmat, f, pz, px, src_cell, src_w, rec_cell, rec_w, pml_width, df=None, free_surface=False, fd_order=4,

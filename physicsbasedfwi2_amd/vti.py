@@ -12,9 +12,9 @@ arithmetic is in libmifwi.so; there is no CPU path.
 import numpy as np
 import torch
 
-from . import _lib, elastic
+from . import _lib, _psv, elastic
 from ._lib import MifwiError
-from ._driver import _Geometry, _Plan, _require_cuda, _stream, Physics, Propagate, linearised
+from ._driver import _Geometry, _Plan, Propagate
 from .elastic import DEFAULT_SNAPSHOT_BUDGET, SOURCE_TYPES  # noqa: F401
 
 
@@ -89,57 +89,16 @@ class VtiPlan(_Plan):
                                   source_type, fd_order), device_index)
 
 
-def _forward_call(plan, coef, f_d, geo, rec):
-    """``forward(snap_ptr, work_ptr, b, e, flags)`` as the drivers take it; rec = [rec_vx, rec_vz], or None: a re-run that
-    samples nothing."""
-    lib = _lib.load()
-    rvx, rvz = rec if rec else (None, None)
-    args = (plan.handle, *coef, _lib.ptr(f_d), *geo, _lib.ptr(rvx), _lib.ptr(rvz))
-    return lambda snap, work, b, e, flags: _lib.check(lib.mifwi_vti_forward(*args, snap, work, b, e, flags, _stream()))
-
-
-def _adjoint_call(plan, coef, geo, g, grad_mat, grad_f, work):
-    """``adjoint(snap_ptr, snap_first, hi, lo, flags)`` as the backward driver takes it; g = [g_vx, g_vz]."""
-    lib = _lib.load()
-    return lambda snap, first, hi, lo, flags: _lib.check(lib.mifwi_vti_backward(
-        plan.handle, *coef, *geo, _lib.ptr(g[0]), _lib.ptr(g[1]), snap, first, _lib.ptr(grad_mat), _lib.ptr(grad_f),
-        _lib.ptr(work), hi, lo, flags, _stream()))
-
-
-def _born_call(plan, coef, dmat_p, df_d, geo, snap, drec, work, nt):
-    _lib.check(_lib.load().mifwi_vti_born(plan.handle, coef[0], _lib.ptr(dmat_p), *coef[1:], _lib.ptr(df_d), *geo,
-                                          _lib.ptr(snap), 0, _lib.ptr(drec[0]), _lib.ptr(drec[1]), _lib.ptr(work), 0, nt,
-                                          _lib.ZERO_STATE, _stream()))
-
-
-class _Vti(Physics):
-    """The VTI scheme as :class:`_driver.Propagate` and :func:`_driver.linearised` see it.  opts: pml_width,
-    shots_per_group, free_surface, source_type, fd_order - the plan's."""
+class _Vti(_psv.Psv, planes=6):
+    """The VTI scheme.  opts: pml_width, shots_per_group, free_surface, source_type, fd_order - the plan's."""
     name = "vti"
-    rule = "elastic"
-    model = "mat"
-    grad_planes = (6,)
-    not_served = "Born modelling across time checkpoints is not served"
-    weight_returns = "(g_vx, g_vz) of the shape of its arguments"
-    forward_call, adjoint_call, born_call = (staticmethod(fn) for fn in (_forward_call, _adjoint_call, _born_call))
+    mat_from = " (vti.materials)"
     Plan = VtiPlan
-    inputs = staticmethod(lambda mat, pz, px, gp, o: elastic._padded_inputs(mat, pz, px, gp))
-    traces = staticmethod(lambda o: 2)
-
-    @staticmethod
-    def adjoint_sources(plan, g, shape, dev, o):
-        return [torch.zeros(shape, device=dev) if t is None else t.to(dtype=torch.float32).contiguous() for t in g[:2]]
 
 
 def _options(pml_width, shots_per_group, free_surface, source_type, fd_order):
     return dict(pml_width=int(pml_width), shots_per_group=int(shots_per_group), free_surface=1 if free_surface else 0,
                 source_type=elastic.source_type_code(source_type), fd_order=int(fd_order))
-
-
-def _check_mat(mat):
-    _require_cuda(mat, "mat")
-    if mat.dim() != 3 or mat.shape[0] != 6:
-        raise MifwiError("mat must be [6, nz, nx] (vti.materials)")
 
 
 def propagate(mat, f, pz, px, src_cell, src_w, rec_cell, rec_w, pml_width, shots_per_group=0,
@@ -155,7 +114,7 @@ def propagate(mat, f, pz, px, src_cell, src_w, rec_cell, rec_w, pml_width, shots
     ``pseudo_hessian`` is refused: the VTI parameter table of the pseudo-Hessian is not built.
     With ``mat[5] == mat[1]`` the seismograms are those of :func:`elastic.propagate` on ``mat[:5]`` bit for bit.  Repeated
     calls return the same bits under the conditions of :func:`elastic.propagate`."""
-    _check_mat(mat)
+    _Vti.check_mat(mat)
     if pseudo_hessian is not None:
         raise MifwiError("vti.propagate: the pseudo-Hessian is not served for VTI media (pseudo_hessian must be None)")
     geom = _Geometry.get(src_cell, src_w, rec_cell, rec_w, mat.device)
@@ -166,16 +125,10 @@ def propagate(mat, f, pz, px, src_cell, src_w, rec_cell, rec_w, pml_width, shots
 
 def _linearised(name, mat, dmat, f, pz, px, src_cell, src_w, rec_cell, rec_w, pml_width, df, free_surface, fd_order,
                 snapshot_budget, source_type, adjoint, weight):
-    _check_mat(mat)
+    _Vti.check_mat(mat)
     opts = _options(pml_width, 0, free_surface, source_type, fd_order)
-    if opts["source_type"] != 0:
-        raise MifwiError("%s serves explosive sources only (a force source needs df from the density at the source node)"
-                         % name)
-    if tuple(dmat.shape) != tuple(mat.shape):
-        raise MifwiError("dmat must have the shape of mat, %s (got %s)" % (tuple(mat.shape), tuple(dmat.shape)))
-    _require_cuda(dmat, "dmat")
-    return linearised(_Vti, name, mat, dmat, f, df, pz, px, (src_cell, src_w, rec_cell, rec_w), snapshot_budget, adjoint,
-                      weight, opts)
+    return _psv.linearised(_Vti, name, mat, dmat, f, df, pz, px, (src_cell, src_w, rec_cell, rec_w), snapshot_budget,
+                           adjoint, weight, opts)
 
 
 def born(mat, dmat, f, pz, px, src_cell, src_w, rec_cell, rec_w, pml_width, df=None, free_surface=False, fd_order=4,
