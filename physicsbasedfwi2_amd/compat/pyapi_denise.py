@@ -25,6 +25,7 @@ chain rule to Vp/Vs/rho) on the current HIP device; nothing is written except
 import math
 import os
 import struct
+from collections import namedtuple
 
 import numpy as np
 import torch
@@ -242,6 +243,38 @@ def _convolve_host(h, lag_before, wav):
         if lo < hi:
             out[:, lo:hi] += h[:, i:i + 1] * wav[lo - k:hi - k].T
     return out
+
+
+# ---- the media a run can ask for --------------------------------------------------------------------------------------
+# Denise._medium() runs the refusals and answers with one of these; nothing else in the class asks which medium runs.
+# extra: the attribute with the model planes after (vp, vs, rho); gradients: the one grad() leaves gradients four and five
+# in; force_amplitude: dt/(h^2 rho) at the node of a point force; vmax: the fastest velocity, for the stability limit
+_Medium = namedtuple("_Medium", "extra gradients force_amplitude vmax materials propagate")
+
+
+def _vmax_visco(d, model, src):
+    # Model.vp is the phase velocity at F_REF; the fastest the medium carries is the unrelaxed one
+    d._f_ref = float(d.F_REF) if d.F_REF is not None else float(np.atleast_1d(src.f)[0])
+    return visco.max_velocity(model.vp, d._attenuation[0], d._f_ref, float(d.FL1))
+
+
+# PHYSICS = 1 with L = 0, and PHYSICS = 2 as the same velocity-stress solver in a fluid, Vs = 0 everywhere
+_PSV = _Medium(None, None, elastic.force_amplitude, lambda d, model, src: float(model.vp.max()),
+               lambda d, prm, dt, h, fs: elastic.staggered_materials(prm[0], prm[1], prm[2], dt, h, free_surface=fs),
+               lambda d, a, kw, dt, ph: elastic.propagate(*a, record_pressure=d.SEISMO in (2, 4), pseudo_hessian=ph, **kw))
+# PHYSICS = 2 with acoustic_kernels = "fluid" (the fluid kernels never see Vs: its gradient is 0)
+_FLUID = _Medium(None, None, fluid.force_amplitude, _PSV.vmax,
+                 lambda d, prm, dt, h, fs: fluid.materials(prm[0], prm[2], dt, h, free_surface=fs),
+                 lambda d, a, kw, dt, ph: fluid.propagate(*a, record_pressure=d.SEISMO in (2, 4), **kw))
+# PHYSICS = 3, gradients (Vp0, Vs0, rho, epsilon, delta); elastic.force_amplitude reads planes 3 and 4, the VTI planes' too
+_VTI = _Medium("_thomsen", "_gradients_thomsen", elastic.force_amplitude,
+               lambda d, model, src: vti.max_velocity(model.vp, *d._thomsen),
+               lambda d, prm, dt, h, fs: vti.materials(*prm, dt, h, free_surface=fs),
+               lambda d, a, kw, dt, ph: vti.propagate(*a, **kw))
+# L = 1, gradients (Vp, Vs, rho, Qp, Qs)
+_VISCO = _Medium("_attenuation", "_gradients_q", elastic.force_amplitude, _vmax_visco,
+                 lambda d, prm, dt, h, fs: visco.materials(*prm, d._f_ref, float(d.FL1), dt, h, free_surface=fs),
+                 lambda d, a, kw, dt, ph: visco.propagate(*a, float(d.FL1), dt, **kw))
 
 
 # ---- what an assignment `d.NAME = value` means here -----------------------------------------------------------------
@@ -547,25 +580,21 @@ class Denise:
         self.set_observed(np.stack(vx), np.stack(vy))
 
     # -- numerics -----------------------------------------------------------------------------------
-    def _fluid(self):
-        """True when this run goes through the fluid kernels; what they do not serve is refused before any device work."""
-        if self.acoustic_kernels != "fluid":
-            return False
-        if self.PHYSICS != 2:
+    def _refuse_kernels(self, model):
+        if self.acoustic_kernels == "fluid" and self.PHYSICS != 2:
             raise MifwiError("acoustic_kernels=\"fluid\" serves PHYSICS = 2 only (PHYSICS=%s)" % self.PHYSICS)
-        if int(self.EPRECOND) != 0:
+        if self.acoustic_kernels == "fluid" and int(self.EPRECOND) != 0:
             raise MifwiError("acoustic_kernels=\"fluid\": the pseudo-Hessian (EPRECOND=%s) is not built for the fluid "
                              "plan; use acoustic_kernels=\"elastic\"" % self.EPRECOND)
-        return True
+        if self.PHYSICS not in (1, 2, 3):
+            raise MifwiError("PHYSICS=%s not implemented (1 = P-SV elastic, 2 = acoustic, 3 = P-SV VTI)" % self.PHYSICS)
 
-    def _vti(self, model=None):
-        """True when this run is a ``PHYSICS = 3`` (P-SV VTI) run; what the VTI propagator does not serve is refused before
-        any device work."""
+    def _refuse_vti(self, model):
         if self.PHYSICS != 3:
-            return False
+            return
         if self._thomsen is None:
             raise MifwiError("PHYSICS=3 (P-SV VTI) needs Thomsen's parameters: d.set_thomsen(epsilon, delta)")
-        if model is not None and self._thomsen[0].shape != model.vp.shape:
+        if self._thomsen[0].shape != model.vp.shape:
             raise MifwiError("set_thomsen: epsilon and delta are %s, the model is %s"
                              % (self._thomsen[0].shape, model.vp.shape))
         if int(self.INVMAT1) != 1:
@@ -575,13 +604,10 @@ class Denise:
         if self.SEISMO != 1 or self.QUELLTYPB == 4:
             raise MifwiError("PHYSICS=3: pressure seismograms (SEISMO=%s, QUELLTYPB=%s) are not served; SEISMO = 1 and "
                              "QUELLTYPB 1, 2 or 3" % (self.SEISMO, self.QUELLTYPB))
-        return True
 
-    def _visco(self, model=None):
-        """True when this run is an ``L = 1`` (viscoelastic P-SV) run; what the viscoelastic propagator does not serve is
-        refused before any device work."""
+    def _refuse_visco(self, model):
         if int(self.L) == 0:
-            return False
+            return
         if self.PHYSICS != 1:
             raise MifwiError("L=1 (attenuation) serves PHYSICS = 1 only (PHYSICS=%s): Q with the acoustic or the VTI medium "
                              "is not built" % self.PHYSICS)
@@ -592,27 +618,41 @@ class Denise:
                              "QUELLTYPB 1, 2 or 3" % (self.SEISMO, self.QUELLTYPB))
         if self._attenuation is None:
             raise MifwiError("L=1 needs the Qp and Qs models: d.set_attenuation(qp, qs)")
-        if model is not None and self._attenuation[0].shape != model.vp.shape:
+        if self._attenuation[0].shape != model.vp.shape:
             raise MifwiError("set_attenuation: qp and qs are %s, the model is %s"
                              % (self._attenuation[0].shape, model.vp.shape))
-        return True
 
-    def _setup(self, model, src, rec):
-        self._fluid()
-        if self.PHYSICS not in (1, 2, 3):
-            raise MifwiError("PHYSICS=%s not implemented (1 = P-SV elastic, 2 = acoustic, 3 = P-SV VTI)" % self.PHYSICS)
-        self._visco(model)             # (refusals come before the device is looked up)
+    def _refuse_grad(self, model):
+        if int(self.INVMAT1) not in (1, 2, 3):
+            raise MifwiError("INVMAT1=%s not implemented (1: Vp, Vs, rho; 2: Zp, Zs, rho; 3: lambda, mu, rho)" % self.INVMAT1)
+        if int(self.EPRECOND) not in (0, 1):
+            raise MifwiError("EPRECOND=%s not implemented (0: off, 1: pseudo-Hessian of the forward wavefields; the "
+                             "receiver-side term of 3 is not built)" % self.EPRECOND)
+        if not float(self.EPSILON_WE) > 0:
+            raise MifwiError("EPSILON_WE=%s: the water level of the preconditioner must be > 0" % self.EPSILON_WE)
+        if int(self.INV_STF) == 1 and self._stf is None:
+            raise MifwiError("INV_STF=1 needs the reach of the matching filter: d.set_stf(before=..., after=... [s], "
+                             "water_level=1e-2)")
+
+    def _medium(self, model, grad=False):
+        """Which medium this run is, once per forward() / grad(); what it does not serve is refused here, before any device
+        work.  Of several refusals the first in this order is heard: grad() has always asked the VTI and viscoelastic ones
+        first and its own before the kernels', forward() the kernels' first."""
+        kernels, visco_, vti_ = self._refuse_kernels, self._refuse_visco, self._refuse_vti
+        for refuse in ((vti_, visco_, self._refuse_grad, kernels) if grad else (kernels, visco_, vti_)):
+            refuse(model)
+        if int(self.L) != 0:
+            return _VISCO
+        if self.PHYSICS == 3:
+            return _VTI
+        return _FLUID if self.acoustic_kernels == "fluid" else _PSV
+
+    def _setup(self, model, src, rec, medium=None):
+        medium = medium or self._medium(model)
         dev = torch.device(self.device) if self.device is not None else \
             torch.device("cuda", torch.cuda.current_device())
         h = model.dx
-        vmax = float(model.vp.max())
-        if self._vti(model):
-            # the fastest qP phase velocity of a Thomsen medium is bounded by vp0 sqrt(1 + 2 max(epsilon, delta, 0))
-            vmax = vti.max_velocity(model.vp, *self._thomsen)
-        if self._visco(model):
-            # Model.vp is the phase velocity at F_REF; the fastest the medium carries is the unrelaxed one
-            self._f_ref = float(self.F_REF) if self.F_REF is not None else float(np.atleast_1d(src.f)[0])
-            vmax = visco.max_velocity(model.vp, self._attenuation[0], self._f_ref, float(self.FL1))
+        vmax = medium.vmax(self, model, src)
         # FD_ORDER (left commented at networks.py:10447): 2 or 4 are built (Taylor weights, MAXRELERROR = 0)
         if int(self.FD_ORDER) not in (2, 4):
             raise MifwiError("FD_ORDER=%s not implemented: the staggered-grid stencils are built for order 2 "
@@ -673,51 +713,30 @@ class Denise:
                                                self.k_max_PML))
         return dev, h, dt, nt, geom, f, pz, px, fw, fsurf
 
-    def _materials(self, model, dev, dt, h, requires_grad, fsurf=False):
+    def _materials(self, medium, model, dev, dt, h, requires_grad, fsurf=False):
         # undo the caller's flipud: internally row 0 is the surface
         # PHYSICS = 2 (acoustic): the same velocity-stress solver in a fluid, Vs = 0 everywhere
         vs = model.vs if self.PHYSICS in (1, 3) else np.zeros_like(model.vs)
-        planes = (model.vp, vs, model.rho) + (self._thomsen if self._vti(model) else ())
-        planes = planes + (self._attenuation if self._visco(model) else ())
+        planes = (model.vp, vs, model.rho) + (getattr(self, medium.extra) if medium.extra else ())
         prm = [torch.tensor(np.flipud(a).copy(), device=dev, requires_grad=requires_grad) for a in planes]
-        if self._visco():
-            return prm, visco.materials(*prm, self._f_ref, float(self.FL1), dt, h, free_surface=fsurf)
-        if self._vti():
-            return prm, vti.materials(*prm, dt, h, free_surface=fsurf)
-        if self._fluid():
-            return prm, fluid.materials(prm[0], prm[2], dt, h, free_surface=fsurf)
-        return prm, elastic.staggered_materials(prm[0], prm[1], prm[2], dt, h, free_surface=fsurf)
+        return prm, medium.materials(self, prm, dt, h, fsurf)
 
-    def _propagate(self, mat, f, pz, px, g, fw, fsurf, h, pseudo_hessian=None, dt=None):
+    def _propagate(self, medium, mat, f, pz, px, g, fw, fsurf, h, pseudo_hessian=None, dt=None):
         kind = {1: "explosive", 2: "fx", 3: "fz"}[self.QUELLTYP]
-        if self._fluid():
-            if kind != "explosive":
-                f = fluid.force_amplitude(f, mat, g["sc"], g["sw"], h, kind)
-            out = fluid.propagate(mat, f, pz, px, g["sc"], g["sw"], g["rc"], g["rw"], fw, free_surface=fsurf,
-                                  source_type=kind, record_pressure=self.SEISMO in (2, 4), fd_order=int(self.FD_ORDER))
-            return (out[0], out[1], -out[2]) if len(out) == 3 else (out[0], out[1], None)
         if kind != "explosive":
-            f = elastic.force_amplitude(f, mat, g["sc"], g["sw"], h, kind)      # planes 3 and 4: the VTI planes' too
-        if self._visco():
-            out = visco.propagate(mat, f, pz, px, g["sc"], g["sw"], g["rc"], g["rw"], fw, float(self.FL1), dt,
-                                  free_surface=fsurf, source_type=kind, fd_order=int(self.FD_ORDER))
-            return out[0], out[1], None
-        if self._vti():
-            out = vti.propagate(mat, f, pz, px, g["sc"], g["sw"], g["rc"], g["rw"], fw, free_surface=fsurf,
-                                source_type=kind, fd_order=int(self.FD_ORDER))
-            return out[0], out[1], None
-        out = elastic.propagate(mat, f, pz, px, g["sc"], g["sw"], g["rc"], g["rw"], fw,
-                                free_surface=fsurf, source_type=kind, record_pressure=self.SEISMO in (2, 4),
-                                fd_order=int(self.FD_ORDER), pseudo_hessian=pseudo_hessian)
+            f = medium.force_amplitude(f, mat, g["sc"], g["sw"], h, kind)
+        out = medium.propagate(self, (mat, f, pz, px, g["sc"], g["sw"], g["rc"], g["rw"], fw),
+                               dict(free_surface=fsurf, source_type=kind, fd_order=int(self.FD_ORDER)), dt, pseudo_hessian)
         # DENISE's pressure seismogram: p = -(sxx + syy) at the receiver node
         return (out[0], out[1], -out[2]) if len(out) == 3 else (out[0], out[1], None)
 
     def forward(self, model, src, rec):
         """Forward modelling; seismograms are kept in memory (``get_shots``)."""
-        dev, h, dt, nt, g, f, pz, px, fw, fsurf = self._setup(model, src, rec)
+        medium = self._medium(model)
+        dev, h, dt, nt, g, f, pz, px, fw, fsurf = self._setup(model, src, rec, medium)
         with torch.no_grad():
-            _, mat = self._materials(model, dev, dt, h, False, fsurf)
-            vx, vy, p = self._propagate(mat, f.to(dev), pz, px, g, fw, fsurf, h, dt=dt)
+            _, mat = self._materials(medium, model, dev, dt, h, False, fsurf)
+            vx, vy, p = self._propagate(medium, mat, f.to(dev), pz, px, g, fw, fsurf, h, dt=dt)
         self._shots = (vx.permute(1, 2, 0).cpu().numpy(), vy.permute(1, 2, 0).cpu().numpy())
         self._shots_p = None if p is None else p.permute(1, 2, 0).cpu().numpy()
         self.DT_used = dt
@@ -749,22 +768,11 @@ class Denise:
         if int(self.ITERMAX) != 1:
             raise MifwiError("ITERMAX=%s: grad() is one gradient evaluation (the reference sets ITERMAX = 1 and lets its "
                              "own optimiser update the model)" % self.ITERMAX)
-        self._vti(model)
-        self._visco(model)
-        if int(self.INVMAT1) not in (1, 2, 3):
-            raise MifwiError("INVMAT1=%s not implemented (1: Vp, Vs, rho; 2: Zp, Zs, rho; 3: lambda, mu, rho)" % self.INVMAT1)
-        if int(self.EPRECOND) not in (0, 1):
-            raise MifwiError("EPRECOND=%s not implemented (0: off, 1: pseudo-Hessian of the forward wavefields; the "
-                             "receiver-side term of 3 is not built)" % self.EPRECOND)
-        if not float(self.EPSILON_WE) > 0:
-            raise MifwiError("EPSILON_WE=%s: the water level of the preconditioner must be > 0" % self.EPSILON_WE)
-        if int(self.INV_STF) == 1 and self._stf is None:
-            raise MifwiError("INV_STF=1 needs the reach of the matching filter: d.set_stf(before=..., after=... [s], "
-                             "water_level=1e-2)")
-        dev, h, dt, nt, g, f, pz, px, fw, fsurf = self._setup(model, src, rec)
-        prm, mat = self._materials(model, dev, dt, h, True, fsurf)
+        medium = self._medium(model, grad=True)
+        dev, h, dt, nt, g, f, pz, px, fw, fsurf = self._setup(model, src, rec, medium)
+        prm, mat = self._materials(medium, model, dev, dt, h, True, fsurf)
         self._pseudo_hessian = elastic.PseudoHessian() if int(self.EPRECOND) == 1 else None
-        vx, vy, p = self._propagate(mat, f.to(dev), pz, px, g, fw, fsurf, h, self._pseudo_hessian, dt=dt)
+        vx, vy, p = self._propagate(medium, mat, f.to(dev), pz, px, g, fw, fsurf, h, self._pseudo_hessian, dt=dt)
         ox, oy = (o.to(dev).permute(1, 0, 2) for o in self._observed)     # -> [nt, ns, nrec]
         if ox.shape != vx.shape:
             raise MifwiError("observed data %s do not match modelled %s (nt, nshot, nrec)"
@@ -837,11 +845,10 @@ class Denise:
             w = torch.tensor(gradient_taper(model.ny, h, self.GRADT1, self.GRADT2, self.GRADT3, self.GRADT4,
                                             self.EXP_TAPER_GRAD_HOR), device=dev)[:, None]
             grads = [g * w for g in grads]
-        # PHYSICS = 3: five gradients, (Vp0, Vs0, rho, epsilon, delta); the first three go where they always go
-        # L = 1: five as well, (Vp, Vs, rho, Qp, Qs)
-        extra = tuple(np.flipud(g.cpu().numpy()).copy() for g in grads[3:]) if len(grads) == 5 else None
-        self._gradients_thomsen = None if self._visco() else extra
-        self._gradients_q = extra if self._visco() else None
+        # gradients four and five are the medium's own; the first three go where they always go
+        self._gradients_thomsen = self._gradients_q = None
+        if medium.gradients:
+            setattr(self, medium.gradients, tuple(np.flipud(g.cpu().numpy()).copy() for g in grads[3:]))
         grads = grads[:3]
         self._gradients_dev = torch.stack(grads)           # [vp, vs, rho] (INVMAT1 = 2: Zp, Zs, rho; 3: lambda, mu, rho), row 0 = surface
         gvp, gvs, grho = (np.flipud(g.cpu().numpy()).copy() for g in grads)

@@ -1,15 +1,27 @@
-"""TEST INFRASTRUCTURE ONLY: the yardstick of the VTI propagator.
+"""TEST INFRASTRUCTURE ONLY: the yardstick of the P-SV media beyond the isotropic one (VTI, viscoelastic).
 
-A float64 torch (CPU) restatement of the staggered-grid recursion documented in oracle/elastic.c and include/mifwi.h,
-with the sixth material plane of the VTI section of the header:
+A float64 torch (CPU) restatement of the staggered-grid recursion documented in oracle/elastic.c and include/mifwi.h.
+V, the C-PML recursion on every derivative, the odd mirroring under a free surface, sources, receivers and the order of the
+steps are the isotropic scheme and exist once; a medium is its material planes (the stiffnesses times dt/h) and its
+stress update S:
 
-    mat6 = c13, c11, c44_xz, dt/(h rho_x), dt/(h rho_z), c33          (the stiffnesses times dt/h)
+``medium="vti"``, the six planes of the VTI section of the header:
+
+    mat6 = c13, c11, c44_xz, dt/(h rho_x), dt/(h rho_z), c33
     S:  sxx += c11 e1' + c13 e2';  szz += c13 e1' + c33 e2';  sxz += c44 (e3' + e4')
 
-Everything else - V, the C-PML recursion on every derivative, the odd mirroring under a free surface, sources, receivers,
-the order of the steps - is the isotropic scheme, so ``mat6 = cat(mat5, mat5[1:2])`` must reproduce the C oracle
-(tests/test_vti_host.py pins that to rounding).  Autograd through :func:`forward` gives the gradients with respect to
-``mat6`` and ``f``; a central difference of it gives J.  Shots are vectorised, time is a Python loop.
+``medium="visco"``, the eight planes of the viscoelastic section (one relaxation mechanism, ``relax`` = (a, b), memory
+variables rxx, rzz, rxz holding dt times DENISE's r):
+
+    mat8 = lam_u, lam2mu_u, mu_u_xz, dt/(h rho_x), dt/(h rho_z), R2, R1, rmu_xz
+    S:  qxx = R1 e1' + R2 e2';  qzz = R2 e1' + R1 e2';  qxz = rmu_xz (e3' + e4')
+        sxx += lam2mu_u e1' + lam_u e2' + ((1 + a)/2 rxx - b/2 qxx)      (szz, sxz alike)
+        r*  = a r* - b q*
+
+So ``mat6 = cat(mat5, mat5[1:2])`` must reproduce the C oracle (tests/test_vti_host.py pins that to rounding), and
+``mat8 = cat(mat5, 0, 0, 0)`` that isotropic limit (tests/test_visco_host.py).  Autograd through :func:`forward` gives the
+gradients with respect to the planes and ``f``; a central difference of it gives J.  Shots are vectorised, time is a
+Python loop.
 """
 import numpy as np
 import torch
@@ -58,19 +70,54 @@ class _Taps:
         return (self.w * v).sum(dim=-1)
 
 
-def forward(mat6, pz, px, f, src_cell, src_w, rec_cell, rec_w, free_surface=0, fd_order=4, source_type=0):
-    """mat6 [6,nz,nx], pz [6,nz], px [6,nx], f [nt,ns,nsrc]; cells [ns,n,ntap] (negative: inactive).  Returns
-    (rec_vx, rec_vz), float64 tensors [nt,ns,nrec]; ``mat6`` and ``f`` may require gradients."""
-    mat6, pz, px, f = _t(mat6), _t(pz), _t(px), _t(f)
-    _, nz, nx = mat6.shape
+def _stress_vti(mat, relax):
+    """S of a VTI medium: stresses, memory variables (none), strains -> stresses, memory variables."""
+    c13, c11, c44, c33 = mat[0][None], mat[1][None], mat[2][None], mat[5][None]
+
+    def update(sxx, szz, sxz, r, e1, e2, e3, e4):
+        return sxx + c11 * e1 + c13 * e2, szz + c13 * e1 + c33 * e2, sxz + c44 * (e3 + e4), r
+    return update
+
+
+def _stress_visco(mat, relax):
+    """S of a viscoelastic medium, with the memory variables r = (rxx, rzz, rxz)."""
+    lam, lam2mu, mu, R2, R1, rmu = (mat[k][None] for k in (0, 1, 2, 5, 6, 7))
+    ra, rb = float(relax[0]), float(relax[1])
+
+    def update(sxx, szz, sxz, r, e1, e2, e3, e4):
+        rxx, rzz, rxz = r
+        e3 = e3 + e4
+        qxx = R1 * e1 + R2 * e2
+        qzz = R2 * e1 + R1 * e2
+        qxz = rmu * e3
+        sxx = sxx + lam2mu * e1 + lam * e2 + (0.5 * (1.0 + ra) * rxx - 0.5 * rb * qxx)
+        szz = szz + lam * e1 + lam2mu * e2 + (0.5 * (1.0 + ra) * rzz - 0.5 * rb * qzz)
+        sxz = sxz + mu * e3 + (0.5 * (1.0 + ra) * rxz - 0.5 * rb * qxz)
+        return sxx, szz, sxz, (ra * rxx - rb * qxx, ra * rzz - rb * qzz, ra * rxz - rb * qxz)
+    return update
+
+
+_MEDIA = {"vti": (6, _stress_vti), "visco": (8, _stress_visco)}
+
+
+def forward(mat, pz, px, f, src_cell, src_w, rec_cell, rec_w, medium, relax=None, free_surface=0, fd_order=4,
+            source_type=0):
+    """mat [6 or 8,nz,nx] (``medium`` "vti" or "visco", the latter with relax = (a, b)), pz [6,nz], px [6,nx],
+    f [nt,ns,nsrc]; cells [ns,n,ntap] (negative: inactive).  Returns (rec_vx, rec_vz), float64 tensors [nt,ns,nrec];
+    ``mat`` and ``f`` may require gradients."""
+    mat, pz, px, f = _t(mat), _t(pz), _t(px), _t(f)
+    nplanes, stress = _MEDIA[medium]
+    assert mat.shape[0] == nplanes and (relax is not None) == (medium == "visco")
+    _, nz, nx = mat.shape
     nt, ns, _ = f.shape
     c1, c2 = (1.0, 0.0) if fd_order == 2 else (9.0 / 8.0, -1.0 / 24.0)
-    c13, c11, c44, bx, bz, c33 = (mat6[k][None] for k in range(6))
+    bx, bz = mat[3][None], mat[4][None]
     X = [px[k][None, None, :] for k in range(6)]
     Z = [pz[k][None, :, None] for k in range(6)]
     src, rec = _Taps(src_cell, src_w, nz * nx), _Taps(rec_cell, rec_w, nz * nx)
     zero = torch.zeros(ns, nz, nx, dtype=torch.float64)
     vx = vz = sxx = szz = sxz = zero
+    update, r = stress(mat, relax), (zero, zero, zero)
     psi = [zero] * 8
     keep = torch.ones(1, nz, 1, dtype=torch.float64)
     keep[0, 0, 0] = 0.0
@@ -107,9 +154,7 @@ def forward(mat6, pz, px, f, src_cell, src_w, rec_cell, rec_w, free_surface=0, f
         e2 = pml(5, Z, False, dm(Pvz, 0))
         e3 = pml(6, Z, True, dp(Pvx, 0))
         e4 = pml(7, X, True, dp(Pvz, 1))
-        sxx = sxx + c11 * e1 + c13 * e2
-        szz = szz + c13 * e1 + c33 * e2
-        sxz = sxz + c44 * (e3 + e4)
+        sxx, szz, sxz, r = update(sxx, szz, sxz, r, e1, e2, e3, e4)
         if source_type == 0:
             a = src.scatter(f[n]).reshape(ns, nz, nx)
             sxx = sxx + a
@@ -121,26 +166,26 @@ def forward(mat6, pz, px, f, src_cell, src_w, rec_cell, rec_w, free_surface=0, f
     return torch.stack(out_x), torch.stack(out_z)
 
 
-def gradients(mat6, pz, px, f, src_cell, src_w, rec_cell, rec_w, g_vx, g_vz, **kw):
-    """(rec_vx, rec_vz, grad_mat6, grad_f) as float64 numpy arrays: the traces and the gradient of
+def gradients(mat, pz, px, f, src_cell, src_w, rec_cell, rec_w, g_vx, g_vz, medium, relax=None, **kw):
+    """(rec_vx, rec_vz, grad_mat, grad_f) as float64 numpy arrays: the traces and the gradient of
     sum(g_vx rec_vx + g_vz rec_vz) by autograd.  ``g_vx`` may be a callable (rec_vx, rec_vz) -> (g_vx, g_vz) of the
     traces as numpy arrays (``g_vz`` is then ignored)."""
-    m = _t(mat6).clone().requires_grad_(True)
+    m = _t(mat).clone().requires_grad_(True)
     ff = _t(f).clone().requires_grad_(True)
-    rvx, rvz = forward(m, pz, px, ff, src_cell, src_w, rec_cell, rec_w, **kw)
+    rvx, rvz = forward(m, pz, px, ff, src_cell, src_w, rec_cell, rec_w, medium, relax, **kw)
     if callable(g_vx):
         g_vx, g_vz = g_vx(rvx.detach().numpy(), rvz.detach().numpy())
     ((rvx * _t(g_vx)).sum() + (rvz * _t(g_vz)).sum()).backward()
     return rvx.detach().numpy(), rvz.detach().numpy(), m.grad.numpy(), ff.grad.numpy()
 
 
-def jvp(mat6, dmat6, pz, px, f, df, src_cell, src_w, rec_cell, rec_w, eps=1e-5, **kw):
-    """J (dmat6, df) [2,nt,ns,nrec] by a central difference of :func:`forward` (``df`` None: no source perturbation)."""
-    m, dm_, ff = _t(mat6), _t(dmat6), _t(f)
+def jvp(mat, dmat, pz, px, f, df, src_cell, src_w, rec_cell, rec_w, medium, relax=None, eps=1e-5, **kw):
+    """J (dmat, df) [2,nt,ns,nrec] by a central difference of :func:`forward` (``df`` None: no source perturbation)."""
+    m, dm_, ff = _t(mat), _t(dmat), _t(f)
     dff = torch.zeros_like(ff) if df is None else _t(df)
     with torch.no_grad():
-        p = forward(m + eps * dm_, pz, px, ff + eps * dff, src_cell, src_w, rec_cell, rec_w, **kw)
-        q = forward(m - eps * dm_, pz, px, ff - eps * dff, src_cell, src_w, rec_cell, rec_w, **kw)
+        p = forward(m + eps * dm_, pz, px, ff + eps * dff, src_cell, src_w, rec_cell, rec_w, medium, relax, **kw)
+        q = forward(m - eps * dm_, pz, px, ff - eps * dff, src_cell, src_w, rec_cell, rec_w, medium, relax, **kw)
     return np.stack([((a - b) / (2 * eps)).numpy() for a, b in zip(p, q)])
 
 
@@ -149,6 +194,19 @@ def thomsen_mat6(vp0, vs0, rho, epsilon, delta, dt, h, free_surface=False):
     from physicsbasedfwi2_amd import vti
     t = [torch.tensor(np.asarray(a, dtype=np.float64)) for a in (vp0, vs0, rho, epsilon, delta)]
     return vti.materials(*t, dt, h, free_surface=free_surface).numpy()
+
+
+def visco_mat8(vp, vs, rho, qp, qs, f_ref, f_relax, dt, h, free_surface=False):
+    """float64 numpy planes of ``visco.materials`` (the product's torch expression on CPU float64 is the definition)."""
+    from physicsbasedfwi2_amd import visco
+    t = [torch.tensor(np.asarray(a, dtype=np.float64)) for a in (vp, vs, rho, qp, qs)]
+    return visco.materials(*t, f_ref, f_relax, dt, h, free_surface=free_surface).numpy()
+
+
+def sls_q(f, f_relax, tau):
+    """Q(w) = (1 + w^2 tau_sigma^2 (1 + tau)) / (w tau_sigma tau) of one standard linear solid, tau_sigma = 1 / (2 pi f_relax)."""
+    x = f / f_relax                       # w tau_sigma
+    return (1.0 + x * x * (1.0 + tau)) / (x * tau)
 
 
 def peak_time(trace):
@@ -163,8 +221,8 @@ def peak_time(trace):
 
 def pin_case(epsilon, delta, vp0=2000.0, vs0=1100.0, rho=2000.0, n=121, h=10.0, dt=1e-3, nt=330, f0=15.0):
     """The homogeneous physics pin: 121 x 121, no absorbing layer, explosive 15 Hz Ricker (delayed by 1.2 / f0) at
-    (60, 60), a vx receiver 40 cells along x and a vz receiver 40 rows along z.  Returns the arguments of :func:`forward`
-    as float64 numpy arrays: (mat6, pz, px, f, sc, sw, rc, rw)."""
+    (60, 60), a vx receiver 40 cells along x and a vz receiver 40 rows along z.  Returns the first eight arguments of
+    :func:`forward` as float64 numpy arrays: (mat6, pz, px, f, sc, sw, rc, rw)."""
     from oracle import helpers as H
     full = lambda v: np.full((n, n), float(v))
     mat6 = thomsen_mat6(full(vp0), full(vs0), full(rho), full(epsilon), full(delta), dt, h)

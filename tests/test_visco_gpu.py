@@ -1,344 +1,39 @@
-"""The viscoelastic propagator on the GPU (physicsbasedfwi2_amd.visco, mifwi_visco_*) against its yardstick
-tests/visco_reference.py (float64; tests/test_visco_host.py pins it to the fp64 C oracle in the elastic limit and to the
-attenuation law of a standard linear solid) and against today's isotropic kernels.
-
-Shapes: A = the default 44 x 60 x 120 steps case (15 groups: less than one column block, a partial tile in z), B = 37 x 150,
-3 shots, 50 steps (three column blocks with the last partial, nx no multiple of 4).  Both with an 8-cell C-PML, A also
-without a layer and with a free surface; stencil orders 2 and 4.  Smooth seeded qp in [20, 200] and qs in [10, 100] over the
-solid, qp = 1000 in the water rows; f_relax = 8 Hz, the wavelet's centre frequency, f_ref = 30 Hz.  Inputs are rounded to f32
-first (what the device computes with).  Bounds: 2e-6 rel-L2 for an f32 recursion against its fp64 reference (the project's
-bound), 2e-5 for gradients summed in another order, and for the gradients of the new medium max(2e-5, 4 E_iso) with E_iso
-the error of today's isotropic kernels against the same reference in the elastic limit on the same geometry, measured in
-the same test and printed.  Every reference result is computed once per case and left unchanged.
-Measured on the MI355X: the elastic limit's traces and gradients the same bits as elastic.propagate's; attenuating traces
-8.2e-8 ... 3.3e-7 from the reference (and 2 ... 7 % from the elastic reference, the live shots), gradients of the eight planes
-and of f 4.6e-8 ... 1.14e-6, E_iso 5.4e-8 ... 8.5e-7 (so the bound in force was 2e-5 everywhere); Born 1.8e-7 ... 6.8e-7;
-identities 2.5e-8 ... 9.8e-6; time checkpoints and shot groups: gradients <= 3.3e-7 from the resident run, traces the same
-bits; the shim against the by-hand composition and L = 1 with Q = inf against L = 0: the same bits."""
+"""What the viscoelastic propagator (physicsbasedfwi2_amd.visco, mifwi_visco_*) has of its own on the GPU: L = 1 of the
+pyapi_denise shim and the refusals of the C entry points, the elastic ones' of the other media's plans included.  The
+elastic limit and the parity with the float64 reference keep their names here and run the checks of tests/psv_media.py that
+the VTI medium runs too (shapes, bounds and what was measured: there and in tests/test_psv_media_gpu.py, which has Born and
+the driver forms).
+Measured on the MI355X: the shim against the by-hand composition and L = 1 with Q = inf against L = 0: the same bits."""
 import ctypes
 
 import numpy as np
 import pytest
 import torch
 
-import visco_reference as R
-from cases import elastic_case, rel_l2
+import psv_media as M
+from cases import rel_l2
+from psv_media import CASES, TOL_TRACE
 
 pytestmark = pytest.mark.gpu
-CASES = {"A": dict(), "A_fw0": dict(fw=0), "A_fs": dict(free_surface=True), "B": dict(nz=37, nx=150, ns=3, nt=50)}
-PER_STEP = {"MIFWI_EL_CLUSTER": "0", "MIFWI_EL_CLUSTER_ADJ": "0", "MIFWI_EL_FUSED": "0"}
-PLANES = ("lam", "lam2mu", "mu", "bx", "bz", "R2", "R1", "rmu")
-ISO_OF = {"lam": "L", "lam2mu": "M", "mu": "mu", "bx": "bx", "bz": "bz", "R2": "L", "R1": "M", "rmu": "mu", "f": "f"}
-TOL_TRACE, TOL_SUM = 2e-6, 2e-5
-WATER = 6
-# f_relax at the wavelet's centre frequency; the velocities are given at 30 Hz, above the wavelet's band, as a model from
-# sonic logs or from another survey would be: the medium then differs from the elastic one by the dispersion of the standard
-# linear solid as well as by its loss.  (With f_ref = 10 Hz and any Q field inside the ranges the one live shot of the
-# free-surface case at order 2, whose receivers record mostly water-borne energy, moves by 0.6 ... 0.9 %, short of the percent
-# that test_attenuating_traces_and_gradients_match_the_reference asks first; with 30 Hz it moves by 6.5 %.)
-F_RELAX, F_REF = 8.0, 30.0
-_cache = {}
-
-
-def _f32(a):
-    return np.asarray(a, dtype=np.float32).astype(np.float64)
-
-
-def _case(name):
-    """The elastic case with its inputs rounded to f32, seeded smooth qp in [20, 200] and qs in [10, 100] over the solid
-    (qp = 1000 in the water rows), the eight planes of visco.materials (CPU float64, then rounded), the elastic limit
-    cat(mat5, 0, 0, 0) and seeded 1 % perturbations of the planes and of the source amplitudes."""
-    if name not in _cache:
-        from physicsbasedfwi2_amd import visco
-        cfg = CASES[name]
-        c = elastic_case(seed=83, **cfg)
-        nz, nx = c["vp"].shape
-        rng = np.random.default_rng(31)
-        z, x = np.meshgrid(np.arange(nz) / nz, np.arange(nx) / nx, indexing="ij")
-        ph = 2 * np.pi * rng.random(4)
-        # u, v smooth in [0, 1]; cubed, the fields spend most of the grid in the lower, attenuating part of their ranges
-        # (means about 57 and 33): the 120 steps of case A are two periods of the wavelet, little time for a Q of 100 to act
-        u = 0.5 + 0.5 * np.sin(2 * np.pi * (1.3 * z + 0.7 * x) + ph[0]) * np.cos(2 * np.pi * 0.9 * x + ph[1])
-        v = 0.5 + 0.5 * np.sin(2 * np.pi * (0.8 * z - 1.1 * x) + ph[2]) * np.cos(2 * np.pi * 0.6 * z + ph[3])
-        qp, qs = 20 + 180 * u ** 3, 10 + 90 * v ** 3
-        qp[:WATER] = 1000.0
-        assert 20 <= qp[WATER:].min() and qp[WATER:].max() <= 200 and 10 <= qs.min() and qs.max() <= 100
-        assert qp[WATER:].std() > 10 and qs[WATER:].std() > 5 and not c["vs"][:WATER].any()
-        c["qp"], c["qs"] = qp, qs
-        c["relax"] = visco.relaxation(F_RELAX, c["dt"])
-        c["mat8"] = R.visco_mat8(_f32(c["vp"]), _f32(c["vs"]), _f32(c["rho"]), _f32(qp), _f32(qs), F_REF, F_RELAX, c["dt"],
-                                 c["h"], free_surface=bool(c["fs"]))
-        for k in ("mat", "mat8", "pz", "px", "f", "sw", "rw"):
-            c[k] = _f32(c[k])
-        c["mat8iso"] = np.concatenate([c["mat"], np.zeros((3,) + c["mat"].shape[1:])])
-        assert all(np.abs(c["mat8"][k]).max() > 0 for k in range(8))
-        prng = np.random.default_rng(100)
-        c["dmat8"] = _f32(0.01 * prng.standard_normal(c["mat8"].shape) * c["mat8"])
-        c["df"] = _f32(0.01 * prng.standard_normal(c["f"].shape) * np.abs(c["f"]).max())
-        for v in c.values():
-            if isinstance(v, np.ndarray):
-                v.setflags(write=False)
-        _cache[name] = c
-    return _cache[name]
-
-
-def _g_of(rvx, rvz):
-    """The adjoint source of the gradient tests: seeded noise at the size of each trace set."""
-    rng = np.random.default_rng(12)
-    return [_f32(rng.standard_normal(a.shape) * np.abs(a).max()) for a in (rvx, rvz)]
-
-
-def _geo(c):
-    return c["sc"], c["sw"], c["rc"], c["rw"]
-
-
-def _ref(name, order, which):
-    """The reference on ``which`` = "mat8" / "mat8iso": traces, the adjoint source built from them, gradients."""
-    key = ("ref", name, order, which)
-    if key not in _cache:
-        c = _case(name)
-        rvx, rvz, g8, gf = R.gradients(c[which], c["pz"], c["px"], c["f"], *_geo(c), _g_of, None, c["relax"],
-                                       free_surface=c["fs"], fd_order=order)
-        out = dict(rvx=rvx, rvz=rvz, g=_g_of(rvx, rvz), f=gf)
-        out.update({p: g8[k] for k, p in enumerate(PLANES)})
-        for v in out.values():
-            for a in (v if isinstance(v, list) else [v]):
-                a.setflags(write=False)
-        _cache[key] = out
-    return _cache[key]
-
-
-def _ref_jvp(name, order):
-    key = ("jvp", name, order)
-    if key not in _cache:
-        c = _case(name)
-        d = R.jvp(c["mat8"], c["dmat8"], c["pz"], c["px"], c["f"], None, *_geo(c), c["relax"], eps=1e-5,
-                  free_surface=c["fs"], fd_order=order)
-        d.setflags(write=False)
-        _cache[key] = d
-    return _cache[key]
-
-
-def _dev(a):
-    a = np.asarray(a)
-    return torch.tensor(a, device="cuda:0", dtype=torch.int32 if a.dtype.kind == "i" else torch.float32)
-
-
-def _args(c, mat, f=None):
-    """(mat, f, pz, px, src_cell, src_w, rec_cell, rec_w, pml_width)"""
-    return [mat, _dev(c["f"]) if f is None else f] + [_dev(c[k]) for k in ("pz", "px", "sc", "sw", "rc", "rw")] + [c["fw"]]
-
-
-def _run(mod, c, mat_np, order, g=None, need_f=True, **kw):
-    """propagate (+ backward with the adjoint source ``g``) of ``mod`` = visco / elastic: traces, grad_mat, grad_f as float64."""
-    from physicsbasedfwi2_amd import visco
-    mat = _dev(mat_np).requires_grad_(g is not None)
-    f = _dev(c["f"]).requires_grad_(g is not None and need_f)
-    extra = [F_RELAX, c["dt"]] if mod is visco else []
-    rvx, rvz = mod.propagate(*_args(c, mat, f), *extra, free_surface=bool(c["fs"]), fd_order=order, **kw)
-    if g is None:
-        return rvx, rvz
-    torch.autograd.backward([rvx, rvz], [_dev(a) for a in g])
-    return rvx.detach(), rvz.detach(), mat.grad.double().cpu().numpy(), (f.grad.double().cpu().numpy() if need_f else None)
-
-
-def _pair(a, b):
-    return torch.stack([a, b]).double().cpu().numpy()
-
-
-def _setenv(monkeypatch, env):
-    for k, v in env.items():
-        monkeypatch.setenv(k, v)
-
-
-def _dot(a, b):
-    return float((a.double() * b.double()).sum())
-
-
-def _close(a, b, tol, what):
-    print("%s: %.9e vs %.9e, |diff| / max = %.2e" % (what, a, b, abs(a - b) / max(abs(a), abs(b))))
-    assert abs(a - b) <= tol * max(abs(a), abs(b)), what
+VISCO = M.MEDIA["visco"]
 
 
 @pytest.fixture(autouse=True)
 def _no_fallback():
-    """No call of this module may count a fall-back (the counter is the process's: other modules move it on purpose)."""
-    from physicsbasedfwi2_amd import _lib
-    before = _lib.load().mifwi_fallback_count()
-    yield
-    assert _lib.load().mifwi_fallback_count() == before
+    yield from M.no_fallback()
 
 
-# ---- the elastic limit at mat level -------------------------------------------------------------------------------------
+# ---- the elastic limit at mat level (the per-step kernels' only), attenuating parity: the shared checks ------------------
 @pytest.mark.parametrize("order", [2, 4])
 @pytest.mark.parametrize("name", list(CASES))
 def test_elastic_limit_is_the_elastic_propagator(monkeypatch, name, order):
-    from physicsbasedfwi2_amd import elastic, visco
-    _setenv(monkeypatch, PER_STEP)
-    c = _case(name)
-    g = _ref(name, order, "mat8iso")["g"]
-    evx, evz, eg, egf = _run(elastic, c, c["mat"], order, g)
-    vvx, vvz, vg, vgf = _run(visco, c, c["mat8iso"], order, g)
-    assert evx.abs().max() > 0 and evz.abs().max() > 0
-    assert torch.equal(vvx, evx) and torch.equal(vvz, evz)
-    want = {"L": eg[0], "M": eg[1], "mu": eg[2], "bx": eg[3], "bz": eg[4], "f": egf}
-    got = {"L": vg[0], "M": vg[1], "mu": vg[2], "bx": vg[3], "bz": vg[4], "f": vgf}
-    errs = {k: rel_l2(got[k], want[k]) for k in want}
-    print("visco(elastic limit) vs elastic gradients rel-L2", {k: "%.2e" % v for k, v in errs.items()})
-    for k, v in errs.items():
-        assert np.abs(want[k]).max() > 0, k
-        assert v <= TOL_SUM, (k, v)
+    M.check_limit_is_the_elastic_propagator(VISCO, monkeypatch, name, "per_step", order)
 
 
-# ---- attenuating traces and all gradients against the reference ---------------------------------------------------------
 @pytest.mark.parametrize("order", [2, 4])
 @pytest.mark.parametrize("name", list(CASES))
 def test_attenuating_traces_and_gradients_match_the_reference(name, order):
-    from physicsbasedfwi2_amd import elastic, visco
-    c = _case(name)
-    iso, ref = _ref(name, order, "mat8iso"), _ref(name, order, "mat8")
-    # today's isotropic kernels against the same reference in the elastic limit: the case's own error level
-    evx, evz, eg, egf = _run(elastic, c, c["mat"], order, iso["g"])
-    e_tr = rel_l2(_pair(evx, evz), np.stack([iso["rvx"], iso["rvz"]]))
-    e_iso = {"L": rel_l2(eg[0], iso["lam"]), "M": rel_l2(eg[1], iso["lam2mu"]), "mu": rel_l2(eg[2], iso["mu"]),
-             "bx": rel_l2(eg[3], iso["bx"]), "bz": rel_l2(eg[4], iso["bz"]), "f": rel_l2(egf, iso["f"])}
-    print("E_iso %s order %d: traces %.2e, gradients %s" % (name, order, e_tr, {k: "%.2e" % v for k, v in e_iso.items()}))
-    assert e_tr <= TOL_TRACE, "the isotropic kernels miss the trace bound on this case: not a case for this test"
-    vvx, vvz, vg, vgf = _run(visco, c, c["mat8"], order, ref["g"])
-    assert np.abs(ref["rvx"]).max() > 0 and np.abs(ref["rvz"]).max() > 0
-    want_tr, iso_tr, got_tr = np.stack([ref["rvx"], ref["rvz"]]), np.stack([iso["rvx"], iso["rvz"]]), _pair(vvx, vvz)
-    shots = range(want_tr.shape[2])
-    # the case attenuates for real: some shot's traces move by more than a percent, as test_vti_gpu.py asks of its medium.
-    # (Under the free surface shot 0 is shot and recorded on row 0 in the water, whose effective moduli are all zero: its
-    # traces never see the medium, are the same bits in both references and carry nearly all the energy of the case, so
-    # all shots pooled move by 7e-7 there whatever Q is.)
-    moved = [rel_l2(want_tr[:, :, s], iso_tr[:, :, s]) for s in shots]
-    print("visco vs elastic reference traces: rel-L2 shot by shot %s, pooled %.2e"
-          % (["%.2e" % m for m in moved], rel_l2(want_tr, iso_tr)))
-    assert max(moved) > 0.01
-    err = rel_l2(got_tr, want_tr)
-    print("visco traces vs reference: rel-L2 %.2e, shot by shot %s"
-          % (err, ["%.2e" % rel_l2(got_tr[:, :, s], want_tr[:, :, s]) for s in shots]))
-    assert err <= TOL_TRACE
-    got = dict(zip(PLANES, vg), f=vgf)
-    for k in got:
-        want = ref[k]
-        e = rel_l2(got[k], want)
-        tol = max(TOL_SUM, 4 * e_iso[ISO_OF[k]])
-        print("gradient %-6s rel-L2 %.2e (bound %.2e)" % (k, e, tol))
-        assert np.abs(want).max() > 0, k
-        assert e <= tol, (k, e, tol)
-
-
-# ---- Born ---------------------------------------------------------------------------------------------------------------
-def _born(c, order, dmat=None, df=None, **kw):
-    from physicsbasedfwi2_amd import visco
-    a = _args(c, _dev(c["mat8"]))
-    return visco.born(a[0], _dev(c["dmat8"]) if dmat is None else dmat, *a[1:], F_RELAX, c["dt"], df=df,
-                      free_surface=bool(c["fs"]), fd_order=order, **kw)
-
-
-@pytest.mark.parametrize("order", [2, 4])
-@pytest.mark.parametrize("name", list(CASES))
-def test_born_is_the_directional_derivative_of_the_reference(name, order):
-    c = _case(name)
-    want = _ref_jvp(name, order)
-    _, _, dvx, dvz = _born(c, order)
-    got = _pair(dvx, dvz)
-    err = rel_l2(got, want)
-    print("visco.born vs central difference of the reference, %s order %d: rel-L2 %.3e" % (name, order, err))
-    assert np.abs(want).max() > 0
-    assert err <= TOL_TRACE
-
-
-@pytest.mark.parametrize("name", ["A", "A_fs", "B"])
-def test_born_background_dot_products_and_gauss_newton(name):
-    from physicsbasedfwi2_amd import visco
-    c = _case(name)
-    order = 4
-    mat8 = _dev(c["mat8"])
-    rvx, rvz, dvx, dvz = _born(c, order, df=_dev(c["df"]))
-    pvx, pvz = _run(visco, c, c["mat8"], order)
-    assert torch.equal(rvx, pvx) and torch.equal(rvz, pvz)                         # the background traces
-    # <J (dm, df), g> = <dm, J^T g> + <df, J^T g>
-    g = [_dev(a) for a in _g_of(rvx.cpu().numpy(), rvz.cpu().numpy())]
-    _, _, gm, gf = _run(visco, c, c["mat8"], order, [a.cpu().numpy() for a in g])
-    _, _, mvx, mvz = _born(c, order)                                              # dm alone
-    _close(_dot(mvx, g[0]) + _dot(mvz, g[1]), float((gm * c["dmat8"]).sum()), TOL_SUM, "<J dm, g> vs <dm, J^T g>")
-    # the three new planes alone: their Born terms against their gradients
-    only = np.array(c["dmat8"])
-    only[:5] = 0.0
-    _, _, qvx, qvz = _born(c, order, dmat=_dev(only))
-    assert float(qvx.abs().max()) > 0
-    # (a sum of terms of both signs that partly cancel: the f32 gradients' error, bounded by TOL_SUM per plane, is relative
-    # to the terms, so this identity is held to TOL_SUM of their absolute sum)
-    lhs, rhs, size = _dot(qvx, g[0]) + _dot(qvz, g[1]), float((gm[5:] * only[5:]).sum()), float(np.abs(gm[5:] * only[5:]).sum())
-    print("<J dR, g> = %.9e, <dR, J^T g> = %.9e, sum |terms| = %.3e, |diff| / sum = %.2e" % (lhs, rhs, size, abs(lhs - rhs) / size))
-    assert abs(lhs - rhs) <= TOL_SUM * size
-    zero = torch.zeros_like(mat8)
-    _, _, fvx, fvz = _born(c, order, dmat=zero, df=_dev(c["df"]))                 # df alone
-    _close(_dot(fvx, g[0]) + _dot(fvz, g[1]), float((gf * c["df"]).sum()), TOL_SUM, "<J df, g> vs <df, J^T g>")
-    assert rel_l2(_pair(mvx + fvx, mvz + fvz), _pair(dvx, dvz)) <= TOL_TRACE       # J is linear
-    # Gauss-Newton: <H a, b> = <a, H b>
-    a = _args(c, mat8)
-    kw = dict(free_surface=bool(c["fs"]), fd_order=order)
-    other = _dev(_f32(0.01 * np.random.default_rng(5).standard_normal(c["mat8"].shape) * c["mat8"]))
-    ha, hvx, hvz = visco.gauss_newton_product(a[0], _dev(c["dmat8"]), *a[1:], F_RELAX, c["dt"], **kw)
-    hb, _, _ = visco.gauss_newton_product(a[0], other, *a[1:], F_RELAX, c["dt"], **kw)
-    assert ha.shape == mat8.shape and torch.equal(hvx, mvx) and torch.equal(hvz, mvz)
-    _close(_dot(ha, other), _dot(hb, _dev(c["dmat8"])), TOL_SUM, "<H a, b> vs <a, H b>")
-    _close(_dot(ha, _dev(c["dmat8"])), _dot(mvx, mvx) + _dot(mvz, mvz), TOL_SUM, "<H a, a> vs |J a|^2")
-
-
-# ---- driver forms: time checkpoints, shot groups, shot chunks, repeats -------------------------------------------------------
-def _step_bytes(c, ns=None):
-    from physicsbasedfwi2_amd import visco
-    nz, nx = c["vp"].shape
-    nt, n, nsrc = c["f"].shape
-    plan = visco.ViscoPlan(nz, nx, nt, ns or n, nsrc, c["rc"].shape[1], 1, c["fw"], 0, *c["relax"], free_surface=c["fs"])
-    assert plan.cluster_slabs(False) == 0 and plan.cluster_slabs(True) == 0
-    lay = plan.layout
-    pitch_rows = (nz + 4) * lay.pitch
-    assert lay.state_elems >= 8 * pitch_rows * (ns or n)              # eight fields per shot: the memory variables are state
-    b = 4 * lay.snap_step_elems
-    plan.close()
-    return b
-
-
-@pytest.mark.parametrize("name", ["A", "B"])
-def test_checkpoints_groups_chunks_and_repeats(name):
-    """Time checkpoints save and restore the state of a shot: a checkpoint without the memory variables would restart every
-    segment but the first from r = 0 and move traces (recorded once, by the first pass) not at all but gradients by far
-    more than rounding."""
-    from physicsbasedfwi2_amd import visco
-    c = _case(name)
-    order = 4
-    nt = c["f"].shape[0]
-    g = _ref(name, order, "mat8")["g"]
-    base = _run(visco, c, c["mat8"], order, g)
-    again = _run(visco, c, c["mat8"], order, g)
-    host = lambda t: np.asarray(t.cpu() if torch.is_tensor(t) else t)
-    for a, b in zip(base, again):                                                  # a repeated call: the same bits
-        assert np.array_equal(host(a), host(b))
-    # time checkpoints: segments of 7 steps, at least three of them
-    seg = _run(visco, c, c["mat8"], order, g, snapshot_budget=14 * _step_bytes(c) + 1)
-    assert nt > 3 * 7
-    assert torch.equal(seg[0], base[0]) and torch.equal(seg[1], base[1])
-    errs = [rel_l2(seg[2][k], base[2][k]) for k in range(8)] + [rel_l2(seg[3], base[3])]
-    print("time checkpoints vs resident snapshots: gradients rel-L2 %s" % ["%.1e" % e for e in errs])
-    assert max(errs) <= TOL_SUM
-    # shots per gradient accumulator
-    for gs in (1, 2):
-        r = _run(visco, c, c["mat8"], order, g, shots_per_group=gs)
-        assert torch.equal(r[0], base[0]) and torch.equal(r[1], base[1])
-        errs = [rel_l2(r[2][k], base[2][k]) for k in range(8)] + [rel_l2(r[3], base[3])]
-        print("shots_per_group %d vs 0: gradients rel-L2 %s" % (gs, ["%.1e" % e for e in errs]))
-        assert max(errs) <= TOL_SUM
-    # Born in shot chunks of one
-    whole = _born(c, order, df=_dev(c["df"]))
-    chunked = _born(c, order, df=_dev(c["df"]), snapshot_budget=int(1.5 * nt * _step_bytes(c, 1)))
-    for a, b in zip(whole, chunked):
-        assert torch.equal(a, b)
+    M.check_traces_and_gradients_match_the_reference(VISCO, name, order)
 
 
 # ---- the pyapi_denise shim ------------------------------------------------------------------------------------------------

@@ -1,20 +1,17 @@
-"""The viscoelastic propagator's host side without a GPU: the yardstick (tests/visco_reference.py) against the VTI yardstick
+"""The viscoelastic propagator's host side without a GPU: the yardstick (tests/psv_reference.py) against its VTI form
 in the elastic limit (itself pinned to the fp64 C oracle), against the attenuation law of a standard linear solid and
 against its own central differences; ``visco.materials`` / ``materials_jvp`` / ``max_velocity`` / ``relaxation`` on CPU
 float64; the C ABI of the ``mifwi_visco_*`` structs."""
 import ctypes
-import os
-import subprocess
 
 import numpy as np
 import pytest
 import torch
 
-import visco_reference as R
-import vti_reference as RV
+import psv_reference as R
 from cases import elastic_case, rel_l2
+from psv_media import check_struct_layouts, seeded_model
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 RELAX = (0.9, 0.1)             # any pair inside (0, 1): with planes 5-7 zero it must not matter
 
 
@@ -22,7 +19,7 @@ RELAX = (0.9, 0.1)             # any pair inside (0, 1): with planes 5-7 zero it
 @pytest.mark.parametrize("order", [2, 4])
 @pytest.mark.parametrize("fs", [False, True], ids=["absorbing_top", "free_surface"])
 def test_reference_is_the_vti_reference_in_the_elastic_limit(fs, order):
-    """Planes 5-7 zero: the memory variables stay 0 and every stress update is the VTI reference's in its isotropic limit,
+    """Planes 5-7 zero: the memory variables stay 0 and every stress update is the VTI form's in its isotropic limit,
     which tests/test_vti_host.py pins to the fp64 oracle.  Same operations in the same order: the bound is 1e-16 rel-L2
     (measured 0)."""
     c = elastic_case(seed=4, free_surface=fs)
@@ -30,8 +27,8 @@ def test_reference_is_the_vti_reference_in_the_elastic_limit(fs, order):
     mat8 = np.concatenate([c["mat"], np.zeros((3,) + c["mat"].shape[1:])])
     mat6 = np.concatenate([c["mat"], c["mat"][1:2]])
     with torch.no_grad():
-        got = R.forward(mat8, c["pz"], c["px"], c["f"], *geo, RELAX, free_surface=c["fs"], fd_order=order)
-        want = RV.forward(mat6, c["pz"], c["px"], c["f"], *geo, free_surface=c["fs"], fd_order=order)
+        got = R.forward(mat8, c["pz"], c["px"], c["f"], *geo, "visco", RELAX, free_surface=c["fs"], fd_order=order)
+        want = R.forward(mat6, c["pz"], c["px"], c["f"], *geo, "vti", free_surface=c["fs"], fd_order=order)
     got, want = np.stack([a.numpy() for a in got]), np.stack([a.numpy() for a in want])
     err = rel_l2(got, want)
     print("visco reference (planes 5-7 zero) vs vti reference (isotropic): rel-L2 %.2e" % err)
@@ -61,7 +58,7 @@ def _att_traces(qp, qs):
     sc, sw = H.cell_taps(np.array([[sz]]), np.array([[sx]]), nx)
     rc, rw = H.cell_taps(np.array([[sz, sz]]), np.array([[sx + o for o in a["offsets"]]]), nx)
     with torch.no_grad():
-        vx, _ = R.forward(mat, tz, tx, f, sc, sw, rc, rw, visco.relaxation(a["f0"], a["dt"]))
+        vx, _ = R.forward(mat, tz, tx, f, sc, sw, rc, rw, "visco", visco.relaxation(a["f0"], a["dt"]))
     return vx.numpy()[:, 0, :]
 
 
@@ -94,15 +91,9 @@ def test_reference_attenuates_as_the_standard_linear_solid():
 
 
 # ---- 3: visco.materials and its companions on CPU float64 ----------------------------------------------------------------
-def _model(nz=5, nx=6, seed=0, water=1):
-    rng = np.random.default_rng(seed)
-    vp = 2000 + 1000 * rng.random((nz, nx))
-    vs = vp * (0.4 + 0.2 * rng.random((nz, nx)))
-    rho = 1800 + 600 * rng.random((nz, nx))
-    qp = 20 + 180 * rng.random((nz, nx))
-    qs = 10 + 90 * rng.random((nz, nx))
-    vs[:water] = 0.0
-    return [torch.tensor(a, dtype=torch.float64) for a in (vp, vs, rho, qp, qs)]
+def _model(*a, **kw):
+    """vp, vs, rho, qp in [20, 200], qs in [10, 100]"""
+    return seeded_model((20, 180), (10, 90), *a, **kw)
 
 
 def test_materials_without_attenuation_are_the_elastic_planes():
@@ -248,13 +239,13 @@ def test_reference_gradient_is_its_central_difference(fs):
     def g_of(rvx, rvz):
         r = np.random.default_rng(4)
         return [r.standard_normal(a.shape) * np.abs(a).max() for a in (rvx, rvz)]
-    rvx, rvz, gm, gf = R.gradients(mat8, c["pz"], c["px"], c["f"], *geo, g_of, None, relax, **kw)
+    rvx, rvz, gm, gf = R.gradients(mat8, c["pz"], c["px"], c["f"], *geo, g_of, None, "visco", relax, **kw)
     g = g_of(rvx, rvz)
     dmat = 0.01 * rng.standard_normal(mat8.shape) * mat8
     df = 0.01 * rng.standard_normal(c["f"].shape) * np.abs(c["f"]).max()
     assert all(np.abs(dmat[k]).max() > 0 and np.abs(gm[k]).max() > 0 for k in range(8))
     for what, dm, dff, lhs in (("mat", dmat, None, float((gm * dmat).sum())), ("f", 0 * dmat, df, float((gf * df).sum()))):
-        J = R.jvp(mat8, dm, c["pz"], c["px"], c["f"], dff, *geo, relax, eps=1e-3, **kw)
+        J = R.jvp(mat8, dm, c["pz"], c["px"], c["f"], dff, *geo, "visco", relax, eps=1e-3, **kw)
         rhs = float((J[0] * g[0]).sum() + (J[1] * g[1]).sum())
         err = abs(lhs - rhs) / max(abs(lhs), abs(rhs))
         print("<grad_%s, d> = %.12e, <g, J d> by central difference = %.12e, relative difference %.2e" % (what, lhs, rhs, err))
@@ -265,21 +256,7 @@ def test_reference_gradient_is_its_central_difference(fs):
 def test_visco_struct_layouts_match_header(tmp_path):
     from physicsbasedfwi2_amd import _lib
     structs = {"mifwi_visco_desc": _lib.ViscoDesc, "mifwi_visco_layout": _lib.ViscoLayout}
-    lines = ['#include <stdio.h>', '#include <stddef.h>', '#include "mifwi.h"', 'int main(void) {']
-    for cname, cls in structs.items():
-        lines.append('printf("%s %%zu\\n", sizeof(%s));' % (cname, cname))
-        for fname, _ in cls._fields_:
-            lines.append('printf("%s.%s %%zu\\n", offsetof(%s, %s));' % (cname, fname, cname, fname))
-    lines.append("return 0; }")
-    src = tmp_path / "abi.c"
-    src.write_text("\n".join(lines))
-    exe = tmp_path / "abi"
-    subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), "-o", str(exe), str(src)])
-    got = dict(l.split() for l in subprocess.check_output([str(exe)], text=True).splitlines())
-    for cname, cls in structs.items():
-        assert int(got[cname]) == ctypes.sizeof(cls), cname
-        for fname, _ in cls._fields_:
-            assert int(got["%s.%s" % (cname, fname)]) == getattr(cls, fname).offset, (cname, fname)
+    check_struct_layouts(structs, tmp_path)
     assert ctypes.sizeof(_lib.ViscoDesc) == 14 * 4
     assert [n for n, _ in _lib.ViscoDesc._fields_] == [n for n, _ in _lib.VtiDesc._fields_] + ["relax_a", "relax_b"]
     # the elastic and VTI descriptors and the version stay

@@ -1,303 +1,42 @@
-"""The VTI propagator on the GPU (physicsbasedfwi2_amd.vti, mifwi_vti_*) against its yardstick tests/vti_reference.py
-(float64, pinned to the fp64 C oracle in the isotropic limit by tests/test_vti_host.py) and against today's isotropic
-kernels.
-
-Shapes: A = the default 44 x 60 x 120 steps case (15 groups: less than one column block, a partial tile in z), B = 37 x 150,
-3 shots, 50 steps (three column blocks with the last partial, nx no multiple of 4).  Both with an 8-cell C-PML, A also
-without a layer and with a free surface; stencil orders 2 and 4.  Inputs are rounded to f32 first (what the device computes
-with).  Bounds: 2e-6 rel-L2 for an f32 recursion against its fp64 reference (the project's bound; measured 6.1e-7 on the
-isotropic kernels), 2e-5 for gradients summed in another order, and for the anisotropic gradients max(2e-5, 4 E_iso) with
-E_iso the error of today's isotropic kernels against the same reference in the isotropic limit on the same geometry,
-measured in the same test and printed.  Every reference result is computed once per case and left unchanged.
-Measured on the MI355X: traces 7.2e-8 ... 5.0e-7, gradients <= 1.1e-6, E_iso 5.4e-8 ... 8.5e-7, Born 1.9e-7 ... 1.8e-6 (the
-largest on B at order 2, whose 50 steps record only the precursor of the wave), identities <= 7.9e-6."""
+"""What the VTI propagator (physicsbasedfwi2_amd.vti, mifwi_vti_*) has of its own on the GPU: Thomsen's kinematics on the
+kernels, PHYSICS = 3 of the pyapi_denise shim and the refusals of the C entry points.  The isotropic limit and the parity with
+the float64 reference keep their names here and run the checks of tests/psv_media.py that the viscoelastic medium runs too
+(shapes, bounds and what was measured: there and in tests/test_psv_media_gpu.py, which has Born and the driver forms)."""
 import ctypes
 
 import numpy as np
 import pytest
 import torch
 
-import vti_reference as R
-from cases import elastic_case, rel_l2
+import psv_media as M
+import psv_reference as R
+from cases import rel_l2
+from psv_media import CASES, TOL_TRACE, dev as _dev
 
 pytestmark = pytest.mark.gpu
-CASES = {"A": dict(), "A_fw0": dict(fw=0), "A_fs": dict(free_surface=True), "B": dict(nz=37, nx=150, ns=3, nt=50)}
-PER_STEP = {"MIFWI_EL_CLUSTER": "0", "MIFWI_EL_CLUSTER_ADJ": "0", "MIFWI_EL_FUSED": "0"}
-PLANES = ("c13", "c11", "c44", "bx", "bz", "c33")
-ISO_OF = {"c13": "L", "c11": "M", "c33": "M", "c44": "mu", "bx": "bx", "bz": "bz", "f": "f"}
-TOL_TRACE, TOL_SUM = 2e-6, 2e-5
-WATER = 6
-_cache = {}
+VTI = M.MEDIA["vti"]
 
 
-def _f32(a):
-    return np.asarray(a, dtype=np.float32).astype(np.float64)
+@pytest.fixture(autouse=True)
+def _no_fallback():
+    yield from M.no_fallback()
 
 
-def _case(name):
-    """The elastic case with its inputs rounded to f32, seeded smooth epsilon in [0, 0.25] and delta in [-0.1, 0.15] over
-    the solid (0 in the water rows), the six VTI planes of vti.materials (CPU float64, then rounded), the isotropic
-    limit cat(mat5, mat5[1:2]) and seeded 1 % perturbations of the planes and of the source amplitudes."""
-    if name not in _cache:
-        cfg = CASES[name]
-        c = elastic_case(seed=83, **cfg)
-        nz, nx = c["vp"].shape
-        rng = np.random.default_rng(31)
-        z, x = np.meshgrid(np.arange(nz) / nz, np.arange(nx) / nx, indexing="ij")
-        ph = 2 * np.pi * rng.random(4)
-        eps = 0.125 + 0.125 * np.sin(2 * np.pi * (1.3 * z + 0.7 * x) + ph[0]) * np.cos(2 * np.pi * 0.9 * x + ph[1])
-        dl = 0.025 + 0.125 * np.sin(2 * np.pi * (0.8 * z - 1.1 * x) + ph[2]) * np.cos(2 * np.pi * 0.6 * z + ph[3])
-        eps[:WATER] = 0.0
-        dl[:WATER] = 0.0
-        assert 0 <= eps.min() and eps.max() <= 0.25 and -0.1 <= dl.min() and dl.max() <= 0.15
-        assert eps[WATER:].std() > 0.03 and dl[WATER:].std() > 0.03 and not c["vs"][:WATER].any()
-        c["eps"], c["delta"] = eps, dl
-        c["mat6"] = R.thomsen_mat6(_f32(c["vp"]), _f32(c["vs"]), _f32(c["rho"]), _f32(eps), _f32(dl), c["dt"], c["h"],
-                                   free_surface=bool(c["fs"]))
-        for k in ("mat", "mat6", "pz", "px", "f", "sw", "rw"):
-            c[k] = _f32(c[k])
-        c["mat6iso"] = np.concatenate([c["mat"], c["mat"][1:2]])
-        assert rel_l2(c["mat6"][1], c["mat6"][5]) > 0.05          # anisotropic for real
-        prng = np.random.default_rng(100)
-        c["dmat6"] = _f32(0.01 * prng.standard_normal(c["mat6"].shape) * c["mat6"])
-        c["df"] = _f32(0.01 * prng.standard_normal(c["f"].shape) * np.abs(c["f"]).max())
-        for v in c.values():
-            if isinstance(v, np.ndarray):
-                v.setflags(write=False)
-        _cache[name] = c
-    return _cache[name]
-
-
-def _g_of(rvx, rvz):
-    """The adjoint source of the gradient tests: seeded noise at the size of each trace set."""
-    rng = np.random.default_rng(12)
-    return [_f32(rng.standard_normal(a.shape) * np.abs(a).max()) for a in (rvx, rvz)]
-
-
-def _geo(c):
-    return c["sc"], c["sw"], c["rc"], c["rw"]
-
-
-def _ref(name, order, which):
-    """The reference on ``which`` = "mat6" / "mat6iso": traces, the adjoint source built from them, gradients."""
-    key = ("ref", name, order, which)
-    if key not in _cache:
-        c = _case(name)
-        rvx, rvz, g6, gf = R.gradients(c[which], c["pz"], c["px"], c["f"], *_geo(c), _g_of, None, free_surface=c["fs"],
-                                       fd_order=order)
-        out = dict(rvx=rvx, rvz=rvz, g=_g_of(rvx, rvz), f=gf)
-        out.update({p: g6[k] for k, p in enumerate(PLANES)})
-        for v in out.values():
-            for a in (v if isinstance(v, list) else [v]):
-                a.setflags(write=False)
-        _cache[key] = out
-    return _cache[key]
-
-
-def _ref_jvp(name, order):
-    key = ("jvp", name, order)
-    if key not in _cache:
-        c = _case(name)
-        d = R.jvp(c["mat6"], c["dmat6"], c["pz"], c["px"], c["f"], None, *_geo(c), eps=1e-5, free_surface=c["fs"],
-                  fd_order=order)
-        d.setflags(write=False)
-        _cache[key] = d
-    return _cache[key]
-
-
-def _dev(a):
-    a = np.asarray(a)
-    return torch.tensor(a, device="cuda:0", dtype=torch.int32 if a.dtype.kind == "i" else torch.float32)
-
-
-def _args(c, mat, f=None):
-    """(mat, f, pz, px, src_cell, src_w, rec_cell, rec_w, pml_width)"""
-    return [mat, _dev(c["f"]) if f is None else f] + [_dev(c[k]) for k in ("pz", "px", "sc", "sw", "rc", "rw")] + [c["fw"]]
-
-
-def _run(mod, c, mat_np, order, g=None, need_f=True, **kw):
-    """propagate (+ backward with the adjoint source ``g``) of ``mod`` = vti / elastic: traces, grad_mat, grad_f as float64."""
-    mat = _dev(mat_np).requires_grad_(g is not None)
-    f = _dev(c["f"]).requires_grad_(g is not None and need_f)
-    rvx, rvz = mod.propagate(*_args(c, mat, f), free_surface=bool(c["fs"]), fd_order=order, **kw)
-    if g is None:
-        return rvx, rvz
-    torch.autograd.backward([rvx, rvz], [_dev(a) for a in g])
-    return rvx.detach(), rvz.detach(), mat.grad.double().cpu().numpy(), (f.grad.double().cpu().numpy() if need_f else None)
-
-
-def _pair(a, b):
-    return torch.stack([a, b]).double().cpu().numpy()
-
-
-def _setenv(monkeypatch, env):
-    for k, v in env.items():
-        monkeypatch.setenv(k, v)
-
-
-def _dot(a, b):
-    return float((a.double() * b.double()).sum())
-
-
-def _close(a, b, tol, what):
-    print("%s: %.9e vs %.9e, |diff| / max = %.2e" % (what, a, b, abs(a - b) / max(abs(a), abs(b))))
-    assert abs(a - b) <= tol * max(abs(a), abs(b)), what
-
-
-# ---- 5: the isotropic limit at mat level --------------------------------------------------------------------------
+# ---- the isotropic limit at mat level, anisotropic parity: the shared checks --------------------------------------------
 @pytest.mark.parametrize("order", [2, 4])
 @pytest.mark.parametrize("form", ["default", "per_step"])
 @pytest.mark.parametrize("name", list(CASES))
 def test_isotropic_limit_is_the_elastic_propagator(monkeypatch, name, form, order):
-    from physicsbasedfwi2_amd import elastic, vti
-    _setenv(monkeypatch, PER_STEP if form == "per_step" else {})
-    c = _case(name)
-    g = _ref(name, order, "mat6iso")["g"]
-    evx, evz, eg, egf = _run(elastic, c, c["mat"], order, g)
-    vvx, vvz, vg, vgf = _run(vti, c, c["mat6iso"], order, g)
-    assert evx.abs().max() > 0 and evz.abs().max() > 0
-    assert torch.equal(vvx, evx) and torch.equal(vvz, evz)
-    want = {"L": eg[0], "mu": eg[2], "bx": eg[3], "bz": eg[4], "M": eg[1], "f": egf}
-    got = {"L": vg[0], "mu": vg[2], "bx": vg[3], "bz": vg[4], "M": vg[1] + vg[5], "f": vgf}
-    errs = {k: rel_l2(got[k], want[k]) for k in want}
-    print("vti(iso) vs elastic gradients rel-L2", {k: "%.2e" % v for k, v in errs.items()})
-    for k, v in errs.items():
-        assert np.abs(want[k]).max() > 0, k
-        assert v <= TOL_SUM, (k, v)
+    M.check_limit_is_the_elastic_propagator(VTI, monkeypatch, name, form, order)
 
 
-# ---- 6: anisotropic parity ------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("order", [2, 4])
 @pytest.mark.parametrize("name", list(CASES))
 def test_anisotropic_traces_and_gradients_match_the_reference(name, order):
-    from physicsbasedfwi2_amd import elastic, vti
-    c = _case(name)
-    iso, ref = _ref(name, order, "mat6iso"), _ref(name, order, "mat6")
-    # today's isotropic kernels against the same reference in the isotropic limit: the case's own error level
-    evx, evz, eg, egf = _run(elastic, c, c["mat"], order, iso["g"])
-    e_tr = rel_l2(_pair(evx, evz), np.stack([iso["rvx"], iso["rvz"]]))
-    e_iso = {"L": rel_l2(eg[0], iso["c13"]), "M": rel_l2(eg[1], iso["c11"] + iso["c33"]), "mu": rel_l2(eg[2], iso["c44"]),
-             "bx": rel_l2(eg[3], iso["bx"]), "bz": rel_l2(eg[4], iso["bz"]), "f": rel_l2(egf, iso["f"])}
-    print("E_iso %s order %d: traces %.2e, gradients %s" % (name, order, e_tr, {k: "%.2e" % v for k, v in e_iso.items()}))
-    assert e_tr <= TOL_TRACE, "the isotropic kernels miss the trace bound on this case: not a case for this test"
-    vvx, vvz, vg, vgf = _run(vti, c, c["mat6"], order, ref["g"])
-    assert np.abs(ref["rvx"]).max() > 0 and np.abs(ref["rvz"]).max() > 0
-    want_tr, iso_tr, got_tr = np.stack([ref["rvx"], ref["rvz"]]), np.stack([iso["rvx"], iso["rvz"]]), _pair(vvx, vvz)
-    shots = range(want_tr.shape[2])
-    # another medium: some shot's traces move by more than a percent (a shot shot and recorded in the water sees none of it)
-    assert max(rel_l2(want_tr[:, :, s], iso_tr[:, :, s]) for s in shots) > 0.01
-    err = rel_l2(got_tr, want_tr)
-    print("vti traces vs reference: rel-L2 %.2e, shot by shot %s"
-          % (err, ["%.2e" % rel_l2(got_tr[:, :, s], want_tr[:, :, s]) for s in shots]))
-    assert err <= TOL_TRACE
-    got = dict(zip(PLANES, vg), f=vgf)
-    r0 = 1 if c["fs"] else 0               # c33 of the surface row never acts (szz = 0 there): both gradients are 0
-    for k in got:
-        want = ref[k]
-        if k == "c33" and c["fs"]:
-            assert not got[k][0].any() and not want[0].any()
-            e = rel_l2(got[k][r0:], want[r0:])
-        else:
-            e = rel_l2(got[k], want)
-        tol = max(TOL_SUM, 4 * e_iso[ISO_OF[k]])
-        print("gradient %-3s rel-L2 %.2e (bound %.2e)" % (k, e, tol))
-        assert np.abs(want).max() > 0, k
-        assert e <= tol, (k, e, tol)
+    M.check_traces_and_gradients_match_the_reference(VTI, name, order)
 
 
-# ---- 7: Born ----------------------------------------------------------------------------------------------------------
-def _born(c, order, dmat=None, df=None, **kw):
-    from physicsbasedfwi2_amd import vti
-    a = _args(c, _dev(c["mat6"]))
-    return vti.born(a[0], _dev(c["dmat6"]) if dmat is None else dmat, *a[1:], df=df, free_surface=bool(c["fs"]),
-                    fd_order=order, **kw)
-
-
-@pytest.mark.parametrize("order", [2, 4])
-@pytest.mark.parametrize("name", list(CASES))
-def test_born_is_the_directional_derivative_of_the_reference(name, order):
-    c = _case(name)
-    want = _ref_jvp(name, order)
-    _, _, dvx, dvz = _born(c, order)
-    got = _pair(dvx, dvz)
-    err = rel_l2(got, want)
-    print("vti.born vs central difference of the reference, %s order %d: rel-L2 %.3e" % (name, order, err))
-    assert np.abs(want).max() > 0
-    assert err <= TOL_TRACE
-
-
-@pytest.mark.parametrize("name", ["A", "A_fs", "B"])
-def test_born_background_dot_products_and_gauss_newton(name):
-    from physicsbasedfwi2_amd import vti
-    c = _case(name)
-    order = 4
-    mat6 = _dev(c["mat6"])
-    rvx, rvz, dvx, dvz = _born(c, order, df=_dev(c["df"]))
-    pvx, pvz = _run(vti, c, c["mat6"], order)
-    assert torch.equal(rvx, pvx) and torch.equal(rvz, pvz)                         # the background traces
-    # <J (dm, df), g> = <dm, J^T g> + <df, J^T g>
-    g = [_dev(a) for a in _g_of(rvx.cpu().numpy(), rvz.cpu().numpy())]
-    _, _, gm, gf = _run(vti, c, c["mat6"], order, [a.cpu().numpy() for a in g])
-    _, _, mvx, mvz = _born(c, order)                                              # dm alone
-    _close(_dot(mvx, g[0]) + _dot(mvz, g[1]), float((gm * c["dmat6"]).sum()), TOL_SUM, "<J dm, g> vs <dm, J^T g>")
-    zero = torch.zeros_like(mat6)
-    _, _, fvx, fvz = _born(c, order, dmat=zero, df=_dev(c["df"]))                 # df alone
-    _close(_dot(fvx, g[0]) + _dot(fvz, g[1]), float((gf * c["df"]).sum()), TOL_SUM, "<J df, g> vs <df, J^T g>")
-    assert rel_l2(_pair(mvx + fvx, mvz + fvz), _pair(dvx, dvz)) <= TOL_TRACE       # J is linear
-    # Gauss-Newton: <H a, b> = <a, H b>
-    a = _args(c, mat6)
-    other = _dev(_f32(0.01 * np.random.default_rng(5).standard_normal(c["mat6"].shape) * c["mat6"]))
-    ha, hvx, hvz = vti.gauss_newton_product(a[0], _dev(c["dmat6"]), *a[1:], free_surface=bool(c["fs"]), fd_order=order)
-    hb, _, _ = vti.gauss_newton_product(a[0], other, *a[1:], free_surface=bool(c["fs"]), fd_order=order)
-    assert ha.shape == mat6.shape and torch.equal(hvx, mvx) and torch.equal(hvz, mvz)
-    _close(_dot(ha, other), _dot(hb, _dev(c["dmat6"])), TOL_SUM, "<H a, b> vs <a, H b>")
-    _close(_dot(ha, _dev(c["dmat6"])), _dot(mvx, mvx) + _dot(mvz, mvz), TOL_SUM, "<H a, a> vs |J a|^2")
-
-
-# ---- 8: driver forms -------------------------------------------------------------------------------------------------
-def _step_bytes(c, ns=None):
-    from physicsbasedfwi2_amd import vti
-    nz, nx = c["vp"].shape
-    nt, n, nsrc = c["f"].shape
-    plan = vti.VtiPlan(nz, nx, nt, ns or n, nsrc, c["rc"].shape[1], 1, c["fw"], 0, free_surface=c["fs"])
-    assert plan.cluster_slabs(False) == 0 and plan.cluster_slabs(True) == 0
-    b = 4 * plan.layout.snap_step_elems
-    plan.close()
-    return b
-
-
-@pytest.mark.parametrize("name", ["A", "B"])
-def test_checkpoints_groups_chunks_and_repeats(name):
-    from physicsbasedfwi2_amd import vti
-    c = _case(name)
-    order = 4
-    nt = c["f"].shape[0]
-    g = _ref(name, order, "mat6")["g"]
-    base = _run(vti, c, c["mat6"], order, g)
-    again = _run(vti, c, c["mat6"], order, g)
-    host = lambda t: np.asarray(t.cpu() if torch.is_tensor(t) else t)
-    for a, b in zip(base, again):                                                  # a repeated call: the same bits
-        assert np.array_equal(host(a), host(b))
-    # time checkpoints: segments of 7 steps
-    seg = _run(vti, c, c["mat6"], order, g, snapshot_budget=14 * _step_bytes(c) + 1)
-    assert nt > 3 * 7
-    for a, b in zip(base, seg):
-        assert np.array_equal(host(a), host(b))
-    # shots per gradient accumulator
-    for gs in (1, 2):
-        r = _run(vti, c, c["mat6"], order, g, shots_per_group=gs)
-        assert torch.equal(r[0], base[0]) and torch.equal(r[1], base[1])
-        errs = [rel_l2(r[2][k], base[2][k]) for k in range(6)] + [rel_l2(r[3], base[3])]
-        print("shots_per_group %d vs 0: gradients rel-L2 %s" % (gs, ["%.1e" % e for e in errs]))
-        assert max(errs) <= TOL_SUM
-    # Born in shot chunks of one
-    whole = _born(c, order, df=_dev(c["df"]))
-    chunked = _born(c, order, df=_dev(c["df"]), snapshot_budget=int(1.5 * nt * _step_bytes(c, 1)))
-    for a, b in zip(whole, chunked):
-        assert torch.equal(a, b)
-
-
-# ---- 9: the physics pin on the kernels --------------------------------------------------------------------------------
+# ---- the physics pin on the kernels --------------------------------------------------------------------------------
 def test_kernels_travel_at_the_thomsen_velocities():
     from physicsbasedfwi2_amd import vti
 
@@ -307,7 +46,7 @@ def test_kernels_travel_at_the_thomsen_velocities():
     R.pin_check(run)
 
 
-# ---- 10: the pyapi_denise shim ----------------------------------------------------------------------------------------
+# ---- the pyapi_denise shim ----------------------------------------------------------------------------------------
 def _denise(tmp_path, physics):
     import physicsbasedfwi2_amd.compat.pyapi_denise as api
     rng = np.random.default_rng(3)
@@ -399,7 +138,7 @@ def test_shim_physics3_isotropic_limit_gradients_and_refusals(tmp_path, monkeypa
         d1.get_thomsen_gradients()
 
 
-# ---- 11: the C entry points ---------------------------------------------------------------------------------------------
+# ---- the C entry points ---------------------------------------------------------------------------------------------
 def test_c_entry_points_refuse_nulls_bad_ranges_and_born_with_a_force_source():
     from physicsbasedfwi2_amd import _lib, vti
     lib = _lib.load()

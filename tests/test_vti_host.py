@@ -1,18 +1,16 @@
-"""The VTI propagator's host side without a GPU: the yardstick (tests/vti_reference.py) against the fp64 C oracle in the
+"""The VTI propagator's host side without a GPU: the yardstick (tests/psv_reference.py) against the fp64 C oracle in the
 isotropic limit and against Thomsen kinematics, ``vti.materials`` / ``vti.max_velocity`` on CPU float64, and the C ABI
 of the ``mifwi_vti_*`` entry points."""
 import ctypes
-import os
-import subprocess
 
 import numpy as np
 import pytest
 import torch
 
-import vti_reference as R
+import psv_reference as R
 from cases import elastic_case, rel_l2
+from psv_media import check_struct_layouts, seeded_model
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 _cache = {}
 
 
@@ -31,7 +29,7 @@ def _iso(fs, order):
         g = [rng.standard_normal(a.shape) * np.abs(a).max() for a in (ovx, ovz)]
         gm, gf = o64.elastic_backward(c["mat"], c["pz"], c["px"], *geo, g[0], g[1], S, free_surface=c["fs"], fd_order=order)
         mat6 = np.concatenate([c["mat"], c["mat"][1:2]])
-        ref = R.gradients(mat6, c["pz"], c["px"], c["f"], *geo, g[0], g[1], free_surface=c["fs"], fd_order=order)
+        ref = R.gradients(mat6, c["pz"], c["px"], c["f"], *geo, g[0], g[1], "vti", free_surface=c["fs"], fd_order=order)
         _cache[key] = (ovx, ovz, gm, gf), ref
     return _cache[key]
 
@@ -58,20 +56,14 @@ def test_reference_is_the_oracle_in_the_isotropic_limit(fs, order):
 def test_reference_travels_at_the_thomsen_velocities():
     def run(mat6, pz, px, f, sc, sw, rc, rw):
         with torch.no_grad():
-            return [a.numpy() for a in R.forward(mat6, pz, px, f, sc, sw, rc, rw)]
+            return [a.numpy() for a in R.forward(mat6, pz, px, f, sc, sw, rc, rw, "vti")]
     R.pin_check(run)
 
 
 # ---- 3: vti.materials / max_velocity on CPU float64 --------------------------------------------------------------------
-def _model(nz=5, nx=6, seed=0, water=1):
-    rng = np.random.default_rng(seed)
-    vp = 2000 + 1000 * rng.random((nz, nx))
-    vs = vp * (0.4 + 0.2 * rng.random((nz, nx)))
-    rho = 1800 + 600 * rng.random((nz, nx))
-    eps = 0.25 * rng.random((nz, nx))
-    dl = -0.1 + 0.25 * rng.random((nz, nx))
-    vs[:water] = 0.0
-    return [torch.tensor(a, dtype=torch.float64) for a in (vp, vs, rho, eps, dl)]
+def _model(*a, **kw):
+    """vp0, vs0, rho, epsilon in [0, 0.25], delta in [-0.1, 0.15]"""
+    return seeded_model((0.0, 0.25), (-0.1, 0.25), *a, **kw)
 
 
 def test_materials_obey_thomsens_definitions():
@@ -164,21 +156,7 @@ def test_max_velocity_bounds_the_christoffel_qp_velocity():
 def test_vti_struct_layouts_match_header(tmp_path):
     from physicsbasedfwi2_amd import _lib
     structs = {"mifwi_vti_desc": _lib.VtiDesc, "mifwi_vti_layout": _lib.VtiLayout}
-    lines = ['#include <stdio.h>', '#include <stddef.h>', '#include "mifwi.h"', 'int main(void) {']
-    for cname, cls in structs.items():
-        lines.append('printf("%s %%zu\\n", sizeof(%s));' % (cname, cname))
-        for fname, _ in cls._fields_:
-            lines.append('printf("%s.%s %%zu\\n", offsetof(%s, %s));' % (cname, fname, cname, fname))
-    lines.append("return 0; }")
-    src = tmp_path / "abi.c"
-    src.write_text("\n".join(lines))
-    exe = tmp_path / "abi"
-    subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), "-o", str(exe), str(src)])
-    got = dict(l.split() for l in subprocess.check_output([str(exe)], text=True).splitlines())
-    for cname, cls in structs.items():
-        assert int(got[cname]) == ctypes.sizeof(cls), cname
-        for fname, _ in cls._fields_:
-            assert int(got["%s.%s" % (cname, fname)]) == getattr(cls, fname).offset, (cname, fname)
+    check_struct_layouts(structs, tmp_path)
     assert ctypes.sizeof(_lib.VtiDesc) == 12 * 4
     assert [n for n, _ in _lib.VtiDesc._fields_] == [n for n, _ in _lib.ElasticDesc._fields_
                                                      if n not in ("record_pressure", "snapshot_format")]
