@@ -26,32 +26,24 @@
 // the whole time loop in one launch instead (mifwi_elastic_cluster.h); point forces (source_type 1 / 2) and
 // the opt-in fused V+S launch (el_step_fused) live on the per-step path only.
 // VTI (mifwi_vti_*): the same scheme with c11, c13, c33, c44 for lambda + 2 mu, lambda, mu - one more material plane (M_C33), a
-// compile-time variant of el_step_s, el_adj_s / stage_E and el_finalize on the per-step path; with c33 == c11 the same bits.
+// compile-time variant of el_step_s, el_adj_s / stage_E and finalize_groups on the per-step path; with c33 == c11 the same bits.
 // Viscoelastic (mifwi_visco_*): one relaxation mechanism - three memory variables behind the five fields of a shot, three more
 // material planes; a compile-time VISCO variant of el_step_s, el_adj_s / stage_E, el_adj_v (which advances the adjoint memory
-// variables) and el_finalize on the per-step path; with the three planes zero the same bits.
+// variables) and finalize_groups on the per-step path; with the three planes zero the same bits.
+// What this scheme shares with the fluid one below the cell arithmetic (stencil and C-PML primitives, strip and tile
+// helpers, build_tile_taps / sample_force / finalize_groups, the plan's grid geometry) is in mifwi_stagger.h.
 // Arithmetic = the explicit fmaf chain of oracle/elastic.c (build with -ffp-contract=off).
 #include "mifwi_cluster_host.h"
-#include "mifwi_host.h"
+#include "mifwi_stagger.h"
 
-#include <algorithm>
 #include <cmath>
 #include <cstdlib>
 
 namespace {
 
-constexpr int kThreads = 256;
 #ifndef MIFWI_EL_MINWAVES
 #define MIFWI_EL_MINWAVES 1
 #endif
-// staggered-grid first-derivative weights (mifwi_elastic_desc.fd_order): Taylor order 4 = (9/8, -1/24),
-// order 2 = (1, 0) - the same four-point form, so every kernel serves both
-struct FdK { float c1, c2; };
-inline FdK fd_weights(int order)
-{
-    return order == 2 ? FdK{1.0f, 0.0f} : FdK{(float)(9.0 / 8.0), (float)(-1.0 / 24.0)};
-}
-
 enum { F_VX = 0, F_VZ = 1, F_SXX = 2, F_SZZ = 3, F_SXZ = 4 };
 enum { M_L = 0, M_M = 1, M_MU = 2, M_BX = 3, M_BZ = 4 };
 // VTI variant (mifwi_vti_*): the same planes with c13 at M_L, c11 at M_M, c44_xz at M_MU, and c33 appended as a sixth plane
@@ -60,7 +52,6 @@ enum { M_C33 = 5 };
 // behind the five unrelaxed ones: R2 = pi_r tau_p - 2 mu_r tau_s, R1 = pi_r tau_p, mu_r tau_s at the sxz node (all times dt/h)
 enum { F_RXX = 5, F_RZZ = 6, F_RXZ = 7 };
 enum { M_RL = 5, M_RM = 6, M_RMU = 7 };
-enum { PA = 0, PB = 1, PK = 2, PAH = 3, PBH = 4, PKH = 5 };
 // psi index: x strips hold (0: d1 sxx_x @half, 1: d3 sxz_x @int, 2: e1 vx_x @int, 3: e4 vz_x @half)
 //            z strips hold (0: d2 sxz_z @int, 1: d4 szz_z @half, 2: e2 vz_z @int, 3: e3 vx_z @half)
 
@@ -102,11 +93,6 @@ struct ElParams {
     float rel_a, rel_b;          // viscoelastic plans: r <- a r - b q per step, a = (2 - eta) / (2 + eta), b = 2 eta / (2 + eta)
 };
 
-__device__ __forceinline__ float comp(const float4 &v, int c)
-{
-    return c == 0 ? v.x : c == 1 ? v.y : c == 2 ? v.z : v.w;
-}
-__device__ __forceinline__ float4 ld4(const float *p) { return *reinterpret_cast<const float4 *>(p); }
 // uniform base + 32-bit lane offset (in floats): selects the `global_* v_off, s[base]` addressing form - no 64-bit
 // vector address per plane and lane
 __device__ __forceinline__ const float *el_at(const float *base, unsigned off)
@@ -124,31 +110,6 @@ __device__ __forceinline__ int f_opaque(int x)
     asm volatile("" : "+v"(x));
     return x;
 }
-__device__ __forceinline__ float2 ld2(const float *p) { return *reinterpret_cast<const float2 *>(p); }
-__device__ __forceinline__ void st4(float *p, const float4 &v) { *reinterpret_cast<float4 *>(p) = v; }
-__device__ __forceinline__ float dfw(const FdK &K, float fm1, float f0, float f1, float f2)   // Dp at "0"
-{
-    return fmaf(K.c1, f1 - f0, K.c2 * (f2 - fm1));
-}
-__device__ __forceinline__ float dbw(const FdK &K, float fm2, float fm1, float f0, float f1)  // Dm at "0"
-{
-    return fmaf(K.c1, f0 - fm1, K.c2 * (f1 - fm2));
-}
-// forward C-PML: psi <- b psi + a d ; returns d*ik + psi
-__device__ __forceinline__ float pml(float &psi, float a, float b, float ik, float d)
-{
-    psi = fmaf(b, psi, a * d);
-    return fmaf(d, ik, psi);
-}
-// transposed C-PML: P = psib + db ; returns ik*db + a*P ; psib <- b*P
-__device__ __forceinline__ float pmlT(float psib, float a, float b, float ik, float db,
-                                      float &psib_new)
-{
-    const float P = psib + db;
-    psib_new = b * P;
-    return fmaf(ik, db, a * P);
-}
-
 // ---- bf16 snapshot planes (plan snapshot_format = 1): the five per-step planes the material gradient needs are
 // rounded to bf16 (round to nearest even, v_cvt_pk_bf16_f32) on their way to memory and widened again by the
 // adjoint: 10 instead of 20 B per cell-step each way.  Arithmetic stays f32.  Layout of one shot-step, in
@@ -201,43 +162,20 @@ __device__ __forceinline__ void bf_widen(const BfPlanes &q, float4 &S1, float4 &
 }
 
 // Offset (floats) of group g of row j inside a snapshot plane.  Row-major [nz][gp] (the layout the single-launch
-// kernels share), or - per-step family, plans without a single-launch kernel - blocked by columns of 16 groups:
-// [g / 16][j][64 floats].  Every kernel of the family works on tiles 16 groups wide, so a tile row is 256 contiguous,
-// 256-byte aligned bytes of the plane and consecutive rows follow each other: whole 128-byte lines on the way out
-// and on the way back in.  (Row-major rows are gp * 4 bytes apart, not a multiple of 128 in general: a 256-byte tile
-// row straddles three lines, and the adjoint read 33 B per cell-step of the 20 B snapshot stream.)
+// kernels share), or - per-step family, plans without a single-launch kernel - blocked by columns of 16 groups
+// (snap_cell_blocked).
 __device__ __forceinline__ unsigned snap_cell(const ElParams &p, int j, int g)
 {
-    return p.sblk ? ((unsigned)(g >> 4) * (unsigned)p.nz + (unsigned)j) * 64u + 4u * (unsigned)(g & 15)
-                  : (unsigned)j * p.gp + 4u * (unsigned)g;
+    return p.sblk ? snap_cell_blocked(p.nz, j, g) : (unsigned)j * p.gp + 4u * (unsigned)g;
 }
 
-// x-strip column offset of group g (or -1)
-__device__ __forceinline__ int xstrip(const ElParams &p, int g)
-{
-    if (p.W == 0) return -1;
-    const int c0 = 4 * g;
-    if (c0 < p.wl) return c0;
-    if (c0 >= p.xr0) return p.wl + (c0 - p.xr0);
-    return -1;
-}
-// z-strip row index of row j (or -1)
-__device__ __forceinline__ int zstrip(const ElParams &p, int j)
-{
-    if (p.W == 0) return -1;
-    if (j < p.W) return j;
-    if (j >= p.nz - p.W) return j - (p.nz - 2 * p.W);
-    return -1;
-}
-
-// Workgroups are dealt to the 8 XCDs round-robin in launch order, each XCD with an L2 of its own: with
-// the plain blockIdx -> tile map, neighbouring tiles never share an L2 and every halo row/column is
-// fetched from memory again.  Remap (a bijection on the launch grid):
-//  * z slices (shots / shot groups) in full sets of eight: XCD c takes the slices c, c+8, ... WHOLE, walking
+// XCD-aware tile order (p.xcd; a bijection on the launch grid in every mode).  3: tile-major over the shots of the launch
+// (xcd_tile_major_index).  Otherwise:
+//  * 2, z slices (shots / shot groups) in full sets of eight: XCD c takes the slices c, c+8, ... WHOLE, walking
 //    each in row-major tile order - every halo a tile reads was fetched by the same L2 one tile row earlier
 //    (measured on 350x1700, 8 shots per launch: the halo rows of a 2.7-tile-row run per XCD came from the
 //    other XCDs' runs, i.e. from beyond L2);
-//  * the remaining slices: each XCD walks one contiguous, row-major run of the (x, y) tiles of the slice.
+//  * 1 and the remaining slices of 2: each XCD walks one contiguous, row-major run of the (x, y) tiles of the slice.
 __device__ __forceinline__ void xcd_tile(const ElParams &p, int &bx, int &by, int &bz)
 {
     bx = (int)blockIdx.x; by = (int)blockIdx.y; bz = (int)blockIdx.z;
@@ -246,16 +184,7 @@ __device__ __forceinline__ void xcd_tile(const ElParams &p, int &bx, int &by, in
     const unsigned z8 = gridDim.z & ~7u;          // p.xcd == 2: whole slices per XCD
     unsigned T;
     if (p.xcd == 3) {
-        // tile-major, slice-minor: the sequence (tile 0: slices 0 .. gz-1), (tile 1: ...), ... is cut into eight
-        // contiguous pieces, one per XCD - all shots of the launch pass through a tile back to back on ONE XCD, so the
-        // tile's material planes come from memory once per launch, not once per shot (grids whose five planes outgrow the
-        // L2s: 60 MB at 1000x3000), and neighbouring tiles still follow each other on that XCD
-        const unsigned gz = gridDim.z, total = n2 * gz;
-        const unsigned L = blockIdx.x + gx * blockIdx.y + n2 * blockIdx.z;
-        const unsigned c = L & 7u, idx = L >> 3, q = total >> 3, r = total & 7u;
-        const unsigned e = c * q + (c < r ? c : r) + idx;
-        T = e / gz;
-        bz = (int)(e - T * gz);
+        T = xcd_tile_major_index(bz);
     } else if (p.xcd == 2 && blockIdx.z < z8) {
         const unsigned L = blockIdx.x + gx * blockIdx.y + n2 * blockIdx.z;
         const unsigned c = L & 7u, idx = L >> 3, zl = idx / n2;
@@ -666,22 +595,8 @@ __global__ __launch_bounds__(kThreads, MIFWI_EL_MINWAVES) void el_step_s(const E
 }
 
 // ================================================================================================
-// adjoint launches.  Tile = TZ x (4*GXO) owned cells, staged on (TZ+4) x 4*(GXO+2) in LDS.
+// adjoint launches, on the tile of mifwi_stagger.h (ATZ x 4*AGO owned cells, staged on ASZ x ASX in LDS)
 // ================================================================================================
-constexpr int ATZ = 16;          // owned rows
-constexpr int AGO = 16;          // owned groups per row: a quarter wave reads one contiguous LDS row
-constexpr int AGX = AGO + 2;     // staged groups per row (1 halo group each side)
-constexpr int ASZ = ATZ + 4;     // staged rows
-constexpr int ASX = 4 * AGX;     // staged columns (72 floats: consecutive rows start 8 banks apart)
-static_assert(ATZ * AGO == kThreads, "one owned 4-cell group per thread");
-
-// x stencils on the 8 values {L.z, L.w, C.x .. C.w, R.x, R.y} around an owned group
-struct Row8 { float v[8]; };
-__device__ __forceinline__ Row8 row8(const float *row, int cb)
-{
-    const float4 l = ld4(row + cb - 4), c = ld4(row + cb), r = ld4(row + cb + 4);
-    return Row8{{l.z, l.w, c.x, c.y, c.z, c.w, r.x, r.y}};
-}
 
 // staged coordinates of the halo group a thread stages besides its own group (threads 0..kHalo-1):
 // the two rows above and below the tile, then the left/right halo group of every owned row
@@ -773,41 +688,6 @@ __device__ __forceinline__ void stage_E(const ElParams &p, int s, int j, int g, 
     }
     E1 = make_float4(e1[0], e1[1], e1[2], e1[3]); E2 = make_float4(e2[0], e2[1], e2[2], e2[3]);
     E3 = make_float4(e3[0], e3[1], e3[2], e3[3]); E4 = make_float4(e4[0], e4[1], e4[2], e4[3]);
-}
-
-// Receiver taps (adjoint sources) of every tile of el_adj_s, one block per shot: start[s][tile .. tile+1) indexes
-// list[s][], which holds tap numbers (receiver * ntap + tap) sorted by tile, ascending inside a tile.  Built once
-// per backward call; the time loop then injects v_bar += R^T g inside el_adj_s, by the tile that owns the cells
-// (workgroup-uniform branch, taken by the few tiles that hold receivers), instead of a launch of its own per step
-// and shot pass (4.7 us each: 5 % of a step where the passes are small, e.g. the chunks of a shot-chunked gradient).
-__global__ void el_build_tile_taps(const int *cell, int ntaps, int nx, int tx, int ntiles, int *start, int *cursor,
-                                   int *list)
-{
-    const int s = (int)blockIdx.x, t = (int)threadIdx.x, T = (int)blockDim.x;
-    start += (long long)s * (ntiles + 1); cursor += (long long)s * ntiles; list += (long long)s * ntaps;
-    cell += (long long)s * ntaps;
-    for (int k = t; k < ntiles; k += T) cursor[k] = 0;
-    __syncthreads();
-    auto tile_of = [&](int c) { const int j = c / nx, i = c - j * nx; return (j / ATZ) * tx + (i >> 2) / AGO; };
-    for (int e = t; e < ntaps; e += T)
-        if (cell[e] >= 0) atomicAdd(cursor + tile_of(cell[e]), 1);
-    __syncthreads();
-    if (t == 0) {
-        int run = 0;
-        for (int k = 0; k < ntiles; ++k) { start[k] = run; run += cursor[k]; cursor[k] = start[k]; }
-        start[ntiles] = run;
-    }
-    __syncthreads();
-    for (int e = t; e < ntaps; e += T)
-        if (cell[e] >= 0) list[atomicAdd(cursor + tile_of(cell[e]), 1)] = e;
-    __syncthreads();
-    for (int k = t; k < ntiles; k += T)                   // ascending tap order inside a tile (a few entries each)
-        for (int a = start[k] + 1; a < start[k + 1]; ++a) {
-            const int v = list[a];
-            int b = a - 1;
-            while (b >= start[k] && list[b] > v) { list[b + 1] = list[b]; --b; }
-            list[b + 1] = v;
-        }
 }
 
 // S^T:  E = C^T sigma_bar through the transposed C-PML;  v_bar -= stencils(E);  all five material-gradient
@@ -1209,26 +1089,6 @@ __global__ void el_inject_force(const ElParams p, int comp)
     }
 }
 
-// adjoint: grad_f[n] = sum w * v_bar[cell], sampled between S^T and V^T
-__global__ void el_sample_force(const ElParams p, int comp)
-{
-    const int idx = (int)(blockIdx.x * blockDim.x + threadIdx.x);     // over the p.gs shots of this pass
-    if (idx >= p.gs * p.nsmp) return;
-    const int s = p.s0 + idx / p.nsmp;
-    if (s >= p.nshot) return;
-    const int e = s * p.nsmp + idx % p.nsmp;
-    const float *v = p.fields + (long long)s * p.shot_stride + (comp == 1 ? F_VX : F_VZ) * (long long)p.field_stride;
-    float a = 0.f;
-    for (int t = 0; t < p.ntap_smp; ++t) {
-        const long long ee = (long long)e * p.ntap_smp + t;
-        const int cell = p.smp_cell[ee];
-        if (cell < 0) continue;
-        const int j = cell / p.nx, i = cell - j * p.nx;
-        a = fmaf(p.smp_w[ee], v[(unsigned)(j + 2) * p.pitch + 4 + i], a);
-    }
-    p.smp_out0[e] = a;
-}
-
 // ---- pressure receivers (desc.record_pressure): launches of their own on the per-step path -----------------
 // forward: rec_p[n] = sum w (sxx + szz)[cell] after S and the source term, for the p.gs shots of this pass
 __global__ void el_sample_pressure(const ElParams p)
@@ -1271,36 +1131,6 @@ __global__ void el_inject_pressure(const ElParams p)
     atomicAdd(fl + F_SZZ * (long long)p.field_stride + off, a);
 }
 
-// grad[k][cell] = sum over shot groups of acc[group][k][cell]; grad is row-major [5][nz][gp] (the C-ABI's layout), the
-// accumulator planes are `aplane` floats apart and column-blocked when sblk (snap_cell)
-template <int NP>
-__device__ __forceinline__ void el_finalize_body(const float *acc, int ngroups, int nz, int gp, long long aplane, int sblk, float *grad)
-{
-    const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x, ncell = (long long)nz * gp;
-    if (idx >= NP * ncell) return;
-    const int k = (int)(idx / ncell);
-    const long long c = idx - (long long)k * ncell;
-    const int j = (int)(c / gp), i = (int)(c - (long long)j * gp), g = i >> 2;
-    const long long off = sblk ? ((long long)(g >> 4) * nz + j) * 64 + 4 * (g & 15) + (i & 3) : c;
-    float a = 0.f;
-    for (int gidx = 0; gidx < ngroups; ++gidx) a += acc[((long long)gidx * NP + k) * aplane + off];
-    grad[idx] = a;
-}
-__global__ void el_finalize(const float *acc, int ngroups, int nz, int gp, long long aplane, int sblk, float *grad)
-{
-    el_finalize_body<5>(acc, ngroups, nz, gp, aplane, sblk, grad);
-}
-// VTI: grad [6][nz][gp] from six accumulator planes per group
-__global__ void el_finalize_vti(const float *acc, int ngroups, int nz, int gp, long long aplane, int sblk, float *grad)
-{
-    el_finalize_body<6>(acc, ngroups, nz, gp, aplane, sblk, grad);
-}
-// viscoelastic: grad [8][nz][gp] from eight accumulator planes per group
-__global__ void el_finalize_visco(const float *acc, int ngroups, int nz, int gp, long long aplane, int sblk, float *grad)
-{
-    el_finalize_body<8>(acc, ngroups, nz, gp, aplane, sblk, grad);
-}
-
 #include "mifwi_elastic_cluster.h"
 
 using mifwi::env_int;
@@ -1308,7 +1138,7 @@ using mifwi::env_int;
 // ---- the medium of a plan ---------------------------------------------------------------------------
 // Every plan of this file is a mifwi_elastic_plan; its medium says which kernels serve it and how many planes they take.
 // Isotropic plans have all kernel families; the other media run one launch per half step: el_step_s / el_adj_s with VTI
-// or VISCO = true, el_adj_v_visco, el_finalize_vti / _visco (el_step_variant, el_adj_variant).  A further medium is a row
+// or VISCO = true, el_adj_v_visco, finalize_groups<6> / <8> (el_step_variant, el_adj_variant).  A further medium is a row
 // here, a case in those two selectors and its three entry points.
 enum ElMedium { kIsotropic = 0, kVti = 1, kVisco = 2 };
 struct ElMediumInfo {
@@ -1322,11 +1152,11 @@ constexpr ElMediumInfo kMedia[] = {{5, 5, "mifwi_elastic_plan_create"}, {6, 5, "
 }  // namespace
 
 // ================================================================================================
-struct mifwi_elastic_plan {
+struct mifwi_elastic_plan : StaggerGrid {    // grid, pitch and strips: stagger_grid with four memory variables per strip cell
     mifwi_elastic_desc d;
     int device;
-    int ng, gp, pitch, lx, rz, gs, ngroups;
-    int W, wl, xr0, wx, xcd;
+    int lx, rz, gs, ngroups;
+    int xcd;
     float *rec_p;          // pressure receivers bound by mifwi_elastic_plan_bind_pressure (or null)
     const float *g_p;
     int snap_bf16;         // snapshot planes as bf16 (per-step kernels on both sides only)
@@ -1337,8 +1167,7 @@ struct mifwi_elastic_plan {
     int pass_groups;       // adjoint per-step family: shot groups per pass
     int fused;             // forward V+S in one launch (second copy of the state in the work buffer)
     int fused_pass_shots;  // shots per pass of the fused forward (both copies of the state in the Infinity Cache)
-    long long field_stride, shot_stride, fields_elems, psix_elems, psiz_elems, coef_elems;
-    long long psix_shot, psiz_shot;        // memory variables of one shot: x strips, z strips
+    long long shot_stride, fields_elems, psix_elems, psiz_elems;
     long long psi_elems;  // psix+psiz rounded up to 64
     // cluster path (LDS-resident time loop); 0 when a shot does not fit
     int cluster, NW, PL, fwd_PL, adj_PL, cl_shots, cl_lds, cl_ng;
@@ -1406,9 +1235,9 @@ struct ElAdjKernels { ElKernel s, v; ElFinalizeKernel finalize; };
 ElAdjKernels el_adj_variant(ElMedium medium, bool bf16)
 {
     switch (medium) {
-    case kVti: return {el_adj_s<false, true>, el_adj_v, el_finalize_vti};
-    case kVisco: return {el_adj_s<false, false, true>, el_adj_v_visco, el_finalize_visco};
-    default: return {bf16 ? el_adj_s<true> : el_adj_s<false>, el_adj_v, el_finalize};
+    case kVti: return {el_adj_s<false, true>, el_adj_v, finalize_groups<6>};
+    case kVisco: return {el_adj_s<false, false, true>, el_adj_v_visco, finalize_groups<8>};
+    default: return {bf16 ? el_adj_s<true> : el_adj_s<false>, el_adj_v, finalize_groups<5>};
     }
 }
 // el_cluster_fwd<SAVE, NG, AG, XH>: snapshots; one | two groups per thread; granules published at agent scope; x-halo from
@@ -1521,10 +1350,7 @@ void el_cluster_setup(mifwi_elastic_plan *pl)
     if (skew & 2) pl->adj_PL = 4 * Pskew;
     pl->cl_lds = 0; pl->xbuf_elems = 0; pl->xcc_elems = 0;
     pl->cl_adj = 0; pl->adj_NW = 0; pl->adj_shots = 0; pl->adj_lds = 0; pl->adj_ng = 0; pl->adj_zrows = 0; pl->list_elems = 0;
-    {   // el_build_tile_taps: start [nshot][ntiles + 1], cursor [nshot][ntiles], list [nshot][nrec * ntap]
-        const long long ntiles = (long long)mifwi::ceil_div(pl->ng, AGO) * mifwi::ceil_div(pl->d.nz, ATZ);
-        pl->tile_elems = std::max<long long>(1024, mifwi::round_up64(pl->d.nshot * (2 * ntiles + 1 + (long long)pl->d.nrec * pl->d.ntap), 64));
-    }
+    pl->tile_elems = tile_taps_elems(pl->d.nshot, pl->d.nz, pl->ng, pl->d.nrec, pl->d.ntap);
     if (pl->medium != kIsotropic || pl->d.ntap != 1 || pl->d.source_type != 0 || pl->d.record_pressure) return;   // per-step kernels only
     const bool want_fwd = env_int("MIFWI_EL_CLUSTER", 1) != 0;
     int ncu = 0;
@@ -1694,57 +1520,29 @@ int el_plan_create(mifwi_elastic_plan **plan, int device, const mifwi_elastic_de
                    float rel_b = 0.f)
 {
     if (!plan || !d) return mifwi::fail(MIFWI_EINVAL, "null plan/desc");
-    if (d->nz < 1 || d->nx < 1 || d->nt < 1 || d->nshot < 1 || d->nsrc < 0 || d->nrec < 0)
-        return mifwi::fail(MIFWI_EINVAL, "bad sizes nz=%d nx=%d nt=%d nshot=%d", d->nz, d->nx, d->nt,
-                           d->nshot);
-    if (d->ntap != 1 && d->ntap != 4) return mifwi::fail(MIFWI_EINVAL, "ntap must be 1 or 4");
-    if (d->free_surface != 0 && d->free_surface != 1)
-        return mifwi::fail(MIFWI_EINVAL, "free_surface must be 0 or 1");
-    if (d->free_surface && d->nz < 4) return mifwi::fail(MIFWI_EINVAL, "free surface needs nz >= 4");
-    if (d->pml_width < 0) return mifwi::fail(MIFWI_EINVAL, "pml_width < 0");
+    int rc = check_stagger_desc(d, 4);
+    if (rc) return rc;
     if (d->record_pressure != 0 && d->record_pressure != 1)
         return mifwi::fail(MIFWI_EINVAL, "record_pressure must be 0 or 1");
-    if (d->source_type < 0 || d->source_type > 2)
-        return mifwi::fail(MIFWI_EINVAL, "source_type must be 0 (explosive), 1 (force x) or 2 (force z)");
-    if (d->fd_order != 0 && d->fd_order != 2 && d->fd_order != 4)
-        return mifwi::fail(MIFWI_EINVAL, "fd_order %d: the staggered-grid stencils are built for order 2 and 4", d->fd_order);
+    if ((rc = check_stagger_scheme(d))) return rc;
     if (d->snapshot_format != MIFWI_SNAPSHOT_F32 && d->snapshot_format != MIFWI_SNAPSHOT_BF16)
         return mifwi::fail(MIFWI_EINVAL, "snapshot_format must be MIFWI_SNAPSHOT_F32 or MIFWI_SNAPSHOT_BF16");
-    int rc = mifwi::check_device(device);
-    if (rc) return rc;
+    if ((rc = mifwi::check_device(device))) return rc;
     // function attributes and CU counts queried during set-up belong to THIS device (one process per
     // GPU sees all eight devices)
     MIFWI_HIP_TRY(hipSetDevice(device));
+    StaggerGrid grid;
+    if ((rc = stagger_grid(d->nz, d->nx, d->pml_width, 4, &grid))) return rc;
     mifwi_elastic_plan *pl = new mifwi_elastic_plan;
+    static_cast<StaggerGrid &>(*pl) = grid;
     pl->d = *d;
     if (pl->d.fd_order == 0) pl->d.fd_order = 4;
     pl->device = device;
     pl->medium = medium;
     pl->rel_a = rel_a; pl->rel_b = rel_b;
     pl->rec_p = nullptr; pl->g_p = nullptr;
-    pl->ng = mifwi::ceil_div(d->nx, 4);
-    pl->gp = 4 * pl->ng;
-    pl->pitch = (int)mifwi::round_up64(4 * (pl->ng + 3), 32);
-    pl->field_stride = (long long)(d->nz + 4) * pl->pitch;
     pl->shot_stride = kMedia[medium].nfield * pl->field_stride;
     pl->fields_elems = pl->shot_stride * d->nshot;
-    pl->coef_elems = (long long)d->nz * pl->gp;
-    // strip geometry: W = pml_width + 1 nodes per side (half-node profiles reach one node further)
-    pl->W = d->pml_width > 0 ? d->pml_width + 1 : 0;
-    if (pl->W > 0) {
-        pl->wl = (int)mifwi::round_up64(pl->W, 4);
-        pl->xr0 = ((d->nx - pl->W) / 4) * 4;
-        if (pl->xr0 < pl->wl || 2 * pl->W > d->nz) {
-            delete pl;
-            return mifwi::fail(MIFWI_EINVAL, "grid %dx%d too small for a %d-node C-PML", d->nz,
-                               d->nx, d->pml_width);
-        }
-        pl->wx = pl->wl + (pl->gp - pl->xr0);
-    } else {
-        pl->wl = pl->xr0 = pl->wx = 0;
-    }
-    pl->psix_shot = 4LL * d->nz * pl->wx;
-    pl->psiz_shot = 4LL * 2 * pl->W * pl->gp;
     pl->psix_elems = pl->psix_shot * d->nshot;
     pl->psiz_elems = pl->psiz_shot * d->nshot;
     pl->lx = mifwi::pick_lx(pl->ng);
@@ -1754,15 +1552,10 @@ int el_plan_create(mifwi_elastic_plan **plan, int device, const mifwi_elastic_de
     // the tiles of each shot; 2: whole shots per XCD.  Measured (r04): 350x1700 x 6 shots forward 43.5 -> 40.5 us per step
     // with 3 against 1, adjoint pair and the 1000x3000 passes (2-3 shots per launch) unchanged
     pl->xcd = env_int("MIFWI_EL_XCD", 3);
-    int gs = d->shots_per_group;
-    if (gs <= 0) gs = env_int("MIFWI_EL_GS", 4);
-    if (gs <= 0) gs = 1;
-    if (gs > d->nshot) gs = d->nshot;
-    // groups of equal size where a slightly smaller one gives them (a 6-shot chunk of a shot-chunked gradient pass: 3 + 3
-    // instead of 4 + 2 - the workgroups of the short group would idle while the others finish their fourth shot)
-    if (d->shots_per_group <= 0 && env_int("MIFWI_EL_GS", 0) <= 0 && gs == 4 && d->nshot % 4 != 0 && d->nshot % 3 == 0) gs = 3;
-    pl->gs = gs;
-    pl->ngroups = mifwi::ceil_div(d->nshot, gs);
+    // MIFWI_EL_GS, where set, names the size as the caller's shots_per_group does (no 4 -> 3 rule then)
+    pl->gs = default_group_size(d->shots_per_group > 0 ? d->shots_per_group : env_int("MIFWI_EL_GS", 0), d->nshot,
+                                env_int("MIFWI_EL_GS", 4));
+    pl->ngroups = mifwi::ceil_div(d->nshot, pl->gs);
     pl->psi_elems = mifwi::round_up64(pl->psix_elems + pl->psiz_elems, 64);
     el_cluster_setup(pl);
     // bf16 snapshot planes: the per-step kernels only (the single-launch time loops are not bound by the
@@ -1771,7 +1564,7 @@ int el_plan_create(mifwi_elastic_plan **plan, int device, const mifwi_elastic_de
     // column-blocked snapshot planes (snap_cell): plans that never run a single-launch kernel (those write and read
     // row-major planes, and a call may change family between checkpoint segments); MIFWI_EL_SNAP_BLOCKED=0: row-major
     pl->sblk = (!pl->cluster && !pl->cl_adj && env_int("MIFWI_EL_SNAP_BLOCKED", 1) != 0) ? 1 : 0;
-    pl->splane = pl->sblk ? 64LL * d->nz * mifwi::ceil_div(pl->ng, 16) : pl->coef_elems;
+    pl->splane = pl->sblk ? blocked_plane_elems(d->nz, pl->ng) : pl->coef_elems;
     pl->snap_shot = pl->snap_bf16 ? mifwi::round_up64(5 * pl->splane / 2, 4) : 5 * pl->splane;
     {
         // Infinity Cache residency (per-step family, large grids): a pass over the time range takes only as
@@ -2061,7 +1854,7 @@ int el_backward(mifwi_elastic_plan *pl, const float *mat, const float *pz, const
         tile_start = base;
         int *cursor = base + (long long)d.nshot * (ntiles + 1);
         tile_list = cursor + (long long)d.nshot * ntiles;
-        hipLaunchKernelGGL(el_build_tile_taps, dim3(d.nshot), dim3(256), 0, st, rec_cell, d.nrec * d.ntap, d.nx, tiles_x,
+        hipLaunchKernelGGL(build_tile_taps, dim3(d.nshot), dim3(256), 0, st, rec_cell, d.nrec * d.ntap, d.nx, tiles_x,
                            ntiles, tile_start, cursor, tile_list);
     };
     const ElAdjKernels adj = el_adj_variant(pl->medium, pl->snap_bf16);
@@ -2127,8 +1920,8 @@ int el_backward(mifwi_elastic_plan *pl, const float *mat, const float *pz, const
         if (want_f && force) {
             ElParams pq = ps;
             pq.gs = cs; pq.smp_out0 = grad_f + (long long)n * d.nshot * d.nsrc;
-            hipLaunchKernelGGL(el_sample_force, dim3(mifwi::ceil_div(cs * d.nsrc, 64)), dim3(64), 0, st, pq,
-                               d.source_type);
+            hipLaunchKernelGGL(sample_force<ElParams>, dim3(mifwi::ceil_div(cs * d.nsrc, 64)), dim3(64), 0, st, pq,
+                               d.source_type == 1 ? F_VX : F_VZ);
         }
         hipLaunchKernelGGL(adj.v, dim3(tx, tz, cs), dim3(kThreads), 0, st, p);
     }

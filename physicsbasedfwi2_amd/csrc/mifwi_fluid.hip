@@ -5,7 +5,8 @@
 //
 // Replaces (reference tree): the DENISE runs with PHYSICS = 2 behind pyapi_denise, models/networks.py:10445-10453.
 //
-// Same grid, staggering, Dp / Dm, pml / pmlT and pz / px tables as the elastic kernels; the seismograms are those of the
+// Same grid, staggering, Dp / Dm, pml / pmlT and pz / px tables as the elastic kernels - one copy of them, of the strip
+// and tile helpers, of the three cold kernels and of the plan geometry, in mifwi_stagger.h; the seismograms are those of the
 // elastic scheme on mat = [K, K, 0, bx, bz] bit for bit (with Ms == Ls its two stress updates are one fmaf chain).
 // Forward: two launches per time step.  V: vx, vz from p, with the point force (source_type 1 / 2) added by the tile
 // that owns the cells; P: p from the new velocities, with the explosive source, and the velocity receivers sampled by
@@ -24,22 +25,12 @@
 // Snapshot moments (the pseudo-Hessian's ingredient): mifwi_fluid_moments.h, included at the end.
 // Arithmetic = the explicit fmaf chain stated in include/mifwi.h (build with -ffp-contract=off).
 #include "mifwi_cluster_host.h"      // mifwi::env_int
-#include "mifwi_host.h"
-
-#include <algorithm>
+#include "mifwi_stagger.h"
 
 namespace {
 
-constexpr int kThreads = 256;
-struct FdK { float c1, c2; };
-inline FdK fd_weights(int order)
-{
-    return order == 2 ? FdK{1.0f, 0.0f} : FdK{(float)(9.0 / 8.0), (float)(-1.0 / 24.0)};
-}
-
 enum { F_VX = 0, F_VZ = 1, F_P = 2 };
 enum { M_K = 0, M_BX = 1, M_BZ = 2 };
-enum { PA = 0, PB = 1, PK = 2, PAH = 3, PBH = 4, PKH = 5 };
 enum { PSI_HALF = 0, PSI_INT = 1 };      // plane of a strip: the V launch's derivative (d1 / d4), the P launch's (e1 / e2)
 
 struct FlParams {
@@ -75,55 +66,8 @@ struct FlParams {
     FdK fd;
 };
 
-__device__ __forceinline__ float comp(const float4 &v, int c) { return c == 0 ? v.x : c == 1 ? v.y : c == 2 ? v.z : v.w; }
-__device__ __forceinline__ float4 ld4(const float *p) { return *reinterpret_cast<const float4 *>(p); }
-__device__ __forceinline__ float2 ld2(const float *p) { return *reinterpret_cast<const float2 *>(p); }
-__device__ __forceinline__ void st4(float *p, const float4 &v) { *reinterpret_cast<float4 *>(p) = v; }
-__device__ __forceinline__ float4 mk4(const float *a) { return make_float4(a[0], a[1], a[2], a[3]); }
-__device__ __forceinline__ float dfw(const FdK &K, float fm1, float f0, float f1, float f2)   // Dp at "0"
-{
-    return fmaf(K.c1, f1 - f0, K.c2 * (f2 - fm1));
-}
-__device__ __forceinline__ float dbw(const FdK &K, float fm2, float fm1, float f0, float f1)  // Dm at "0"
-{
-    return fmaf(K.c1, f0 - fm1, K.c2 * (f1 - fm2));
-}
-// forward C-PML: psi <- b psi + a d ; returns d*ik + psi
-__device__ __forceinline__ float pml(float &psi, float a, float b, float ik, float d)
-{
-    psi = fmaf(b, psi, a * d);
-    return fmaf(d, ik, psi);
-}
-// transposed C-PML: P = psib + db ; returns ik*db + a*P ; psib <- b*P
-__device__ __forceinline__ float pmlT(float psib, float a, float b, float ik, float db, float &psib_new)
-{
-    const float P = psib + db;
-    psib_new = b * P;
-    return fmaf(ik, db, a * P);
-}
-
-// offset (floats) of group g of row j inside a snapshot / accumulator plane: [g / 16][j][64 floats]
-__device__ __forceinline__ unsigned snap_cell(const FlParams &p, int j, int g)
-{
-    return ((unsigned)(g >> 4) * (unsigned)p.nz + (unsigned)j) * 64u + 4u * (unsigned)(g & 15);
-}
-// x-strip column offset of group g (or -1)
-__device__ __forceinline__ int xstrip(const FlParams &p, int g)
-{
-    if (p.W == 0) return -1;
-    const int c0 = 4 * g;
-    if (c0 < p.wl) return c0;
-    if (c0 >= p.xr0) return p.wl + (c0 - p.xr0);
-    return -1;
-}
-// z-strip row index of row j (or -1)
-__device__ __forceinline__ int zstrip(const FlParams &p, int j)
-{
-    if (p.W == 0) return -1;
-    if (j < p.W) return j;
-    if (j >= p.nz - p.W) return j - (p.nz - 2 * p.W);
-    return -1;
-}
+// offset (floats) of group g of row j inside a snapshot / accumulator plane: always column-blocked
+__device__ __forceinline__ unsigned snap_cell(const FlParams &p, int j, int g) { return snap_cell_blocked(p.nz, j, g); }
 // memory variables of one group: plane k of the shot's x strips (row j) / z strips (strip row zs)
 __device__ __forceinline__ long long psix_at(const FlParams &p, int s, int k, int j, int xs_off)
 {
@@ -132,21 +76,6 @@ __device__ __forceinline__ long long psix_at(const FlParams &p, int s, int k, in
 __device__ __forceinline__ long long psiz_at(const FlParams &p, int s, int k, int zs, int g)
 {
     return (long long)s * p.psiz_shot + ((long long)k * 2 * p.W + zs) * p.gp + 4 * g;
-}
-
-// Workgroups are dealt to the 8 XCDs round-robin in launch order, each XCD with an L2 of its own.  Remap (a bijection on
-// the launch grid): the sequence (tile 0: slices 0 .. gz-1), (tile 1: ...), ... is cut into eight contiguous pieces, one
-// per XCD - all shots of the launch pass through a tile back to back on one XCD (its material planes come from memory
-// once per launch), and neighbouring tiles follow each other on that XCD (the halo a tile reads was fetched by the same L2).
-__device__ __forceinline__ void xcd_tile(int &bx, int &by, int &bz)
-{
-    const unsigned gx = gridDim.x, n2 = gx * gridDim.y, gz = gridDim.z, total = n2 * gz;
-    const unsigned L = blockIdx.x + gx * blockIdx.y + n2 * blockIdx.z;
-    const unsigned c = L & 7u, idx = L >> 3, q = total >> 3, r = total & 7u;
-    const unsigned e = c * q + (c < r ? c : r) + idx;
-    const unsigned T = e / gz;
-    bz = (int)(e - T * gz);
-    by = (int)(T / gx); bx = (int)(T - (unsigned)by * gx);
 }
 
 // sampling workgroups (the rows by >= tiles_z of a launch), p.gs shots per z slice.
@@ -228,7 +157,7 @@ __global__ __launch_bounds__(kThreads) void fl_step_v(const FlParams p)
     constexpr int LZ = kThreads / LX, TX = LX * 4;
     __shared__ float inj[LZ * TX];
     int bx, by, bz;
-    xcd_tile(bx, by, bz);
+    xcd_tile_major(bx, by, bz);
     const int lx = (int)threadIdx.x % LX, lz = (int)threadIdx.x / LX;
     const int g = bx * LX + lx, j = by * LZ + lz;
     const int s = p.s0 + bz;
@@ -323,7 +252,7 @@ __global__ __launch_bounds__(kThreads) void fl_step_p(const FlParams p)
     constexpr int LZ = kThreads / LX, TX = LX * 4;
     __shared__ float inj[LZ * TX];
     int bx, by, bz;
-    xcd_tile(bx, by, bz);
+    xcd_tile_major(bx, by, bz);
     if (by >= p.tiles_z) {
         sample_points<0>(p, bx, by, bz, 1);
         return;
@@ -399,22 +328,8 @@ __global__ __launch_bounds__(kThreads) void fl_step_p(const FlParams p)
 }
 
 // ================================================================================================
-// adjoint launches.  Tile = ATZ x (4*AGO) owned cells, staged on (ATZ+4) x 4*(AGO+2) in LDS.
+// adjoint launches, on the tile of mifwi_stagger.h (ATZ x 4*AGO owned cells, staged on ASZ x ASX in LDS)
 // ================================================================================================
-constexpr int ATZ = 16;          // owned rows
-constexpr int AGO = 16;          // owned groups per row: a quarter wave reads one contiguous LDS row
-constexpr int AGX = AGO + 2;     // staged groups per row (1 halo group each side)
-constexpr int ASZ = ATZ + 4;     // staged rows
-constexpr int ASX = 4 * AGX;     // staged columns (72 floats: consecutive rows start 8 banks apart)
-static_assert(ATZ * AGO == kThreads, "one owned 4-cell group per thread");
-
-// x stencils on the 8 values {L.z, L.w, C.x .. C.w, R.x, R.y} around an owned group
-struct Row8 { float v[8]; };
-__device__ __forceinline__ Row8 row8(const float *row, int cb)
-{
-    const float4 l = ld4(row + cb - 4), c = ld4(row + cb), r = ld4(row + cb + 4);
-    return Row8{{l.z, l.w, c.x, c.y, c.z, c.w, r.x, r.y}};
-}
 
 // Staged coordinates of the halo group a thread stages besides its own group (threads 0..kHalo-1): the two rows above
 // and below the tile (owned columns only: they serve the z stencil), then the left / right halo group of every owned
@@ -469,38 +384,6 @@ __device__ __forceinline__ float4 mul4(const float4 &a, const float4 &b)
     return make_float4(a.x * b.x, a.y * b.y, a.z * b.z, a.w * b.w);
 }
 
-// Receiver taps (adjoint sources) of every tile of fl_adj_p, one block per shot: start[s][tile .. tile+1) indexes
-// list[s][], which holds tap numbers (receiver * ntap + tap) sorted by tile, ascending inside a tile.  Built once per
-// backward call; the time loop then adds v_bar += R^T g inside fl_adj_p, by the tile that owns the cells.
-__global__ void fl_build_tile_taps(const int *cell, int ntaps, int nx, int tx, int ntiles, int *start, int *cursor, int *list)
-{
-    const int s = (int)blockIdx.x, t = (int)threadIdx.x, T = (int)blockDim.x;
-    start += (long long)s * (ntiles + 1); cursor += (long long)s * ntiles; list += (long long)s * ntaps;
-    cell += (long long)s * ntaps;
-    for (int k = t; k < ntiles; k += T) cursor[k] = 0;
-    __syncthreads();
-    auto tile_of = [&](int c) { const int j = c / nx, i = c - j * nx; return (j / ATZ) * tx + (i >> 2) / AGO; };
-    for (int e = t; e < ntaps; e += T)
-        if (cell[e] >= 0) atomicAdd(cursor + tile_of(cell[e]), 1);
-    __syncthreads();
-    if (t == 0) {
-        int run = 0;
-        for (int k = 0; k < ntiles; ++k) { start[k] = run; run += cursor[k]; cursor[k] = start[k]; }
-        start[ntiles] = run;
-    }
-    __syncthreads();
-    for (int e = t; e < ntaps; e += T)
-        if (cell[e] >= 0) list[atomicAdd(cursor + tile_of(cell[e]), 1)] = e;
-    __syncthreads();
-    for (int k = t; k < ntiles; k += T)                   // ascending tap order inside a tile (a few entries each)
-        for (int a = start[k] + 1; a < start[k + 1]; ++a) {
-            const int v = list[a];
-            int b = a - 1;
-            while (b >= start[k] && list[b] > v) { list[b + 1] = list[b]; --b; }
-            list[b + 1] = v;
-        }
-}
-
 // P^T:  acc_K += S0 p_bar;  E1, E2 = pmlT(K p_bar);  vx_bar -= Dp_x E1,  vz_bar -= Dp_z E2;  acc_bx += S1 vx_bar,
 //       acc_bz += S2 vz_bar.  The adjoint sources of the tile's cells (v_bar += R^T g, the head of an adjoint step) are
 //       added to the loaded v_bar first (p.tile_start set).  Extra workgroups sample p_bar at the explosive sources.
@@ -508,7 +391,7 @@ __global__ __launch_bounds__(kThreads) void fl_adj_p(const FlParams p)
 {
     const FdK K = p.fd;
     int bx, by, bz;
-    xcd_tile(bx, by, bz);
+    xcd_tile_major(bx, by, bz);
     if (by >= p.tiles_z) {
         sample_points<1>(p, bx, by, bz, p.gs);
         return;
@@ -628,7 +511,7 @@ __global__ __launch_bounds__(kThreads) void fl_adj_v(const FlParams p)
     const FdK K = p.fd;
     __shared__ float D[2][ASZ][ASX];
     int bx, by, bz;
-    xcd_tile(bx, by, bz);
+    xcd_tile_major(bx, by, bz);
     const int tile_j = by * ATZ, tile_g = bx * AGO;
     const int s = p.s0 + bz;
     const unsigned fs = p.field_stride;
@@ -733,53 +616,17 @@ __global__ void fl_inject_pressure(const FlParams p)
               a + a);
 }
 
-// adjoint of a point force: grad_f[n] = sum w v_bar[cell], sampled between P^T and V^T
-__global__ void fl_sample_force(const FlParams p, int field)
-{
-    const int idx = (int)(blockIdx.x * blockDim.x + threadIdx.x);     // over the p.gs shots of this pass
-    if (idx >= p.gs * p.nsmp) return;
-    const int s = p.s0 + idx / p.nsmp;
-    if (s >= p.nshot) return;
-    const int e = s * p.nsmp + idx % p.nsmp;
-    const float *v = p.fields + (long long)s * p.shot_stride + field * (long long)p.field_stride;
-    float a = 0.f;
-    for (int t = 0; t < p.ntap_smp; ++t) {
-        const long long ee = (long long)e * p.ntap_smp + t;
-        const int cell = p.smp_cell[ee];
-        if (cell < 0) continue;
-        const int j = cell / p.nx, i = cell - j * p.nx;
-        a = fmaf(p.smp_w[ee], v[(unsigned)(j + 2) * p.pitch + 4 + i], a);
-    }
-    p.smp_out0[e] = a;
-}
-
-// grad[k][cell] = sum over shot groups of acc[group][k][cell], in group order; grad is row-major [3][nz][gp]
-__global__ void fl_finalize(const float *acc, int ngroups, int nz, int gp, long long aplane, float *grad)
-{
-    const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x, ncell = (long long)nz * gp;
-    if (idx >= 3 * ncell) return;
-    const int k = (int)(idx / ncell);
-    const long long c = idx - (long long)k * ncell;
-    const int j = (int)(c / gp), i = (int)(c - (long long)j * gp), g = i >> 2;
-    const long long off = ((long long)(g >> 4) * nz + j) * 64 + 4 * (g & 15) + (i & 3);
-    float a = 0.f;
-    for (int gidx = 0; gidx < ngroups; ++gidx) a += acc[((long long)gidx * 3 + k) * aplane + off];
-    grad[idx] = a;
-}
-
 }  // namespace
 
 // ================================================================================================
-struct mifwi_fluid_plan {
+struct mifwi_fluid_plan : StaggerGrid {      // grid, pitch and strips: stagger_grid with two memory variables per strip cell
     mifwi_fluid_desc d;
     int device;
-    int ng, gp, pitch, lx, gs, ngroups;
-    int W, wl, xr0, wx;
+    int lx, gs, ngroups;
     long long splane;      // floats per snapshot / accumulator plane
     int pass_shots;        // forward: shots per pass over the time range
     int pass_groups;       // adjoint: shot groups per pass
-    long long field_stride, shot_stride, fields_elems, psix_elems, psiz_elems, coef_elems;
-    long long psix_shot, psiz_shot, psi_elems;
+    long long shot_stride, fields_elems, psix_elems, psiz_elems, psi_elems;
     long long tile_elems;  // per-tile receiver lists of fl_adj_p (ints, in floats)
 };
 
@@ -878,59 +725,27 @@ extern "C" {
 int mifwi_fluid_plan_create(mifwi_fluid_plan **plan, int device, const mifwi_fluid_desc *d)
 {
     if (!plan || !d) return mifwi::fail(MIFWI_EINVAL, "null plan/desc");
-    if (d->nz < 1 || d->nx < 1 || d->nt < 1 || d->nshot < 1 || d->nsrc < 0 || d->nrec < 0)
-        return mifwi::fail(MIFWI_EINVAL, "bad sizes nz=%d nx=%d nt=%d nshot=%d", d->nz, d->nx, d->nt, d->nshot);
-    if (d->ntap != 1 && d->ntap != 4) return mifwi::fail(MIFWI_EINVAL, "ntap must be 1 or 4");
-    if (d->free_surface != 0 && d->free_surface != 1) return mifwi::fail(MIFWI_EINVAL, "free_surface must be 0 or 1");
-    if (d->free_surface && d->nz < 3) return mifwi::fail(MIFWI_EINVAL, "free surface needs nz >= 3");
-    if (d->pml_width < 0) return mifwi::fail(MIFWI_EINVAL, "pml_width < 0");
-    if (d->source_type < 0 || d->source_type > 2)
-        return mifwi::fail(MIFWI_EINVAL, "source_type must be 0 (explosive), 1 (force x) or 2 (force z)");
-    if (d->fd_order != 0 && d->fd_order != 2 && d->fd_order != 4)
-        return mifwi::fail(MIFWI_EINVAL, "fd_order %d: the staggered-grid stencils are built for order 2 and 4", d->fd_order);
-    int rc = mifwi::check_device(device);
+    int rc = check_stagger_desc(d, 3);
+    if (!rc) rc = check_stagger_scheme(d);
+    if (!rc) rc = mifwi::check_device(device);
+    StaggerGrid grid;
+    if (!rc) rc = stagger_grid(d->nz, d->nx, d->pml_width, 2, &grid);
     if (rc) return rc;
     mifwi_fluid_plan *pl = new mifwi_fluid_plan;
+    static_cast<StaggerGrid &>(*pl) = grid;
     pl->d = *d;
     if (pl->d.fd_order == 0) pl->d.fd_order = 4;
     pl->device = device;
-    pl->ng = mifwi::ceil_div(d->nx, 4);
-    pl->gp = 4 * pl->ng;
-    pl->pitch = (int)mifwi::round_up64(4 * (pl->ng + 3), 32);
-    pl->field_stride = (long long)(d->nz + 4) * pl->pitch;
     pl->shot_stride = 3 * pl->field_stride;
     pl->fields_elems = pl->shot_stride * d->nshot;
-    pl->coef_elems = (long long)d->nz * pl->gp;
-    // strip geometry: W = pml_width + 1 nodes per side (half-node profiles reach one node further)
-    pl->W = d->pml_width > 0 ? d->pml_width + 1 : 0;
-    if (pl->W > 0) {
-        pl->wl = (int)mifwi::round_up64(pl->W, 4);
-        pl->xr0 = ((d->nx - pl->W) / 4) * 4;
-        if (pl->xr0 < pl->wl || 2 * pl->W > d->nz) {
-            delete pl;
-            return mifwi::fail(MIFWI_EINVAL, "grid %dx%d too small for a %d-node C-PML", d->nz, d->nx, d->pml_width);
-        }
-        pl->wx = pl->wl + (pl->gp - pl->xr0);
-    } else {
-        pl->wl = pl->xr0 = pl->wx = 0;
-    }
-    pl->psix_shot = 2LL * d->nz * pl->wx;
-    pl->psiz_shot = 2LL * 2 * pl->W * pl->gp;
     pl->psix_elems = pl->psix_shot * d->nshot;
     pl->psiz_elems = pl->psiz_shot * d->nshot;
     pl->psi_elems = mifwi::round_up64(pl->psix_elems + pl->psiz_elems, 64);
     pl->lx = mifwi::pick_lx(pl->ng);
-    int gs = d->shots_per_group > 0 ? d->shots_per_group : 4;
-    if (gs > d->nshot) gs = d->nshot;
-    // groups of equal size where a slightly smaller one gives them (6 shots: 3 + 3 instead of 4 + 2)
-    if (d->shots_per_group <= 0 && gs == 4 && d->nshot % 4 != 0 && d->nshot % 3 == 0) gs = 3;
-    pl->gs = gs;
-    pl->ngroups = mifwi::ceil_div(d->nshot, gs);
-    pl->splane = 64LL * d->nz * mifwi::ceil_div(pl->ng, 16);
-    {   // fl_build_tile_taps: start [nshot][ntiles + 1], cursor [nshot][ntiles], list [nshot][nrec * ntap]
-        const long long ntiles = (long long)mifwi::ceil_div(pl->ng, AGO) * mifwi::ceil_div(d->nz, ATZ);
-        pl->tile_elems = std::max<long long>(1024, mifwi::round_up64(d->nshot * (2 * ntiles + 1 + (long long)d->nrec * d->ntap), 64));
-    }
+    pl->gs = default_group_size(d->shots_per_group, d->nshot, 4);
+    pl->ngroups = mifwi::ceil_div(d->nshot, pl->gs);
+    pl->splane = blocked_plane_elems(d->nz, pl->ng);
+    pl->tile_elems = tile_taps_elems(d->nshot, d->nz, pl->ng, d->nrec, d->ntap);
     {
         // Infinity Cache residency: a pass over the time range takes only as many shots (shot groups) as keep state,
         // materials and accumulators under the bounds the elastic per-step family measured on this cache (250 MB; the
@@ -1083,7 +898,7 @@ int mifwi_fluid_backward(mifwi_fluid_plan *pl, const float *mat, const float *pz
         int *start = reinterpret_cast<int *>(work + m.tile);
         int *cursor = start + (long long)d.nshot * (ntiles + 1);
         int *list = cursor + (long long)d.nshot * ntiles;
-        hipLaunchKernelGGL(fl_build_tile_taps, dim3(d.nshot), dim3(256), 0, st, rec_cell, d.nrec * d.ntap, d.nx, tx, ntiles,
+        hipLaunchKernelGGL(build_tile_taps, dim3(d.nshot), dim3(256), 0, st, rec_cell, d.nrec * d.ntap, d.nx, tx, ntiles,
                            start, cursor, list);
         p.tile_start = start; p.tile_list = list;
     }
@@ -1115,15 +930,15 @@ int mifwi_fluid_backward(mifwi_fluid_plan *pl, const float *mat, const float *pz
         if (want_f && force) {
             FlParams pq = p;
             pq.gs = cs; pq.smp_out0 = grad_f + (long long)n * d.nshot * d.nsrc;
-            hipLaunchKernelGGL(fl_sample_force, dim3(mifwi::ceil_div(cs * d.nsrc, 64)), dim3(64), 0, st, pq,
+            hipLaunchKernelGGL(sample_force<FlParams>, dim3(mifwi::ceil_div(cs * d.nsrc, 64)), dim3(64), 0, st, pq,
                                d.source_type == 1 ? F_VX : F_VZ);
         }
         hipLaunchKernelGGL(fl_adj_v, dim3(tx, tz, cs), dim3(kThreads), 0, st, p);
     }
     if (flags & MIFWI_FINALIZE) {
         const long long n3 = 3LL * pl->coef_elems;
-        hipLaunchKernelGGL(fl_finalize, dim3((unsigned)((n3 + 255) / 256)), dim3(256), 0, st, acc, pl->ngroups, d.nz, pl->gp,
-                           pl->splane, grad_mat);
+        hipLaunchKernelGGL(finalize_groups<3>, dim3((unsigned)((n3 + 255) / 256)), dim3(256), 0, st, acc, pl->ngroups, d.nz,
+                           pl->gp, pl->splane, 1, grad_mat);
     }
     MIFWI_HIP_TRY(hipGetLastError());
     return MIFWI_OK;

@@ -1,7 +1,8 @@
-// What the three propagators share besides the single-launch driver (mifwi_cluster_host.h, which holds host code only):
+// What every propagator (scalar acoustic, elastic, fluid) shares besides the single-launch driver (mifwi_cluster_host.h, which holds host code only):
 // the selector -> kernel dispatch behind every variant table, the opening of a C-ABI call, the plan-time rules for the
 // tile width and the Infinity Cache passes - and the shared device code: the bounding box of a shot's point set (per-step
-// kernels), the row-slab split and the per-slab receiver lists (single-launch kernels and their plans).
+// kernels), the row-slab split and the per-slab receiver lists (single-launch kernels and their plans).  What only the two
+// staggered-grid families share is in mifwi_stagger.h.
 #pragma once
 #include "mifwi_common.h"
 

@@ -79,7 +79,7 @@ def elastic_case(seed=0, nz=44, nx=60, fw=8, nt=120, ns=2, nsrc=1, nrec=9, h=20.
                 rho=rho, dt=dt, h=h, fs=1 if free_surface else 0)
 
 
-ADJ_TILE = (16, 64)       # rows x columns of one el_adj_s tile (ATZ, 4 * AGO in csrc/mifwi_elastic.hip)
+ADJ_TILE = (16, 64)       # rows x columns of one el_adj_s / fl_adj_p tile (ATZ, 4 * AGO in csrc/mifwi_stagger.h)
 
 
 def taps_per_cell(cells, ncell):

@@ -43,7 +43,7 @@ COLS = VCLASSES + ["valu", "salu", "s_nop", "lds", "global"]
 def fingerprint():
     """sha1 over the sources the time loops are compiled from"""
     h = hashlib.sha1()
-    for f in ("mifwi_elastic.hip", "mifwi_elastic_cluster.h", "mifwi_common.h"):
+    for f in ("mifwi_elastic.hip", "mifwi_elastic_cluster.h", "mifwi_stagger.h", "mifwi_common.h"):
         h.update(open(os.path.join(CSRC, f), "rb").read())
     return h.hexdigest()[:12]
 
