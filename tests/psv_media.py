@@ -1,14 +1,19 @@
 """TEST INFRASTRUCTURE ONLY: what the tests of the P-SV media beyond the isotropic one share (tests/test_psv_media_gpu.py,
 test_vti_gpu.py, test_visco_gpu.py and the two host modules): the seeded cases, the cached float64 references
-(tests/psv_reference.py), the device helpers, ``MEDIA``, which names what differs between the media, and the two checks that
-the media's own files run under the names their cases have always had.
+(tests/psv_reference.py), the device helpers, ``MEDIA``, which names what differs between the media, and the checks that
+the media's own files run under the names their cases have always had (and, on random configurations,
+tests/test_psv_fuzz_gpu.py).
 
 A new medium is one more entry of ``MEDIA`` and one more branch of psv_reference's stress update; a test that needs more
 of a medium than an entry holds belongs in the medium's own file.
 
 Shapes: A = the default 44 x 60 x 120 steps case (15 groups: less than one column block, a partial tile in z), B = 37 x 150,
-3 shots, 50 steps (three column blocks with the last partial, nx no multiple of 4).  Both with an 8-cell C-PML, A also
-without a layer and with a free surface.  Inputs are rounded to f32 first (what the device computes with).  Every
+3 shots, 50 steps (three column blocks with the last partial, nx no multiple of 4): both run at 16 lanes per row
+(``pick_lx``).  C = 41 x 117, 2 shots, 70 steps (30 groups: 32 lanes with two idle, nx % 4 = 1), D = 35 x 230, 2 shots, 60
+steps (58 groups: 64 lanes, nx % 4 = 2).  All with an 8-cell C-PML, A and C also without a layer, A and D also with a free
+surface (not C: both its sources would sit on the surface row in the water and never see the medium; the reference's
+rec_vz and four of its gradient planes are all zero there).  A case is a name of ``CASES`` or a configuration (``case``): the draws of tests/test_psv_fuzz_gpu.py are built,
+referenced and checked by the same functions.  Inputs are rounded to f32 first (what the device computes with).  Every
 reference result is computed once per case and left unchanged."""
 import ctypes
 import importlib
@@ -21,9 +26,12 @@ import torch
 
 import psv_reference as R
 from cases import elastic_case, rel_l2
+from oracle import helpers as H
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CASES = {"A": dict(), "A_fw0": dict(fw=0), "A_fs": dict(free_surface=True), "B": dict(nz=37, nx=150, ns=3, nt=50)}
+_C, _D = dict(nz=41, nx=117, ns=2, nt=70), dict(nz=35, nx=230, ns=2, nt=60)
+CASES = {"A": dict(), "A_fw0": dict(fw=0), "A_fs": dict(free_surface=True), "B": dict(nz=37, nx=150, ns=3, nt=50),
+         "C": _C, "C_fw0": dict(_C, fw=0), "D": _D, "D_fs": dict(_D, free_surface=True)}
 PER_STEP = {"MIFWI_EL_CLUSTER": "0", "MIFWI_EL_CLUSTER_ADJ": "0", "MIFWI_EL_FUSED": "0"}
 TOL_TRACE, TOL_SUM = 2e-6, 2e-5
 WATER = 6
@@ -101,13 +109,60 @@ def module(m):
     return importlib.import_module("physicsbasedfwi2_amd." + m.name)
 
 
-def case(m, name):
-    """The elastic case with its inputs rounded to f32, the medium's planes "matm" of smooth seeded fields, its limit
-    "matlim" that must run as the elastic propagator, "relax" (None without memory variables) and seeded 1 % perturbations
-    "dmat" of the planes and "df" of the source amplitudes."""
-    key = (m.name, name)
+def pick_lx(ng):
+    """The plan's rule for the forward tile width (mifwi::pick_lx in csrc/mifwi_host.h), restated: 64 lanes per row, then
+    32, where padding a row of ng four-cell groups to a multiple of that costs at most 20 %; otherwise 16."""
+    for cand in (64, 32):
+        if -(-ng // cand) * cand * 10 <= ng * 12:
+            return cand
+    return 16
+
+
+def _config(spec):
+    """(configuration, cache key) of ``spec``: a name of ``CASES``, or a configuration itself - the keywords of
+    cases.elastic_case and, optionally, "seed" (83), "source_type" (0; 1 / 2: a point force fx / fz), "ntap" (1) and
+    "surface_receivers" (True; False: under a free surface shot 0 is recorded on the buried line of the other shots, not on
+    row 0, where its own source's injection is 1e5 times everything the other shots record)."""
+    cfg = dict(CASES[spec] if isinstance(spec, str) else spec)
+    return cfg, (spec if isinstance(spec, str) else tuple(sorted(cfg.items())))
+
+
+def width(spec):
+    """Lanes per row the plan picks for the case's grid."""
+    return pick_lx(-(-_config(spec)[0].get("nx", 60) // 4))
+
+
+def _four_taps(c, seed):
+    """The case's one-tap points as bilinear four-tap points (oracle.helpers.bilinear_taps) at seeded fractional positions
+    inside the cells elastic_case chose: every tap active, no weight 0 or 1."""
+    nz, nx = c["vp"].shape
+    rng = np.random.default_rng([seed, 4])
+    for cell, w in (("sc", "sw"), ("rc", "rw")):
+        q = np.asarray(c[cell])[..., 0]
+        pos = np.stack([q // nx, q % nx], axis=-1) + rng.uniform(0.05, 0.95, q.shape + (2,))
+        c[cell], c[w] = H.bilinear_taps(pos * c["h"], (c["h"], c["h"]), 0, (nz, nx))
+        assert c[cell].shape == q.shape + (4,) and (c[cell] >= 0).all() and ((c[w] > 0) & (c[w] < 1)).all()
+        assert np.array_equal(c[cell][..., 0], q)
+
+
+def case(m, spec):
+    """The elastic case of ``spec`` (a name of ``CASES`` or a configuration, see ``_config``) with its inputs rounded to f32,
+    the medium's planes "matm" of smooth seeded fields, its limit "matlim" that must run as the elastic propagator, "relax"
+    (None without memory variables), "st", the source type (a force's amplitudes are scaled by 1e-3, as the elastic sweep
+    scales them) and seeded 1 % perturbations "dmat" of the planes and "df" of the source amplitudes."""
+    cfg, key = _config(spec)
+    key = (m.name, key)
     if key not in _cache:
-        c = elastic_case(seed=83, **CASES[name])
+        seed, st, ntap = cfg.pop("seed", 83), cfg.pop("source_type", 0), cfg.pop("ntap", 1)
+        on_surface = cfg.pop("surface_receivers", True)
+        c = elastic_case(seed=seed, **cfg)
+        c["st"] = st
+        if c["fs"] and not on_surface:
+            c["rc"][0], c["rw"][0] = c["rc"][1], c["rw"][1]           # shot 0 recorded on the buried line of the others
+        if st:
+            c["f"] = c["f"] * 1e-3
+        if ntap == 4:
+            _four_taps(c, seed)
         nz, nx = c["vp"].shape
         rng = np.random.default_rng(31)
         z, x = np.meshgrid(np.arange(nz) / nz, np.arange(nx) / nx, indexing="ij")
@@ -140,13 +195,13 @@ def geo(c):
     return c["sc"], c["sw"], c["rc"], c["rw"]
 
 
-def ref(m, name, order, which):
+def ref(m, spec, order, which):
     """The reference on ``which`` = "matm" / "matlim": traces, the adjoint source built from them, gradients."""
-    key = ("ref", m.name, name, order, which)
+    key = ("ref", m.name, _config(spec)[1], order, which)
     if key not in _cache:
-        c = case(m, name)
+        c = case(m, spec)
         rvx, rvz, gm, gf = R.gradients(c[which], c["pz"], c["px"], c["f"], *geo(c), g_of, None, m.name, c["relax"],
-                                       free_surface=c["fs"], fd_order=order)
+                                       free_surface=c["fs"], fd_order=order, source_type=c["st"])
         out = dict(rvx=rvx, rvz=rvz, g=g_of(rvx, rvz), f=gf, planes=gm)
         out.update({p: gm[k] for k, p in enumerate(m.planes)})
         for v in out.values():
@@ -156,10 +211,11 @@ def ref(m, name, order, which):
     return _cache[key]
 
 
-def ref_jvp(m, name, order):
-    key = ("jvp", m.name, name, order)
+def ref_jvp(m, spec, order):
+    key = ("jvp", m.name, _config(spec)[1], order)
     if key not in _cache:
-        c = case(m, name)
+        c = case(m, spec)
+        assert c["st"] == 0                                   # Born modelling serves explosive sources only
         d = R.jvp(c["matm"], c["dmat"], c["pz"], c["px"], c["f"], None, *geo(c), m.name, c["relax"], eps=1e-5,
                   free_surface=c["fs"], fd_order=order)
         d.setflags(write=False)
@@ -189,7 +245,7 @@ def run(m, c, mat_np, order, g=None, need_f=True, **kw):
     mat = dev(mat_np).requires_grad_(g is not None)
     f = dev(c["f"]).requires_grad_(g is not None and need_f)
     mod, more = (elastic, []) if m is None else (module(m), extra(m, c))
-    rvx, rvz = mod.propagate(*args(c, mat, f), *more, free_surface=bool(c["fs"]), fd_order=order, **kw)
+    rvx, rvz = mod.propagate(*args(c, mat, f), *more, free_surface=bool(c["fs"]), fd_order=order, source_type=c["st"], **kw)
     if g is None:
         return rvx, rvz
     torch.autograd.backward([rvx, rvz], [dev(a) for a in g])
@@ -202,19 +258,43 @@ def born(m, c, order, dmat=None, df=None, **kw):
                           free_surface=bool(c["fs"]), fd_order=order, **kw)
 
 
-def step_bytes(m, c, ns=None):
-    """Bytes of one time step's snapshots for ``ns`` shots (default: the case's), from the medium's own plan."""
+def plan(m, c, ns=None, order=4, gs=0):
+    """The plan a propagate call on the case creates, for ``ns`` shots (default: the case's); ``m`` None: the elastic
+    propagator's.  The caller closes it."""
+    from physicsbasedfwi2_amd import elastic
     nz, nx = c["vp"].shape
     nt, n, nsrc = c["f"].shape
-    plan = getattr(module(m), m.plan)(nz, nx, nt, ns or n, nsrc, c["rc"].shape[1], 1, c["fw"], 0, *(c["relax"] or ()),
-                                      free_surface=c["fs"])
-    assert plan.cluster_slabs(False) == 0 and plan.cluster_slabs(True) == 0
-    lay = plan.layout
-    if m.state_fields:
-        assert lay.state_elems >= m.state_fields * (nz + 4) * lay.pitch * (ns or n)
+    make, relax = (elastic.ElasticPlan, ()) if m is None else (getattr(module(m), m.plan), c["relax"] or ())
+    return make(nz, nx, nt, ns or n, nsrc, c["rc"].shape[1], c["rc"].shape[2], c["fw"], 0, *relax, shots_per_group=gs,
+                free_surface=c["fs"], source_type=c["st"], fd_order=order)
+
+
+def step_bytes(m, c, ns=None, order=4, gs=0):
+    """Bytes of one time step's snapshots for ``ns`` shots (default: the case's), from the medium's own plan (``m`` None:
+    the elastic propagator's, which may run a single-launch loop)."""
+    nz, n = c["vp"].shape[0], c["f"].shape[1]
+    pl = plan(m, c, ns, order, gs)
+    lay = pl.layout
+    if m is not None:
+        assert pl.cluster_slabs(False) == 0 and pl.cluster_slabs(True) == 0
+        if m.state_fields:
+            assert lay.state_elems >= m.state_fields * (nz + 4) * lay.pitch * (ns or n)
     b = 4 * lay.snap_step_elems
-    plan.close()
+    pl.close()
     return b
+
+
+def segment_budget(m, c, segments, order=4, gs=0):
+    """The snapshot budget that cuts the case's time range into ``segments`` time-checkpoint segments on the plan of ``m``
+    (None: the elastic propagator's): one segment's snapshots and as much again for the checkpoints."""
+    from physicsbasedfwi2_amd._driver import checkpoint_schedule, segment_length
+    nt = c["f"].shape[0]
+    sb = step_bytes(m, c, order=order, gs=gs)
+    seg = -(-nt // segments)
+    budget = 2 * seg * sb
+    assert segment_length(budget, torch.device("cuda:0"), sb, nt) == seg
+    assert len(checkpoint_schedule(nt, seg, "elastic")[0]) >= 2
+    return budget
 
 
 def pair(a, b):
@@ -267,18 +347,36 @@ def check_limit_is_the_elastic_propagator(m, monkeypatch, name, form, order):
         assert v <= TOL_SUM, (k, v)
 
 
-def check_traces_and_gradients_match_the_reference(m, name, order):
-    """The medium's traces within TOL_TRACE and every gradient within max(TOL_SUM, 4 E_iso) of the float64 reference"""
+def live_shots(tr, floor):
+    """Shots whose traces [2, nt, ns, nrec] hold at least ``floor`` of the largest shot's norm (the wave has not reached the
+    receivers of the others: their samples are stencil leakage of size 1e-30, whose ratios mean nothing)."""
+    norms = [np.linalg.norm(tr[:, :, s]) for s in range(tr.shape[2])]
+    return [s for s, v in enumerate(norms) if v >= floor * max(norms)]
+
+
+def moved_from_the_limit(m, spec, order, floor=0.0):
+    """rel-L2, shot by shot, between the reference's traces in the medium and in its limit, over the live shots"""
+    iso, ref_m = ref(m, spec, order, "matlim"), ref(m, spec, order, "matm")
+    ref_mtr, iso_tr = np.stack([ref_m["rvx"], ref_m["rvz"]]), np.stack([iso["rvx"], iso["rvz"]])
+    return [rel_l2(ref_mtr[:, :, s], iso_tr[:, :, s]) for s in live_shots(ref_mtr, floor)]
+
+
+def check_traces_and_gradients_match_the_reference(m, name, order, floor=0.0, segments=0, **kw):
+    """The medium's traces within TOL_TRACE and every gradient within max(TOL_SUM, 4 E_iso) of the float64 reference.
+    ``name``: a name of CASES or a configuration; ``floor``: see live_shots; ``segments`` > 0: that many time-checkpoint
+    segments, each propagator's budget from its own plan; ``kw``: further options of both propagate calls.  Returns the
+    measured errors {"traces", the planes, "f", "E_iso"} and what the medium's run returned."""
     c = case(m, name)
     iso, ref_m = ref(m, name, order, "matlim"), ref(m, name, order, "matm")
+    budget = lambda mm: dict(snapshot_budget=segment_budget(mm, c, segments, order, kw.get("shots_per_group", 0))) if segments else {}
     # today's isotropic kernels against the same reference in the isotropic limit: the case's own error level
-    evx, evz, eg, egf = run(None, c, c["mat"], order, iso["g"])
+    evx, evz, eg, egf = run(None, c, c["mat"], order, iso["g"], **budget(None), **kw)
     e_tr = rel_l2(pair(evx, evz), np.stack([iso["rvx"], iso["rvz"]]))
     iso_g = dict(m.iso(iso["planes"]), f=iso["f"])
     e_iso = {k: rel_l2(e, iso_g[k]) for k, e in zip(ISO_KEYS, list(eg) + [egf])}
     print("E_iso %s order %d: traces %.2e, gradients %s" % (name, order, e_tr, {k: "%.2e" % v for k, v in e_iso.items()}))
     assert e_tr <= TOL_TRACE, "the isotropic kernels miss the trace bound on this case: not a case for this test"
-    vvx, vvz, vg, vgf = run(m, c, c["matm"], order, ref_m["g"])
+    vvx, vvz, vg, vgf = run(m, c, c["matm"], order, ref_m["g"], **budget(m), **kw)
     assert np.abs(ref_m["rvx"]).max() > 0 and np.abs(ref_m["rvz"]).max() > 0
     ref_mtr, iso_tr, got_tr = np.stack([ref_m["rvx"], ref_m["rvz"]]), np.stack([iso["rvx"], iso["rvz"]]), pair(vvx, vvz)
     shots = range(ref_mtr.shape[2])
@@ -286,8 +384,8 @@ def check_traces_and_gradients_match_the_reference(m, name, order):
     # recorded on row 0 in the water, whose effective moduli are all zero: its traces never see the medium, are the same
     # bits in both references and carry nearly all the energy of the case, so all shots pooled move by 7e-7 there whatever
     # Q is.)
-    moved = [rel_l2(ref_mtr[:, :, s], iso_tr[:, :, s]) for s in shots]
-    print("%s vs elastic reference traces: rel-L2 shot by shot %s, pooled %.2e"
+    moved = moved_from_the_limit(m, name, order, floor)
+    print("%s vs elastic reference traces: rel-L2 of the live shots %s, pooled %.2e"
           % (m.name, ["%.2e" % v for v in moved], rel_l2(ref_mtr, iso_tr)))
     assert max(moved) > 0.01
     err = rel_l2(got_tr, ref_mtr)
@@ -296,6 +394,7 @@ def check_traces_and_gradients_match_the_reference(m, name, order):
     assert err <= TOL_TRACE
     got = dict(zip(m.planes, vg), f=vgf)
     width = max(len(p) for p in m.planes)
+    errs = dict(traces=err, E_iso=max(e_iso.values()))
     for k in got:
         want = ref_m[k]
         if k == "c33" and c["fs"]:
@@ -308,6 +407,31 @@ def check_traces_and_gradients_match_the_reference(m, name, order):
         print("gradient %-*s rel-L2 %.2e (bound %.2e)" % (width, k, e, tol))
         assert np.abs(want).max() > 0, k
         assert e <= tol, (k, e, tol)
+        errs[k] = e
+    return errs, (got_tr, vg, vgf)
+
+
+def check_forced_width(m, monkeypatch, name, lx, order):
+    """MIFWI_EL_LX = ``lx`` on a case whose plan would pick 16 lanes per row: traces, every gradient and Born against the
+    same cached references within the same bounds; the largest difference from the 16-lane run is printed, not bounded."""
+    c = case(m, name)
+    assert width(name) == 16 and lx in (32, 64)
+    g = ref(m, name, order, "matm")["g"]
+    base = run(m, c, c["matm"], order, g)
+    base_born = pair(*born(m, c, order)[2:])
+    monkeypatch.setenv("MIFWI_EL_LX", str(lx))
+    errs, (tr, vg, vgf) = check_traces_and_gradients_match_the_reference(m, name, order)
+    got = pair(*born(m, c, order)[2:])
+    want = ref_jvp(m, name, order)
+    e_born = rel_l2(got, want)
+    print("%s.born at %d lanes vs central difference of the reference, %s order %d: rel-L2 %.3e" % (m.name, lx, name, order, e_born))
+    assert np.abs(want).max() > 0
+    assert e_born <= TOL_TRACE
+    diffs = dict(traces=rel_l2(tr, pair(base[0], base[1])), f=rel_l2(vgf, base[3]), born=rel_l2(got, base_born))
+    diffs.update({p: rel_l2(vg[k], base[2][k]) for k, p in enumerate(m.planes)})
+    print("%s %s order %d: %d lanes vs 16 lanes, rel-L2 %s, largest %.2e"
+          % (m.name, name, order, lx, {k: "%.1e" % v for k, v in diffs.items()}, max(diffs.values())))
+    return errs, e_born
 
 
 # ---- the host modules (no GPU) ----------------------------------------------------------------------------------------

@@ -17,7 +17,12 @@ Viscoelastic: the elastic limit's traces and gradients the same bits as elastic.
 8.2e-8 ... 3.3e-7 from the reference (and 2 ... 7 % from the elastic reference, the live shots), gradients of the eight planes
 and of f 4.6e-8 ... 1.14e-6, E_iso 5.4e-8 ... 8.5e-7 (so the bound in force was 2e-5 everywhere); Born 1.8e-7 ... 6.8e-7;
 identities 2.5e-8 ... 9.8e-6; time checkpoints and shot groups: gradients <= 3.3e-7 from the resident run, traces the same
-bits."""
+bits.
+Shapes: A and B run at 16 lanes per row, C (41 x 117) at 32, D (35 x 230) at 64 (tests/psv_media.py;
+tests/test_psv_host.py pins the widths).  On C, C_fw0, D and D_fs, VTI: traces 3.5e-8 ... 4.0e-7, gradients 8.7e-8 ... 1.1e-6,
+Born 3.0e-8 ... 4.1e-7; viscoelastic: traces 4.3e-8 ... 1.6e-7, gradients 4.2e-8 ... 5.7e-7, Born 2.1e-8 ... 1.9e-7; E_iso
+<= 5.4e-7.  A and B forced to 32 and 64 lanes (MIFWI_EL_LX; test_forced_tile_width_matches_the_reference of the media's own
+files): traces, gradients and Born the same bits as at 16 lanes.  Random configurations: tests/test_psv_fuzz_gpu.py."""
 import numpy as np
 import pytest
 import torch
@@ -50,7 +55,7 @@ def test_born_is_the_directional_derivative_of_the_reference(medium, name, order
     assert err <= TOL_TRACE
 
 
-@pytest.mark.parametrize("name", ["A", "A_fs", "B"])
+@pytest.mark.parametrize("name", ["A", "A_fs", "B", "D"])
 @pytest.mark.parametrize("medium", list(MEDIA))
 def test_born_background_dot_products_and_gauss_newton(medium, name):
     m = MEDIA[medium]
@@ -93,7 +98,7 @@ def test_born_background_dot_products_and_gauss_newton(medium, name):
 
 
 # ---- driver forms: time checkpoints, shot groups, shot chunks, repeats -------------------------------------------------------
-@pytest.mark.parametrize("name", ["A", "B"])
+@pytest.mark.parametrize("name", ["A", "B", "D"])
 @pytest.mark.parametrize("medium", list(MEDIA))
 def test_checkpoints_groups_chunks_and_repeats(medium, name):
     """Time checkpoints save and restore the state of a shot: a checkpoint without the memory variables would restart every

@@ -1,7 +1,8 @@
 """What the VTI propagator (physicsbasedfwi2_amd.vti, mifwi_vti_*) has of its own on the GPU: Thomsen's kinematics on the
 kernels, PHYSICS = 3 of the pyapi_denise shim and the refusals of the C entry points.  The isotropic limit and the parity with
 the float64 reference keep their names here and run the checks of tests/psv_media.py that the viscoelastic medium runs too
-(shapes, bounds and what was measured: there and in tests/test_psv_media_gpu.py, which has Born and the driver forms)."""
+(shapes A ... D, bounds and what was measured: there and in tests/test_psv_media_gpu.py, which has Born and the driver
+forms), as does the run of A and B at forced tile widths."""
 import ctypes
 
 import numpy as np
@@ -34,6 +35,13 @@ def test_isotropic_limit_is_the_elastic_propagator(monkeypatch, name, form, orde
 @pytest.mark.parametrize("name", list(CASES))
 def test_anisotropic_traces_and_gradients_match_the_reference(name, order):
     M.check_traces_and_gradients_match_the_reference(VTI, name, order)
+
+
+@pytest.mark.parametrize("order", [2, 4])
+@pytest.mark.parametrize("name,lx", [("B", 32), ("B", 64), ("A", 64)])
+def test_forced_tile_width_matches_the_reference(monkeypatch, name, lx, order):
+    """B (38 groups) at 32 lanes: two tile columns, the second with 6 live lanes; at 64: one partial column; A: 15 of 64"""
+    M.check_forced_width(VTI, monkeypatch, name, lx, order)
 
 
 # ---- the physics pin on the kernels --------------------------------------------------------------------------------
@@ -180,6 +188,8 @@ def test_c_entry_points_refuse_nulls_bad_ranges_and_born_with_a_force_source():
         assert born(dm=None) == EINVAL and born(s=None) == EINVAL and born(e=11) == EINVAL
         if st == 1:
             assert born() == EINVAL and b"point-force" in lib.mifwi_last_error()
+            assert fwd() == 0 and bwd() == 0                          # a force source is refused by Born alone
+            torch.cuda.synchronize()
         else:
             assert fwd() == 0 and bwd() == 0 and born() == 0          # the valid calls pass
             torch.cuda.synchronize()
