@@ -1,4 +1,4 @@
-// Shared host-side plumbing of libmifwi (error reporting, launch checks).
+// Shared host-side plumbing of libmifwi (error reporting, launch checks, selector -> kernel instance).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -7,6 +7,7 @@
 #include <atomic>
 #include <cstdlib>
 #include <cstring>
+#include <type_traits>
 
 #include "../../include/mifwi.h"
 
@@ -109,6 +110,27 @@ inline int check_device(int device)
     if (device < 0 || device >= n)
         return fail(MIFWI_ENODEVICE, "device %d out of range (0..%d)", device, n - 1);
     return MIFWI_OK;
+}
+
+// the call's device made current (one process may drive all eight), the caller's stream
+inline int select_device(int device, void *stream, hipStream_t *st)
+{
+    int rc = check_device(device);
+    if (rc) return rc;
+    MIFWI_HIP_TRY(hipSetDevice(device));
+    *st = (hipStream_t)stream;
+    return MIFWI_OK;
+}
+
+// A runtime selector handed to `f` as a std::integral_constant, so that `f` names one instantiation of a kernel family;
+// with_int takes the values the family is built for, the last one serving every other value.
+template <class F>
+auto with_bool(bool b, F &&f) { return b ? f(std::true_type{}) : f(std::false_type{}); }
+template <int V, int... Rest, class F>
+auto with_int(int v, F &&f)
+{
+    if constexpr (sizeof...(Rest) == 0) return f(std::integral_constant<int, V>{});
+    else return v == V ? f(std::integral_constant<int, V>{}) : with_int<Rest...>(v, f);
 }
 
 // Dynamic-LDS ceiling requested for every cluster kernel.  The attribute is per function, not per

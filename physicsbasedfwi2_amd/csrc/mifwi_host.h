@@ -7,7 +7,6 @@
 #include "mifwi_common.h"
 
 #include <cmath>
-#include <type_traits>
 
 namespace mifwi {
 
@@ -15,16 +14,7 @@ namespace mifwi {
 // A kernel family has ONE function that maps its runtime selectors to the address of an instantiation (ac_cluster_variant,
 // el_step_variant, ...): the launch calls it and launches through the pointer, the LDS-attribute pass walks its whole
 // domain (mifwi::lds_cap_once).  The instantiations named inside that function are the ones the library carries.
-// with_bool / with_int hand a runtime selector to `f` as a std::integral_constant; with_int takes the values the family
-// is built for, the last one serving every other value.
-template <class F>
-auto with_bool(bool b, F &&f) { return b ? f(std::true_type{}) : f(std::false_type{}); }
-template <int V, int... Rest, class F>
-auto with_int(int v, F &&f)
-{
-    if constexpr (sizeof...(Rest) == 0) return f(std::integral_constant<int, V>{});
-    else return v == V ? f(std::integral_constant<int, V>{}) : with_int<Rest...>(v, f);
-}
+// with_bool / with_int (mifwi_common.h) hand a runtime selector to it as a std::integral_constant.
 
 // ---- the opening of a call ----------------------------------------------------------------------------
 // Range checks shared by the entry points (forward / Born: steps [n_begin, n_end); a pass that reads snapshots: the
@@ -46,15 +36,6 @@ inline int check_snapshots(int snap_first, int needed)
 {
     if (snap_first > needed)
         return fail(MIFWI_EINVAL, "snapshots start at step %d but step %d is needed", snap_first, needed);
-    return MIFWI_OK;
-}
-// the plan's device made current (one process may drive all eight), the caller's stream
-inline int select_device(int device, void *stream, hipStream_t *st)
-{
-    int rc = check_device(device);
-    if (rc) return rc;
-    MIFWI_HIP_TRY(hipSetDevice(device));
-    *st = (hipStream_t)stream;
     return MIFWI_OK;
 }
 // A propagation call once its arguments are checked (`m`: the physics' work_map of the call's work buffer): device and

@@ -13,30 +13,69 @@
 //       (a trace with |s| = 0 or |o| = 0 contributes nothing)
 // Layout [nt][ntrace] (trace = shot*nrec + receiver fastest), i.e. the propagators' own output.
 //
+// L2 and GLOBAL_CORRELATION also run on the traces of a frequency stage and of a trace selection, in ONE launch: F the
+// stage filter (mifwi_misfit_filter.h), W the selection (mifwi_misfit_select.h), either absent or both,
+//     L2                  r = float(W F(pred - obs));  loss = 1/2 sum r^2;  adj = float(F^T W r)
+//     GLOBAL_CORRELATION  s = float(W F pred), o = float(W F obs);  loss = -sum_traces <s,o>/(|s||o|);
+//                         adj = float(F^T W (ka o + kb s))
+// Each objective has one kernel body per grid, W in it as the SELECT instances (the others hold no trace of W):
+//     with a stage   misfit_staged_l2<NSEC, W...>, misfit_staged_gc<NSEC, W...>      one lane per trace, one wave
+//     without        misfit_gc<W...>, misfit_selected_l2_plain, misfit_l1_trace_norm  64 traces x 16 time slices
+//                    misfit_l2<VEC> (no F, no W: every sample on its own)             flat
+//
 // One workgroup = 64 neighbouring traces x 16 interleaved time slices: every wave reads whole
 // 256-byte rows, traces never leave their lane, the 16 slices of a trace meet twice in LDS
 // (max/argmax, then the sum the max's gradient needs).  HBM-bound: pred/direct are read twice,
 // obs once, adj written once = 28 B per sample (20 without a direct wave).
 #include "mifwi_common.h"
 
+#include "mifwi_misfit_filter.h"
+#include "mifwi_misfit_select.h"
+
 namespace {
 
-constexpr int kTr = 64, kSl = 16;          // traces x time slices per workgroup (1024 threads)
+using mifwi_filter::kLanes;                // traces per workgroup
+using mifwi_filter::Sos;
+using mifwi_filter::sweep;
+using mifwi_select::kSl;                   // time slices per workgroup of the kernels without a stage (1024 threads)
+using mifwi_select::pick;
+using mifwi_select::Sel;
+using mifwi_select::Trace;
+using mifwi_select::TraceOf;
 constexpr float kEps = 1e-10f;
 
 __device__ __forceinline__ float sgn(float x) { return x > 0.f ? 1.f : (x < 0.f ? -1.f : 0.f); }
 
-template <bool DIRECT>
-__global__ __launch_bounds__(kTr *kSl) void misfit_l1_trace_norm(const float *pred, const float *obs,
-                                                                 const float *direct, int nt, long long ntrace,
-                                                                 float inv_n, float *adj, double *partial)
+__device__ __forceinline__ double wave_sum(double v)
 {
-    __shared__ float s_max[kSl][kTr];
-    __shared__ int s_arg[kSl][kTr];
-    __shared__ float s_c[kSl][kTr];
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
+    return v;
+}
+
+// workgroup sum of the 64 x 16 kernels in a fixed order: the lanes of a wave, then the 16 waves
+__device__ __forceinline__ void block_sum(double v, double *s_loss, int lane, int sl, double *partial)
+{
+    v = wave_sum(v);
+    if (lane == 0) s_loss[sl] = v;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double tot = 0.0;
+        for (int k = 0; k < kSl; ++k) tot += s_loss[k];
+        partial[blockIdx.x] = tot;
+    }
+}
+
+template <bool DIRECT>
+__global__ __launch_bounds__(kLanes *kSl) void misfit_l1_trace_norm(const float *pred, const float *obs,
+                                                                    const float *direct, int nt, long long ntrace,
+                                                                    float inv_n, float *adj, double *partial)
+{
+    __shared__ float s_max[kSl][kLanes];
+    __shared__ int s_arg[kSl][kLanes];
+    __shared__ float s_c[kSl][kLanes];
     __shared__ double s_loss[kSl];
-    const int lane = (int)threadIdx.x % kTr, sl = (int)threadIdx.x / kTr;
-    const long long tr = (long long)blockIdx.x * kTr + lane;
+    const int lane = (int)threadIdx.x % kLanes, sl = (int)threadIdx.x / kLanes;
+    const long long tr = (long long)blockIdx.x * kLanes + lane;
     const bool live = tr < ntrace;
     // ---- pass 1: max |d| and the first time it is reached --------------------------------------
     float m = -1.f;
@@ -71,15 +110,7 @@ __global__ __launch_bounds__(kTr *kSl) void misfit_l1_trace_norm(const float *pr
             if (adj) adj[o] = a * inv;
         }
     s_c[sl][lane] = c;
-    // workgroup loss: wave reduction, then the 16 waves in order
-    for (int off = 32; off > 0; off >>= 1) loss += __shfl_down(loss, off, 64);
-    if (lane == 0) s_loss[sl] = loss;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        double tot = 0.0;
-        for (int k = 0; k < kSl; ++k) tot += s_loss[k];
-        partial[blockIdx.x] = tot;
-    }
+    block_sum(loss, s_loss, lane, sl, partial);          // its barrier publishes s_c as well
     // ---- the max feeds every sample of its trace: d(dn_t)/d(d_t*) = -d_t sign(d_t*) / (m+eps)^2 --
     if (live && adj && sl == arg % kSl) {
         float ctot = 0.f;
@@ -91,20 +122,33 @@ __global__ __launch_bounds__(kTr *kSl) void misfit_l1_trace_norm(const float *pr
     }
 }
 
-// global correlation: pass 1 the three inner products of a trace (fp64, fixed order), pass 2 the adjoint source
-__global__ __launch_bounds__(kTr *kSl) void misfit_global_correlation(const float *pred, const float *obs, int nt,
-                                                                      long long ntrace, float *adj, double *partial)
+// global correlation without a stage: pass 1 the three inner products of a trace (fp64, fixed order), pass 2 the adjoint
+// source.  W... = Sel (SELECT): of W pred, W obs; a killed trace is never read.  Where the body asks for SELECT by name
+// (here and in misfit_staged_gc) the two instances differ in which loads and sums they issue and in what order, not in
+// what they compute from finite data: each keeps the device code it was measured with.
+template <class... W>
+__global__ __launch_bounds__(kLanes *kSl) void misfit_gc(const W... sel, const float *pred, const float *obs, int nt,
+                                                         long long ntrace, float *adj, double *partial)
 {
-    __shared__ double s_ss[kSl][kTr], s_oo[kSl][kTr], s_so[kSl][kTr];
+    constexpr bool SELECT = sizeof...(W) != 0;
+    __shared__ double s_ss[kSl][kLanes], s_oo[kSl][kLanes], s_so[kSl][kLanes];
     __shared__ double s_loss[kSl];
-    const int lane = (int)threadIdx.x % kTr, sl = (int)threadIdx.x / kTr;
-    const long long tr = (long long)blockIdx.x * kTr + lane;
-    const bool live = tr < ntrace;
+    const int lane = (int)threadIdx.x % kLanes, sl = (int)threadIdx.x / kLanes;
+    const long long tr = (long long)blockIdx.x * kLanes + lane;
+    const bool inside = tr < ntrace;
+    const TraceOf<W...> s(sel..., tr, inside);
+    const bool live = SELECT ? s.live() : inside;
+    // s, o of sample t as the sums see them: rounded to float after W
+    auto sample = [&](int t, long long o, double &a, double &b) {
+        const auto w = s.w(t);
+        a = (double)(float)pick(w, (double)pred[o]); b = (double)(float)pick(w, (double)obs[o]);
+        return w;
+    };
     double ss = 0.0, oo = 0.0, so = 0.0;
     if (live)
         for (int t = sl; t < nt; t += kSl) {
-            const long long o = (long long)t * ntrace + tr;
-            const double a = (double)pred[o], b = (double)obs[o];
+            double a, b;
+            sample(t, (long long)t * ntrace + tr, a, b);
             ss += a * a; oo += b * b; so += a * b;
         }
     s_ss[sl][lane] = ss; s_oo[sl][lane] = oo; s_so[sl][lane] = so;
@@ -114,24 +158,165 @@ __global__ __launch_bounds__(kTr *kSl) void misfit_global_correlation(const floa
     for (int k = 0; k < kSl; ++k) { ss += s_ss[k][lane]; oo += s_oo[k][lane]; so += s_so[k][lane]; }
     const bool ok = live && ss > 0.0 && oo > 0.0;
     const double ns = sqrt(ss), no = sqrt(oo);
-    const double c = ok ? so / (ns * no) : 0.0;
-    if (adj && live) {
+    const double cc = ok ? so / (ns * no) : 0.0;
+    if (adj && inside) {
         // in double: on a weak trace the two coefficients overflow a float long before their combination does
         const double ka = ok ? -1.0 / (ns * no) : 0.0;               // coefficient of o
-        const double kb = ok ? c / ss : 0.0;                         // coefficient of s
+        const double kb = ok ? cc / ss : 0.0;                        // coefficient of s
         for (int t = sl; t < nt; t += kSl) {
             const long long o = (long long)t * ntrace + tr;
-            adj[o] = (float)(ka * (double)obs[o] + kb * (double)pred[o]);
+            float g = 0.f;
+            if constexpr (SELECT) {
+                if (ok) {
+                    double a, b;
+                    const auto w = sample(t, o, a, b);
+                    g = (float)pick(w, ka * b + kb * a);
+                }
+            } else {                                                 // a trace without energy gets 0 * its samples
+                g = (float)(ka * (double)obs[o] + kb * (double)pred[o]);
+            }
+            adj[o] = g;
         }
     }
-    double loss = sl == 0 ? -c : 0.0;                                   // one slice speaks for the trace
-    for (int off = 32; off > 0; off >>= 1) loss += __shfl_down(loss, off, 64);
-    if (lane == 0) s_loss[sl] = loss;
-    __syncthreads();
-    if (threadIdx.x == 0) partial[blockIdx.x] = s_loss[0];
+    double loss = sl == 0 ? -cc : 0.0;                                  // one slice speaks for the trace
+    if constexpr (SELECT) {
+        block_sum(loss, s_loss, lane, sl, partial);
+    } else {                                                            // the other fifteen slots hold zeros
+        for (int off = 32; off > 0; off >>= 1) loss += __shfl_down(loss, off, 64);
+        if (lane == 0) s_loss[sl] = loss;
+        __syncthreads();
+        if (threadIdx.x == 0) partial[blockIdx.x] = s_loss[0];
+    }
 }
 
-// VEC: pred, obs and adj are 16-byte aligned (decided on the host, mifwi_misfit); otherwise every group of four is
+// L2 of W (pred - obs) without a stage (without W as well: misfit_l2); a killed trace is never read
+__global__ __launch_bounds__(kLanes *kSl) void misfit_selected_l2_plain(const Sel sel, const float *pred, const float *obs,
+                                                                        int nt, long long ntrace, float *adj, double *partial)
+{
+    __shared__ double s_loss[kSl];
+    const int lane = (int)threadIdx.x % kLanes, sl = (int)threadIdx.x / kLanes;
+    const long long tr = (long long)blockIdx.x * kLanes + lane;
+    const bool inside = tr < ntrace;
+    const Trace s(sel, tr, inside);
+    double loss = 0.0;
+    if (inside)
+        for (int t = sl; t < nt; t += kSl) {
+            const long long o = (long long)t * ntrace + tr;
+            float g = 0.f;
+            if (s.live()) {
+                const double w = s.w(t);
+                const float r = (float)pick(w, (double)pred[o] - (double)obs[o]);
+                loss += (double)r * (double)r;
+                g = (float)pick(w, (double)r);
+            }
+            if (adj) adj[o] = g;
+        }
+    block_sum(loss, s_loss, lane, sl, partial);
+}
+
+// ---- with a stage: mifwi_filter::sweep, one lane per trace, one wave per workgroup --------------------------------
+// W... = Sel (SELECT): W after the forward sweep, W again before the reverse one.  A killed lane among live ones runs the
+// recurrence on zeros - its rows are requested like the others' (every load of a chunk stays unconditional) and dropped -
+// and a wave without a live trace runs no sweep and writes zeros.
+template <int NSEC, class... W>
+__global__ __launch_bounds__(kLanes) void misfit_staged_l2(const Sos c, const W... sel, const float *pred, const float *obs,
+                                                           int nt, long long ntrace, float *adj, double *partial)
+{
+    constexpr bool SELECT = sizeof...(W) != 0;
+    const long long tr = (long long)blockIdx.x * kLanes + threadIdx.x;
+    const bool inside = tr < ntrace;
+    const TraceOf<W...> s(sel..., tr, inside);
+    const bool live = s.live();
+    double loss = 0.0;
+    if (!SELECT || __any(live)) {
+        if (inside) {
+            // forward: r = W F(pred - obs), rounded to float where it is stored AND where it is summed
+            sweep<NSEC, 1, false>(c, nt,
+                                  [&](int t, double *v) {
+                                      const long long o = (long long)t * ntrace + tr;
+                                      const double x = (double)pred[o] - (double)obs[o];
+                                      v[0] = live ? x : 0.0;
+                                  },
+                                  [&](int t, const double *v) {
+                                      const float r = (float)pick(s.w(t), v[0]);
+                                      loss += (double)r * (double)r;
+                                      if (adj) adj[(long long)t * ntrace + tr] = r;
+                                  });
+            // backward: adj <- F^T W r in place (a lane only ever touches its own column)
+            if (adj)
+                sweep<NSEC, 1, true>(c, nt,
+                                     [&](int t, double *v) { v[0] = pick(s.w(t), (double)adj[(long long)t * ntrace + tr]); },
+                                     [&](int t, const double *v) { adj[(long long)t * ntrace + tr] = live ? (float)v[0] : 0.f; });
+        }
+    } else if (adj && inside) {
+        for (int t = 0; t < nt; ++t) adj[(long long)t * ntrace + tr] = 0.f;
+    }
+    loss = wave_sum(loss);
+    if (threadIdx.x == 0) partial[blockIdx.x] = loss;
+}
+
+// fobs [nt][ntrace]: W F obs, kept between the two sweeps
+template <int NSEC, class... W>
+__global__ __launch_bounds__(kLanes) void misfit_staged_gc(const Sos c, const W... sel, const float *pred, const float *obs,
+                                                           int nt, long long ntrace, float *adj, float *fobs, double *partial)
+{
+    constexpr bool SELECT = sizeof...(W) != 0;
+    const long long tr = (long long)blockIdx.x * kLanes + threadIdx.x;
+    const bool inside = tr < ntrace;
+    const TraceOf<W...> s(sel..., tr, inside);
+    const bool live = s.live();
+    double loss = 0.0;
+    if (!SELECT || __any(live)) {
+        if (inside) {
+            double ss = 0.0, oo = 0.0, so = 0.0;
+            sweep<NSEC, 2, false>(c, nt,
+                                  [&](int t, double *v) {
+                                      const long long o = (long long)t * ntrace + tr;
+                                      const double x = (double)pred[o], y = (double)obs[o];
+                                      v[0] = live ? x : 0.0;
+                                      v[1] = live ? y : 0.0;
+                                  },
+                                  [&](int t, const double *v) {
+                                      const auto w = s.w(t);
+                                      const float a = (float)pick(w, v[0]), b = (float)pick(w, v[1]);
+                                      ss += (double)a * (double)a; oo += (double)b * (double)b; so += (double)a * (double)b;
+                                      if (adj) {
+                                          const long long o = (long long)t * ntrace + tr;
+                                          adj[o] = a; fobs[o] = b;
+                                      }
+                                  });
+            const bool ok = ss > 0.0 && oo > 0.0;
+            const double ns = sqrt(ss), no = sqrt(oo);
+            const double cc = ok ? so / (ns * no) : 0.0;
+            loss = -cc;
+            if (adj) {
+                // coefficients as in misfit_gc; a trace without energy on either side gets zeros (SELECT: +0 as stored
+                // here; otherwise what the recurrence makes of zeros, of either sign)
+                const double ka = ok ? -1.0 / (ns * no) : 0.0, kb = ok ? cc / ss : 0.0;
+                sweep<NSEC, 1, true>(c, nt,
+                                     [&](int t, double *v) {
+                                         const long long o = (long long)t * ntrace + tr;
+                                         // SELECT: both rows requested whatever `ok` says, like every other row of a chunk
+                                         if constexpr (SELECT) {
+                                             const double x = ka * (double)fobs[o] + kb * (double)adj[o];
+                                             v[0] = ok ? pick(s.w(t), x) : 0.0;
+                                         } else {
+                                             v[0] = ok ? ka * (double)fobs[o] + kb * (double)adj[o] : 0.0;
+                                         }
+                                     },
+                                     [&](int t, const double *v) {
+                                         adj[(long long)t * ntrace + tr] = !SELECT || ok ? (float)v[0] : 0.f;
+                                     });
+            }
+        }
+    } else if (adj && inside) {
+        for (int t = 0; t < nt; ++t) adj[(long long)t * ntrace + tr] = 0.f;
+    }
+    loss = wave_sum(loss);
+    if (threadIdx.x == 0) partial[blockIdx.x] = loss;
+}
+
+// VEC: pred, obs and adj are 16-byte aligned (decided on the host, misfit_run); otherwise every group of four is
 // read one float at a time
 template <bool VEC>
 __global__ __launch_bounds__(256) void misfit_l2(const float *pred, const float *obs, long long n, float *adj,
@@ -177,131 +362,114 @@ __global__ __launch_bounds__(256) void misfit_finish(const double *partial, int 
     if (threadIdx.x == 0) *loss_out = (float)(s[0] * scale);
 }
 
+// ---- host: one size function and one path behind the three entry points ------------------------------------------
 int l2_blocks(long long n) { return (int)std::min<long long>(2048, (n / 4 + 255) / 256 + 1); }
 
-}  // namespace
+// the head of every work buffer: one double per workgroup, counted in floats
+int64_t partial_elems(long long blocks) { return mifwi::round_up64(2 * blocks + 2, 64); }
 
-#include "mifwi_misfit_filter.h"
-#include "mifwi_misfit_select.h"
-
-extern "C" {
-
-int64_t mifwi_misfit_work_elems(int32_t kind, int64_t nt, int64_t ntrace)
+// staged: the call has a stage filter; may_select: it may carry a selection.  Without a stage, L2 without a selection is
+// misfit_l2, which sums over another grid than every other kernel: a call that may go either way gets the larger buffer.
+int64_t work_elems(int32_t kind, int64_t nt, int64_t ntrace, bool staged, bool may_select)
 {
     if (nt < 1 || ntrace < 1) return 0;
-    const long long blocks = kind == MIFWI_MISFIT_L2 ? l2_blocks(nt * ntrace) : (ntrace + kTr - 1) / kTr;
-    return mifwi::round_up64(2 * blocks + 2, 64);          // doubles, counted in floats
+    const long long by_trace = mifwi_filter::blocks(ntrace);
+    if (staged) return partial_elems(by_trace) + (kind == MIFWI_MISFIT_GLOBAL_CORRELATION ? nt * ntrace : 0);   // + W F obs
+    const long long flat = kind == MIFWI_MISFIT_L2 ? l2_blocks(nt * ntrace) : by_trace;
+    return partial_elems(may_select ? std::max(flat, by_trace) : flat);
 }
 
-int mifwi_misfit(int device, int32_t kind, const float *pred, const float *obs, const float *direct,
-                 int64_t nt, int64_t ntrace, float *loss_out, float *adj_out, float *work, void *stream)
+// Loss and adjoint source of `kind`.  staged: F = sos[nsec] (HOST) applies; sel: W applies (NULL: nothing selected);
+// direct: L1_TRACE_NORM alone.  Nothing is enqueued before every argument is checked.
+int misfit_run(int device, int32_t kind, const float *pred, const float *obs, const float *direct, int64_t nt, int64_t ntrace,
+               bool staged, const double *sos, int32_t nsec, const Sel *sel, float *loss_out, float *adj_out, float *work,
+               void *stream)
 {
-    if (!pred || !obs || !loss_out || !work) return mifwi::fail(MIFWI_EINVAL, "null argument");
-    if (nt < 1 || ntrace < 1 || nt > 0x7fffffff)
-        return mifwi::fail(MIFWI_EINVAL, "bad sizes nt=%lld ntrace=%lld", (long long)nt, (long long)ntrace);
+    if (!pred || !obs || (staged && !sos) || !loss_out || !work) return mifwi::fail(MIFWI_EINVAL, "null argument");
+    if (staged && kind == MIFWI_MISFIT_L1_TRACE_NORM)
+        return mifwi::fail(MIFWI_EINVAL, "the trace-normalised L1 misfit has no stage filter (the acoustic protocol has no stage)");
     if (kind != MIFWI_MISFIT_L1_TRACE_NORM && kind != MIFWI_MISFIT_L2 && kind != MIFWI_MISFIT_GLOBAL_CORRELATION)
         return mifwi::fail(MIFWI_EINVAL, "unknown misfit kind %d", kind);
     if (kind != MIFWI_MISFIT_L1_TRACE_NORM && direct)
         return mifwi::fail(MIFWI_EINVAL, "only the trace-normalised L1 misfit takes a direct wave");
     if ((reinterpret_cast<uintptr_t>(work) & 7) != 0) return mifwi::fail(MIFWI_EINVAL, "work must be 8-byte aligned");
-    int rc = mifwi::check_device(device);
+    const bool flat = kind == MIFWI_MISFIT_L2 && !staged && !sel;          // misfit_l2; every other kernel: 64 traces a group
+    Sos c;
+    int rc = staged ? mifwi_filter::check(nt, ntrace, sos, nsec, &c) : mifwi_filter::check_sizes(nt, ntrace, !flat);
     if (rc) return rc;
-    MIFWI_HIP_TRY(hipSetDevice(device));
-    hipStream_t st = (hipStream_t)stream;
+    hipStream_t st;
+    rc = mifwi::select_device(device, stream, &st);
+    if (rc) return rc;
+
+    const int T = (int)nt;
+    const long long N = ntrace, n = nt * ntrace;
+    const int nblk = flat ? l2_blocks(n) : (int)mifwi_filter::blocks(ntrace);
+    const dim3 grid(nblk), wave(kLanes), slices(kLanes * kSl);
     double *partial = reinterpret_cast<double *>(work);
-    const long long n = nt * ntrace;
+    double scale = kind == MIFWI_MISFIT_L2 ? 0.5 : 1.0;
     if (kind == MIFWI_MISFIT_L1_TRACE_NORM) {
-        const long long blocks = (ntrace + kTr - 1) / kTr;
-        if (blocks > 0x7fffffff) return mifwi::fail(MIFWI_EINVAL, "too many traces");
-        const float inv_n = (float)(1.0 / (double)n);
-        if (direct)
-            hipLaunchKernelGGL(misfit_l1_trace_norm<true>, dim3((unsigned)blocks), dim3(kTr * kSl), 0, st, pred, obs,
-                               direct, (int)nt, (long long)ntrace, inv_n, adj_out, partial);
-        else
-            hipLaunchKernelGGL(misfit_l1_trace_norm<false>, dim3((unsigned)blocks), dim3(kTr * kSl), 0, st, pred, obs,
-                               direct, (int)nt, (long long)ntrace, inv_n, adj_out, partial);
-        hipLaunchKernelGGL(misfit_finish, dim3(1), dim3(256), 0, st, partial, (int)blocks, 1.0 / (double)n, loss_out);
-    } else if (kind == MIFWI_MISFIT_GLOBAL_CORRELATION) {
-        const long long blocks = (ntrace + kTr - 1) / kTr;
-        if (blocks > 0x7fffffff) return mifwi::fail(MIFWI_EINVAL, "too many traces");
-        hipLaunchKernelGGL(misfit_global_correlation, dim3((unsigned)blocks), dim3(kTr * kSl), 0, st, pred, obs, (int)nt,
-                           (long long)ntrace, adj_out, partial);
-        hipLaunchKernelGGL(misfit_finish, dim3(1), dim3(256), 0, st, partial, (int)blocks, 1.0, loss_out);
-    } else {
-        const int blocks = l2_blocks(n);
+        scale = 1.0 / (double)n;
+        mifwi::with_bool(direct != nullptr, [&](auto D) {
+            hipLaunchKernelGGL(misfit_l1_trace_norm<decltype(D)::value>, grid, slices, 0, st, pred, obs, direct, T, N,
+                               (float)scale, adj_out, partial);
+        });
+    } else if (flat) {
         // float4 loads and stores only where all three pointers allow them: a view such as buf[1:] is contiguous but
         // only 4-byte aligned, and the callers pass such views through unchanged
         const bool vec = ((reinterpret_cast<uintptr_t>(pred) | reinterpret_cast<uintptr_t>(obs) |
                            reinterpret_cast<uintptr_t>(adj_out)) & 15) == 0;
-        if (vec)
-            hipLaunchKernelGGL(misfit_l2<true>, dim3(blocks), dim3(256), 0, st, pred, obs, n, adj_out, partial);
+        mifwi::with_bool(vec, [&](auto VEC) {
+            hipLaunchKernelGGL(misfit_l2<decltype(VEC)::value>, grid, dim3(256), 0, st, pred, obs, n, adj_out, partial);
+        });
+    } else if (!staged) {
+        if (kind == MIFWI_MISFIT_L2)
+            hipLaunchKernelGGL(misfit_selected_l2_plain, grid, slices, 0, st, *sel, pred, obs, T, N, adj_out, partial);
+        else if (sel)
+            hipLaunchKernelGGL(misfit_gc<Sel>, grid, slices, 0, st, *sel, pred, obs, T, N, adj_out, partial);
         else
-            hipLaunchKernelGGL(misfit_l2<false>, dim3(blocks), dim3(256), 0, st, pred, obs, n, adj_out, partial);
-        hipLaunchKernelGGL(misfit_finish, dim3(1), dim3(256), 0, st, partial, blocks, 0.5, loss_out);
+            hipLaunchKernelGGL(misfit_gc<>, grid, slices, 0, st, pred, obs, T, N, adj_out, partial);
+    } else {
+        float *fobs = work + partial_elems(nblk);
+        mifwi::with_int<1, 2, 3, 4, 5, 6, 7, 8>(nsec, [&](auto NSEC) {
+            constexpr int S = decltype(NSEC)::value;
+            if (kind == MIFWI_MISFIT_L2 && sel)
+                hipLaunchKernelGGL((misfit_staged_l2<S, Sel>), grid, wave, 0, st, c, *sel, pred, obs, T, N, adj_out, partial);
+            else if (kind == MIFWI_MISFIT_L2)
+                hipLaunchKernelGGL(misfit_staged_l2<S>, grid, wave, 0, st, c, pred, obs, T, N, adj_out, partial);
+            else if (sel)
+                hipLaunchKernelGGL((misfit_staged_gc<S, Sel>), grid, wave, 0, st, c, *sel, pred, obs, T, N, adj_out, fobs, partial);
+            else
+                hipLaunchKernelGGL(misfit_staged_gc<S>, grid, wave, 0, st, c, pred, obs, T, N, adj_out, fobs, partial);
+        });
     }
+    hipLaunchKernelGGL(misfit_finish, dim3(1), dim3(256), 0, st, partial, nblk, scale, loss_out);
     MIFWI_HIP_TRY(hipGetLastError());
     return MIFWI_OK;
 }
 
-int mifwi_trace_filter(int device, const float *x, float *y, int64_t nt, int64_t ntrace, const double *sos,
-                       int32_t nsec, int32_t transpose, void *stream)
+}  // namespace
+
+extern "C" {
+
+int64_t mifwi_misfit_work_elems(int32_t kind, int64_t nt, int64_t ntrace) { return work_elems(kind, nt, ntrace, false, false); }
+
+int mifwi_misfit(int device, int32_t kind, const float *pred, const float *obs, const float *direct,
+                 int64_t nt, int64_t ntrace, float *loss_out, float *adj_out, float *work, void *stream)
 {
-    if (!x || !y || !sos) return mifwi::fail(MIFWI_EINVAL, "null argument");
-    mifwi_filter::Sos c;
-    int rc = mifwi_filter::check(nt, ntrace, sos, nsec, &c);
-    if (rc) return rc;
-    rc = mifwi::check_device(device);
-    if (rc) return rc;
-    MIFWI_HIP_TRY(hipSetDevice(device));
-    mifwi_filter::launch_plain(nsec, transpose != 0, (unsigned)mifwi_filter::blocks(ntrace), (hipStream_t)stream, c, x, y,
-                               (int)nt, (long long)ntrace);
-    MIFWI_HIP_TRY(hipGetLastError());
-    return MIFWI_OK;
+    return misfit_run(device, kind, pred, obs, direct, nt, ntrace, false, nullptr, 0, nullptr, loss_out, adj_out, work, stream);
 }
 
-int64_t mifwi_misfit_filtered_work_elems(int32_t kind, int64_t nt, int64_t ntrace)
-{
-    if (nt < 1 || ntrace < 1) return 0;
-    const int64_t partials = mifwi::round_up64(2 * mifwi_filter::blocks(ntrace) + 2, 64);      // doubles, counted in floats
-    return kind == MIFWI_MISFIT_GLOBAL_CORRELATION ? partials + nt * ntrace : partials;        // + the filtered obs
-}
+int64_t mifwi_misfit_filtered_work_elems(int32_t kind, int64_t nt, int64_t ntrace) { return work_elems(kind, nt, ntrace, true, false); }
 
 int mifwi_misfit_filtered(int device, int32_t kind, const float *pred, const float *obs, int64_t nt, int64_t ntrace,
                           const double *sos, int32_t nsec, float *loss_out, float *adj_out, float *work, void *stream)
 {
-    if (!pred || !obs || !sos || !loss_out || !work) return mifwi::fail(MIFWI_EINVAL, "null argument");
-    if (kind == MIFWI_MISFIT_L1_TRACE_NORM)
-        return mifwi::fail(MIFWI_EINVAL, "the trace-normalised L1 misfit has no stage filter (the acoustic protocol has no stage)");
-    if (kind != MIFWI_MISFIT_L2 && kind != MIFWI_MISFIT_GLOBAL_CORRELATION)
-        return mifwi::fail(MIFWI_EINVAL, "unknown misfit kind %d", kind);
-    if ((reinterpret_cast<uintptr_t>(work) & 7) != 0) return mifwi::fail(MIFWI_EINVAL, "work must be 8-byte aligned");
-    mifwi_filter::Sos c;
-    int rc = mifwi_filter::check(nt, ntrace, sos, nsec, &c);
-    if (rc) return rc;
-    rc = mifwi::check_device(device);
-    if (rc) return rc;
-    MIFWI_HIP_TRY(hipSetDevice(device));
-    hipStream_t st = (hipStream_t)stream;
-    const long long nblk = mifwi_filter::blocks(ntrace);
-    double *partial = reinterpret_cast<double *>(work);
-    if (kind == MIFWI_MISFIT_L2) {
-        mifwi_filter::launch_l2(nsec, (unsigned)nblk, st, c, pred, obs, (int)nt, (long long)ntrace, adj_out, partial);
-        hipLaunchKernelGGL(misfit_finish, dim3(1), dim3(256), 0, st, partial, (int)nblk, 0.5, loss_out);
-    } else {
-        float *fobs = work + mifwi::round_up64(2 * nblk + 2, 64);
-        mifwi_filter::launch_gc(nsec, (unsigned)nblk, st, c, pred, obs, (int)nt, (long long)ntrace, adj_out, fobs, partial);
-        hipLaunchKernelGGL(misfit_finish, dim3(1), dim3(256), 0, st, partial, (int)nblk, 1.0, loss_out);
-    }
-    MIFWI_HIP_TRY(hipGetLastError());
-    return MIFWI_OK;
+    return misfit_run(device, kind, pred, obs, nullptr, nt, ntrace, true, sos, nsec, nullptr, loss_out, adj_out, work, stream);
 }
 
 int64_t mifwi_misfit_selected_work_elems(int32_t kind, int64_t nt, int64_t ntrace, int32_t nsec)
 {
-    if (nt < 1 || ntrace < 1) return 0;
-    if (nsec > 0) return mifwi_misfit_filtered_work_elems(kind, nt, ntrace);
-    // without a selection the call is mifwi_misfit, whose L2 sums over another grid
-    return std::max<int64_t>(mifwi_misfit_work_elems(kind, nt, ntrace), mifwi::round_up64(2 * mifwi_filter::blocks(ntrace) + 2, 64));
+    return work_elems(kind, nt, ntrace, nsec > 0, true);
 }
 
 int mifwi_misfit_selected(int device, int32_t kind, const float *pred, const float *obs, int64_t nt, int64_t ntrace,
@@ -314,38 +482,29 @@ int mifwi_misfit_selected(int device, int32_t kind, const float *pred, const flo
         return mifwi::fail(MIFWI_EINVAL, "sos and nsec=%d disagree: sos is NULL exactly when nsec is 0 (no stage)", nsec);
     int rc = mifwi_select::check(t_on, t_off, gamma);
     if (rc) return rc;
-    if (!trace_w && !t_on)         // nothing selected: the very kernels of the calls without a selection
-        return sos ? mifwi_misfit_filtered(device, kind, pred, obs, nt, ntrace, sos, nsec, loss_out, adj_out, work, stream)
-                   : mifwi_misfit(device, kind, pred, obs, nullptr, nt, ntrace, loss_out, adj_out, work, stream);
-    if (!pred || !obs || !loss_out || !work) return mifwi::fail(MIFWI_EINVAL, "null argument");
-    if (kind != MIFWI_MISFIT_L2 && kind != MIFWI_MISFIT_GLOBAL_CORRELATION)
-        return mifwi::fail(MIFWI_EINVAL, "unknown misfit kind %d", kind);
-    if ((reinterpret_cast<uintptr_t>(work) & 7) != 0) return mifwi::fail(MIFWI_EINVAL, "work must be 8-byte aligned");
-    mifwi_filter::Sos c;
-    if (sos) {
-        rc = mifwi_filter::check(nt, ntrace, sos, nsec, &c);
-        if (rc) return rc;
-    } else {
-        if (nt < 1 || ntrace < 1 || nt > 0x7fffffff)
-            return mifwi::fail(MIFWI_EINVAL, "bad sizes nt=%lld ntrace=%lld", (long long)nt, (long long)ntrace);
-        if (mifwi_filter::blocks(ntrace) > 0x7fffffff) return mifwi::fail(MIFWI_EINVAL, "too many traces");
-        memset(&c, 0, sizeof(c));
-    }
-    rc = mifwi::check_device(device);
+    // nothing selected: the very instances of the calls without a selection
+    const Sel sel = {trace_w, t_on, t_off, gamma};
+    return misfit_run(device, kind, pred, obs, nullptr, nt, ntrace, sos != nullptr, sos, nsec, trace_w || t_on ? &sel : nullptr,
+                      loss_out, adj_out, work, stream);
+}
+
+int mifwi_trace_filter(int device, const float *x, float *y, int64_t nt, int64_t ntrace, const double *sos,
+                       int32_t nsec, int32_t transpose, void *stream)
+{
+    if (!x || !y || !sos) return mifwi::fail(MIFWI_EINVAL, "null argument");
+    Sos c;
+    int rc = mifwi_filter::check(nt, ntrace, sos, nsec, &c);
     if (rc) return rc;
-    MIFWI_HIP_TRY(hipSetDevice(device));
-    hipStream_t st = (hipStream_t)stream;
-    const long long nblk = mifwi_filter::blocks(ntrace);
-    const mifwi_select::Sel sel = {trace_w, t_on, t_off, gamma};
-    double *partial = reinterpret_cast<double *>(work);
-    if (kind == MIFWI_MISFIT_L2) {
-        mifwi_select::launch_l2(nsec, (unsigned)nblk, st, c, sel, pred, obs, (int)nt, (long long)ntrace, adj_out, partial);
-        hipLaunchKernelGGL(misfit_finish, dim3(1), dim3(256), 0, st, partial, (int)nblk, 0.5, loss_out);
-    } else {
-        float *fobs = work + mifwi::round_up64(2 * nblk + 2, 64);          // read with a stage only
-        mifwi_select::launch_gc(nsec, (unsigned)nblk, st, c, sel, pred, obs, (int)nt, (long long)ntrace, adj_out, fobs, partial);
-        hipLaunchKernelGGL(misfit_finish, dim3(1), dim3(256), 0, st, partial, (int)nblk, 1.0, loss_out);
-    }
+    hipStream_t st;
+    rc = mifwi::select_device(device, stream, &st);
+    if (rc) return rc;
+    mifwi::with_int<1, 2, 3, 4, 5, 6, 7, 8>(nsec, [&](auto NSEC) {
+        mifwi::with_bool(transpose != 0, [&](auto REV) {
+            hipLaunchKernelGGL((mifwi_filter::trace_filter<decltype(NSEC)::value, decltype(REV)::value>),
+                               dim3((unsigned)mifwi_filter::blocks(ntrace)), dim3(kLanes), 0, st, c, x, y, (int)nt,
+                               (long long)ntrace);
+        });
+    });
     MIFWI_HIP_TRY(hipGetLastError());
     return MIFWI_OK;
 }
@@ -354,18 +513,16 @@ int mifwi_trace_window(int device, const float *x, float *y, int64_t nt, int64_t
                        const float *t_on, const float *t_off, double gamma, void *stream)
 {
     if (!x || !y) return mifwi::fail(MIFWI_EINVAL, "null argument");
-    if (nt < 1 || ntrace < 1 || nt > 0x7fffffff)
-        return mifwi::fail(MIFWI_EINVAL, "bad sizes nt=%lld ntrace=%lld", (long long)nt, (long long)ntrace);
-    if (mifwi_filter::blocks(ntrace) > 0x7fffffff) return mifwi::fail(MIFWI_EINVAL, "too many traces");
-    int rc = mifwi_select::check(t_on, t_off, gamma);
+    int rc = mifwi_filter::check_sizes(nt, ntrace);
     if (rc) return rc;
-    rc = mifwi::check_device(device);
+    rc = mifwi_select::check(t_on, t_off, gamma);
     if (rc) return rc;
-    MIFWI_HIP_TRY(hipSetDevice(device));
-    const mifwi_select::Sel sel = {trace_w, t_on, t_off, gamma};
-    hipLaunchKernelGGL(mifwi_select::trace_window, dim3((unsigned)mifwi_filter::blocks(ntrace)),
-                       dim3(mifwi_select::kLanes * mifwi_select::kSl), 0, (hipStream_t)stream, sel, x, y, (int)nt,
-                       (long long)ntrace);
+    hipStream_t st;
+    rc = mifwi::select_device(device, stream, &st);
+    if (rc) return rc;
+    const Sel sel = {trace_w, t_on, t_off, gamma};
+    hipLaunchKernelGGL(mifwi_select::trace_window, dim3((unsigned)mifwi_filter::blocks(ntrace)), dim3(kLanes * kSl), 0, st,
+                       sel, x, y, (int)nt, (long long)ntrace);
     MIFWI_HIP_TRY(hipGetLastError());
     return MIFWI_OK;
 }

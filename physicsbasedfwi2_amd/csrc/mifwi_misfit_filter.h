@@ -1,8 +1,7 @@
-// Stage-filtered misfit kernels (included by mifwi_misfit.hip): the causal recursive Butterworth filter F that DENISE's
-// frequency stages apply along time (add_fwi_stage(fc_low, fc_high), models/networks.py:6374 ... 11676), its transpose,
-// and the two objectives of the elastic protocol evaluated on the filtered traces in ONE launch:
-//     L2                  r = F(pred - obs);  loss = 1/2 sum r^2;              adj = F^T r
-//     GLOBAL_CORRELATION  s = F pred, o = F obs;  loss = -sum_traces <s,o>/(|s||o|);  adj = F^T(ka o + kb s)
+// The stage filter F of the misfit kernels (included by mifwi_misfit.hip): the causal recursive Butterworth filter that
+// DENISE's frequency stages apply along time (add_fwi_stage(fc_low, fc_high), models/networks.py:6374 ... 11676) and its
+// transpose, as the sweep that the staged objectives of mifwi_misfit.hip (misfit_staged_l2, misfit_staged_gc) run inside
+// their one launch, and as a kernel of its own (trace_filter).
 // F is a cascade of nsec second-order sections in transposed direct form II with zero initial state,
 //     y = b0 x + s1;   s1 = b1 x - a1 y + s2;   s2 = b2 x - a2 y;     (x of the next section = y)
 // which is what scipy.signal.sosfilt runs; F^T is the same recurrence from the last sample to the first (exact for a finite
@@ -85,12 +84,6 @@ __device__ __forceinline__ void sweep(const Sos &c, int nt, In in, Out out)
     }
 }
 
-__device__ __forceinline__ double wave_sum(double v)
-{
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-    return v;
-}
-
 // y = F x (REV: F^T x); y == x allowed
 template <int NSEC, bool REV>
 __global__ __launch_bounds__(kLanes) void trace_filter(const Sos c, const float *x, float *y, int nt, long long ntrace)
@@ -101,83 +94,23 @@ __global__ __launch_bounds__(kLanes) void trace_filter(const Sos c, const float 
                         [&](int t, const double *v) { y[(long long)t * ntrace + tr] = (float)v[0]; });
 }
 
-template <int NSEC>
-__global__ __launch_bounds__(kLanes) void misfit_filtered_l2(const Sos c, const float *pred, const float *obs, int nt,
-                                                             long long ntrace, float *adj, double *partial)
-{
-    const long long tr = (long long)blockIdx.x * kLanes + threadIdx.x;
-    double loss = 0.0;
-    if (tr < ntrace) {
-        // forward: r = F(pred - obs), rounded to float where it is stored AND where it is summed
-        sweep<NSEC, 1, false>(c, nt,
-                              [&](int t, double *v) {
-                                  const long long o = (long long)t * ntrace + tr;
-                                  v[0] = (double)pred[o] - (double)obs[o];
-                              },
-                              [&](int t, const double *v) {
-                                  const float r = (float)v[0];
-                                  loss += (double)r * (double)r;
-                                  if (adj) adj[(long long)t * ntrace + tr] = r;
-                              });
-        // backward: adj <- F^T r in place (a lane only ever touches its own column)
-        if (adj)
-            sweep<NSEC, 1, true>(c, nt, [&](int t, double *v) { v[0] = (double)adj[(long long)t * ntrace + tr]; },
-                                 [&](int t, const double *v) { adj[(long long)t * ntrace + tr] = (float)v[0]; });
-    }
-    loss = wave_sum(loss);
-    if (threadIdx.x == 0) partial[blockIdx.x] = loss;
-}
-
-template <int NSEC>
-__global__ __launch_bounds__(kLanes) void misfit_filtered_gc(const Sos c, const float *pred, const float *obs, int nt,
-                                                             long long ntrace, float *adj, float *fobs, double *partial)
-{
-    const long long tr = (long long)blockIdx.x * kLanes + threadIdx.x;
-    double loss = 0.0;
-    if (tr < ntrace) {
-        double ss = 0.0, oo = 0.0, so = 0.0;
-        sweep<NSEC, 2, false>(c, nt,
-                              [&](int t, double *v) {
-                                  const long long o = (long long)t * ntrace + tr;
-                                  v[0] = (double)pred[o];
-                                  v[1] = (double)obs[o];
-                              },
-                              [&](int t, const double *v) {
-                                  const float a = (float)v[0], b = (float)v[1];
-                                  ss += (double)a * (double)a; oo += (double)b * (double)b; so += (double)a * (double)b;
-                                  if (adj) {
-                                      const long long o = (long long)t * ntrace + tr;
-                                      adj[o] = a; fobs[o] = b;
-                                  }
-                              });
-        const bool ok = ss > 0.0 && oo > 0.0;
-        const double ns = sqrt(ss), no = sqrt(oo);
-        const double cc = ok ? so / (ns * no) : 0.0;
-        loss = -cc;
-        if (adj) {
-            // coefficients as in misfit_global_correlation; a trace without energy on either side gets exact zeros
-            const double ka = ok ? -1.0 / (ns * no) : 0.0, kb = ok ? cc / ss : 0.0;
-            sweep<NSEC, 1, true>(c, nt,
-                                 [&](int t, double *v) {
-                                     const long long o = (long long)t * ntrace + tr;
-                                     v[0] = ok ? ka * (double)fobs[o] + kb * (double)adj[o] : 0.0;
-                                 },
-                                 [&](int t, const double *v) { adj[(long long)t * ntrace + tr] = (float)v[0]; });
-        }
-    }
-    loss = wave_sum(loss);
-    if (threadIdx.x == 0) partial[blockIdx.x] = loss;
-}
 #endif  // __HIPCC__
 
 inline long long blocks(long long ntrace) { return (ntrace + kLanes - 1) / kLanes; }
 
-// sizes as mifwi_misfit rejects them; sos: HOST [nsec][6] rows b0 b1 b2 a0 a1 a2 (scipy's order), a0 == 1
-inline int check(int64_t nt, int64_t ntrace, const double *sos, int32_t nsec, Sos *c)
+// sizes as every misfit entry point rejects them; by_trace: the grid has one workgroup per kLanes traces
+inline int check_sizes(int64_t nt, int64_t ntrace, bool by_trace = true)
 {
     if (nt < 1 || ntrace < 1 || nt > 0x7fffffff)
         return mifwi::fail(MIFWI_EINVAL, "bad sizes nt=%lld ntrace=%lld", (long long)nt, (long long)ntrace);
-    if (blocks(ntrace) > 0x7fffffff) return mifwi::fail(MIFWI_EINVAL, "too many traces");
+    if (by_trace && blocks(ntrace) > 0x7fffffff) return mifwi::fail(MIFWI_EINVAL, "too many traces");
+    return MIFWI_OK;
+}
+
+// sos: HOST [nsec][6] rows b0 b1 b2 a0 a1 a2 (scipy's order), a0 == 1
+inline int check(int64_t nt, int64_t ntrace, const double *sos, int32_t nsec, Sos *c)
+{
+    if (int rc = check_sizes(nt, ntrace)) return rc;
     if (nsec < 1 || nsec > MIFWI_FILTER_MAX_SECTIONS)
         return mifwi::fail(MIFWI_EINVAL, "nsec=%d: a stage filter has 1 ... %d second-order sections", nsec,
                            (int)MIFWI_FILTER_MAX_SECTIONS);
@@ -191,48 +124,5 @@ inline int check(int64_t nt, int64_t ntrace, const double *sos, int32_t nsec, So
     }
     return MIFWI_OK;
 }
-
-#ifdef __HIPCC__
-#define MIFWI_FILTER_BY_NSEC(CALL)                                                                                   \
-    switch (nsec) {                                                                                                  \
-    case 1: CALL(1); break;                                                                                          \
-    case 2: CALL(2); break;                                                                                          \
-    case 3: CALL(3); break;                                                                                          \
-    case 4: CALL(4); break;                                                                                          \
-    case 5: CALL(5); break;                                                                                          \
-    case 6: CALL(6); break;                                                                                          \
-    case 7: CALL(7); break;                                                                                          \
-    default: CALL(8); break;                                                                                         \
-    }
-
-inline void launch_plain(int nsec, bool rev, unsigned nblk, hipStream_t st, const Sos &c, const float *x, float *y, int nt,
-                         long long ntrace)
-{
-#define MIFWI_CALL(N)                                                                                                \
-    if (rev) hipLaunchKernelGGL((trace_filter<N, true>), dim3(nblk), dim3(kLanes), 0, st, c, x, y, nt, ntrace);      \
-    else hipLaunchKernelGGL((trace_filter<N, false>), dim3(nblk), dim3(kLanes), 0, st, c, x, y, nt, ntrace)
-    MIFWI_FILTER_BY_NSEC(MIFWI_CALL)
-#undef MIFWI_CALL
-}
-
-inline void launch_l2(int nsec, unsigned nblk, hipStream_t st, const Sos &c, const float *pred, const float *obs, int nt,
-                      long long ntrace, float *adj, double *partial)
-{
-#define MIFWI_CALL(N) \
-    hipLaunchKernelGGL(misfit_filtered_l2<N>, dim3(nblk), dim3(kLanes), 0, st, c, pred, obs, nt, ntrace, adj, partial)
-    MIFWI_FILTER_BY_NSEC(MIFWI_CALL)
-#undef MIFWI_CALL
-}
-
-inline void launch_gc(int nsec, unsigned nblk, hipStream_t st, const Sos &c, const float *pred, const float *obs, int nt,
-                      long long ntrace, float *adj, float *fobs, double *partial)
-{
-#define MIFWI_CALL(N) \
-    hipLaunchKernelGGL(misfit_filtered_gc<N>, dim3(nblk), dim3(kLanes), 0, st, c, pred, obs, nt, ntrace, adj, fobs, partial)
-    MIFWI_FILTER_BY_NSEC(MIFWI_CALL)
-#undef MIFWI_CALL
-}
-#undef MIFWI_FILTER_BY_NSEC
-#endif  // __HIPCC__
 
 }  // namespace mifwi_filter

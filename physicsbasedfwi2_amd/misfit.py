@@ -40,59 +40,63 @@ from . import _lib
 
 
 class _MisfitFn(torch.autograd.Function):
+    """Loss and adjoint source of ``kind`` in one call: mifwi_misfit_selected with ``select``, mifwi_misfit_filtered with
+    ``sos`` alone, mifwi_misfit with neither (the only one that takes ``direct``)."""
+
     @staticmethod
-    def forward(ctx, pred, obs, direct, kind):
+    def forward(ctx, pred, obs, direct, sos, select, kind):
         if not pred.is_cuda:
             raise _lib.MifwiError("misfit needs CUDA/HIP tensors (libmifwi has no CPU fallback)")
         if pred.dim() < 2 or obs.shape != pred.shape or (direct is not None and direct.shape != pred.shape):
-            raise ValueError("pred, obs (and direct) must share one [nt, ...] shape")
+            raise ValueError("pred%s must share one [nt, ...] shape" % (", obs (and direct)" if sos is None and select is None
+                                                                         else " and obs"))
+        sel = None if select is None else select._on(pred.device, pred.shape[1:])
         lib = _lib.load()
         p = pred.detach().contiguous().float()
         o = obs.detach().contiguous().float()
         d = None if direct is None else direct.detach().contiguous().float()
         nt = p.shape[0]
         ntrace = p.numel() // nt
-        need_adj = pred.requires_grad
-        adj = torch.empty_like(p) if need_adj else None
+        adj = torch.empty_like(p) if pred.requires_grad else None
         loss = torch.empty((), device=p.device, dtype=torch.float32)
-        work = torch.empty(lib.mifwi_misfit_work_elems(kind, nt, ntrace), device=p.device, dtype=torch.float32)
-        _lib.check(lib.mifwi_misfit(p.device.index or 0, kind, _lib.ptr(p), _lib.ptr(o), _lib.ptr(d), nt,
-                                    ntrace, _lib.ptr(loss), _lib.ptr(adj), _lib.ptr(work),
-                                    torch.cuda.current_stream(p.device).cuda_stream))
+        head = (p.device.index or 0, kind, _lib.ptr(p), _lib.ptr(o))
+        stage = (None, 0) if sos is None else (_sos_ptr(sos), sos.shape[0])
+        if select is not None:
+            elems = lib.mifwi_misfit_selected_work_elems(kind, nt, ntrace, stage[1])
+            call, args = lib.mifwi_misfit_selected, head + (nt, ntrace) + stage + tuple(map(_lib.ptr, sel)) + (select.gamma,)
+        elif sos is not None:
+            elems = lib.mifwi_misfit_filtered_work_elems(kind, nt, ntrace)
+            call, args = lib.mifwi_misfit_filtered, head + (nt, ntrace) + stage
+        else:
+            elems = lib.mifwi_misfit_work_elems(kind, nt, ntrace)
+            call, args = lib.mifwi_misfit, head + (_lib.ptr(d), nt, ntrace)
+        work = torch.empty(elems, device=p.device, dtype=torch.float32)
+        _lib.check(call(*args, _lib.ptr(loss), _lib.ptr(adj), _lib.ptr(work), torch.cuda.current_stream(p.device).cuda_stream))
         ctx.adj = adj
         return loss
 
     @staticmethod
     def backward(ctx, g):
         # the adjoint source stays with the graph (a second backward through a retained graph gets it again)
-        return (None if ctx.adj is None else ctx.adj * g), None, None, None
+        return (None if ctx.adj is None else ctx.adj * g), None, None, None, None, None
 
 
 def l1_trace_normalized(pred, obs_norm, direct=None):
     """mean |(pred - direct) / (max_t |pred - direct| + 1e-10) - obs_norm|, time on axis 0."""
-    return _MisfitFn.apply(pred, obs_norm, direct, _lib.MISFIT_L1_TRACE_NORM)
+    return _MisfitFn.apply(pred, obs_norm, direct, None, None, _lib.MISFIT_L1_TRACE_NORM)
 
 
 def l2_half(pred, obs, sos=None, select=None):
     """0.5 * sum((pred - obs)**2); with ``sos`` (:func:`butterworth_sos`) of the stage-filtered traces,
     0.5 * sum(F(pred - obs)**2), time on axis 0; with ``select`` (:class:`TraceSelection`) 0.5 * sum((W F(pred - obs))**2)."""
-    if select is not None:
-        return _SelectedMisfitFn.apply(pred, obs, None if sos is None else _sos_array(sos), _lib.MISFIT_L2, select)
-    if sos is not None:
-        return _FilteredMisfitFn.apply(pred, obs, _sos_array(sos), _lib.MISFIT_L2)
-    return _MisfitFn.apply(pred, obs, None, _lib.MISFIT_L2)
+    return _MisfitFn.apply(pred, obs, None, None if sos is None else _sos_array(sos), select, _lib.MISFIT_L2)
 
 
 def global_correlation(pred, obs, sos=None, select=None):
     """-sum over traces of <pred, obs> / (|pred| |obs|), time on axis 0 (insensitive to trace amplitudes); with ``sos``
     (:func:`butterworth_sos`) of the stage-filtered traces F pred, F obs; with ``select`` (:class:`TraceSelection`) of
     W F pred, W F obs."""
-    if select is not None:
-        return _SelectedMisfitFn.apply(pred, obs, None if sos is None else _sos_array(sos), _lib.MISFIT_GLOBAL_CORRELATION,
-                                       select)
-    if sos is not None:
-        return _FilteredMisfitFn.apply(pred, obs, _sos_array(sos), _lib.MISFIT_GLOBAL_CORRELATION)
-    return _MisfitFn.apply(pred, obs, None, _lib.MISFIT_GLOBAL_CORRELATION)
+    return _MisfitFn.apply(pred, obs, None, None if sos is None else _sos_array(sos), select, _lib.MISFIT_GLOBAL_CORRELATION)
 
 
 def butterworth_sos(dt, fc_low=0.0, fc_high=0.0, order=6):
@@ -160,32 +164,6 @@ def trace_filter(x, sos, transpose=False):
     zero initial conditions); ``transpose=True``: y = F^T x, the same recurrence from the last sample to the first.
     Differentiable: the backward of one is the other."""
     return _TraceFilterFn.apply(x, _sos_array(sos), bool(transpose))
-
-
-class _FilteredMisfitFn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, pred, obs, sos, kind):
-        if not pred.is_cuda:
-            raise _lib.MifwiError("misfit needs CUDA/HIP tensors (libmifwi has no CPU fallback)")
-        if pred.dim() < 2 or obs.shape != pred.shape:
-            raise ValueError("pred and obs must share one [nt, ...] shape")
-        lib = _lib.load()
-        p = pred.detach().contiguous().float()
-        o = obs.detach().contiguous().float()
-        nt = p.shape[0]
-        ntrace = p.numel() // nt
-        adj = torch.empty_like(p) if pred.requires_grad else None
-        loss = torch.empty((), device=p.device, dtype=torch.float32)
-        work = torch.empty(lib.mifwi_misfit_filtered_work_elems(kind, nt, ntrace), device=p.device, dtype=torch.float32)
-        _lib.check(lib.mifwi_misfit_filtered(p.device.index or 0, kind, _lib.ptr(p), _lib.ptr(o), nt, ntrace, _sos_ptr(sos),
-                                             sos.shape[0], _lib.ptr(loss), _lib.ptr(adj), _lib.ptr(work),
-                                             torch.cuda.current_stream(p.device).cuda_stream))
-        ctx.adj = adj
-        return loss
-
-    @staticmethod
-    def backward(ctx, g):
-        return (None if ctx.adj is None else ctx.adj * g), None, None, None
 
 
 class TraceSelection:
@@ -267,35 +245,6 @@ class TraceSelection:
             self._dev[device] = tuple(None if a is None else torch.from_numpy(a).to(device)
                                       for a in (self.weight, self.t_on, self.t_off))
         return self._dev[device]
-
-
-class _SelectedMisfitFn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, pred, obs, sos, kind, select):
-        if not pred.is_cuda:
-            raise _lib.MifwiError("misfit needs CUDA/HIP tensors (libmifwi has no CPU fallback)")
-        if pred.dim() < 2 or obs.shape != pred.shape:
-            raise ValueError("pred and obs must share one [nt, ...] shape")
-        a, on, off = select._on(pred.device, pred.shape[1:])
-        lib = _lib.load()
-        p = pred.detach().contiguous().float()
-        o = obs.detach().contiguous().float()
-        nt = p.shape[0]
-        ntrace = p.numel() // nt
-        nsec = 0 if sos is None else sos.shape[0]
-        adj = torch.empty_like(p) if pred.requires_grad else None
-        loss = torch.empty((), device=p.device, dtype=torch.float32)
-        work = torch.empty(lib.mifwi_misfit_selected_work_elems(kind, nt, ntrace, nsec), device=p.device, dtype=torch.float32)
-        _lib.check(lib.mifwi_misfit_selected(p.device.index or 0, kind, _lib.ptr(p), _lib.ptr(o), nt, ntrace,
-                                             None if sos is None else _sos_ptr(sos), nsec, _lib.ptr(a), _lib.ptr(on),
-                                             _lib.ptr(off), select.gamma, _lib.ptr(loss), _lib.ptr(adj), _lib.ptr(work),
-                                             torch.cuda.current_stream(p.device).cuda_stream))
-        ctx.adj = adj
-        return loss
-
-    @staticmethod
-    def backward(ctx, g):
-        return (None if ctx.adj is None else ctx.adj * g), None, None, None, None
 
 
 class _TraceWindowFn(torch.autograd.Function):

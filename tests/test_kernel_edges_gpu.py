@@ -166,7 +166,7 @@ def _gc_check(pred, obs, where):
 
 
 def test_global_correlation_edges():
-    """misfit_global_correlation: nt = 1, a trace with |pred| ~ 1e-30 (its two coefficients overflow a float: the double
+    """misfit_gc: nt = 1, a trace with |pred| ~ 1e-30 (its two coefficients overflow a float: the double
     path), and dead traces on either side for every trace count remainder modulo the 64-trace workgroup."""
     rng = np.random.default_rng(41)
     for nt in (1, 37):

@@ -45,10 +45,12 @@ def kernel_resources():
                           stderr=subprocess.PIPE).stderr
     out = {}
     for block in text.split("Function Name: ")[1:]:
-        m = re.match(r"_ZN12mifwi_filter\d+(trace_filter|misfit_filtered_l2|misfit_filtered_gc)ILi(\d)E(?:Lb([01])E)?", block)
+        # misfit_filtered_l2 / _gc: the instances of misfit_staged_l2 / _gc<NSEC, W...> without a selection (W... empty)
+        m = re.match(r"_ZN12mifwi_filter\d+(trace_filter)ILi(\d)ELb([01])E|_ZN12_GLOBAL__N_1\d+misfit_staged_(l2|gc)ILi(\d)EJEEE", block)
         if not m:
             continue
-        name = "%s<nsec=%s%s>" % (m.group(1), m.group(2), "" if m.group(3) is None else ", transpose=%s" % m.group(3))
+        name = ("trace_filter<nsec=%s, transpose=%s>" % m.group(2, 3) if m.group(1) else
+                "misfit_filtered_%s<nsec=%s>" % m.group(4, 5))
         grab = lambda key: int(re.search(re.escape(key) + r": (\d+)", block).group(1))
         out[name] = {"vgprs": grab("VGPRs"), "sgprs": grab("TotalSGPRs"), "sgprs_spilled_to_vgpr_lanes": grab("SGPRs Spill"),
                      "scratch_bytes_per_lane": grab("ScratchSize [bytes/lane]"),

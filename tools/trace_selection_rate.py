@@ -44,18 +44,21 @@ KINDS = {"l2": misfit.l2_half, "gc": misfit.global_correlation}
 
 
 def kernel_resources():
-    """VGPRs, SGPRs, scratch and occupancy of every kernel of csrc/mifwi_misfit_select.h, from
+    """VGPRs, SGPRs, scratch and occupancy of every kernel that applies a trace selection (csrc/mifwi_misfit_select.h), from
     hipcc -Rpass-analysis=kernel-resource-usage.  Scratch must be 0: the section state lives in registers."""
     flags = [f for f in build.FLAGS if f != "-shared"] + ["-c", "-o", os.devnull, "-Rpass-analysis=kernel-resource-usage"]
     text = subprocess.run([build.HIPCC] + flags + [os.path.join(build.CSRC, "mifwi_misfit.hip")], check=True, text=True,
                           stderr=subprocess.PIPE).stderr
     out = {}
     for block in text.split("Function Name: ")[1:]:
-        m = re.match(r"_ZN12mifwi_select\d+(misfit_selected_l2_plain|misfit_selected_gc_plain|trace_window|misfit_selected_l2|"
-                     r"misfit_selected_gc)(?:ILi(\d)E)?", block)
+        # misfit_selected_l2 / _gc and misfit_selected_gc_plain: the instances of misfit_staged_l2 / _gc<NSEC, W...> and of
+        # misfit_gc<W...> with a selection (W... = mifwi_select::Sel)
+        m = re.match(r"_ZN12mifwi_select\d+(trace_window)|_ZN12_GLOBAL__N_1\d+(?:(misfit_selected_l2_plain)|"
+                     r"misfit_(gc)IJN12mifwi_select3SelEEEE|misfit_staged_(l2|gc)ILi(\d)EJN12mifwi_select3SelEEEE)", block)
         if not m:
             continue
-        name = m.group(1) if m.group(2) is None else "%s<nsec=%s>" % (m.group(1), m.group(2))
+        name = (m.group(1) or m.group(2) or ("misfit_selected_gc_plain" if m.group(3) else
+                                             "misfit_selected_%s<nsec=%s>" % m.group(4, 5)))
         grab = lambda key: int(re.search(re.escape(key) + r": (\d+)", block).group(1))
         out[name] = {"vgprs": grab("VGPRs"), "agprs": grab("AGPRs"), "sgprs": grab("TotalSGPRs"),
                      "sgprs_spilled_to_vgpr_lanes": grab("SGPRs Spill"),
