@@ -737,6 +737,37 @@ int mifwi_trace_convolve(int device, const float *x, float *y, const float *filt
                          int32_t transpose, void *stream);
 
 /* ======================================================================================
+ * ENVELOPE MISFIT: the Hilbert transform along time, the envelope residual and its exact adjoint source (DENISE's lnorm = 6)
+ *
+ * The envelope objective of Chi, Dong and Liu (2014), used for the first low-frequency stages because it does not cycle-skip
+ * where the sample-by-sample objectives do.  This library's documented choice (DENISE's binary is not available to pin against):
+ * H on R^nt: with N the smallest power of two >= nt, zero-pad the trace to N, take the DFT, multiply bin k by -i for
+ * 0 < k < N/2, by +i for N/2 < k < N and by 0 for k = 0 and k = N/2, take the inverse DFT (with its 1/N) and keep the real part
+ * of the first nt samples: scipy.signal.hilbert(x, N=N, axis=0).imag[:nt]; H = 0 for N <= 2.  The multiplier is antisymmetric,
+ * so H^T = -H exactly, and the transposed call returns the negated bits.
+ *     E(x) = sqrt(x^2 + H(x)^2 + eps^2)            eps >= 0, one absolute scalar per call
+ *     s = pred, o = obs, h = H s, r = E(s) - E(o):   loss = 1/2 sum r^2;   adj_out = dloss/ds = r s / E(s) - H(r h / E(s))
+ * A term whose divisor E(s) is zero (possible with eps == 0 only) contributes 0.  |s| / E <= 1 and |h| / E <= 1: the adjoint
+ * source is bounded by 2 |r| even where the envelope is small.
+ * Traces are [nt][ntrace], time slowest; nt <= MIFWI_ENVELOPE_MAX_NT (a padded trace and its transform live in one workgroup's
+ * LDS: an N/2-point complex FFT of the trace's even and odd samples, float arithmetic, twiddle factors rounded once from
+ * double; envelope, residual and loss terms in double).  A trace is transformed on its own: an all-zero trace gives exact zeros.
+ *   mifwi_trace_hilbert    y = H x (transpose != 0: y = H^T x = -H x); y == x allowed
+ *   mifwi_misfit_envelope  one launch for both transforms, envelope, residual and the second Hilbert transform; pred, obs,
+ *     adj_out (NULL = loss only, the same bits), loss_out as for mifwi_misfit.  No atomics: every trace's loss partial goes to
+ *     work and a second kernel adds them in index order, so two identical calls give the same bits.
+ *     work: mifwi_misfit_envelope_work_elems(nt, ntrace) floats, 8-byte aligned.
+ * MIFWI_EINVAL: a null required argument, nt < 1, ntrace < 1, nt > MIFWI_ENVELOPE_MAX_NT (longer records are not supported),
+ * ntrace > 2^31 - 1, eps negative, NaN or infinite, work not 8-byte aligned.
+ * ==================================================================================== */
+enum { MIFWI_ENVELOPE_MAX_NT = 8192 };
+
+int mifwi_trace_hilbert(int device, const float *x, float *y, int64_t nt, int64_t ntrace, int32_t transpose, void *stream);
+int64_t mifwi_misfit_envelope_work_elems(int64_t nt, int64_t ntrace);
+int mifwi_misfit_envelope(int device, const float *pred, const float *obs, int64_t nt, int64_t ntrace, double eps,
+                          float *loss_out, float *adj_out /* NULL: loss only, same bits */, float *work, void *stream);
+
+/* ======================================================================================
  * GRADIENT CONDITIONING on the device (what sits between d.get_fwi_gradients(...) and fake_Vp.backward(grad))
  *
  * Replaces the numpy / scipy post-processing of the model gradients in the elastic prop() methods:

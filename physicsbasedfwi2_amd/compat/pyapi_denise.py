@@ -790,11 +790,12 @@ class Denise:
         fl = (lambda a: butterworth(a, dt, *corners)) if mode == "fft" else (lambda a: a)
         # objective and adjoint sources in one fused pass per component (csrc/mifwi_misfit.hip): lnorm = 2 is the
         # L2 norm every stage of the reference asks for (networks.py:7761, 9863, 10503); 5 is DENISE's
-        # global-correlation norm (numbering as in the DENISE manual; DENISE itself is not in the reference tree)
+        # global-correlation norm, 6 the envelope objective (csrc/mifwi_envelope.hip; composed with the stage filter and
+        # the selection) (numbering as in the DENISE manual; DENISE itself is not in the reference tree)
         lnorm = int(st.get("lnorm", 2))
-        if lnorm not in (2, 5):
-            raise MifwiError("lnorm=%s not implemented (2: L2, 5: global correlation)" % lnorm)
-        kernel = misfit.l2_half if lnorm == 2 else misfit.global_correlation
+        if lnorm not in (2, 5, 6):
+            raise MifwiError("lnorm=%s not implemented (2: L2, 5: global correlation, 6: envelope)" % lnorm)
+        kernel = {2: misfit.l2_half, 5: misfit.global_correlation, 6: misfit.envelope}[lnorm]
         # TRKILL and the time windows: one selection W for every component, after the stage filter and before the norm, in
         # the same launch (csrc/mifwi_misfit_select.h); with the frequency-domain stage W is its own kernel in between
         sel = self._selection(vx.shape[1:], dt)

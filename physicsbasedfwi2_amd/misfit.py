@@ -20,6 +20,13 @@ Drop-in for the torch expressions the reference evaluates between the propagator
   traces, trace weights and time windows (:class:`TraceSelection`, DENISE's TRKILL and TIMEWIN) taken out of the
   objective inside the same launch: W after the stage filter, before the norm; ``trace_window(x, sel)`` is W alone
 
+* ``envelope(pred, obs, sos=None, select=None, eps=None)`` -- ``0.5 * sum((E(pred) - E(obs))**2)`` with the regularised
+  envelope ``E(x) = sqrt(x**2 + H(x)**2 + eps**2)``, DENISE's lnorm = 6 (Chi, Dong and Liu 2014), for the first
+  low-frequency stages: it does not cycle-skip where the three objectives above do.  H is the Hilbert transform through a
+  DFT zero-padded to a power of two, an FFT held in LDS (csrc/mifwi_envelope.hip); one launch delivers the loss and the
+  exact adjoint source.  With ``sos`` / ``select`` it is composed with ``trace_filter`` / ``trace_window``;
+  ``trace_hilbert(x)`` is H alone (its backward is H^T = -H), ``trace_envelope(x, eps)`` the envelope as a torch expression
+
 All return a 0-d tensor that back-propagates into ``pred`` (one kernel pass produces the loss and
 dloss/dpred).  No CPU fallback: CPU tensors raise.
 
@@ -275,6 +282,97 @@ def trace_window(x, select):
     """y = W x, W the diagonal of ``select`` (:class:`TraceSelection`), time on axis 0.  Differentiable: W is its own
     transpose, so the backward is the same call."""
     return _TraceWindowFn.apply(x, select)
+
+
+# ---- envelope objective: Hilbert transform, envelope residual and its adjoint (csrc/mifwi_envelope.hip) ----------------
+class _TraceHilbertFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, transpose):
+        if not x.is_cuda:
+            raise _lib.MifwiError("trace_hilbert needs CUDA/HIP tensors (libmifwi has no CPU fallback)")
+        if x.dim() < 1:
+            raise ValueError("x must be [nt, ...]")
+        lib = _lib.load()
+        xc = x.detach().contiguous().float()
+        y = torch.empty_like(xc)
+        nt = xc.shape[0]
+        if xc.numel():
+            _lib.check(lib.mifwi_trace_hilbert(xc.device.index or 0, _lib.ptr(xc), _lib.ptr(y), nt, xc.numel() // nt,
+                                               int(transpose), torch.cuda.current_stream(xc.device).cuda_stream))
+        ctx.transpose = transpose
+        return y
+
+    @staticmethod
+    def backward(ctx, g):
+        return _TraceHilbertFn.apply(g, not ctx.transpose), None
+
+
+def trace_hilbert(x, transpose=False):
+    """y = H x along axis 0 (any trailing shape): the Hilbert transform through a DFT zero-padded to N, the smallest power
+    of two >= nt, ``scipy.signal.hilbert(x, N=N, axis=0).imag[:nt]``; nt <= 8192.  ``transpose=True``: y = H^T x = -H x, the
+    negated bits.  Differentiable: the backward of one is the other."""
+    return _TraceHilbertFn.apply(x, bool(transpose))
+
+
+def trace_envelope(x, eps):
+    """E(x) = sqrt(x**2 + H(x)**2 + eps**2) along axis 0 as a torch expression over :func:`trace_hilbert`: differentiable
+    through autograd, for quality control and as a cross-check of :func:`envelope`.  ``eps`` > 0 keeps the square root
+    differentiable where the trace is silent."""
+    h = trace_hilbert(x)
+    return torch.sqrt(x * x + h * h + float(eps) ** 2)
+
+
+class _EnvelopeFn(torch.autograd.Function):
+    """Loss and adjoint source of the envelope objective in one call of mifwi_misfit_envelope."""
+
+    @staticmethod
+    def forward(ctx, pred, obs, eps):
+        if not pred.is_cuda:
+            raise _lib.MifwiError("misfit needs CUDA/HIP tensors (libmifwi has no CPU fallback)")
+        if pred.dim() < 2 or obs.shape != pred.shape:
+            raise ValueError("pred and obs must share one [nt, ...] shape")
+        lib = _lib.load()
+        p = pred.detach().contiguous().float()
+        o = obs.detach().contiguous().float()
+        nt = p.shape[0]
+        ntrace = p.numel() // nt
+        adj = torch.empty_like(p) if pred.requires_grad else None
+        loss = torch.empty((), device=p.device, dtype=torch.float32)
+        work = torch.empty(max(int(lib.mifwi_misfit_envelope_work_elems(nt, ntrace)), 2), device=p.device, dtype=torch.float32)
+        _lib.check(lib.mifwi_misfit_envelope(p.device.index or 0, _lib.ptr(p), _lib.ptr(o), nt, ntrace, float(eps), _lib.ptr(loss),
+                                             _lib.ptr(adj), _lib.ptr(work), torch.cuda.current_stream(p.device).cuda_stream))
+        ctx.adj = adj
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        # as _MisfitFn: the adjoint source stays with the graph
+        return (None if ctx.adj is None else ctx.adj * g), None, None
+
+
+def envelope(pred, obs, sos=None, select=None, eps=None, eps_rel=1e-3):
+    """0.5 * sum((E(pred) - E(obs))**2), E(x) = sqrt(x**2 + H(x)**2 + eps**2) the regularised envelope, time on axis 0
+    (Chi, Dong and Liu 2014; DENISE's lnorm = 6): one launch for the Hilbert transforms, the residual and the exact adjoint
+    source ``r pred / E - H(r H(pred) / E)``, r the envelope residual.  It does not cycle-skip where the sample-by-sample
+    objectives do.  nt <= 8192; H as in :func:`trace_hilbert`.
+
+    With ``sos`` (:func:`butterworth_sos`) and / or ``select`` (:class:`TraceSelection`) it is the composition
+    ``envelope(W F pred, W F obs)`` through :func:`trace_filter` and :func:`trace_window` (``obs`` is detached); autograd
+    carries the adjoint source back through W and F^T.
+
+    ``eps`` is one absolute scalar >= 0.  ``eps=None``: ``eps_rel * max|W F obs|``, a constant of the data, so the gradient
+    stays exact; all-zero data give eps = 0, where a sample with E(pred) == 0 contributes nothing to the adjoint source.
+    Ranks of ``dist.py`` that each hold some of the shots should pass one explicit ``eps``: otherwise every rank derives its
+    own from the shots it holds."""
+    obs = obs.detach()
+    if sos is not None:
+        sos = _sos_array(sos)
+        pred, obs = trace_filter(pred, sos), trace_filter(obs, sos)
+    if select is not None:
+        pred, obs = trace_window(pred, select), trace_window(obs, select)
+    if eps is None:
+        eps = float(eps_rel) * float(obs.abs().max()) if obs.numel() else 0.0
+    return _EnvelopeFn.apply(pred, obs, float(eps))
 
 
 # ---- matching filter: source-wavelet estimation in front of the objective (csrc/mifwi_stf.hip) -------------------------
