@@ -248,8 +248,9 @@ int mifwi_elastic_plan_pass_sizes(const mifwi_elastic_plan *plan, int32_t *forwa
  *         adjoint stress update of step n (the exact transpose of the sampling).                          */
 int mifwi_elastic_plan_bind_pressure(mifwi_elastic_plan *plan, float *rec_p, const float *g_p);
 
-/* mifwi_elastic_forward, _backward and _born refuse a plan of mifwi_vti_plan_create or mifwi_visco_plan_create with
- * MIFWI_EINVAL ("the plan was not created by mifwi_elastic_plan_create"): its kernels read six or eight planes.
+/* mifwi_elastic_forward, _backward and _born refuse a plan of mifwi_vti_plan_create, mifwi_tti_plan_create or
+ * mifwi_visco_plan_create with MIFWI_EINVAL ("the plan was not created by mifwi_elastic_plan_create"): its kernels read six
+ * or eight planes.
  *
  * Steps n = n_begin .. n_end-1.
  *   f [nt][nshot][nsrc] (added to sxx and szz - or to vx / vz, desc.source_type - pre-scaled by the host)
@@ -371,6 +372,89 @@ int mifwi_vti_backward(mifwi_vti_plan *plan, const float *mat, const float *pz, 
                        const float *snap, int32_t snap_first, float *grad_mat, float *grad_f, float *work, int32_t n_hi,
                        int32_t n_lo, int32_t flags, void *stream);
 int mifwi_vti_born(mifwi_vti_plan *plan, const float *mat, const float *dmat, const float *pz, const float *px,
+                   const float *df, const int32_t *src_cell, const float *src_w, const int32_t *rec_cell, const float *rec_w,
+                   const float *snap, int32_t snap_first, float *drec_vx, float *drec_vz, float *work, int32_t n_begin,
+                   int32_t n_end, int32_t flags, void *stream);
+
+/* ======================================================================================
+ * 2-D P-SV ELASTIC propagator in a medium with a TILTED symmetry axis (TTI; forward + exact discrete adjoint)
+ *
+ * Serves pyapi_denise runs with PHYSICS = 4 (this library's number for the P-SV TTI medium): Thomsen media whose symmetry
+ * axis follows dipping beds.  The VTI scheme above - same grid, staggering, Dp / Dm, C-PML recursion, pz / px tables, free
+ * surface, sources, receivers and five snapshot planes - with the stiffnesses rotated by the tilt, which adds c15 and
+ * c35: the normal stresses feel the shear strain and the shear stress the normal strains.
+ *   mat [8][nz][gp] = c13, c11, c55_xz, dt/(h rho_x), dt/(h rho_z), c33, c15, c35, the stiffnesses times dt/h.  Planes 0..5
+ *                     stand where the VTI planes stand; c15 and c35 sit on the sxx node.  Columns >= nx must be 0; under a
+ *                     free surface row 0 is kept VTI-like: c13 = c15 = c35 = 0 and c11 - c13^2 / c33 there (no tilted
+ *                     surface row; in marine data that row is water, where all three vanish anyway).
+ * sxx, szz and S0 = e1', S1 = e2' sit at (j, i); sxz and S2 = e3' + e4' at (j + 1/2, i + 1/2); all strains after their C-PML
+ * recursion.  Two four-point averages, entries outside the grid taken as 0:
+ *   A,   sxz nodes -> sxx node:  (A q)(j,i)   = 1/4 [q(j,i) + q(j-1,i) + q(j,i-1) + q(j-1,i-1)]
+ *   A^T, sxx nodes -> sxz node:  (A^T p)(j,i) = 1/4 [p(j,i) + p(j+1,i) + p(j,i+1) + p(j+1,i+1)]
+ * and w = (c55_xz != 0), a 0/1 mask on the sxz node.
+ * Forward step n:
+ *   V:   unchanged (the elastic V launch); S3, S4.   source_type 1 / 2: vx / vz [cell] += w f[n]
+ *   S:   sxx = fmaf(c11, S0, fmaf(c13, S1, sxx)) + c15 A(w S2);  szz = fmaf(c13, S0, fmaf(c33, S1, szz)) + c35 A(w S2)
+ *        sxz = fmaf(c55_xz, S2, sxz) + w A^T(c15 S0 + c35 S1)
+ *   source_type 0: sxx, szz [cell] += w f[n];  free surface: szz(0,.) = 0
+ * The coupling terms are added after the VTI fmaf chain: with c15 = c35 = 0 the seismograms of mifwi_vti_forward on
+ * planes 0..5 bit for bit.  The mask is part of the scheme: where the harmonic c55_xz is 0 (a fluid-solid interface)
+ * A^T(c15 e1') would drive a shear stress that nothing restores, the stiffness operator becomes indefinite and the run
+ * grows without bound; with w the 3 x 3 operator stays symmetric and the runs stay bounded.
+ * Adjoint step n = nt-1 .. 0, the exact transpose (the operator is symmetric: the same form on the adjoint stresses):
+ *   S^T: e1_bar = c11 sxx_bar + c13 szz_bar + c15 A(w sxz_bar);  e2_bar = c13 sxx_bar + c33 szz_bar + c35 A(w sxz_bar)
+ *        e5_bar = c55_xz sxz_bar + w A^T(c15 sxx_bar + c35 szz_bar);  then the transposed C-PML and the stencils as elastic
+ *        g_c15 += sxx_bar A(w S2) + S0 A(w sxz_bar);  g_c35 += szz_bar A(w S2) + S1 A(w sxz_bar);  planes 0..5 as VTI
+ *        (w is a constant for every derivative)
+ * Born step: dmat[0..7] on S0..S2 of the background run in the same pattern, w from the background c55_xz.
+ * A node needs its neighbours' C-PML-corrected strains, so the stress half step is two launches (strains, then stresses)
+ * and so is its transpose; V and V^T are one each.  No single-launch and no fused V+S form, no bf16 snapshot planes, no
+ * pressure receivers.  Snapshots are f32 [nshot][5][nz][gp] planes, blocked by columns of 16 four-cell groups;
+ * work_forward_elems and work_backward_elems hold three more planes per shot than a VTI plan's (the strains between the two
+ * launches); grad_mat and dmat are [8][nz][gp] like mat.
+ * ==================================================================================== */
+typedef struct {
+    int32_t nz, nx;          /* grid, z = depth is the slow axis                              */
+    int32_t nt, nshot, nsrc, nrec, ntap;
+    int32_t pml_width;       /* C-PML nodes per side (0 = none)                               */
+    int32_t free_surface;    /* 1: stress-free surface on row 0 (needs nz >= 4)               */
+    int32_t shots_per_group; /* adjoint: shots sharing one gradient accumulator; 0 = auto     */
+    int32_t source_type;     /* 0: explosive (sxx, szz), 1 / 2: point force on vx / vz        */
+    int32_t fd_order;        /* 4 (0 means 4) or 2                                            */
+} mifwi_tti_desc;
+
+typedef struct {
+    int32_t gp, pitch, ngroups, shots_per_group;
+    int64_t coef_elems;           /* nz*gp: one material / gradient plane                     */
+    int64_t state_elems;          /* forward state (5 fields + memory variables) at the start
+                                     of `work`: what a time checkpoint copies                 */
+    int64_t work_forward_elems;
+    int64_t work_backward_elems;
+    int64_t snap_step_elems;      /* floats one time step of the snapshot buffer takes (all shots) */
+} mifwi_tti_layout;
+
+typedef struct mifwi_tti_plan mifwi_tti_plan;
+
+/* MIFWI_EINVAL as mifwi_elastic_plan_create: nulls, bad sizes, ntap other than 1 or 4, a grid too small for the layer */
+int mifwi_tti_plan_create(mifwi_tti_plan **plan, int device, const mifwi_tti_desc *desc);
+int mifwi_tti_plan_destroy(mifwi_tti_plan *plan);
+int mifwi_tti_plan_layout(const mifwi_tti_plan *plan, mifwi_tti_layout *out);
+/* shots per forward pass, shot groups per adjoint pass over the time range (Infinity Cache residency, eight planes) */
+int mifwi_tti_plan_pass_sizes(const mifwi_tti_plan *plan, int32_t *forward_shots, int32_t *adjoint_groups);
+/* always 0: the TTI plan runs one launch per half-step phase */
+int mifwi_tti_plan_cluster_slabs(const mifwi_tti_plan *plan, int32_t adjoint);
+
+/* Arguments, step ranges, flags and refusals as mifwi_elastic_forward / _backward / _born; mat, grad_mat, dmat
+ * [8][nz][gp].  Born is served for source_type 0 only. */
+int mifwi_tti_forward(mifwi_tti_plan *plan, const float *mat, const float *pz, const float *px, const float *f,
+                      const int32_t *src_cell, const float *src_w, const int32_t *rec_cell, const float *rec_w,
+                      float *rec_vx, float *rec_vz, float *snap, float *work, int32_t n_begin, int32_t n_end,
+                      int32_t flags, void *stream);
+int mifwi_tti_backward(mifwi_tti_plan *plan, const float *mat, const float *pz, const float *px, const int32_t *src_cell,
+                       const float *src_w, const int32_t *rec_cell, const float *rec_w, const float *g_vx, const float *g_vz,
+                       const float *snap, int32_t snap_first, float *grad_mat, float *grad_f, float *work, int32_t n_hi,
+                       int32_t n_lo, int32_t flags, void *stream);
+int mifwi_tti_born(mifwi_tti_plan *plan, const float *mat, const float *dmat, const float *pz, const float *px,
                    const float *df, const int32_t *src_cell, const float *src_w, const int32_t *rec_cell, const float *rec_w,
                    const float *snap, int32_t snap_first, float *drec_vx, float *drec_vz, float *work, int32_t n_begin,
                    int32_t n_end, int32_t flags, void *stream);

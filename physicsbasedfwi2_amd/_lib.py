@@ -75,6 +75,14 @@ class VtiLayout(ctypes.Structure):
     _fields_ = list(FluidLayout._fields_)
 
 
+class TtiDesc(ctypes.Structure):
+    _fields_ = list(VtiDesc._fields_)
+
+
+class TtiLayout(ctypes.Structure):
+    _fields_ = list(FluidLayout._fields_)
+
+
 class ViscoDesc(ctypes.Structure):
     _fields_ = list(VtiDesc._fields_) + [("relax_a", ctypes.c_float), ("relax_b", ctypes.c_float)]
 
@@ -139,6 +147,14 @@ SIGNATURES = {
     "mifwi_vti_forward": (ctypes.c_int, [_P] * 13 + [ctypes.c_int32] * 3 + [_P]),
     "mifwi_vti_backward": (ctypes.c_int, [_P] * 11 + [ctypes.c_int32] + [_P] * 3 + [ctypes.c_int32] * 3 + [_P]),
     "mifwi_vti_born": (ctypes.c_int, [_P] * 11 + [ctypes.c_int32] + [_P] * 3 + [ctypes.c_int32] * 3 + [_P]),
+    "mifwi_tti_plan_create": (ctypes.c_int, [ctypes.POINTER(_P), ctypes.c_int, ctypes.POINTER(TtiDesc)]),
+    "mifwi_tti_plan_destroy": (ctypes.c_int, [_P]),
+    "mifwi_tti_plan_layout": (ctypes.c_int, [_P, ctypes.POINTER(TtiLayout)]),
+    "mifwi_tti_plan_pass_sizes": (ctypes.c_int, [_P, _P, _P]),
+    "mifwi_tti_plan_cluster_slabs": (ctypes.c_int, [_P, ctypes.c_int32]),
+    "mifwi_tti_forward": (ctypes.c_int, [_P] * 13 + [ctypes.c_int32] * 3 + [_P]),
+    "mifwi_tti_backward": (ctypes.c_int, [_P] * 11 + [ctypes.c_int32] + [_P] * 3 + [ctypes.c_int32] * 3 + [_P]),
+    "mifwi_tti_born": (ctypes.c_int, [_P] * 11 + [ctypes.c_int32] + [_P] * 3 + [ctypes.c_int32] * 3 + [_P]),
     "mifwi_visco_plan_create": (ctypes.c_int, [ctypes.POINTER(_P), ctypes.c_int, ctypes.POINTER(ViscoDesc)]),
     "mifwi_visco_plan_destroy": (ctypes.c_int, [_P]),
     "mifwi_visco_plan_layout": (ctypes.c_int, [_P, ctypes.POINTER(ViscoLayout)]),

@@ -1,4 +1,4 @@
-"""What the three P-SV propagators (:mod:`elastic`, :mod:`vti`, :mod:`visco`) share on the host: they are one scheme on one
+"""What the four P-SV propagators (:mod:`elastic`, :mod:`vti`, :mod:`tti`, :mod:`visco`) share on the host: they are one scheme on one
 plan of csrc/mifwi_elastic.hip - the medium decides the number of material planes and the names of the C entry points -
 so they are one :class:`_driver.Physics` description, one set of calls into libmifwi.so and one set of argument checks.
 A module keeps its material maps, its plan class, its options and its public functions; a further medium adds those and a

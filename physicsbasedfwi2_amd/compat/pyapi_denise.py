@@ -30,7 +30,7 @@ from collections import namedtuple
 import numpy as np
 import torch
 
-from .. import elastic, fluid, misfit, profiles, visco, vti
+from .. import elastic, fluid, misfit, profiles, tti, visco, vti
 from .._lib import STF_MAX_LAGS, MifwiError
 
 
@@ -271,6 +271,10 @@ _VTI = _Medium("_thomsen", "_gradients_thomsen", elastic.force_amplitude,
                lambda d, model, src: vti.max_velocity(model.vp, *d._thomsen),
                lambda d, prm, dt, h, fs: vti.materials(*prm, dt, h, free_surface=fs),
                lambda d, a, kw, dt, ph: vti.propagate(*a, **kw))
+# PHYSICS = 4, gradients (Vp0, Vs0, rho, epsilon, delta, theta); a rotation changes no phase velocity
+_TTI = _Medium("_thomsen_tilted", "_gradients_thomsen", elastic.force_amplitude, _VTI.vmax,
+               lambda d, prm, dt, h, fs: tti.materials(*prm, dt, h, free_surface=fs),
+               lambda d, a, kw, dt, ph: tti.propagate(*a, **kw))
 # L = 1, gradients (Vp, Vs, rho, Qp, Qs)
 _VISCO = _Medium("_attenuation", "_gradients_q", elastic.force_amplitude, _vmax_visco,
                  lambda d, prm, dt, h, fs: visco.materials(*prm, d._f_ref, float(d.FL1), dt, h, free_surface=fs),
@@ -289,7 +293,8 @@ _SERVED = frozenset((
     "EPRECOND", "EPSILON_WE", "TRKILL", "INV_STF", "fwi_stages", "loss", "DT_used", "acoustic_kernels", "stf_filters",
     "stf_wavelets", "L", "FL1", "F_REF"))
 # (L = 1, attenuation with one relaxation mechanism, takes the Qp and Qs models through d.set_attenuation(): arrays)
-# (PHYSICS = 3, the P-SV VTI medium, takes Thomsen's epsilon and delta through d.set_thomsen(): arrays, not attributes)
+# (PHYSICS = 3, the P-SV VTI medium, takes Thomsen's epsilon and delta through d.set_thomsen(): arrays, not attributes;
+# PHYSICS = 4, the P-SV TTI medium, the tilt of the symmetry axis as its third argument)
 # DENISE parameters that cannot change what ONE gradient evaluation (ITERMAX = 1) returns: the MPI decomposition, names of
 # files this shim keeps in memory, logging, model bounds and line-search / optimiser settings that only act on model
 # updates, grid sizes that come from the Model object.  Accepted; one warning per name says so.
@@ -409,7 +414,8 @@ class Denise:
         self._shots = None
         self._shots_p = None
         self._observed_p = None
-        self._thomsen = None               # (epsilon, delta) of set_thomsen, for PHYSICS = 3
+        self._thomsen = None               # (epsilon, delta) of set_thomsen, for PHYSICS = 3 and 4
+        self._tilt = None                  # theta of set_thomsen, for PHYSICS = 4
         self._gradients_thomsen = None
         # L: relaxation mechanisms of the P-SV medium - 0 elastic, 1 one standard linear solid with relaxation frequency FL1
         # [Hz] and the Qp / Qs models of set_attenuation().  F_REF [Hz]: the frequency at which Model.vp and Model.vs are
@@ -445,19 +451,30 @@ class Denise:
                           torch.as_tensor(np.asarray(vy) if not torch.is_tensor(vy) else vy).float())
         self._observed_p = None if p is None else torch.as_tensor(np.asarray(p) if not torch.is_tensor(p) else p).float()
 
-    # -- anisotropy (PHYSICS = 3) -------------------------------------------------------------------
-    def set_thomsen(self, epsilon, delta):
+    # -- anisotropy (PHYSICS = 3, 4) ----------------------------------------------------------------
+    def set_thomsen(self, epsilon, delta, theta=None):
         """Thomsen's epsilon and delta of a ``PHYSICS = 3`` (P-SV VTI) run: [ny, nx] arrays in the caller's flipud
         convention, like the planes of :class:`Model`, whose vp and vs are then the vertical velocities.  ``None, None``
-        forgets them."""
+        forgets them.  ``theta`` [ny, nx]: the tilt of the symmetry axis in radians of a ``PHYSICS = 4`` (P-SV TTI) run -
+        for theta > 0 the axis points along (sin theta, cos theta) in (x, depth) - and vp, vs are the velocities along
+        the axis."""
         if epsilon is None and delta is None:
-            self._thomsen = None
+            self._thomsen = self._tilt = None
             return
-        e, dl = (np.asarray(a.detach().cpu().numpy() if torch.is_tensor(a) else a, dtype=np.float32) for a in (epsilon, delta))
+        planes = (epsilon, delta) + (() if theta is None else (theta,))
+        planes = [np.asarray(a.detach().cpu().numpy() if torch.is_tensor(a) else a, dtype=np.float32) for a in planes]
+        e, dl = planes[:2]
         if e.ndim != 2 or e.shape != dl.shape:
             raise MifwiError("set_thomsen: epsilon and delta are [ny, nx] arrays of one shape (got %s and %s)"
                              % (e.shape, dl.shape))
+        if theta is not None and planes[2].shape != e.shape:
+            raise MifwiError("set_thomsen: theta is %s, epsilon and delta are %s" % (planes[2].shape, e.shape))
         self._thomsen = (e, dl)
+        self._tilt = None if theta is None else planes[2]
+
+    @property
+    def _thomsen_tilted(self):
+        return self._thomsen + (self._tilt,)
 
     # -- attenuation (L = 1) ------------------------------------------------------------------------
     def set_attenuation(self, qp, qs):
@@ -586,31 +603,40 @@ class Denise:
         if self.acoustic_kernels == "fluid" and int(self.EPRECOND) != 0:
             raise MifwiError("acoustic_kernels=\"fluid\": the pseudo-Hessian (EPRECOND=%s) is not built for the fluid "
                              "plan; use acoustic_kernels=\"elastic\"" % self.EPRECOND)
-        if self.PHYSICS not in (1, 2, 3):
-            raise MifwiError("PHYSICS=%s not implemented (1 = P-SV elastic, 2 = acoustic, 3 = P-SV VTI)" % self.PHYSICS)
+        if self.PHYSICS not in (1, 2, 3, 4):
+            raise MifwiError("PHYSICS=%s not implemented (1 = P-SV elastic, 2 = acoustic, 3 = P-SV VTI, 4 = P-SV TTI)"
+                             % self.PHYSICS)
 
     def _refuse_vti(self, model):
-        if self.PHYSICS != 3:
+        if self.PHYSICS not in (3, 4):
             return
+        tilted = self.PHYSICS == 4
+        ph, kind = ("PHYSICS=4", "TTI") if tilted else ("PHYSICS=3", "VTI")
         if self._thomsen is None:
-            raise MifwiError("PHYSICS=3 (P-SV VTI) needs Thomsen's parameters: d.set_thomsen(epsilon, delta)")
+            raise MifwiError("%s (P-SV %s) needs Thomsen's parameters: d.set_thomsen(epsilon, delta%s)"
+                             % (ph, kind, ", theta" if tilted else ""))
+        if tilted and self._tilt is None:
+            raise MifwiError("PHYSICS=4 (P-SV TTI) needs the tilt of the symmetry axis: d.set_thomsen(epsilon, delta, theta)")
+        if not tilted and self._tilt is not None and self._tilt.any():
+            raise MifwiError("PHYSICS=3 (P-SV VTI): set_thomsen was given a tilt theta != 0; a tilted axis is PHYSICS = 4")
         if self._thomsen[0].shape != model.vp.shape:
             raise MifwiError("set_thomsen: epsilon and delta are %s, the model is %s"
                              % (self._thomsen[0].shape, model.vp.shape))
         if int(self.INVMAT1) != 1:
-            raise MifwiError("PHYSICS=3: INVMAT1=%s is not served (1: Vp0, Vs0, rho, epsilon, delta)" % self.INVMAT1)
+            raise MifwiError("%s: INVMAT1=%s is not served (1: Vp0, Vs0, rho, epsilon, delta%s)"
+                             % (ph, self.INVMAT1, ", theta" if tilted else ""))
         if int(self.EPRECOND) != 0:
-            raise MifwiError("PHYSICS=3: the pseudo-Hessian (EPRECOND=%s) is not built for VTI media" % self.EPRECOND)
+            raise MifwiError("%s: the pseudo-Hessian (EPRECOND=%s) is not built for %s media" % (ph, self.EPRECOND, kind))
         if self.SEISMO != 1 or self.QUELLTYPB == 4:
-            raise MifwiError("PHYSICS=3: pressure seismograms (SEISMO=%s, QUELLTYPB=%s) are not served; SEISMO = 1 and "
-                             "QUELLTYPB 1, 2 or 3" % (self.SEISMO, self.QUELLTYPB))
+            raise MifwiError("%s: pressure seismograms (SEISMO=%s, QUELLTYPB=%s) are not served; SEISMO = 1 and "
+                             "QUELLTYPB 1, 2 or 3" % (ph, self.SEISMO, self.QUELLTYPB))
 
     def _refuse_visco(self, model):
         if int(self.L) == 0:
             return
         if self.PHYSICS != 1:
-            raise MifwiError("L=1 (attenuation) serves PHYSICS = 1 only (PHYSICS=%s): Q with the acoustic or the VTI medium "
-                             "is not built" % self.PHYSICS)
+            raise MifwiError("L=1 (attenuation) serves PHYSICS = 1 only (PHYSICS=%s): Q with the acoustic, the VTI or the TTI "
+                             "medium is not built" % self.PHYSICS)
         if int(self.EPRECOND) != 0:
             raise MifwiError("L=1: the pseudo-Hessian (EPRECOND=%s) is not built for viscoelastic media" % self.EPRECOND)
         if self.SEISMO != 1 or self.QUELLTYPB == 4:
@@ -643,8 +669,8 @@ class Denise:
             refuse(model)
         if int(self.L) != 0:
             return _VISCO
-        if self.PHYSICS == 3:
-            return _VTI
+        if self.PHYSICS in (3, 4):
+            return _TTI if self.PHYSICS == 4 else _VTI
         return _FLUID if self.acoustic_kernels == "fluid" else _PSV
 
     def _setup(self, model, src, rec, medium=None):
@@ -716,7 +742,7 @@ class Denise:
     def _materials(self, medium, model, dev, dt, h, requires_grad, fsurf=False):
         # undo the caller's flipud: internally row 0 is the surface
         # PHYSICS = 2 (acoustic): the same velocity-stress solver in a fluid, Vs = 0 everywhere
-        vs = model.vs if self.PHYSICS in (1, 3) else np.zeros_like(model.vs)
+        vs = model.vs if self.PHYSICS in (1, 3, 4) else np.zeros_like(model.vs)
         planes = (model.vp, vs, model.rho) + (getattr(self, medium.extra) if medium.extra else ())
         prm = [torch.tensor(np.flipud(a).copy(), device=dev, requires_grad=requires_grad) for a in planes]
         return prm, medium.materials(self, prm, dt, h, fsurf)
@@ -871,10 +897,11 @@ class Denise:
 
 
     def get_thomsen_gradients(self):
-        """(epsilon, delta) gradients of the last ``PHYSICS = 3`` grad(), [ny, nx] arrays in the caller's flipud
-        convention, the depth taper of SWS_TAPER_GRAD_HOR applied as to the other three."""
+        """(epsilon, delta) gradients of the last ``PHYSICS = 3`` grad() - (epsilon, delta, theta) of a ``PHYSICS = 4``
+        one - [ny, nx] arrays in the caller's flipud convention, the depth taper of SWS_TAPER_GRAD_HOR applied as to the
+        other three."""
         if self._gradients_thomsen is None:
-            raise MifwiError("run grad() with PHYSICS = 3 first")
+            raise MifwiError("run grad() with PHYSICS = 3 or 4 first")
         return self._gradients_thomsen
 
 

@@ -30,6 +30,9 @@
 // Viscoelastic (mifwi_visco_*): one relaxation mechanism - three memory variables behind the five fields of a shot, three more
 // material planes; a compile-time VISCO variant of el_step_s, el_adj_s / stage_E, el_adj_v (which advances the adjoint memory
 // variables) and finalize_groups on the per-step path; with the three planes zero the same bits.
+// TTI (mifwi_tti_*): the VTI stiffnesses rotated by a tilt field - two more planes (c15, c35) that couple the normal stresses to
+// the shear strain through four-point averages; the stress half step and its transpose are two launches each, kernels of
+// their own in mifwi_tti.h (tti_strain + tti_stress, tti_adj_e + tti_adj_s) around the V launches of every medium.
 // What this scheme shares with the fluid one below the cell arithmetic (stencil and C-PML primitives, strip and tile
 // helpers, build_tile_taps / sample_force / finalize_groups, the plan's grid geometry) is in mifwi_stagger.h.
 // Arithmetic = the explicit fmaf chain of oracle/elastic.c (build with -ffp-contract=off).
@@ -1065,6 +1068,7 @@ __global__ __launch_bounds__(kThreads) void el_adj_v(const ElParams p) { el_adj_
 __global__ __launch_bounds__(kThreads) void el_adj_v_visco(const ElParams p) { el_adj_v_body<true>(p); }
 
 #include "mifwi_elastic_fused.h"
+#include "mifwi_tti.h"
 
 // receivers of the state in p.fields (the last step of a fused range)
 __global__ __launch_bounds__(kThreads) void el_sample_v(const ElParams p)
@@ -1139,15 +1143,16 @@ using mifwi::env_int;
 // Every plan of this file is a mifwi_elastic_plan; its medium says which kernels serve it and how many planes they take.
 // Isotropic plans have all kernel families; the other media run one launch per half step: el_step_s / el_adj_s with VTI
 // or VISCO = true, el_adj_v_visco, finalize_groups<6> / <8> (el_step_variant, el_adj_variant).  A further medium is a row
-// here, a case in those two selectors and its three entry points.
-enum ElMedium { kIsotropic = 0, kVti = 1, kVisco = 2 };
+// here, a case in those two selectors and its three entry points.  TTI plans run the kernels of mifwi_tti.h in place of
+// el_step_s / el_adj_s (tti_step_variant; el_two_launch_steps and el_backward launch them).
+enum ElMedium { kIsotropic = 0, kVti = 1, kVisco = 2, kTti = 3 };
 struct ElMediumInfo {
     int nmat;                // material / gradient / accumulator planes
     int nfield;              // fields per shot: the five of the scheme (+ the three memory variables F_RXX..F_RXZ)
     const char *created_by;  // the family's plan_create, as messages name it
 };
 constexpr ElMediumInfo kMedia[] = {{5, 5, "mifwi_elastic_plan_create"}, {6, 5, "mifwi_vti_plan_create"},
-                                   {8, 8, "mifwi_visco_plan_create"}};
+                                   {8, 8, "mifwi_visco_plan_create"}, {8, 5, "mifwi_tti_plan_create"}};
 
 }  // namespace
 
@@ -1182,6 +1187,7 @@ struct mifwi_elastic_plan : StaggerGrid {    // grid, pitch and strips: stagger_
 // a VTI or viscoelastic plan is an elastic plan of that medium (el_plan_create); the C ABI keeps the handle types apart
 struct mifwi_vti_plan;
 struct mifwi_visco_plan;
+struct mifwi_tti_plan;
 
 namespace {
 
@@ -1224,6 +1230,18 @@ ElStepKernels el_step_variant(ElMedium medium, int lx, int save)
         else return with_int<kBorn, 1, 0>(save, pair);
     }); });
 }
+// the V launch alone (every medium's) and the two launches of a TTI stress half step: lanes per row 64 | 32 | 16; Born or not
+ElKernel el_step_v_variant(int lx, int save) { return el_step_variant(kVti, lx, save).v; }
+using TtiKernel = void (*)(TtiParams);
+struct TtiStepKernels { TtiKernel strain, stress; };
+TtiStepKernels tti_step_variant(int lx, bool born)
+{
+    return with_int<64, 32, 16>(lx, [&](auto LX) {
+    return with_bool(born, [&](auto B) {
+        constexpr int L = decltype(LX)::value;
+        return TtiStepKernels{tti_strain<L>, tti_stress<L, decltype(B)::value>};
+    }); });
+}
 // el_fwd_fused<SAVE>: save 2 | 1 | 0 (no Born form: that pass runs the two launches)
 ElKernel el_fwd_fused_variant(int save)
 {
@@ -1237,6 +1255,7 @@ ElAdjKernels el_adj_variant(ElMedium medium, bool bf16)
     switch (medium) {
     case kVti: return {el_adj_s<false, true>, el_adj_v, finalize_groups<6>};
     case kVisco: return {el_adj_s<false, false, true>, el_adj_v_visco, finalize_groups<8>};
+    case kTti: return {nullptr, el_adj_v, finalize_groups<8>};       // S^T: tti_adj_e + tti_adj_s (el_backward)
     default: return {bf16 ? el_adj_s<true> : el_adj_s<false>, el_adj_v, finalize_groups<5>};
     }
 }
@@ -1265,18 +1284,20 @@ EaKernel el_cluster_adj_variant(int ng, bool agent, bool xh)
     }); }); });
 }
 
-void launch_v(const mifwi_elastic_plan *pl, ElKernel kernel, const ElParams &p, int nshot, hipStream_t st)
+template <class P>
+void launch_v(const mifwi_elastic_plan *pl, void (*kernel)(P), const P &p, int nshot, hipStream_t st)
 {
     const int lz = kThreads / pl->lx;
     dim3 grid(mifwi::ceil_div(pl->ng, pl->lx), mifwi::ceil_div(pl->d.nz, lz), nshot);
     hipLaunchKernelGGL(kernel, grid, dim3(kThreads), 0, st, p);
 }
 
-void launch_s(const mifwi_elastic_plan *pl, ElKernel kernel, const ElParams &p0, int nshot, hipStream_t st)
+template <class P>
+void launch_s(const mifwi_elastic_plan *pl, void (*kernel)(P), const P &p0, int nshot, hipStream_t st)
 {
     const int lz = kThreads / pl->lx;
     const int tiles_x = mifwi::ceil_div(pl->ng, pl->lx);
-    ElParams p = p0;
+    P p = p0;
     p.tiles_z = mifwi::ceil_div(pl->d.nz, lz);
     int extra = 0;
     if (p.smp_out0 != nullptr && p.nsmp > 0)
@@ -1418,7 +1439,10 @@ void el_cluster_setup(mifwi_elastic_plan *pl)
 // second: the fused forward's other copy of the state.  It starts where xbuf does: a plan has one or the other (`fused`
 // needs `!cluster`), and the fused loop first touches it after a single-launch attempt has been given up and rolled
 // back, when nobody reads xbuf or backup any more; `total` counts room for both all the same.
-struct ElWork { long long fields, psi, psiB, acc, bbox, xbuf, lists, backup, second, tile, state, total; };
+// strain (TTI plans): three planes per shot of the snapshot planes' layout behind everything else - the strains between
+// tti_strain and tti_stress (forward and Born; unused while the step's snapshot planes take them), e_bar between tti_adj_e
+// and tti_adj_s (backward).  Scratch inside a step: not part of the state.
+struct ElWork { long long fields, psi, psiB, acc, bbox, xbuf, lists, backup, second, tile, strain, state, total; };
 ElWork work_map(const mifwi_elastic_plan *pl, bool backward)
 {
     const bool single = backward ? pl->cl_adj : pl->cluster;
@@ -1430,7 +1454,8 @@ ElWork work_map(const mifwi_elastic_plan *pl, bool backward)
     m.lists = m.xbuf + (single ? pl->xbuf_elems : 0);
     m.backup = m.lists + (single && backward ? pl->list_elems : 0);
     m.second = m.xbuf; m.tile = m.backup + (single ? m.state : 0);
-    m.total = backward ? m.tile + pl->tile_elems : m.tile + (pl->fused ? m.state : 0);
+    m.strain = backward ? m.tile + pl->tile_elems : m.tile + (pl->fused ? m.state : 0);
+    m.total = m.strain + (pl->medium == kTti ? 3LL * pl->d.nshot * pl->splane : 0);
     return m;
 }
 
@@ -1475,12 +1500,14 @@ void el_cluster_launch(const mifwi_elastic_plan *pl, void (*kernel)(Params), int
 // snap + (n - snap_first) * snap_step.  rec_vx null: no sampling.
 void el_two_launch_steps(const mifwi_elastic_plan *pl, ElParams p, int save, const float *f, const int32_t *src_cell,
                          const float *src_w, const int *bbox, const int32_t *rec_cell, const float *rec_w, float *rec_vx,
-                         float *rec_vz, float *snap, int snap_first, int n_begin, int n_end, hipStream_t st)
+                         float *rec_vz, float *snap, int snap_first, int n_begin, int n_end, float *strain, hipStream_t st)
 {
     const mifwi_elastic_desc &d = pl->d;
     const long long snap_step = pl->snap_shot * d.nshot;
     const bool want_rec = rec_vx != nullptr;
-    const ElStepKernels step = el_step_variant(pl->medium, pl->lx, save);
+    const bool tti = pl->medium == kTti;       // `strain`: the TTI plan's three work planes per shot (ElWork), else unused
+    const ElStepKernels step = tti ? ElStepKernels{el_step_v_variant(pl->lx, save), nullptr} : el_step_variant(pl->medium, pl->lx, save);
+    const TtiStepKernels tstep = tti_step_variant(pl->lx, save == kBorn);
     ElParams ps = p;
     const bool force = d.source_type != 0;      // point force: injected into vx / vz by a launch of its own
     ps.ninj = (force || !f) ? 0 : d.nsrc; ps.ntap_inj = d.ntap; ps.inj_cell = src_cell; ps.inj_w = src_w;
@@ -1505,7 +1532,17 @@ void el_two_launch_steps(const mifwi_elastic_plan *pl, ElParams p, int save, con
                 hipLaunchKernelGGL(el_inject_force, dim3(mifwi::ceil_div(cs, 64)), dim3(64), 0, st, pf,
                                    d.source_type);
             }
-            launch_s(pl, step.s, ps, cs, st);
+            if (tti) {
+                // the strains go into the step's snapshot planes 0..2 where those are written, else into the work planes
+                TtiParams q;
+                static_cast<ElParams &>(q) = ps;
+                q.E = save == 1 ? Sn : strain;
+                q.e_shot = save == 1 ? pl->snap_shot : 3 * pl->splane;
+                launch_v(pl, tstep.strain, q, cs, st);
+                launch_s(pl, tstep.stress, q, cs, st);
+            } else {
+                launch_s(pl, step.s, ps, cs, st);
+            }
             if (pl->rec_p && want_rec) {
                 ElParams pq = ps;
                 pq.s0 = s0; pq.gs = cs; pq.smp_out0 = pl->rec_p + (long long)n * d.nshot * d.nrec;
@@ -1775,7 +1812,7 @@ int el_forward(mifwi_elastic_plan *pl, const float *mat, const float *pz, const 
     } else {
         p.fields = fields; p.psix = psi_state; p.psiz = psi_state + pl->psix_elems;
         el_two_launch_steps(pl, p, save, f, src_cell, src_w, bbox, rec_cell, rec_w, want_rec ? rec_vx : nullptr,
-                            want_rec ? rec_vz : nullptr, snap, n_begin, n_begin, n_end, st);
+                            want_rec ? rec_vz : nullptr, snap, n_begin, n_begin, n_end, work + m.strain, st);
     }
     MIFWI_HIP_TRY(hipGetLastError());
     return MIFWI_OK;
@@ -1813,7 +1850,7 @@ int el_born(mifwi_elastic_plan *pl, const float *mat, const float *dmat, const f
     const bool want_rec = drec_vx != nullptr && d.nrec > 0;
     el_two_launch_steps(pl, p, kBorn, inject ? df : nullptr, src_cell, src_w, bbox, rec_cell, rec_w,
                         want_rec ? drec_vx : nullptr, want_rec ? drec_vz : nullptr, const_cast<float *>(snap), snap_first,
-                        n_begin, n_end, st);
+                        n_begin, n_end, work + m.strain, st);
     MIFWI_HIP_TRY(hipGetLastError());
     return MIFWI_OK;
 }
@@ -1916,7 +1953,15 @@ int el_backward(mifwi_elastic_plan *pl, const float *mat, const float *pz, const
             hipLaunchKernelGGL(el_inject_pressure, dim3(mifwi::ceil_div(cs * d.nrec * d.ntap, 64)), dim3(64), 0,
                                st, pq);
         }
-        hipLaunchKernelGGL(adj.s, dim3(tx, tz + ex, cg), dim3(kThreads), 0, st, ps);
+        if (pl->medium == kTti) {
+            TtiParams q;
+            static_cast<ElParams &>(q) = ps;
+            q.E = work + m.strain; q.e_shot = 3 * pl->splane;
+            hipLaunchKernelGGL(tti_adj_e, dim3(tx, tz, cg), dim3(kThreads), 0, st, q);
+            hipLaunchKernelGGL(tti_adj_s, dim3(tx, tz + ex, cg), dim3(kThreads), 0, st, q);
+        } else {
+            hipLaunchKernelGGL(adj.s, dim3(tx, tz + ex, cg), dim3(kThreads), 0, st, ps);
+        }
         if (want_f && force) {
             ElParams pq = ps;
             pq.gs = cs; pq.smp_out0 = grad_f + (long long)n * d.nshot * d.nsrc;
@@ -2056,6 +2101,55 @@ int mifwi_vti_born(mifwi_vti_plan *plan, const float *mat, const float *dmat, co
                    int32_t n_end, int32_t flags, void *stream)
 {
     if (const int rc = check_medium(plan_cast(plan), kVti)) return rc;
+    return el_born(plan_cast(plan), mat, dmat, pz, px, df, src_cell, src_w, rec_cell, rec_w, snap, snap_first, drec_vx, drec_vz,
+                   work, n_begin, n_end, flags, stream);
+}
+
+// TTI: eight planes; the stress half step and its transpose are two launches each (mifwi_tti.h)
+int mifwi_tti_plan_create(mifwi_tti_plan **plan, int device, const mifwi_tti_desc *d)
+{
+    if (!plan || !d) return mifwi::fail(MIFWI_EINVAL, "null plan/desc");
+    const mifwi_elastic_desc e = elastic_desc(*d);
+    return el_plan_create(reinterpret_cast<mifwi_elastic_plan **>(plan), device, &e, kTti);
+}
+
+int mifwi_tti_plan_destroy(mifwi_tti_plan *plan) { return mifwi_elastic_plan_destroy(plan_cast(plan)); }
+
+int mifwi_tti_plan_layout(const mifwi_tti_plan *plan, mifwi_tti_layout *out) { return family_layout(plan_cast(plan), out); }
+
+int mifwi_tti_plan_pass_sizes(const mifwi_tti_plan *plan, int32_t *forward_shots, int32_t *adjoint_groups)
+{
+    return mifwi_elastic_plan_pass_sizes(plan_cast(plan), forward_shots, adjoint_groups);
+}
+
+int mifwi_tti_plan_cluster_slabs(const mifwi_tti_plan *, int32_t) { return 0; }
+
+int mifwi_tti_forward(mifwi_tti_plan *plan, const float *mat, const float *pz, const float *px, const float *f,
+                      const int32_t *src_cell, const float *src_w, const int32_t *rec_cell, const float *rec_w,
+                      float *rec_vx, float *rec_vz, float *snap, float *work, int32_t n_begin, int32_t n_end,
+                      int32_t flags, void *stream)
+{
+    if (const int rc = check_medium(plan_cast(plan), kTti)) return rc;
+    return el_forward(plan_cast(plan), mat, pz, px, f, src_cell, src_w, rec_cell, rec_w, rec_vx, rec_vz, snap, work, n_begin,
+                      n_end, flags, stream);
+}
+
+int mifwi_tti_backward(mifwi_tti_plan *plan, const float *mat, const float *pz, const float *px, const int32_t *src_cell,
+                       const float *src_w, const int32_t *rec_cell, const float *rec_w, const float *g_vx, const float *g_vz,
+                       const float *snap, int32_t snap_first, float *grad_mat, float *grad_f, float *work, int32_t n_hi,
+                       int32_t n_lo, int32_t flags, void *stream)
+{
+    if (const int rc = check_medium(plan_cast(plan), kTti)) return rc;
+    return el_backward(plan_cast(plan), mat, pz, px, src_cell, src_w, rec_cell, rec_w, g_vx, g_vz, snap, snap_first, grad_mat,
+                       grad_f, work, n_hi, n_lo, flags, stream);
+}
+
+int mifwi_tti_born(mifwi_tti_plan *plan, const float *mat, const float *dmat, const float *pz, const float *px,
+                   const float *df, const int32_t *src_cell, const float *src_w, const int32_t *rec_cell, const float *rec_w,
+                   const float *snap, int32_t snap_first, float *drec_vx, float *drec_vz, float *work, int32_t n_begin,
+                   int32_t n_end, int32_t flags, void *stream)
+{
+    if (const int rc = check_medium(plan_cast(plan), kTti)) return rc;
     return el_born(plan_cast(plan), mat, dmat, pz, px, df, src_cell, src_w, rec_cell, rec_w, snap, snap_first, drec_vx, drec_vz,
                    work, n_begin, n_end, flags, stream);
 }
