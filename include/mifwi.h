@@ -852,6 +852,38 @@ int mifwi_misfit_envelope(int device, const float *pred, const float *obs, int64
                           float *loss_out, float *adj_out /* NULL: loss only, same bits */, float *work, void *stream);
 
 /* ======================================================================================
+ * TRANSPORT MISFIT: the quadratic Wasserstein distance between normalised traces along time and its exact adjoint source
+ *
+ * The optimal-transport objective of Engquist and Froese (2014) and Yang et al. (2018), trace by trace: it compares where the
+ * energy of a trace sits in time and keeps growing with a time shift where the sample-by-sample objectives and, further out, the
+ * envelope stop.  This library's documented choice; time is counted in samples; b > 0 is one absolute scalar per call.
+ * With s = pred, o = obs of one trace, k = 0 .. nt - 1:
+ *     u_k = softplus(b s_k) = max(z, 0) + log1p(exp(-|z|)), z = b s_k           v_k likewise from o_k
+ *     p = u / U, U = sum u      q = v / V, V = sum v      P_k = sum_{j <= k} p_j      Q_k = sum_{j <= k} q_j      (Q_{-1} = 0)
+ *     Pm_k = P_k - p_k / 2      tau_k = k + 1/2
+ *     j(k) = the first j with Q_j >= Pm_k (clamped to nt - 1)
+ *     T_k  = j + (Pm_k - Q_{j-1}) / q_j              the inverse of the piecewise-linear distribution function of q at Pm_k
+ *     W = sum_k p_k (tau_k - T_k)^2                  loss = 1/2 sum over traces of W
+ *     a_k = 2 p_k (T_k - tau_k) / q_{j(k)}           g_m = (tau_m - T_m)^2 + a_m / 2 + sum_{k > m} a_k
+ *     adj_out_m = dloss/ds_m = 1/2 (g_m - sum_k g_k p_k) / U * b * sigmoid(b s_m)
+ * A term whose divisor q_j is zero (softplus underflowed) contributes 0; a trace with U == 0 or V == 0 contributes 0 and gets a
+ * zero adjoint source.  pred with the bits of obs gives loss == 0 and adj_out == 0 exactly (T_k - tau_k is evaluated as
+ * (j - k) + (Pm_k - Qm_j) / q_j, Qm_j = Q_j - q_j / 2).
+ * Traces are [nt][ntrace], time slowest; nt <= MIFWI_TRANSPORT_MAX_NT (Q and q of a trace live in one workgroup's LDS).  Softplus,
+ * sums, distribution functions, T, the suffix sums and the loss are double.
+ *   mifwi_misfit_transport  one launch, one workgroup per trace; pred, obs, adj_out (NULL = loss only, the same bits), loss_out
+ *     as for mifwi_misfit.  No atomics: every trace's W goes to work and a second kernel adds them in index order, so two
+ *     identical calls give the same bits.  work: mifwi_misfit_transport_work_elems(nt, ntrace) floats, 8-byte aligned.
+ * MIFWI_EINVAL, before any device work: a null required argument, nt < 1, ntrace < 1, nt > MIFWI_TRANSPORT_MAX_NT (longer
+ * records are not supported), ntrace > 2^31 - 1, b <= 0, NaN or infinite, work not 8-byte aligned.
+ * ==================================================================================== */
+enum { MIFWI_TRANSPORT_MAX_NT = 8192 };
+
+int64_t mifwi_misfit_transport_work_elems(int64_t nt, int64_t ntrace);
+int mifwi_misfit_transport(int device, const float *pred, const float *obs, int64_t nt, int64_t ntrace, double b,
+                           float *loss_out, float *adj_out /* NULL: loss only, same bits */, float *work, void *stream);
+
+/* ======================================================================================
  * GRADIENT CONDITIONING on the device (what sits between d.get_fwi_gradients(...) and fake_Vp.backward(grad))
  *
  * Replaces the numpy / scipy post-processing of the model gradients in the elastic prop() methods:

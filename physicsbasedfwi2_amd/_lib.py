@@ -180,6 +180,8 @@ SIGNATURES = {
     "mifwi_trace_hilbert": (ctypes.c_int, [ctypes.c_int] + [_P] * 2 + [ctypes.c_int64] * 2 + [ctypes.c_int32, _P]),
     "mifwi_misfit_envelope_work_elems": (ctypes.c_int64, [ctypes.c_int64] * 2),
     "mifwi_misfit_envelope": (ctypes.c_int, [ctypes.c_int] + [_P] * 2 + [ctypes.c_int64] * 2 + [ctypes.c_double] + [_P] * 4),
+    "mifwi_misfit_transport_work_elems": (ctypes.c_int64, [ctypes.c_int64] * 2),
+    "mifwi_misfit_transport": (ctypes.c_int, [ctypes.c_int] + [_P] * 2 + [ctypes.c_int64] * 2 + [ctypes.c_double] + [_P] * 4),
     "mifwi_gradient_condition_work_elems": (ctypes.c_int64, [ctypes.c_int32]),
     "mifwi_gradient_condition": (ctypes.c_int, [ctypes.c_int] + [_P] * 3 + [ctypes.c_int32] * 3 + [_P, ctypes.c_float] +
                                  [ctypes.c_int32] * 2 + [_P] * 3),
@@ -207,6 +209,7 @@ MISFIT_GLOBAL_CORRELATION = 2
 FILTER_MAX_SECTIONS = 8
 STF_MAX_LAGS = 1024
 ENVELOPE_MAX_NT = 8192
+TRANSPORT_MAX_NT = 8192
 
 _lib = None
 

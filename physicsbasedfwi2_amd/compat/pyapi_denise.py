@@ -818,10 +818,18 @@ class Denise:
         # L2 norm every stage of the reference asks for (networks.py:7761, 9863, 10503); 5 is DENISE's
         # global-correlation norm, 6 the envelope objective (csrc/mifwi_envelope.hip; composed with the stage filter and
         # the selection) (numbering as in the DENISE manual; DENISE itself is not in the reference tree)
-        lnorm = int(st.get("lnorm", 2))
-        if lnorm not in (2, 5, 6):
-            raise MifwiError("lnorm=%s not implemented (2: L2, 5: global correlation, 6: envelope)" % lnorm)
-        kernel = {2: misfit.l2_half, 5: misfit.global_correlation, 6: misfit.envelope}[lnorm]
+        # add_fwi_stage(..., objective="transport", transport_b=None, transport_b_rel=4.0): the optimal-transport objective
+        # (csrc/mifwi_transport.hip), which has no lnorm number in DENISE; a stage without the key goes by its lnorm
+        named = st.get("objective")
+        if named is None:
+            lnorm = int(st.get("lnorm", 2))
+            if lnorm not in (2, 5, 6):
+                raise MifwiError("lnorm=%s not implemented (2: L2, 5: global correlation, 6: envelope)" % lnorm)
+            kernel = {2: misfit.l2_half, 5: misfit.global_correlation, 6: misfit.envelope}[lnorm]
+        elif named == "transport":
+            kernel = lambda v, o, **kw: misfit.transport(v, o, b=st.get("transport_b"), b_rel=st.get("transport_b_rel", 4.0), **kw)
+        else:
+            raise MifwiError("objective=%r not implemented (\"transport\"; the others go by lnorm)" % (named,))
         # TRKILL and the time windows: one selection W for every component, after the stage filter and before the norm, in
         # the same launch (csrc/mifwi_misfit_select.h); with the frequency-domain stage W is its own kernel in between
         sel = self._selection(vx.shape[1:], dt)

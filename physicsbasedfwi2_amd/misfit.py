@@ -27,6 +27,12 @@ Drop-in for the torch expressions the reference evaluates between the propagator
   exact adjoint source.  With ``sos`` / ``select`` it is composed with ``trace_filter`` / ``trace_window``;
   ``trace_hilbert(x)`` is H alone (its backward is H^T = -H), ``trace_envelope(x, eps)`` the envelope as a torch expression
 
+* ``transport(pred, obs, sos=None, select=None, b=None, b_rel=4.0)`` -- ``0.5 * sum over traces of W2**2``, the quadratic
+  Wasserstein distance along time between the traces made positive by ``softplus(b x)`` and normalised to unit mass
+  (Engquist and Froese 2014; Yang et al. 2018): it keeps growing with a time shift where even the envelope flattens.  The
+  distribution functions live in LDS in double (csrc/mifwi_transport.hip); one launch delivers the loss and the exact
+  adjoint source.  With ``sos`` / ``select`` it is composed with ``trace_filter`` / ``trace_window`` as ``envelope`` is
+
 All return a 0-d tensor that back-propagates into ``pred`` (one kernel pass produces the loss and
 dloss/dpred).  No CPU fallback: CPU tensors raise.
 
@@ -373,6 +379,66 @@ def envelope(pred, obs, sos=None, select=None, eps=None, eps_rel=1e-3):
     if eps is None:
         eps = float(eps_rel) * float(obs.abs().max()) if obs.numel() else 0.0
     return _EnvelopeFn.apply(pred, obs, float(eps))
+
+
+# ---- optimal-transport objective: W2 between normalised traces and its adjoint source (csrc/mifwi_transport.hip) --------
+class _TransportFn(torch.autograd.Function):
+    """Loss and adjoint source of the transport objective in one call of mifwi_misfit_transport."""
+
+    @staticmethod
+    def forward(ctx, pred, obs, b):
+        if not pred.is_cuda:
+            raise _lib.MifwiError("misfit needs CUDA/HIP tensors (libmifwi has no CPU fallback)")
+        if pred.dim() < 2 or obs.shape != pred.shape:
+            raise ValueError("pred and obs must share one [nt, ...] shape")
+        lib = _lib.load()
+        p = pred.detach().contiguous().float()
+        o = obs.detach().contiguous().float()
+        nt = p.shape[0]
+        ntrace = p.numel() // nt
+        adj = torch.empty_like(p) if pred.requires_grad else None
+        loss = torch.empty((), device=p.device, dtype=torch.float32)
+        work = torch.empty(max(int(lib.mifwi_misfit_transport_work_elems(nt, ntrace)), 2), device=p.device, dtype=torch.float32)
+        _lib.check(lib.mifwi_misfit_transport(p.device.index or 0, _lib.ptr(p), _lib.ptr(o), nt, ntrace, float(b), _lib.ptr(loss),
+                                              _lib.ptr(adj), _lib.ptr(work), torch.cuda.current_stream(p.device).cuda_stream))
+        ctx.adj = adj
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        # as _MisfitFn: the adjoint source stays with the graph
+        return (None if ctx.adj is None else ctx.adj * g), None, None
+
+
+def transport(pred, obs, sos=None, select=None, b=None, b_rel=4.0):
+    """0.5 * sum over traces of W2(p, q)**2 along time (axis 0, in samples): the quadratic Wasserstein distance between the
+    traces made positive by ``softplus(b x)`` and normalised to unit mass (Engquist and Froese 2014; Yang et al. 2018), every
+    trace on its own.  With P, Q the running sums of p, q and T the inverse of the piecewise-linear Q at the cell midpoints
+    of P, ``W = sum_k p_k (k + 1/2 - T_k)**2``; one launch delivers the loss and its exact adjoint source (the definition in
+    full: include/mifwi.h, "TRANSPORT MISFIT").  It compares where the energy sits in time and keeps growing with a time shift
+    where :func:`l2_half` cycle-skips.  nt <= 8192.  ``pred`` with the bits of ``obs`` gives exact zeros.
+
+    With ``sos`` (:func:`butterworth_sos`) and / or ``select`` (:class:`TraceSelection`) it is the composition
+    ``transport(W F pred, W F obs)`` through :func:`trace_filter` and :func:`trace_window`, as :func:`envelope` composes them
+    (``obs`` is detached); a killed trace is a pair of zero traces there and costs nothing.
+
+    ``b`` is one absolute scalar > 0.  ``b=None``: ``b_rel / max|W F obs|``, a constant of the data, so the gradient stays
+    exact; all-zero observed data then raise ``MifwiError``.  At ``b_rel`` 1 and 2 the loss of a shifted Ricker wavelet does
+    not grow strictly with the shift, at 4 it does: that is the default.  Ranks of ``dist.py`` that each hold some of the
+    shots should pass one explicit ``b``: otherwise every rank derives its own from the shots it holds."""
+    obs = obs.detach()
+    if sos is not None:
+        sos = _sos_array(sos)
+        pred, obs = trace_filter(pred, sos), trace_filter(obs, sos)
+    if select is not None:
+        pred, obs = trace_window(pred, select), trace_window(obs, select)
+    if b is None:
+        peak = float(obs.abs().max()) if obs.numel() else 0.0
+        if not peak > 0.0:
+            raise _lib.MifwiError("transport: the observed data are all zero (or not finite), so b = b_rel / max|obs| does not "
+                                  "exist; pass b")
+        b = float(b_rel) / peak
+    return _TransportFn.apply(pred, obs, float(b))
 
 
 # ---- matching filter: source-wavelet estimation in front of the objective (csrc/mifwi_stf.hip) -------------------------
