@@ -91,7 +91,15 @@ class ViscoLayout(ctypes.Structure):
     _fields_ = list(FluidLayout._fields_)
 
 
-EL_KERNEL_FWD_SINGLE_LAUNCH, EL_KERNEL_ADJ_SINGLE_LAUNCH, EL_KERNEL_FWD_FUSED_STEP, EL_KERNEL_ADJ_FUSED_STEP = 1, 2, 4, 8
+class ViscofluidDesc(ctypes.Structure):
+    _fields_ = list(FluidDesc._fields_) + [("relax_a", ctypes.c_float), ("relax_b", ctypes.c_float)]
+
+
+class ViscofluidLayout(ctypes.Structure):
+    _fields_ = list(FluidLayout._fields_)
+
+
+EL_KERNEL_FWD_SINGLE_LAUNCH,EL_KERNEL_ADJ_SINGLE_LAUNCH, EL_KERNEL_FWD_FUSED_STEP, EL_KERNEL_ADJ_FUSED_STEP = 1, 2, 4, 8
 EL_KERNEL_FWD_LANE_HALO, EL_KERNEL_ADJ_LANE_HALO = 16, 32
 SNAPSHOT_F32, SNAPSHOT_BF16 = 0, 1
 _P = ctypes.c_void_p
@@ -139,6 +147,14 @@ SIGNATURES = {
     "mifwi_fluid_snapshot_moments": (ctypes.c_int, [_P] * 2 + [ctypes.c_int32] * 4 + [_P] * 2 + [ctypes.c_int32, _P]),
     "mifwi_fluid_pseudo_hessian": (ctypes.c_int, [ctypes.c_int, ctypes.c_int32] + [_P] * 3 + [ctypes.c_int32] * 3 +
                                    [ctypes.c_float] + [_P] * 3),
+    "mifwi_viscofluid_plan_create": (ctypes.c_int, [ctypes.POINTER(_P), ctypes.c_int, ctypes.POINTER(ViscofluidDesc)]),
+    "mifwi_viscofluid_plan_destroy": (ctypes.c_int, [_P]),
+    "mifwi_viscofluid_plan_layout": (ctypes.c_int, [_P, ctypes.POINTER(ViscofluidLayout)]),
+    "mifwi_viscofluid_plan_pass_sizes": (ctypes.c_int, [_P, _P, _P]),
+    "mifwi_viscofluid_plan_cluster_slabs": (ctypes.c_int, [_P, ctypes.c_int32]),
+    "mifwi_viscofluid_forward": (ctypes.c_int, [_P] * 14 + [ctypes.c_int32] * 3 + [_P]),
+    "mifwi_viscofluid_backward": (ctypes.c_int, [_P] * 12 + [ctypes.c_int32] + [_P] * 3 + [ctypes.c_int32] * 3 + [_P]),
+    "mifwi_viscofluid_born": (ctypes.c_int, [_P] * 11 + [ctypes.c_int32] + [_P] * 4 + [ctypes.c_int32] * 3 + [_P]),
     "mifwi_vti_plan_create": (ctypes.c_int, [ctypes.POINTER(_P), ctypes.c_int, ctypes.POINTER(VtiDesc)]),
     "mifwi_vti_plan_destroy": (ctypes.c_int, [_P]),
     "mifwi_vti_plan_layout": (ctypes.c_int, [_P, ctypes.POINTER(VtiLayout)]),

@@ -30,7 +30,7 @@ from collections import namedtuple
 import numpy as np
 import torch
 
-from .. import elastic, fluid, misfit, profiles, tti, visco, vti
+from .. import elastic, fluid, misfit, profiles, tti, visco, viscofluid, vti
 from .._lib import STF_MAX_LAGS, MifwiError
 
 
@@ -279,6 +279,13 @@ _TTI = _Medium("_thomsen_tilted", "_gradients_thomsen", elastic.force_amplitude,
 _VISCO = _Medium("_attenuation", "_gradients_q", elastic.force_amplitude, _vmax_visco,
                  lambda d, prm, dt, h, fs: visco.materials(*prm, d._f_ref, float(d.FL1), dt, h, free_surface=fs),
                  lambda d, a, kw, dt, ph: visco.propagate(*a, float(d.FL1), dt, **kw))
+# PHYSICS = 2 with acoustic_kernels = "fluid" and L = 1: the four-field viscoacoustic kernels, gradients (Vp, Vs, rho, Qp, Qs)
+# with Vs and Qs never seen (their gradients are 0)
+_VISCOFLUID = _Medium("_attenuation", "_gradients_q", fluid.force_amplitude, _vmax_visco,
+                      lambda d, prm, dt, h, fs: viscofluid.materials(prm[0], prm[2], prm[3], d._f_ref, float(d.FL1), dt, h,
+                                                                     free_surface=fs),
+                      lambda d, a, kw, dt, ph: viscofluid.propagate(*a, float(d.FL1), dt, record_pressure=d.SEISMO in (2, 4),
+                                                                    **kw))
 
 
 # ---- what an assignment `d.NAME = value` means here -----------------------------------------------------------------
@@ -478,8 +485,9 @@ class Denise:
 
     # -- attenuation (L = 1) ------------------------------------------------------------------------
     def set_attenuation(self, qp, qs):
-        """The quality factors of an ``L = 1`` (viscoelastic P-SV) run: [ny, nx] arrays in the caller's flipud convention,
-        like the planes of :class:`Model`; ``inf`` means lossless.  ``None, None`` forgets them."""
+        """The quality factors of an ``L = 1`` run (viscoelastic P-SV, or viscoacoustic: ``PHYSICS = 2`` on the fluid
+        kernels, which ignores ``qs``): [ny, nx] arrays in the caller's flipud convention, like the planes of
+        :class:`Model`; ``inf`` means lossless.  ``None, None`` forgets them."""
         if qp is None and qs is None:
             self._attenuation = None
             return
@@ -634,12 +642,14 @@ class Denise:
     def _refuse_visco(self, model):
         if int(self.L) == 0:
             return
-        if self.PHYSICS != 1:
-            raise MifwiError("L=1 (attenuation) serves PHYSICS = 1 only (PHYSICS=%s): Q with the acoustic, the VTI or the TTI "
-                             "medium is not built" % self.PHYSICS)
+        fluid_q = self.PHYSICS == 2 and self.acoustic_kernels == "fluid"          # the viscoacoustic kernels
+        if self.PHYSICS != 1 and not fluid_q:
+            raise MifwiError("L=1 (attenuation) serves PHYSICS = 1, and PHYSICS = 2 with acoustic_kernels=\"fluid\" "
+                             "(PHYSICS=%s, acoustic_kernels=%r): Q with the acoustic medium on the P-SV kernels, the VTI or "
+                             "the TTI medium is not built" % (self.PHYSICS, self.acoustic_kernels))
         if int(self.EPRECOND) != 0:
-            raise MifwiError("L=1: the pseudo-Hessian (EPRECOND=%s) is not built for viscoelastic media" % self.EPRECOND)
-        if self.SEISMO != 1 or self.QUELLTYPB == 4:
+            raise MifwiError("L=1: the pseudo-Hessian (EPRECOND=%s) is not built for attenuating media" % self.EPRECOND)
+        if not fluid_q and (self.SEISMO != 1 or self.QUELLTYPB == 4):
             raise MifwiError("L=1: pressure seismograms (SEISMO=%s, QUELLTYPB=%s) are not served; SEISMO = 1 and "
                              "QUELLTYPB 1, 2 or 3" % (self.SEISMO, self.QUELLTYPB))
         if self._attenuation is None:
@@ -668,7 +678,7 @@ class Denise:
         for refuse in ((vti_, visco_, self._refuse_grad, kernels) if grad else (kernels, visco_, vti_)):
             refuse(model)
         if int(self.L) != 0:
-            return _VISCO
+            return _VISCOFLUID if self.PHYSICS == 2 else _VISCO
         if self.PHYSICS in (3, 4):
             return _TTI if self.PHYSICS == 4 else _VTI
         return _FLUID if self.acoustic_kernels == "fluid" else _PSV
@@ -915,7 +925,7 @@ class Denise:
 
     def get_attenuation_gradients(self):
         """(Qp, Qs) gradients of the last ``L = 1`` grad(), [ny, nx] arrays in the caller's flipud convention, the depth
-        taper of SWS_TAPER_GRAD_HOR applied as to the other three."""
+        taper of SWS_TAPER_GRAD_HOR applied as to the other three.  A viscoacoustic run (``PHYSICS = 2``) has no Qs: zeros."""
         if self._gradients_q is None:
             raise MifwiError("run grad() with L = 1 first")
         return self._gradients_q

@@ -22,6 +22,10 @@
 // of 16 groups (whole 128-byte lines per tile row).  There is no single-launch form.
 // Born (mifwi_fluid_born): the same two launches on the perturbed state; instead of writing the step's three snapshot
 // planes they read the background run's and add dmat times them (SAVE = kBorn), the JVP partner of the adjoint's gradients.
+// Viscoacoustic medium (mifwi_viscofluid_*): the same plan with a fourth field r (the memory variable of one standard linear
+// solid, on the p node), a fourth plane R and a fourth accumulator - compile-time variants Q = true of fl_step_p, fl_adj_p and
+// fl_adj_v; the V launch and every point kernel are shared.  R = 0 gives the lossless bits, and on the planes of a model the
+// P launch is el_step_s<..., VISCO> with Vs = 0, operand for operand (include/mifwi.h has the recursion and its transpose).
 // Snapshot moments (the pseudo-Hessian's ingredient): mifwi_fluid_moments.h, included at the end.
 // Arithmetic = the explicit fmaf chain stated in include/mifwi.h (build with -ffp-contract=off).
 #include "mifwi_cluster_host.h"      // mifwi::env_int
@@ -29,14 +33,14 @@
 
 namespace {
 
-enum { F_VX = 0, F_VZ = 1, F_P = 2 };
-enum { M_K = 0, M_BX = 1, M_BZ = 2 };
+enum { F_VX = 0, F_VZ = 1, F_P = 2, F_R = 3 };       // F_R: the memory variable of a viscoacoustic plan (Q kernels only)
+enum { M_K = 0, M_BX = 1, M_BZ = 2, M_R = 3 };       // M_R: its fourth plane, R dt/h
 enum { PSI_HALF = 0, PSI_INT = 1 };      // plane of a strip: the V launch's derivative (d1 / d4), the P launch's (e1 / e2)
 
 struct FlParams {
     int nz, nx, ng, gp, pitch;
     unsigned field_stride;       // (nz+4)*pitch
-    long long shot_stride;       // 3*field_stride
+    long long shot_stride;       // 3*field_stride (viscoacoustic: 4)
     int nshot, gs;               // gs: shots per accumulator group (P^T launch), shots of the pass (point launches)
     int s0;                      // first shot of this pass over the time range (blockIdx.z counts from it)
     int W, wl, xr0, wx;          // C-PML strip geometry; W = 0 disables the layer
@@ -49,7 +53,7 @@ struct FlParams {
     float *psix_out, *psiz_out;  // adjoint: write side (ping-pong)
     float *S;                    // snapshot slice of this step: [nshot][3] planes of splane floats (Born: read)
     unsigned splane;             // floats per snapshot / accumulator plane: nz * 64 * ceil(ng / 16)
-    float *acc;                  // [ngroups][3] planes
+    float *acc;                  // [ngroups][3] planes (viscoacoustic: 4)
     // injection (V: vx | vz += a; P: p += a; P^T: vx += a0, vz += a1)
     int ninj, ntap_inj, inj_field;
     const int *inj_cell;
@@ -64,6 +68,7 @@ struct FlParams {
     float *smp_out0, *smp_out1;
     int tiles_z;
     FdK fd;
+    float rel_a, rel_b;          // Q kernels: r <- a r - b q
 };
 
 // offset (floats) of group g of row j inside a snapshot / accumulator plane: always column-blocked
@@ -245,7 +250,10 @@ __global__ __launch_bounds__(kThreads) void fl_step_v(const FlParams p)
 // ================================================================================================
 // forward P launch:  p += K (Dm_x vx)' + K (Dm_z vz)',  the explosive source of the tile;  extra workgroups sample vx, vz
 // ================================================================================================
-template <int LX, int SAVE>
+// Q (viscoacoustic): q = R (e1' + e2'), p += (1 + a)/2 r - b/2 q after the chain, r = a r - b q - the operand order of
+// el_step_s<..., VISCO> with R1 == R2, so that the P-SV route with Vs = 0 gives the same bits; R = 0 leaves r at 0 and p
+// the lossless chain's.  Born: q += dmat[3] S0.
+template <int LX, int SAVE, bool Q>
 __global__ __launch_bounds__(kThreads) void fl_step_p(const FlParams p)
 {
     const FdK K = p.fd;
@@ -295,6 +303,13 @@ __global__ __launch_bounds__(kThreads) void fl_step_p(const FlParams p)
         B0 = mifwi::ldnt4(p.S + 3LL * s * p.splane + snap_cell(p, j, g));
         dK = ld4(p.dmat + cc);
     }
+    float4 Rs = zero4, rv = zero4, dR = zero4;
+    if (Q) {
+        const unsigned ncell = (unsigned)p.nz * p.gp;
+        Rs = ld4(p.mat + M_R * ncell + cc);
+        rv = ld4(fl + F_R * fs + o);
+        if (SAVE == kBorn) dR = ld4(p.dmat + M_R * ncell + cc);
+    }
     const float xv[8] = {Lvx.x, Lvx.y, cvx.x, cvx.y, cvx.z, cvx.w, Rvx.x, Rvx.y};
     float e1[4], e2[4];
 #pragma unroll
@@ -314,16 +329,24 @@ __global__ __launch_bounds__(kThreads) void fl_step_p(const FlParams p)
         for (int c = 0; c < 4; ++c) e2[c] = pml(t2[c], za, zb, zk, e2[c]);
         st4(q2, mk4(t2));
     }
-    float np[4], s0v[4];
+    float np[4], s0v[4], nr[4];
 #pragma unroll
     for (int c = 0; c < 4; ++c) {
         s0v[c] = e1[c] + e2[c];
         np[c] = fmaf(comp(Ks, c), e1[c], fmaf(comp(Ks, c), e2[c], comp(pv, c)));
         if (SAVE == kBorn) np[c] = fmaf(comp(dK, c), comp(B0, c), np[c]);
+        if (Q) {
+            const float ha = 0.5f * (1.f + p.rel_a), hb = 0.5f * p.rel_b;
+            float q = fmaf(comp(Rs, c), e1[c], comp(Rs, c) * e2[c]);
+            if (SAVE == kBorn) q = fmaf(comp(dR, c), comp(B0, c), q);
+            np[c] += fmaf(ha, comp(rv, c), -(hb * q));
+            nr[c] = fmaf(p.rel_a, comp(rv, c), -(p.rel_b * q));
+        }
         if (has_inj) np[c] += inj[lz * TX + 4 * lx + c];
         if (p.fsurf && j == 0) np[c] = 0.f;
     }
     st4(pp + o, mk4(np));
+    if (Q) st4(fl + F_R * fs + o, mk4(nr));
     if (SAVE == 1) mifwi::stnt4(p.S + 3LL * s * p.splane + snap_cell(p, j, g), mk4(s0v));
 }
 
@@ -383,12 +406,28 @@ __device__ __forceinline__ float4 mul4(const float4 &a, const float4 &b)
 {
     return make_float4(a.x * b.x, a.y * b.y, a.z * b.z, a.w * b.w);
 }
+// Q kernels: w = -b (r_bar + p_bar / 2), the adjoint of q;  K p_bar + R w, what goes through pmlT
+__device__ __forceinline__ float4 adj_w4(float b, const float4 &rb, const float4 &pb)
+{
+    return make_float4(-b * fmaf(0.5f, pb.x, rb.x), -b * fmaf(0.5f, pb.y, rb.y), -b * fmaf(0.5f, pb.z, rb.z),
+                       -b * fmaf(0.5f, pb.w, rb.w));
+}
+__device__ __forceinline__ float4 kp_rw4(const float4 &K, const float4 &pb, const float4 &R, const float4 &w)
+{
+    return make_float4(fmaf(K.x, pb.x, R.x * w.x), fmaf(K.y, pb.y, R.y * w.y), fmaf(K.z, pb.z, R.z * w.z),
+                       fmaf(K.w, pb.w, R.w * w.w));
+}
 
 // P^T:  acc_K += S0 p_bar;  E1, E2 = pmlT(K p_bar);  vx_bar -= Dp_x E1,  vz_bar -= Dp_z E2;  acc_bx += S1 vx_bar,
 //       acc_bz += S2 vz_bar.  The adjoint sources of the tile's cells (v_bar += R^T g, the head of an adjoint step) are
 //       added to the loaded v_bar first (p.tile_start set).  Extra workgroups sample p_bar at the explosive sources.
+// Q (viscoacoustic): w = -b (r_bar + p_bar / 2) on tile and halo from the OLD r_bar (field 3);  acc_R += S0 w;
+//       E1, E2 = pmlT(K p_bar + R w).  r_bar is only read here: neighbouring tiles stage the same cells in no order, so the
+//       owner advances it in fl_adj_v.
+template <bool Q>
 __global__ __launch_bounds__(kThreads) void fl_adj_p(const FlParams p)
 {
+    constexpr int NP = Q ? 4 : 3;
     const FdK K = p.fd;
     int bx, by, bz;
     xcd_tile_major(bx, by, bz);
@@ -414,22 +453,33 @@ __global__ __launch_bounds__(kThreads) void fl_adj_p(const FlParams p)
     const unsigned hcc = (unsigned)hj * p.gp + 4 * hgg;
     const unsigned ho = (unsigned)(hj + 2) * p.pitch + 4 + 4 * hgg;
     const float4 zero4 = make_float4(0.f, 0.f, 0.f, 0.f);
-    float4 acc[3] = {zero4, zero4, zero4};
-    float4 oK = zero4, hK = zero4;
-    float *accp = p.acc + 3LL * (p.s0 / p.gs + bz) * p.splane + osc;
+    float4 acc[NP];
+    float4 oK = zero4, hK = zero4, oR = zero4, hR = zero4;
+    float *accp = p.acc + (long long)NP * (p.s0 / p.gs + bz) * p.splane + osc;
+#pragma unroll
+    for (int k = 0; k < NP; ++k) acc[k] = zero4;
     if (own_ok) {
 #pragma unroll
-        for (int k = 0; k < 3; ++k) acc[k] = ld4(accp + (long long)k * p.splane);
+        for (int k = 0; k < NP; ++k) acc[k] = ld4(accp + (long long)k * p.splane);
         oK = ld4(p.mat + occ);
+        if (Q) oR = ld4(p.mat + M_R * (unsigned)p.nz * p.gp + occ);
     }
-    if (halo_ok) hK = ld4(p.mat + hcc);
+    if (halo_ok) {
+        hK = ld4(p.mat + hcc);
+        if (Q) hR = ld4(p.mat + M_R * (unsigned)p.nz * p.gp + hcc);
+    }
     for (int si = 0; si < p.gs; ++si) {
         const int s = p.s0 + bz * p.gs + si;
         if (s >= p.nshot) break;
         float *fl = p.fields + (long long)s * p.shot_stride;
         float4 pb = zero4, hpb = zero4, vxb = zero4, vzb = zero4, S0 = zero4, S1 = zero4, S2 = zero4;
+        float4 ow = zero4, hw = zero4;                   // Q: r_bar as loaded, then w
         if (own_ok) { pb = ld4(fl + F_P * fs + oo); vxb = ld4(fl + F_VX * fs + oo); vzb = ld4(fl + F_VZ * fs + oo); }
         if (halo_ok) hpb = ld4(fl + F_P * fs + ho);
+        if (Q) {
+            if (own_ok) ow = ld4(fl + F_R * fs + oo);
+            if (halo_ok) hw = ld4(fl + F_R * fs + ho);
+        }
         // ---- adjoint sources of this tile (workgroup-uniform branch; E is free until the staging) -----------------
         if (p.tile_start != nullptr) {
             const int ntiles = (int)gridDim.x * p.tiles_z, per = p.ninj * p.ntap_inj;
@@ -458,15 +508,17 @@ __global__ __launch_bounds__(kThreads) void fl_adj_p(const FlParams p)
         // ---- stage E1, E2 on the tile + halo ------------------------------------------------------------------
         if (p.fsurf && oj == 0) pb = zero4;              // p(0,.) is identically 0 in the forward run: adjoint discarded
         if (p.fsurf && hj == 0) hpb = zero4;
+        if (Q) { ow = adj_w4(p.rel_b, ow, pb); hw = adj_w4(p.rel_b, hw, hpb); }
         {
             float4 E1 = zero4, E2 = zero4;
-            if (own_ok) stage_T(p, s, PSI_INT, 0, oj, og, mul4(oK, pb), true, true, true, E1, E2);
+            if (own_ok) stage_T(p, s, PSI_INT, 0, oj, og, Q ? kp_rw4(oK, pb, oR, ow) : mul4(oK, pb), true, true, true, E1, E2);
             const int x = 4 * (ogrp + 1);
             st4(&E[0][orow + 2][x], E1); st4(&E[1][orow + 2][x], E2);
         }
         if (t < kHalo) {
             float4 E1 = zero4, E2 = zero4;
-            if (halo_ok) stage_T(p, s, PSI_INT, 0, hj, hgg, mul4(hK, hpb), false, !halo_row, halo_row, E1, E2);
+            if (halo_ok)
+                stage_T(p, s, PSI_INT, 0, hj, hgg, Q ? kp_rw4(hK, hpb, hR, hw) : mul4(hK, hpb), false, !halo_row, halo_row, E1, E2);
             if (halo_row) st4(&E[1][hr][4 * hg], E2);       // (two stores: choosing between the two float4 puts both on the stack)
             else st4(&E[0][hr][4 * hg], E1);
         }
@@ -496,16 +548,23 @@ __global__ __launch_bounds__(kThreads) void fl_adj_p(const FlParams p)
             acc[M_BX].z = fmaf(S1.z, nvx[2], acc[M_BX].z); acc[M_BX].w = fmaf(S1.w, nvx[3], acc[M_BX].w);
             acc[M_BZ].x = fmaf(S2.x, nvz[0], acc[M_BZ].x); acc[M_BZ].y = fmaf(S2.y, nvz[1], acc[M_BZ].y);
             acc[M_BZ].z = fmaf(S2.z, nvz[2], acc[M_BZ].z); acc[M_BZ].w = fmaf(S2.w, nvz[3], acc[M_BZ].w);
+            if (Q) {
+                acc[NP - 1].x = fmaf(S0.x, ow.x, acc[NP - 1].x); acc[NP - 1].y = fmaf(S0.y, ow.y, acc[NP - 1].y);
+                acc[NP - 1].z = fmaf(S0.z, ow.z, acc[NP - 1].z); acc[NP - 1].w = fmaf(S0.w, ow.w, acc[NP - 1].w);
+            }
         }
         __syncthreads();          // E is reused by the next shot
     }
     if (own_ok) {
 #pragma unroll
-        for (int k = 0; k < 3; ++k) st4(accp + (long long)k * p.splane, acc[k]);
+        for (int k = 0; k < NP; ++k) st4(accp + (long long)k * p.splane, acc[k]);
     }
 }
 
 // V^T:  D1 = pmlT(bx vx_bar), D4 = pmlT(bz vz_bar);  p_bar -= Dm_x D1 + Dm_z D4;  free surface: p_bar(1,.) += C2 D4(0,.)
+// Q (viscoacoustic): the owner advances r_bar = a r_bar + (1 + a)/2 p_bar with the p_bar that P^T saw (as loaded here,
+//       before this launch updates it; row 0 under a free surface: the cleared one)
+template <bool Q>
 __global__ __launch_bounds__(kThreads) void fl_adj_v(const FlParams p)
 {
     const FdK K = p.fd;
@@ -541,6 +600,8 @@ __global__ __launch_bounds__(kThreads) void fl_adj_v(const FlParams p)
         hb = ld4(p.mat + (halo_row ? M_BZ : M_BX) * ncell + hcc);
     }
     if (own_ok) pb = ld4(fl + F_P * fs + oo);
+    float4 rb = zero4;
+    if (Q && own_ok) rb = ld4(fl + F_R * fs + oo);
     {
         float4 D1 = zero4, D4 = zero4, unused;
         if (own_ok) {
@@ -573,6 +634,12 @@ __global__ __launch_bounds__(kThreads) void fl_adj_v(const FlParams p)
             if (4 * og + c >= p.nx) np[c] = 0.f;
         }
         st4(fl + F_P * fs + oo, mk4(np));
+        if (Q) {
+            const float ha = 0.5f * (1.f + p.rel_a);
+            const float4 ps = (p.fsurf && oj == 0) ? zero4 : pb;
+            st4(fl + F_R * fs + oo, make_float4(fmaf(p.rel_a, rb.x, ha * ps.x), fmaf(p.rel_a, rb.y, ha * ps.y),
+                                                fmaf(p.rel_a, rb.z, ha * ps.z), fmaf(p.rel_a, rb.w, ha * ps.w)));
+        }
     }
 }
 
@@ -619,8 +686,21 @@ __global__ void fl_inject_pressure(const FlParams p)
 }  // namespace
 
 // ================================================================================================
+// ---- the medium of a plan ---------------------------------------------------------------------------
+// Every plan of this file is a mifwi_fluid_plan; its medium says which kernels serve it, how many fields a shot has and how
+// many planes mat, grad_mat and the accumulators take (the kMedia row of mifwi_elastic.hip, on the fluid side).  Lossless:
+// fl_step_p / fl_adj_p / fl_adj_v with Q = false, finalize_groups<3>; viscoacoustic: Q = true, finalize_groups<4>.  The V
+// launch, the point kernels and the three snapshot planes are the same for both.
+namespace {
+enum FlMedium { kLossless = 0, kViscoacoustic = 1 };
+struct FlMediumInfo { int nfield, nmat; const char *created_by; };
+constexpr FlMediumInfo kFlMedia[] = {{3, 3, "mifwi_fluid_plan_create"}, {4, 4, "mifwi_viscofluid_plan_create"}};
+}  // namespace
+
 struct mifwi_fluid_plan : StaggerGrid {      // grid, pitch and strips: stagger_grid with two memory variables per strip cell
     mifwi_fluid_desc d;
+    FlMedium medium;       // kFlMedia[medium]: its fields, planes and entry points
+    float rel_a, rel_b;    // viscoacoustic: the relaxation scalars
     int device;
     int lx, gs, ngroups;
     long long splane;      // floats per snapshot / accumulator plane
@@ -645,20 +725,30 @@ FlParams fl_base(const mifwi_fluid_plan *pl, const float *mat, const float *pz, 
     p.mat = mat; p.pz = pz; p.px = px;
     p.splane = (unsigned)pl->splane;
     p.fd = fd_weights(pl->d.fd_order);
+    p.rel_a = pl->rel_a; p.rel_b = pl->rel_b;
     return p;
 }
 
-// the two launches of a forward step, fl_step_v / fl_step_p<LX, SAVE>: lanes per row 64 | 32 | 16; save kBorn (the
-// background's snapshots read) | 1 (snapshots written) | 0
+// the two launches of a forward step, fl_step_v<LX, SAVE> (both media's) / fl_step_p<LX, SAVE, Q>: lanes per row
+// 64 | 32 | 16; save kBorn (the background's snapshots read) | 1 (snapshots written) | 0; Q: the viscoacoustic medium
 using FlKernel = void (*)(FlParams);
 struct FlStepKernels { FlKernel v, p; };
-FlStepKernels fl_step_variant(int lx, int save)
+FlStepKernels fl_step_variant(FlMedium medium, int lx, int save)
 {
     return mifwi::with_int<64, 32, 16>(lx, [&](auto LX) {
     return mifwi::with_int<kBorn, 1, 0>(save, [&](auto SAVE) {
+    return mifwi::with_bool(medium == kViscoacoustic, [&](auto Q) {
         return FlStepKernels{fl_step_v<decltype(LX)::value, decltype(SAVE)::value>,
-                             fl_step_p<decltype(LX)::value, decltype(SAVE)::value>};
-    }); });
+                             fl_step_p<decltype(LX)::value, decltype(SAVE)::value, decltype(Q)::value>};
+    }); }); });
+}
+// the two launches of an adjoint step
+struct FlAdjKernels { FlKernel p, v; };
+FlAdjKernels fl_adj_variant(FlMedium medium)
+{
+    return mifwi::with_bool(medium == kViscoacoustic, [&](auto Q) {
+        return FlAdjKernels{fl_adj_p<decltype(Q)::value>, fl_adj_v<decltype(Q)::value>};
+    });
 }
 
 // Offsets (in floats) of the regions of the work buffer.  Forward call: [fields | psi | bbox]; backward call:
@@ -671,7 +761,7 @@ FlWork work_map(const mifwi_fluid_plan *pl, bool backward)
     FlWork m;
     m.fields = 0; m.psi = pl->fields_elems; m.psiB = m.psi + pl->psi_elems;
     m.acc = backward ? m.psiB + pl->psi_elems : m.psiB;
-    m.state = m.acc + (backward ? 3LL * pl->ngroups * pl->splane : 0);
+    m.state = m.acc + (backward ? (long long)kFlMedia[pl->medium].nmat * pl->ngroups * pl->splane : 0);
     m.bbox = m.tile = m.state;
     m.total = m.state + (backward ? pl->tile_elems : mifwi::round_up64(4LL * pl->d.nshot, 64));
     return m;
@@ -687,7 +777,7 @@ void fl_forward_steps(const mifwi_fluid_plan *pl, FlParams p, int save, const fl
 {
     const mifwi_fluid_desc &d = pl->d;
     const bool inject = f != nullptr, want_v = rec_vx != nullptr, want_p = rec_p != nullptr;
-    const FlStepKernels step = fl_step_variant(pl->lx, save);
+    const FlStepKernels step = fl_step_variant(pl->medium, pl->lx, save);
     p.ntap_inj = d.ntap; p.inj_cell = src_cell; p.inj_w = src_w; p.inj_bbox = bbox;
     p.inj_field = d.source_type == 1 ? F_VX : F_VZ;
     p.nsmp = d.nrec; p.ntap_smp = d.ntap; p.smp_cell = rec_cell; p.smp_w = rec_w;
@@ -718,11 +808,9 @@ void fl_forward_steps(const mifwi_fluid_plan *pl, FlParams p, int save, const fl
     }
 }
 
-}  // namespace
-
-extern "C" {
-
-int mifwi_fluid_plan_create(mifwi_fluid_plan **plan, int device, const mifwi_fluid_desc *d)
+// a viscoacoustic plan is a fluid plan of that medium; the C ABI keeps the handle types apart
+int fl_plan_create(mifwi_fluid_plan **plan, int device, const mifwi_fluid_desc *d, FlMedium medium, float rel_a = 0.f,
+                   float rel_b = 0.f)
 {
     if (!plan || !d) return mifwi::fail(MIFWI_EINVAL, "null plan/desc");
     int rc = check_stagger_desc(d, 3);
@@ -736,7 +824,9 @@ int mifwi_fluid_plan_create(mifwi_fluid_plan **plan, int device, const mifwi_flu
     pl->d = *d;
     if (pl->d.fd_order == 0) pl->d.fd_order = 4;
     pl->device = device;
-    pl->shot_stride = 3 * pl->field_stride;
+    pl->medium = medium; pl->rel_a = rel_a; pl->rel_b = rel_b;
+    const int nfield = kFlMedia[medium].nfield, nmat = kFlMedia[medium].nmat;
+    pl->shot_stride = nfield * pl->field_stride;
     pl->fields_elems = pl->shot_stride * d->nshot;
     pl->psix_elems = pl->psix_shot * d->nshot;
     pl->psiz_elems = pl->psiz_shot * d->nshot;
@@ -752,18 +842,35 @@ int mifwi_fluid_plan_create(mifwi_fluid_plan **plan, int device, const mifwi_flu
         // forward plans for 230 MB once it has to cut).  MIFWI_FL_PASS_SHOTS / MIFWI_FL_PASS_GROUPS override the two sizes
         // (tests run passes of one shot / one group on small grids; measurements around the defaults)
         constexpr double kResident = 250e6;
-        const double cells = (double)pl->coef_elems, mats = 4.0 * 3.0 * cells;
+        const double cells = (double)pl->coef_elems, mats = 4.0 * nmat * cells;
         const double psi1 = 4.0 * (double)(pl->psix_shot + pl->psiz_shot);
         const double fstate = 4.0 * (double)pl->shot_stride + psi1;
         const int ps = mifwi::env_int("MIFWI_FL_PASS_SHOTS", mifwi::units_per_pass(d->nshot, fstate, mats, kResident, 230e6, 1));
         pl->pass_shots = std::min(d->nshot, std::max(1, ps));
-        const double astate = 4.0 * (double)pl->shot_stride + 2.0 * psi1, accg = 4.0 * 3.0 * cells;
+        const double astate = 4.0 * (double)pl->shot_stride + 2.0 * psi1, accg = 4.0 * nmat * cells;
         const int pg = mifwi::env_int("MIFWI_FL_PASS_GROUPS", mifwi::units_per_pass(pl->ngroups, pl->gs * astate + accg, mats,
                                                                                      kResident, kResident, pl->ngroups));
         pl->pass_groups = std::min(pl->ngroups, std::max(1, pg));
     }
     *plan = pl;
     return MIFWI_OK;
+}
+
+// Refuses the plan of the other medium: its kernels would take kFlMedia[].nmat planes and fields where the caller allocated
+// this one's.  (A null plan passes: the call itself refuses it.)
+int check_medium(const mifwi_fluid_plan *pl, FlMedium medium)
+{
+    return (pl && pl->medium != medium) ? mifwi::fail(MIFWI_EINVAL, "the plan was not created by %s", kFlMedia[medium].created_by)
+                                        : MIFWI_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int mifwi_fluid_plan_create(mifwi_fluid_plan **plan, int device, const mifwi_fluid_desc *d)
+{
+    return fl_plan_create(plan, device, d, kLossless);
 }
 
 int mifwi_fluid_plan_destroy(mifwi_fluid_plan *plan)
@@ -796,10 +903,11 @@ int mifwi_fluid_plan_layout(const mifwi_fluid_plan *pl, mifwi_fluid_layout *out)
     return MIFWI_OK;
 }
 
-int mifwi_fluid_forward(mifwi_fluid_plan *pl, const float *mat, const float *pz, const float *px, const float *f,
-                        const int32_t *src_cell, const float *src_w, const int32_t *rec_cell, const float *rec_w,
-                        float *rec_vx, float *rec_vz, float *rec_p, float *snap, float *work, int32_t n_begin,
-                        int32_t n_end, int32_t flags, void *stream)
+// ---- the three calls of a plan, whatever its medium: what the entry points of both families run ---------------------
+static int fl_forward(mifwi_fluid_plan *pl, const float *mat, const float *pz, const float *px, const float *f,
+                      const int32_t *src_cell, const float *src_w, const int32_t *rec_cell, const float *rec_w,
+                      float *rec_vx, float *rec_vz, float *rec_p, float *snap, float *work, int32_t n_begin,
+                      int32_t n_end, int32_t flags, void *stream)
 {
     if (!pl || !mat || !pz || !px || !work) return mifwi::fail(MIFWI_EINVAL, "null argument");
     const mifwi_fluid_desc &d = pl->d;
@@ -827,10 +935,10 @@ int mifwi_fluid_forward(mifwi_fluid_plan *pl, const float *mat, const float *pz,
     return MIFWI_OK;
 }
 
-int mifwi_fluid_born(mifwi_fluid_plan *pl, const float *mat, const float *dmat, const float *pz, const float *px,
-                     const float *df, const int32_t *src_cell, const float *src_w, const int32_t *rec_cell,
-                     const float *rec_w, const float *snap, int32_t snap_first, float *drec_vx, float *drec_vz,
-                     float *drec_p, float *work, int32_t n_begin, int32_t n_end, int32_t flags, void *stream)
+static int fl_born(mifwi_fluid_plan *pl, const float *mat, const float *dmat, const float *pz, const float *px,
+                   const float *df, const int32_t *src_cell, const float *src_w, const int32_t *rec_cell,
+                   const float *rec_w, const float *snap, int32_t snap_first, float *drec_vx, float *drec_vz,
+                   float *drec_p, float *work, int32_t n_begin, int32_t n_end, int32_t flags, void *stream)
 {
     if (!pl || !mat || !pz || !px) return mifwi::fail(MIFWI_EINVAL, "null argument");
     if (!dmat || !snap || !work) return mifwi::fail(MIFWI_EINVAL, "born: dmat, snap and work must not be null");
@@ -862,11 +970,11 @@ int mifwi_fluid_born(mifwi_fluid_plan *pl, const float *mat, const float *dmat, 
     return MIFWI_OK;
 }
 
-int mifwi_fluid_backward(mifwi_fluid_plan *pl, const float *mat, const float *pz, const float *px,
-                         const int32_t *src_cell, const float *src_w, const int32_t *rec_cell, const float *rec_w,
-                         const float *g_vx, const float *g_vz, const float *g_p, const float *snap, int32_t snap_first,
-                         float *grad_mat, float *grad_f, float *work, int32_t n_hi, int32_t n_lo, int32_t flags,
-                         void *stream)
+static int fl_backward(mifwi_fluid_plan *pl, const float *mat, const float *pz, const float *px,
+                       const int32_t *src_cell, const float *src_w, const int32_t *rec_cell, const float *rec_w,
+                       const float *g_vx, const float *g_vz, const float *g_p, const float *snap, int32_t snap_first,
+                       float *grad_mat, float *grad_f, float *work, int32_t n_hi, int32_t n_lo, int32_t flags,
+                       void *stream)
 {
     if (!pl || !mat || !pz || !px || !work || !snap) return mifwi::fail(MIFWI_EINVAL, "null argument");
     const mifwi_fluid_desc &d = pl->d;
@@ -892,6 +1000,7 @@ int mifwi_fluid_backward(mifwi_fluid_plan *pl, const float *mat, const float *pz
     const long long snap_step = 3 * pl->splane * d.nshot;
     const int tx = mifwi::ceil_div(pl->ng, AGO), tz = mifwi::ceil_div(d.nz, ATZ);
     p.tiles_z = tz;
+    const FlAdjKernels adj = fl_adj_variant(pl->medium);
     // per-tile receiver lists: fl_adj_p adds the velocity adjoint sources of its tile
     if ((g_vx || g_vz) && d.nrec > 0 && n_hi >= n_lo) {
         const int ntiles = tx * tz;
@@ -926,22 +1035,124 @@ int mifwi_fluid_backward(mifwi_fluid_plan *pl, const float *mat, const float *pz
         pp.inj_amp1 = g_vz ? g_vz + rec_n : nullptr;
         pp.smp_out0 = (want_f && !force) ? grad_f + (long long)n * d.nshot * d.nsrc : nullptr;
         const int ex = (want_f && !force) ? mifwi::ceil_div(mifwi::ceil_div(pl->gs * d.nsrc, kThreads), tx) : 0;
-        hipLaunchKernelGGL(fl_adj_p, dim3(tx, tz + ex, cg), dim3(kThreads), 0, st, pp);
+        hipLaunchKernelGGL(adj.p, dim3(tx, tz + ex, cg), dim3(kThreads), 0, st, pp);
         if (want_f && force) {
             FlParams pq = p;
             pq.gs = cs; pq.smp_out0 = grad_f + (long long)n * d.nshot * d.nsrc;
             hipLaunchKernelGGL(sample_force<FlParams>, dim3(mifwi::ceil_div(cs * d.nsrc, 64)), dim3(64), 0, st, pq,
                                d.source_type == 1 ? F_VX : F_VZ);
         }
-        hipLaunchKernelGGL(fl_adj_v, dim3(tx, tz, cs), dim3(kThreads), 0, st, p);
+        hipLaunchKernelGGL(adj.v, dim3(tx, tz, cs), dim3(kThreads), 0, st, p);
     }
     if (flags & MIFWI_FINALIZE) {
-        const long long n3 = 3LL * pl->coef_elems;
-        hipLaunchKernelGGL(finalize_groups<3>, dim3((unsigned)((n3 + 255) / 256)), dim3(256), 0, st, acc, pl->ngroups, d.nz,
+        const long long n3 = (long long)kFlMedia[pl->medium].nmat * pl->coef_elems;
+        const auto fin = pl->medium == kViscoacoustic ? finalize_groups<4> : finalize_groups<3>;
+        hipLaunchKernelGGL(fin, dim3((unsigned)((n3 + 255) / 256)), dim3(256), 0, st, acc, pl->ngroups, d.nz,
                            pl->gp, pl->splane, 1, grad_mat);
     }
     MIFWI_HIP_TRY(hipGetLastError());
     return MIFWI_OK;
+}
+
+// lossless
+int mifwi_fluid_forward(mifwi_fluid_plan *plan, const float *mat, const float *pz, const float *px, const float *f,
+                        const int32_t *src_cell, const float *src_w, const int32_t *rec_cell, const float *rec_w,
+                        float *rec_vx, float *rec_vz, float *rec_p, float *snap, float *work, int32_t n_begin,
+                        int32_t n_end, int32_t flags, void *stream)
+{
+    if (const int rc = check_medium(plan, kLossless)) return rc;
+    return fl_forward(plan, mat, pz, px, f, src_cell, src_w, rec_cell, rec_w, rec_vx, rec_vz, rec_p, snap, work, n_begin,
+                      n_end, flags, stream);
+}
+
+int mifwi_fluid_born(mifwi_fluid_plan *plan, const float *mat, const float *dmat, const float *pz, const float *px,
+                     const float *df, const int32_t *src_cell, const float *src_w, const int32_t *rec_cell,
+                     const float *rec_w, const float *snap, int32_t snap_first, float *drec_vx, float *drec_vz,
+                     float *drec_p, float *work, int32_t n_begin, int32_t n_end, int32_t flags, void *stream)
+{
+    if (const int rc = check_medium(plan, kLossless)) return rc;
+    return fl_born(plan, mat, dmat, pz, px, df, src_cell, src_w, rec_cell, rec_w, snap, snap_first, drec_vx, drec_vz,
+                   drec_p, work, n_begin, n_end, flags, stream);
+}
+
+int mifwi_fluid_backward(mifwi_fluid_plan *plan, const float *mat, const float *pz, const float *px,
+                         const int32_t *src_cell, const float *src_w, const int32_t *rec_cell, const float *rec_w,
+                         const float *g_vx, const float *g_vz, const float *g_p, const float *snap, int32_t snap_first,
+                         float *grad_mat, float *grad_f, float *work, int32_t n_hi, int32_t n_lo, int32_t flags,
+                         void *stream)
+{
+    if (const int rc = check_medium(plan, kLossless)) return rc;
+    return fl_backward(plan, mat, pz, px, src_cell, src_w, rec_cell, rec_w, g_vx, g_vz, g_p, snap, snap_first, grad_mat,
+                       grad_f, work, n_hi, n_lo, flags, stream);
+}
+
+// viscoacoustic: four fields per shot and four planes, the same launches
+static mifwi_fluid_plan *fl_cast(mifwi_viscofluid_plan *h) { return reinterpret_cast<mifwi_fluid_plan *>(h); }
+static const mifwi_fluid_plan *fl_cast(const mifwi_viscofluid_plan *h) { return reinterpret_cast<const mifwi_fluid_plan *>(h); }
+
+int mifwi_viscofluid_plan_create(mifwi_viscofluid_plan **plan, int device, const mifwi_viscofluid_desc *d)
+{
+    if (!plan || !d) return mifwi::fail(MIFWI_EINVAL, "null plan/desc");
+    // a = (2 - eta) / (2 + eta), b = 2 eta / (2 + eta) with 0 < eta < 2: 0 < a < 1 and b = 1 - a
+    if (!(d->relax_a > 0.f && d->relax_a < 1.f && d->relax_b > 0.f && d->relax_b < 1.f))
+        return mifwi::fail(MIFWI_EINVAL, "relax_a = %g, relax_b = %g: both must lie inside (0, 1)", (double)d->relax_a,
+                           (double)d->relax_b);
+    mifwi_fluid_desc e;
+    e.nz = d->nz; e.nx = d->nx; e.nt = d->nt; e.nshot = d->nshot; e.nsrc = d->nsrc; e.nrec = d->nrec; e.ntap = d->ntap;
+    e.pml_width = d->pml_width; e.free_surface = d->free_surface; e.shots_per_group = d->shots_per_group;
+    e.source_type = d->source_type; e.fd_order = d->fd_order;
+    return fl_plan_create(reinterpret_cast<mifwi_fluid_plan **>(plan), device, &e, kViscoacoustic, d->relax_a, d->relax_b);
+}
+
+int mifwi_viscofluid_plan_destroy(mifwi_viscofluid_plan *plan) { return mifwi_fluid_plan_destroy(fl_cast(plan)); }
+
+int mifwi_viscofluid_plan_layout(const mifwi_viscofluid_plan *plan, mifwi_viscofluid_layout *out)
+{
+    if (!plan || !out) return mifwi::fail(MIFWI_EINVAL, "null plan/layout");
+    mifwi_fluid_layout e;
+    if (const int rc = mifwi_fluid_plan_layout(fl_cast(plan), &e)) return rc;
+    out->gp = e.gp; out->pitch = e.pitch; out->ngroups = e.ngroups; out->shots_per_group = e.shots_per_group;
+    out->coef_elems = e.coef_elems; out->state_elems = e.state_elems; out->work_forward_elems = e.work_forward_elems;
+    out->work_backward_elems = e.work_backward_elems; out->snap_step_elems = e.snap_step_elems;
+    return MIFWI_OK;
+}
+
+int mifwi_viscofluid_plan_pass_sizes(const mifwi_viscofluid_plan *plan, int32_t *forward_shots, int32_t *adjoint_groups)
+{
+    return mifwi_fluid_plan_pass_sizes(fl_cast(plan), forward_shots, adjoint_groups);
+}
+
+int mifwi_viscofluid_plan_cluster_slabs(const mifwi_viscofluid_plan *, int32_t) { return 0; }
+
+int mifwi_viscofluid_forward(mifwi_viscofluid_plan *plan, const float *mat, const float *pz, const float *px, const float *f,
+                             const int32_t *src_cell, const float *src_w, const int32_t *rec_cell, const float *rec_w,
+                             float *rec_vx, float *rec_vz, float *rec_p, float *snap, float *work, int32_t n_begin,
+                             int32_t n_end, int32_t flags, void *stream)
+{
+    if (const int rc = check_medium(fl_cast(plan), kViscoacoustic)) return rc;
+    return fl_forward(fl_cast(plan), mat, pz, px, f, src_cell, src_w, rec_cell, rec_w, rec_vx, rec_vz, rec_p, snap, work,
+                      n_begin, n_end, flags, stream);
+}
+
+int mifwi_viscofluid_born(mifwi_viscofluid_plan *plan, const float *mat, const float *dmat, const float *pz, const float *px,
+                          const float *df, const int32_t *src_cell, const float *src_w, const int32_t *rec_cell,
+                          const float *rec_w, const float *snap, int32_t snap_first, float *drec_vx, float *drec_vz,
+                          float *drec_p, float *work, int32_t n_begin, int32_t n_end, int32_t flags, void *stream)
+{
+    if (const int rc = check_medium(fl_cast(plan), kViscoacoustic)) return rc;
+    return fl_born(fl_cast(plan), mat, dmat, pz, px, df, src_cell, src_w, rec_cell, rec_w, snap, snap_first, drec_vx,
+                   drec_vz, drec_p, work, n_begin, n_end, flags, stream);
+}
+
+int mifwi_viscofluid_backward(mifwi_viscofluid_plan *plan, const float *mat, const float *pz, const float *px,
+                              const int32_t *src_cell, const float *src_w, const int32_t *rec_cell, const float *rec_w,
+                              const float *g_vx, const float *g_vz, const float *g_p, const float *snap,
+                              int32_t snap_first, float *grad_mat, float *grad_f, float *work, int32_t n_hi, int32_t n_lo,
+                              int32_t flags, void *stream)
+{
+    if (const int rc = check_medium(fl_cast(plan), kViscoacoustic)) return rc;
+    return fl_backward(fl_cast(plan), mat, pz, px, src_cell, src_w, rec_cell, rec_w, g_vx, g_vz, g_p, snap, snap_first,
+                       grad_mat, grad_f, work, n_hi, n_lo, flags, stream);
 }
 
 }  // extern "C"

@@ -71,6 +71,7 @@ int64_t mifwi_fluid_snapshot_moments_work_elems(const mifwi_fluid_plan *pl)
 int mifwi_fluid_snapshot_moments(mifwi_fluid_plan *pl, const float *snap, int32_t snap_first, int32_t n_begin,
                                  int32_t n_end, int32_t stride, float *moments, float *work, int32_t flags, void *stream)
 {
+    if (const int rc = check_medium(pl, kLossless)) return rc;       // the pseudo-Hessian of a viscoacoustic medium is not built
     return snapshot_moments<FlMomParams>(pl, fl_mom_shape, snap, snap_first, n_begin, n_end, stride, moments, work, flags,
                                          stream, [pl](const FlMomParams &m, int nsplit, hipStream_t st) {
         const FlParams p = fl_base(pl, nullptr, nullptr, nullptr);

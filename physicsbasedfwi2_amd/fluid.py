@@ -67,28 +67,34 @@ def _three(tensors):
     return ptrs(*(list(tensors or ()) + [None] * 3)[:3])
 
 
-def _forward_call(plan, coef, f_d, geo, rec):
-    """``forward(snap_ptr, work_ptr, b, e, flags)`` as the drivers take it; rec = [rec_vx, rec_vz[, rec_p]], or None: a
-    re-run that samples nothing."""
-    lib = _lib.load()
-    args = (plan.handle, *coef, _lib.ptr(f_d), *geo, *_three(rec))
-    return lambda snap, work, b, e, flags: _lib.check(lib.mifwi_fluid_forward(*args, snap, work, b, e, flags, _stream()))
+def _calls(prefix):
+    """(forward_call, adjoint_call, born_call) around the entry points ``mifwi_<prefix>_forward`` / ``_backward`` / ``_born``:
+    the lossless and the viscoacoustic family (:mod:`viscofluid`) take the same argument lists."""
+
+    def forward_call(plan, coef, f_d, geo, rec):
+        """``forward(snap_ptr, work_ptr, b, e, flags)`` as the drivers take it; rec = [rec_vx, rec_vz[, rec_p]], or None: a
+        re-run that samples nothing."""
+        fn = getattr(_lib.load(), "mifwi_%s_forward" % prefix)
+        args = (plan.handle, *coef, _lib.ptr(f_d), *geo, *_three(rec))
+        return lambda snap, work, b, e, flags: _lib.check(fn(*args, snap, work, b, e, flags, _stream()))
+
+    def adjoint_call(plan, coef, geo, g, grad_mat, grad_f, work):
+        """``adjoint(snap_ptr, snap_first, hi, lo, flags)`` as the backward driver takes it; g = [g_vx, g_vz[, g_p]], each a
+        tensor or None."""
+        fn = getattr(_lib.load(), "mifwi_%s_backward" % prefix)
+        return lambda snap, first, hi, lo, flags: _lib.check(fn(
+            plan.handle, *coef, *geo, *_three(g), snap, first, _lib.ptr(grad_mat), _lib.ptr(grad_f), _lib.ptr(work), hi, lo,
+            flags, _stream()))
+
+    def born_call(plan, coef, dmat_p, df_d, geo, snap, drec, work, nt):
+        fn = getattr(_lib.load(), "mifwi_%s_born" % prefix)
+        _lib.check(fn(plan.handle, coef[0], _lib.ptr(dmat_p), *coef[1:], _lib.ptr(df_d), *geo, _lib.ptr(snap), 0,
+                      *_three(drec), _lib.ptr(work), 0, nt, _lib.ZERO_STATE, _stream()))
+
+    return tuple(staticmethod(fn) for fn in (forward_call, adjoint_call, born_call))
 
 
-def _adjoint_call(plan, coef, geo, g, grad_mat, grad_f, work):
-    """``adjoint(snap_ptr, snap_first, hi, lo, flags)`` as the backward driver takes it; g = [g_vx, g_vz[, g_p]], each a
-    tensor or None."""
-    lib = _lib.load()
-    return lambda snap, first, hi, lo, flags: _lib.check(lib.mifwi_fluid_backward(
-        plan.handle, *coef, *geo, *_three(g), snap, first, _lib.ptr(grad_mat), _lib.ptr(grad_f), _lib.ptr(work), hi, lo,
-        flags, _stream()))
-
-
-def _born_call(plan, coef, dmat_p, df_d, geo, snap, drec, work, nt):
-    _lib.check(_lib.load().mifwi_fluid_born(plan.handle, coef[0], _lib.ptr(dmat_p), *coef[1:], _lib.ptr(df_d), *geo,
-                                            _lib.ptr(snap), 0, *_three(drec), _lib.ptr(work), 0, nt, _lib.ZERO_STATE,
-                                            _stream()))
-
+_forward_call, _adjoint_call, _born_call = (fn.__func__ for fn in _calls("fluid"))      # the tools time them directly
 
 class _Fluid(Physics):
     """The three-field scheme as :class:`_driver.Propagate` and :func:`_driver.linearised` see it.  opts: pml_width,
@@ -99,7 +105,7 @@ class _Fluid(Physics):
     grad_planes = moment_planes = (3,)
     not_served = "Born modelling across time checkpoints is not served"
     weight_returns = "%(n)d tensors of the shape of its arguments"
-    forward_call, adjoint_call, born_call = (staticmethod(fn) for fn in (_forward_call, _adjoint_call, _born_call))
+    forward_call, adjoint_call, born_call = _calls("fluid")
     inputs = staticmethod(lambda mat, pz, px, gp, o: elastic._padded_inputs(mat, pz, px, gp))
     traces = staticmethod(lambda o: 3 if o["record_pressure"] else 2)
 
