@@ -122,7 +122,9 @@ def _config(spec):
     """(configuration, cache key) of ``spec``: a name of ``CASES``, or a configuration itself - the keywords of
     cases.elastic_case and, optionally, "seed" (83), "source_type" (0; 1 / 2: a point force fx / fz), "ntap" (1) and
     "surface_receivers" (True; False: under a free surface shot 0 is recorded on the buried line of the other shots, not on
-    row 0, where its own source's injection is 1e5 times everything the other shots record)."""
+    row 0, where its own source's injection is 1e5 times everything the other shots record), "blocks" (none; fluid blocks
+    (row0, row1, col0, col1), bounds inclusive, cut into the solid: vs = 0 there, the elastic planes rebuilt from that vs)
+    and "src" (elastic_case's; the (row, column) of each shot's one source)."""
     cfg = dict(CASES[spec] if isinstance(spec, str) else spec)
     return cfg, (spec if isinstance(spec, str) else tuple(sorted(cfg.items())))
 
@@ -155,8 +157,17 @@ def case(m, spec):
     if key not in _cache:
         seed, st, ntap = cfg.pop("seed", 83), cfg.pop("source_type", 0), cfg.pop("ntap", 1)
         on_surface = cfg.pop("surface_receivers", True)
+        blocks, src = cfg.pop("blocks", ()), cfg.pop("src", None)
         c = elastic_case(seed=seed, **cfg)
-        c["st"] = st
+        c["st"], c["blocks"] = st, blocks
+        if blocks:
+            for r0, r1, c0, c1 in blocks:
+                assert WATER <= r0 <= r1 < c["vs"].shape[0] and 0 <= c0 <= c1 < c["vs"].shape[1]
+                c["vs"][r0:r1 + 1, c0:c1 + 1] = 0.0
+            c["mat"] = H.elastic_materials(c["vp"], c["vs"], c["rho"], c["dt"], c["h"], free_surface=bool(c["fs"]))
+        if src is not None:
+            assert len(src) == c["sc"].shape[0] and c["sc"].shape[1] == 1
+            c["sc"], c["sw"] = H.cell_taps(np.array([[z] for z, _ in src]), np.array([[x] for _, x in src]), c["vp"].shape[1])
         if c["fs"] and not on_surface:
             c["rc"][0], c["rw"][0] = c["rc"][1], c["rw"][1]           # shot 0 recorded on the buried line of the others
         if st:

@@ -1,4 +1,4 @@
-"""What the tests of the VTI and viscoelastic kernels rely on, checked without a GPU: the yardstick (tests/psv_reference.py)
+"""What the tests of the VTI, viscoelastic and TTI kernels rely on, checked without a GPU: the yardstick (tests/psv_reference.py)
 on the axes tests/test_vti_host.py and tests/test_visco_host.py do not reach - point forces and four-tap points - against
 the fp64 C oracle in each medium's limit, the tile widths the cases of tests/psv_media.py are meant to run at, and what
 the draws of tests/test_psv_fuzz_gpu.py cover.  Bounds as in test_vti_host.py: 1e-10 rel-L2 on the traces, 1e-9 on every
@@ -10,6 +10,7 @@ import pytest
 import psv_media as M
 import psv_reference as R
 from cases import elastic_case, elastic_case_taps4, rel_l2
+from tti_reference import MEDIA3
 
 RELAX = (0.9, 0.1)             # any pair inside (0, 1): with planes 5-7 zero it must not matter
 _cache = {}
@@ -32,7 +33,7 @@ def _oracle(key, c, st, order):
 
 
 def _check_limit(medium, key, c, st, order):
-    m = M.MEDIA[medium]
+    m = MEDIA3[medium]
     ovx, ovz, g, gm, gf = _oracle(key, c, st, order)
     rvx, rvz, gp, rgf = R.gradients(m.limit(c["mat"]), c["pz"], c["px"], c["f"], c["sc"], c["sw"], c["rc"], c["rw"], g[0], g[1],
                                     medium, RELAX if m.takes_relax else None, free_surface=c["fs"], fd_order=order,
@@ -55,7 +56,7 @@ def _check_limit(medium, key, c, st, order):
 @pytest.mark.parametrize("order", [2, 4])
 @pytest.mark.parametrize("fs", [False, True], ids=["absorbing_top", "free_surface"])
 @pytest.mark.parametrize("st", [1, 2], ids=["fx", "fz"])
-@pytest.mark.parametrize("medium", list(M.MEDIA))
+@pytest.mark.parametrize("medium", list(MEDIA3))
 def test_reference_with_a_force_source_is_the_oracle_in_the_limit(medium, st, fs, order):
     c = elastic_case(seed=4, free_surface=fs)
     c["f"] = c["f"] * 1e-3                               # as the elastic sweep scales a force's amplitudes
@@ -64,7 +65,7 @@ def test_reference_with_a_force_source_is_the_oracle_in_the_limit(medium, st, fs
 
 @pytest.mark.parametrize("order", [2, 4])
 @pytest.mark.parametrize("fs", [False, True], ids=["absorbing_top", "free_surface"])
-@pytest.mark.parametrize("medium", list(M.MEDIA))
+@pytest.mark.parametrize("medium", list(MEDIA3))
 def test_reference_with_four_tap_points_is_the_oracle_in_the_limit(medium, fs, order):
     _check_limit(medium, ("taps4", fs, order), elastic_case_taps4("T", 21, free_surface=fs), 0, order)
 
@@ -86,3 +87,15 @@ def test_fuzz_draws_of_the_psv_media_cover_what_they_are_meant_to():
     """The committed draws of test_psv_fuzz_gpu.test_random_configuration (that module carries the gpu mark)."""
     import test_psv_fuzz_gpu
     test_psv_fuzz_gpu.test_draws_cover_widths_sources_taps_and_driver_forms()
+    assert list(test_psv_fuzz_gpu.MEDIA) == ["vti", "visco", "tti"]
+
+
+@pytest.mark.parametrize("k", range(12))
+def test_fuzz_draws_meet_the_preconditions_of_the_tilted_medium(k):
+    """The sweep's ``preconditions`` for TTI with the reference alone, draw by draw: nothing compared is all zero, the medium
+    moves some live shot by more than 1 % from its isotropic limit and the tilt by more than 1 % from theta = 0.  (Those of
+    VTI and the viscoelastic medium chose PSV_SEED; TTI meets its own on the same seed.)"""
+    import test_psv_fuzz_gpu as F
+    _, cfg, opt = F._configs()[k]
+    moved = F.preconditions(MEDIA3["tti"], cfg, opt["order"])
+    print("draw %d: moved from the limit %.3f, from theta = 0 %.3f" % (k, moved, F.tilt_moved(cfg, opt["order"])))

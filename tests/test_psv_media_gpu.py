@@ -1,5 +1,6 @@
-"""The P-SV media beyond the isotropic one on the GPU - VTI (physicsbasedfwi2_amd.vti, mifwi_vti_*) and viscoelastic
-(physicsbasedfwi2_amd.visco, mifwi_visco_*) - against their yardstick tests/psv_reference.py (float64; pinned to the fp64
+"""The P-SV media beyond the isotropic one on the GPU - VTI (physicsbasedfwi2_amd.vti, mifwi_vti_*), viscoelastic
+(physicsbasedfwi2_amd.visco, mifwi_visco_*) and TTI (physicsbasedfwi2_amd.tti, mifwi_tti_*; its entry and its stress
+update come from tests/tti_reference.py) - against their yardstick tests/psv_reference.py (float64; pinned to the fp64
 C oracle in the isotropic limit, to Thomsen's kinematics and to the attenuation law of a standard linear solid by
 tests/test_vti_host.py and tests/test_visco_host.py): Born, its identities and the driver forms, once for both media.  The
 limit and the parity with the reference are check_limit_is_the_elastic_propagator and
@@ -22,14 +23,18 @@ Shapes: A and B run at 16 lanes per row, C (41 x 117) at 32, D (35 x 230) at 64 
 tests/test_psv_host.py pins the widths).  On C, C_fw0, D and D_fs, VTI: traces 3.5e-8 ... 4.0e-7, gradients 8.7e-8 ... 1.1e-6,
 Born 3.0e-8 ... 4.1e-7; viscoelastic: traces 4.3e-8 ... 1.6e-7, gradients 4.2e-8 ... 5.7e-7, Born 2.1e-8 ... 1.9e-7; E_iso
 <= 5.4e-7.  A and B forced to 32 and 64 lanes (MIFWI_EL_LX; test_forced_tile_width_matches_the_reference of the media's own
-files): traces, gradients and Born the same bits as at 16 lanes.  Random configurations: tests/test_psv_fuzz_gpu.py."""
+files): traces, gradients and Born the same bits as at 16 lanes.  Random configurations: tests/test_psv_fuzz_gpu.py.
+TTI, the same three tests: Born on the eight cases 7.1e-8 ... 7.6e-7 (the largest on B at order 4); identities 6.7e-9 ...
+1.0e-5 (the largest <H a, b> = <a, H b> on B, whose terms are of size 1e-24); time checkpoints the resident run's bits,
+shot groups <= 3.4e-7 from it, Born in shot chunks the same bits."""
 import numpy as np
 import pytest
 import torch
 
 import psv_media as M
 from cases import rel_l2
-from psv_media import CASES, MEDIA, TOL_SUM, TOL_TRACE
+from psv_media import CASES, TOL_SUM, TOL_TRACE
+from tti_reference import MEDIA3 as MEDIA
 
 pytestmark = pytest.mark.gpu
 

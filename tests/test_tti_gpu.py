@@ -3,7 +3,13 @@ float64 reference of tests/tti_reference.py on the shapes A ... D of tests/psv_m
 steps), forced tile widths, four-tap points and force sources, Born and Gauss-Newton products, time checkpoints, the 45
 degree pin on the kernels, PHYSICS = 4 of the pyapi_denise shim and the refusals of the C entry points.  Bounds: traces
 within TOL_TRACE, every gradient within max(TOL_SUM, 4 E_iso), E_iso measured in the same run on the isotropic kernels -
-the project's bounds for a medium on these kernels (psv_media.check_traces_and_gradients_match_the_reference)."""
+the project's bounds for a medium on these kernels (psv_media.check_traces_and_gradients_match_the_reference).
+On all these cases the only fluid is the water layer, so the mask of the scheme is constant along every row: fluid blocks in
+the solid, the other snapshot layout and the free-surface forms are in tests/test_tti_edges_gpu.py, Born on all eight cases
+and the driver forms in tests/test_psv_media_gpu.py, random configurations in tests/test_psv_fuzz_gpu.py.
+Four-tap points with force sources, measured: fx and fz, orders 2 and 4, absorbing top: traces 8.8e-8 ... 1.3e-7, gradients
+1.3e-7 ... 1.2e-6 (c11, fx at order 4); under a free surface: traces 7.4e-8 ... 2.0e-7, gradients 8.1e-8 ... 1.3e-6 (c11, fx
+at order 4); E_iso <= 7.7e-7."""
 import ctypes
 
 import numpy as np
@@ -97,9 +103,14 @@ def test_forced_tile_width_matches_the_reference(monkeypatch, name, lx, order):
     M.check_forced_width(TTI, monkeypatch, name, lx, order)
 
 
+@pytest.mark.parametrize("order", [2, 4])
+@pytest.mark.parametrize("fs", [False, True], ids=["absorbing_top", "free_surface"])
 @pytest.mark.parametrize("st", [1, 2])
-def test_four_tap_points_and_force_sources(st):
-    M.check_traces_and_gradients_match_the_reference(TTI, dict(source_type=st, ntap=4), 4)
+def test_four_tap_points_and_force_sources(st, fs, order):
+    """Under the free surface shot 0 is recorded on the buried line of shot 1: on row 0 its own source's injection is 1e5
+    times everything else the case records (psv_media._config)"""
+    cfg = dict(source_type=st, ntap=4, free_surface=True, surface_receivers=False) if fs else dict(source_type=st, ntap=4)
+    M.check_traces_and_gradients_match_the_reference(TTI, cfg, order)
 
 
 # ---- Born, Gauss-Newton -------------------------------------------------------------------------------------------------
